@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W            # N=1 directly (no torch in the process)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                  # also writes what the last timed step returned (timed_outputs)
 
 One "step" = one pass of the hot path over this rank's batch of frame pairs, frames already resident
 in HBM.  Default workload = BASELINE.json configs[1]: 720x480 synthetic luma, bs=16, sw=16, exhaustive
@@ -265,6 +266,55 @@ ORACLE_THREADS = max(1, min(8, (os.cpu_count() or 2) - 1))     # the C oracle is
 def parity_sample_size(config, budget_s=PARITY_BUDGET_S, at_least=3):
     """Pairs the parity gate checks: what `budget_s` seconds of wall clock buy with ORACLE_THREADS oracle threads."""
     return int(max(at_least, min(64, budget_s * ORACLE_THREADS / ORACLE_S_PER_PAIR.get(config, 0.1))))
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # --dump-outputs: all arrays of one run together
+DUMP_SAMPLE_SEED = 7
+
+
+def dump_sample(n, row_bytes, budget):
+    """Pairs a per-pair array of `row_bytes` per pair keeps within `budget` bytes: all n, else a fixed seeded sample
+    (sorted) sized so that its float64 index array fits as well.  -> (indices, sampled)"""
+    if n * row_bytes <= budget:
+        return np.arange(n), False
+    k = int(min(n, budget // (row_bytes + 8)))
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False)), True
+
+
+def timed_outputs(seq, shard, last, proc):
+    """What a caller of the timed path received from its last step, as float32 / float64 arrays: block matching -> the
+    motion-vector fields of this rank's pairs (+ the gathered summary rows at N > 1); GME -> parameters, PSNR and the
+    compensated frames of this rank's pairs.  The small arrays are whole; the per-pair array keeps a fixed seeded sample
+    of pairs where the whole would take the total over DUMP_LIMIT_BYTES, its indices written beside it as `<name>_pairs`."""
+    arrays = {}
+    if shard is None:
+        if "gathered" in last:
+            arrays["mv_summary_rows"] = last["gathered"]
+        mv = seq.read_mv()
+        big_name, n, row_bytes = "mv", mv.shape[0], 4 * mv[0].size
+
+        def read(idx):
+            return mv[idx].astype(np.float32)                          # int32 vectors, |v| <= 64: exact
+    else:
+        rows = (last["rows"][:, :6], last["rows"][:, 6]) if proc == -3 else (last["params"], last["psnr"])
+        arrays["params"], arrays["psnr"] = rows
+        big_name, n, row_bytes = "compensated", shard.n_pairs, 4 * shard.H * shard.W
+
+        def read(idx):
+            return np.stack([shard.read_compensated(int(p)) for p in idx]).astype(np.float32)     # uint8: exact
+    arrays = {k: np.ascontiguousarray(v, np.float64) for k, v in arrays.items()}
+    idx, sampled = dump_sample(n, row_bytes, DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values()))
+    if sampled:
+        arrays[big_name + "_pairs"] = idx.astype(np.float64)
+    arrays[big_name] = read(idx)
+    return arrays
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in arrays.items()}}
 
 
 def oracle_map(fn, items):
@@ -661,6 +711,9 @@ def measure(opt, ctx, comm, rank, world):
     if rank != 0:
         release()
         return None
+    dumped = None
+    if getattr(opt, "dump_outputs", None):         # read back before anything below launches on the same buffers
+        dumped = dump_outputs(opt.dump_outputs, timed_outputs(seq, shard, last, proc))
     sys.path.insert(0, os.path.join(REPO, "tests"))
     from helpers import c_oracle, mv_summary_rows, oracle_results_flow
 
@@ -774,6 +827,8 @@ def measure(opt, ctx, comm, rank, world):
                      "kernel_ms_per_launch": kernel_ms, "algorithmic_bytes_per_launch": abytes},
         "parity": parity,
     }
+    if dumped:
+        out["outputs_dumped"] = dumped
     if comm.degraded:
         out["degraded"] = comm.degraded             # `value` then is NOT the product path's exchange; bench.py exits non-zero
     if distributed and not gme:
@@ -1062,7 +1117,12 @@ def main():
     ap.add_argument("--no-content-sweep", action="store_true")
     ap.add_argument("--no-pcie", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs the default line also times")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, at most "
+                         "%d MB in all; seeded inputs, so two builds can be compared output for output)" % (DUMP_LIMIT_BYTES // 10 ** 6))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1079,7 +1139,7 @@ def main():
     comm = Comm(ctx, rank, world, local % max(ndev, 1))
     opt = types.SimpleNamespace(config=args.config, content=args.content, pairs=args.pairs, steps=args.steps, warmup=args.warmup,
                                 cpu_baseline=not args.no_cpu_baseline, content_sweep=not args.no_content_sweep,
-                                pcie=not args.no_pcie, parity_budget_s=PARITY_BUDGET_S)
+                                pcie=not args.no_pcie, parity_budget_s=PARITY_BUDGET_S, dump_outputs=args.dump_outputs)
     out = measure(opt, ctx, comm, rank, world)
     if rank == 0:
         default_command = (args.config == "exh720" and args.content == "synthetic" and world == 1 and args.pairs is None

@@ -574,6 +574,49 @@ def test_bench_helpers():
     assert bench.byte_ops_per_pair(480, 720, 16, 16) == 2891044 * 256
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 .npy files within DUMP_LIMIT_BYTES, values exact; a per-pair array too
+    large to keep whole keeps the same seeded sample of pairs on every run, its indices written beside it."""
+    sys.path.insert(0, REPO)
+    import bench
+
+    class Seq:                                     # the block-matching path: int32 motion-vector fields
+        def __init__(self, n):
+            self.mv = (np.arange(n * 30 * 45 * 2).reshape(n, 30, 45, 2) % 129 - 64).astype(np.int32)
+
+        def read_mv(self):
+            return self.mv
+
+    class Shard:                                   # the GME path: parameters, PSNR, uint8 compensated frames
+        H, W, n_pairs = 24, 32, 40
+
+        def read_compensated(self, p):
+            return np.full((self.H, self.W), p % 256, np.uint8)
+
+    whole = bench.timed_outputs(Seq(8), None, {}, 0)
+    assert list(whole) == ["mv"] and whole["mv"].dtype == np.float32 and np.array_equal(whole["mv"], Seq(8).mv)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 ** 5)
+    runs = [bench.timed_outputs(Seq(64), None, {"gathered": np.ones((2, 64, 6))}, 0) for _ in range(2)]
+    for a in runs:
+        assert sorted(a) == ["mv", "mv_pairs", "mv_summary_rows"] and sum(x.nbytes for x in a.values()) <= 10 ** 5
+        idx = a["mv_pairs"].astype(int)
+        assert 0 < len(idx) < 64 and np.array_equal(a["mv"], Seq(64).mv[idx])
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+    last = {"params": np.arange(240.0).reshape(40, 6), "psnr": np.arange(40.0)}
+    g = bench.timed_outputs(None, Shard(), last, -1)
+    idx = g["compensated_pairs"].astype(int)
+    assert g["compensated"].dtype == np.float32 and np.array_equal(g["compensated"][:, 0, 0], idx)
+    assert np.array_equal(g["params"], last["params"]) and sum(x.nbytes for x in g.values()) <= 10 ** 5
+    rows = np.concatenate([last["params"], last["psnr"][:, None]], axis=1)
+    s = bench.timed_outputs(None, Shard(), {"rows": rows}, -3)
+    assert np.array_equal(s["params"], last["params"]) and np.array_equal(s["psnr"], last["psnr"])
+    info = bench.dump_outputs(str(tmp_path / "out"), g)
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(k + ".npy" for k in g) and info["arrays"]["psnr"]["shape"] == [40]
+    for k in g:
+        x = np.load(tmp_path / "out" / (k + ".npy"))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, g[k])
+
+
 def test_roadmap_model_solves_match_least_squares():
     """roadmap.solve_model (extension, recap_future_updates.md:9-12): from the normal-equation sums alone the
     translation / similarity / affine solves equal np.linalg.lstsq on the underlying block vectors."""
