@@ -7,8 +7,8 @@
 // minimum: it can neither win nor tie, so skipping it keeps the reference's "first strict
 // minimum in scan order" result bit for bit.
 //
-// Two kernels run the same phases: k_exh_sea16 (one tile per workgroup) and k_exh_sea16p (persistent
-// workgroups that prefetch the next tile into registers, bbme_sea_common.h: persistent_tiles).
+// Two kernels run the same phases: k_exh_sea16 (one tile per workgroup, bbme_sea_common.h: one_tile) and k_exh_sea16p
+// (persistent workgroups that prefetch the next tile into registers, bbme_sea_common.h: persistent_tiles).
 // Per tile (NB adjacent macroblocks, one wave each, as in k_exh_qsad16):
 //   A  stage the search window of `cur` and the anchors in LDS; quadrant sums of each anchor;
 //   A' 8x8 box sums S8 of the staged window, in LDS, two separable passes: the horizontal one is
@@ -21,7 +21,7 @@
 //   E  the list is processed 64*NB patches at a time, one patch per lane (R x 16 x 4
 //      v_qsad_pk_u16_u8 against the anchor read from LDS -- lanes of one wave may serve different
 //      blocks), best keys merged with LDS atomicMin; before each chunk entries whose LB exceeds
-//      the tightened UB are dropped; template flag E4: four lanes per patch (large windows);
+//      the tightened UB are dropped; four lanes per patch from R = 3 on (larger windows);
 //   F  lane 0 of each wave stores its block's vector.
 // On the synthetic and the reference's doc frames 2-6 % of the patches survive.
 #include "bbme_sea_common.h"
@@ -29,13 +29,6 @@
 namespace {
 
 using namespace sea;
-
-#ifdef GME_SEA_STAMPS
-#define STAMP(i) do { if (lane == 0) d.stamps[((((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * NB + wave) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-
 
 // B: lower bounds of the 4R x R candidates of one lane (candidate rows prow*R + i, columns
 // q*4R + 4k + e).  GUARD = false is the branch-free body for blocks whose whole window is inside
@@ -75,7 +68,7 @@ __device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int pr
     }
 }
 
-// E, four lanes per patch: lane `sub` of a quad takes anchor rows 4*sub .. 4*sub+3 of the patch's block (R+3 window rows,
+// C2's evaluation, four lanes per patch: lane `sub` of a quad takes anchor rows 4*sub .. 4*sub+3 of the patch's block (R+3 window rows,
 // 16*R QSADs); the four partial u16x4 sums are added inside the quad with DPP moves, then lane `sub` turns column `sub`
 // of the patch into keys (sad << 13 | scan index).  Returns the quad's smallest key (0xFFFFFFFF: none).  Every lane of
 // the wave must call it (DPP); a quad is uniform in `ent` and `active`.
@@ -159,11 +152,14 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaDev& d, const uint3
 // Phases A' .. F of one tile.  On entry the window and the anchors are staged, *count == 0 and the
 // workgroup has passed a barrier; there is no barrier after F.
 // Returns true (workgroup-uniform) when the tile was handed to the redo kernel instead (SeaDev::redo_list).
-template <int R, bool E4>
+template <int R>
 __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                             uint32_t mine, uint32_t a01, uint32_t a23, int tid, int tile_id)
 {
-    const int NB = d.nb, T = blockDim.x;
+    // phase C2 and phase E with four lanes per patch (a quarter of the latency the other waves wait for) from R = 3 on:
+    // +11 % at sw 32, +3 % at sw 16
+    constexpr bool E4 = R >= 3;
+    const int T = blockDim.x;
     const int NC = 2 * d.sw + 16, XQ = d.xq;
     uint32_t* win = lds + L.win;                           // [win_rows][pitch_dw]
     uint32_t* anchor = lds + L.anchor;                     // [NB][ANCHOR_STRIDE]
@@ -178,19 +174,10 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
     const bool wave_ok = wb.ok;                            // ragged last tile of a block row / column
     const int r0 = brow * 16, c0 = bcol * 16;
     const int prow = lane >> 2, q = lane & 3;
-    (void)NB;
 
     // ---- A': 8x8 box sums of the window (bbme_sea_common.h) ------------------------------------
-#if defined(SEA_ABLATE) && SEA_ABLATE >= 3
-    return false;                                          // timing-only build: staging + prep only
-#endif
     box_sums8<R>(d, win, s8, tid);
-    STAMP(3);
     __syncthreads();
-    STAMP(4);
-#if defined(SEA_ABLATE) && SEA_ABLATE >= 2
-    return false;                                          // timing-only build: + box sums
-#endif
 
     // ---- B: lower bounds of the wave's own block --------------------------------------------
     const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, d.H - 16 - r0 + d.sw);
@@ -238,7 +225,6 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
             }
             packed = wave_sum_u32(packed);
             ub_key = min(((packed & 0xFFFFu) << 13) | (uint32_t)idx0, ((packed >> 16) << 13) | (uint32_t)idx1);
-#ifndef SEA_NO_PROBE_PREV
             // third probe: the vector this wave's block of the PREVIOUS tile of the workgroup ended with (the block one
             // tile to the left, or wherever the schedule came from): spatial coherence makes it a good guess when the
             // smallest bound does not name the best candidate.  Skipped (wave-uniform) when it is one of the two candidates
@@ -253,7 +239,6 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
                 const uint32_t sadp = wave_sum_u32(__builtin_amdgcn_sad_u8(v, mine, 0u));
                 ub_key = min(ub_key, (sadp << 13) | (uint32_t)idxp);
             }
-#endif
         }
         // ---- C2 (round 4): ordered evaluation inside a crowded block.  Where the first upper bound leaves more than
         // SeaDev::quota patches (real content: the smallest bound does not name the best candidate, but the best one sits
@@ -263,7 +248,6 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
         // (bbme.py:171: only a smaller key replaces the best one).
         uint32_t own_lim = 0;                              // keys below it were scored here (wave-uniform)
         int n_w = 0;                                       // patches the first upper bound leaves (statistics)
-#ifndef SEA_NO_C2
         if constexpr (E4) {
             // crowded?  Lanes with a surviving patch are counted first (one ballot); the exact count only where it matters
             if (d.quota > 0 && __popcll(__ballot((lane_lb & 0xFFFFE000u) < ub_key)) > d.engage / 3) {
@@ -305,7 +289,6 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
                 }
             }
         }
-#endif
         if (lane == 0) best[2 * wave] = ub_key;
         // ---- D: surviving patches -> workgroup list.  A candidate replaces the best one only with a smaller
         // key (sad << 13 | scan index: bbme.py:171 keeps the FIRST strict minimum), and its key is at least
@@ -325,39 +308,14 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
             if (lane == 0) atomicAdd(count + 4, (uint32_t)(n_w - pushed));
         }
     }
-    STAMP(5);
     __syncthreads();
-    STAMP(6);
-#ifndef SEA_NO_REDO
     if (d.redo_list && (int)*count > d.redo_threshold) {     // workgroup-uniform: hostile tile, brute force is cheaper
         if (tid == 0) push_redo(d, tile_id, (int)(blockIdx.x & 7));
         return true;
     }
-#endif
 
-#if defined(SEA_ABLATE) && SEA_ABLATE >= 1
-    return false;                                          // timing-only build: + bounds, UB, list (no evaluation, no result)
-#endif
-#ifdef SEA_E_CALLS_EVAL
     if constexpr (E4) {
-        // ---- E (variant): four lanes per patch (eval_patch_quad) -----------------------------------
-        const int n = (int)*count;
-        const int sub = lane & 3;
-        for (int base = 0; base < n; base += T / 4) {
-            const int e = base + (tid >> 2);
-            bool active = e < n;
-            uint32_t ent = 0;
-            if (active) ent = work[e];
-            // dropped by a tightened UB (same key rule as phase D); the quad is uniform in `active` (same entry)
-            active = active && (((ent & 0xFFFFu) << 13) | (uint32_t)(((int)((ent >> 19) & 3) * 4 * R + 4 * (int)((ent >> 16) & 7)) * NC + (int)((ent >> 21) & 15) * R)) < best[2 * (ent >> 25)];
-            const uint32_t key = eval_patch_quad<R>(d, win, anchor, ent, active, sub, trow, bcol0, NC);
-            if (active && sub == 0 && key != 0xFFFFFFFFu) atomicMin(&best[2 * (ent >> 25)], key);
-            __syncthreads();
-        }
-
-#else
-    if constexpr (E4) {
-        // ---- E (variant): four lanes per patch (the body of eval_patch_quad, kept inline here: the
+        // ---- E, R >= 3: four lanes per patch (the body of eval_patch_quad, kept inline here: the
         // shared function cost this loop 1.2 % in register allocation, same-box A/B round 4) ---------------------------------------------------
         // Lane `sub` of a quad takes anchor rows 4*sub .. 4*sub+3 (R+3 window rows, 16*R QSADs); the four
         // partial u16x4 sums are added inside the quad with DPP moves.
@@ -443,8 +401,6 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
             }
             __syncthreads();
         }
-
-#endif
     } else {
         // ---- E: evaluate the listed patches, one per lane ---------------------------------------
         const int n = (int)*count;
@@ -517,7 +473,6 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
         }
 
     }
-    STAMP(7);
     // ---- F: result ------------------------------------------------------------------------------
     if (wave_ok && lane == 0) {
         const int idx = (int)(best[2 * wave] & 0x1FFF);
@@ -525,15 +480,13 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
         int32_t* o = d.mf + (((long long)pair * d.nbr + brow) * d.nbc + bcol) * 2;
         o[0] = ci - d.sw;
         o[1] = ri - d.sw;
-#ifndef SEA_NO_PROBE_PREV
         best[2 * wave + 1] = (uint32_t)idx;                   // next tile's third probe
-#endif
     }
     return false;
 }
 
-// What the shared persistent driver (bbme_sea_common.h: persistent_tiles) needs from this kernel.
-template <int R, bool E4>
+// What the shared tile drivers (bbme_sea_common.h: one_tile, persistent_tiles) need from this kernel.
+template <int R>
 struct MaeTile {
     struct Pre { uint32_t a01, a23; };
     static __device__ __forceinline__ Pre prep(const SeaDev&, uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
@@ -548,42 +501,16 @@ struct MaeTile {
     static __device__ __forceinline__ bool phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                   uint32_t mine, const Pre& p, int tid, int tile_id)
     {
-        return tile_phases<R, E4>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, tid, tile_id);
+        return tile_phases<R>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, tid, tile_id);
     }
+    static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.best + 2 * wave + 1; }
 };
 
-template <int R, bool E4>
+template <int R>
 __global__ void __launch_bounds__(1024) k_exh_sea16(SeaDev d)
 {
     extern __shared__ uint32_t lds[];
-    const Layout L = layout_of(d, R);
-    int pair, trow, bcol0;
-    if (!locate(d, &pair, &trow, &bcol0)) return;          // whole workgroup
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int NB = d.nb;
-    (void)NB;
-
-    STAMP(0);
-    // ---- A: window, anchor, quadrant sums ------------------------------------------------
-    stage_window(d, lds + L.win, d.cur + (long long)pair * d.plane_stride, bcol0, trow * d.tr * 16);
-    uint32_t mine = 0;
-    const WaveBlock wb = wave_block(d, trow, bcol0, wave);
-    if (wb.ok) {
-        const uint8_t* aptr = d.prev + (long long)pair * d.plane_stride + (long long)(wb.brow * 16) * d.pitch + wb.bcol * 16;
-        mine = *(const uint32_t*)(aptr + (long long)(lane >> 2) * d.pitch + (lane & 3) * 4);
-    }
-    const typename MaeTile<R, E4>::Pre pre = MaeTile<R, E4>::prep(d, lds, L, wave, lane, wb.ok, mine);
-    if (lane == 0) lds[L.best + 2 * wave + 1] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);      // no previous tile: the zero vector
-    if (threadIdx.x == 0) { lds[L.count] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; }
-    STAMP(1);
-    __syncthreads();
-    STAMP(2);
-    MaeTile<R, E4>::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, pair, trow, bcol0));
-    if (threadIdx.x == 0) {                                // the counts are final behind phase D's barrier
-        atomicAdd(d.status + GME_STATUS_STATS + 16 * (blockIdx.x & 7), lds[L.count] + lds[L.count + 5]);
-        atomicAdd(d.status + GME_STATUS_STATS + 16 * (blockIdx.x & 7) + 2, lds[L.count] + lds[L.count + 4]);
-    }
+    one_tile<MaeTile<R>>(d, lds, layout_of(d, R));
 }
 
 template <int R, int NV, int GEO = 0>
@@ -593,8 +520,41 @@ __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p(SeaDev d)
     fix_geometry<R, GEO>(d);
     const Layout L = layout_of(d, R);
     if ((threadIdx.x & 63) == 0) lds[L.best + 2 * (threadIdx.x >> 6) + 1] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);   // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MaeTile<R, (R >= 3)>>(d, lds, L);
+    persistent_tiles<NV, MaeTile<R>>(d, lds, L);
 }
+
+// What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.
+struct MaeLaunch {
+    static constexpr const char* persistent_name = "k_exh_sea16p";
+    static constexpr const char* one_tile_name = "k_exh_sea16";
+    static int no_plan()
+    {
+        gme_set_error("search window too large for LDS");
+        return GME_ERR_ARG;
+    }
+    static void tables(SeaDev& d, const BbmeJob&) { d.sqbox = nullptr; d.sqbox_stride = 0; }
+    // ordered evaluation inside crowded blocks (phase C2; bbme_sea_common.h: SeaDev::quota); GME_SEA_QUOTA=0 switches it off
+    static void ordered(SeaDev& d)
+    {
+        d.quota = getenv("GME_SEA_QUOTA") ? atoi(getenv("GME_SEA_QUOTA")) : SEA_DEFAULT_QUOTA;
+        d.bisect = getenv("GME_SEA_BISECT") ? atoi(getenv("GME_SEA_BISECT")) : SEA_DEFAULT_BISECT;
+        d.engage = getenv("GME_SEA_ENGAGE") ? atoi(getenv("GME_SEA_ENGAGE")) : SEA_DEFAULT_ENGAGE;
+        if (d.engage < d.quota) d.engage = d.quota;
+    }
+    // R = 2, 3 with more than 8 staging rows per thread would spill the prefetched tile (64 VGPRs at
+    // 8 waves/SIMD); those shapes keep the one-tile kernel
+    static bool fits(int R, int nv) { return R <= 1 || R >= 4 || nv <= 8; }
+    template <int R, int NV, int GEO = 0>
+    static void persistent(dim3 grid, dim3 block, size_t lds, hipStream_t s, const SeaDev& d)
+    {
+        hipLaunchKernelGGL((k_exh_sea16p<R, NV, GEO>), grid, block, lds, s, d);
+    }
+    template <int R>
+    static void one_tile(dim3 grid, dim3 block, size_t lds, hipStream_t s, const SeaDev& d)
+    {
+        hipLaunchKernelGGL((k_exh_sea16<R>), grid, block, lds, s, d);
+    }
+};
 
 }  // namespace
 
@@ -606,101 +566,9 @@ bool bbme_sea_applies(int bs, int sw, int procedure, int pnorm)
     return (NC + 15) / 16 <= 5 && NC * NC <= 8192 && !getenv("GME_FORCE_GENERIC") && !getenv("GME_EXH_BRUTE");
 }
 
-#ifdef GME_SEA_STAMPS
-static long long* g_stamps = nullptr;
-#endif
-
 int launch_bbme_sea(gme_ctx* ctx, const BbmeJob& job, bool* handled)
 {
     *handled = false;
     if (!bbme_sea_applies(job.bs, job.sw, job.procedure, job.pnorm)) return GME_OK;
-    const int NC = 2 * job.sw + 16, R = (NC + 15) / 16;
-    const int nbr = job.H / 16, nbc = job.W / 16;
-    if (nbr == 0 || nbc == 0) return GME_OK;
-    SeaDev d;
-    d.status = (uint32_t*)ctx->status; d.dynamic = 0;
-    d.prev = job.prev; d.cur = job.cur; d.plane_stride = job.plane_stride;
-    d.pairs = job.pairs; d.H = job.H; d.W = job.W; d.pitch = job.pitch; d.sw = job.sw;
-    d.nbr = nbr; d.nbc = nbc; d.mf = job.mf;
-#ifdef GME_SEA_STAMPS
-    d.stamps = g_stamps;
-#endif
-    size_t lds = 0;
-    GME_REQUIRE(plan(R, nbr, nbc, job.sw, &d, &lds), GME_ERR_ARG, "search window too large for LDS");
-    d.sqbox = nullptr; d.sqbox_stride = 0;
-    const dim3 block(64 * d.nb);
-    // hostile tiles (bound prunes little) -> brute-force redo kernel behind this one; GME_SEA_REDO=0 switches it off,
-    // GME_SEA_REDO_FRAC sets the share of a tile's patches from which phase E costs more than evaluating everything
-    d.redo_list = nullptr; d.redo_threshold = 0x7FFFFFFF;
-    // ordered evaluation inside crowded blocks (phase C2; bbme_sea_common.h: SeaDev::quota); GME_SEA_QUOTA=0 switches it off
-    d.quota = getenv("GME_SEA_QUOTA") ? atoi(getenv("GME_SEA_QUOTA")) : SEA_DEFAULT_QUOTA;
-    d.bisect = getenv("GME_SEA_BISECT") ? atoi(getenv("GME_SEA_BISECT")) : SEA_DEFAULT_BISECT;
-    d.engage = getenv("GME_SEA_ENGAGE") ? atoi(getenv("GME_SEA_ENGAGE")) : SEA_DEFAULT_ENGAGE;
-    if (d.engage < d.quota) d.engage = d.quota;
-    const bool redo = !(getenv("GME_SEA_REDO") && atoi(getenv("GME_SEA_REDO")) == 0);
-    if (redo) {
-        int rc = ctx_redo_list(ctx, (size_t)job.pairs * d.wg_per_pair, &d.redo_list);
-        if (rc) return rc;
-        const double frac = getenv("GME_SEA_REDO_FRAC") ? atof(getenv("GME_SEA_REDO_FRAC")) : REDO_DEFAULT_FRAC;
-        d.redo_threshold = (int)(frac * d.nb * 64 * R);
-        if (!job.status_fresh) GME_HIP_TRY(hipMemsetAsync(d.status + GME_STATUS_REDO, 0, 2 * sizeof(uint32_t), ctx->stream));
-    }
-    const PersistPlan pp = plan_persistent(d, lds, job.pairs, ctx->prop.multiProcessorCount);
-    const int nv = pp.nv;
-    // R = 2, 3 with more than 8 staging rows per thread would spill the prefetched tile (64 VGPRs at
-    // 8 waves/SIMD); those shapes keep the one-tile kernel
-    const bool fits = R <= 1 || R >= 4 || nv <= 8;
-    if (pp.use && fits) {
-        const dim3 grid((unsigned)(8 * pp.g));
-        if (pp.dynamic) {
-            d.dynamic = 1;
-            if (!job.status_fresh) GME_HIP_TRY(hipMemsetAsync(d.status + GME_STATUS_TILECTR, 0, 8 * 16 * sizeof(uint32_t), ctx->stream));
-        }
-        // the two BASELINE shapes (720x480 sw 16: 2x4 tiles; 1080p sw 32: 2x6 tiles) have instances with the tile
-        // geometry folded in at compile time; GME_SEA_GENERIC=1 keeps the run-time form (A/B, tests)
-        const bool fixed_ok = !getenv("GME_SEA_GENERIC");
-        const bool fix3 = fixed_ok && R == 3 && nv <= 5 && geometry_matches(d, 3, 2 * 16 + 4);
-        const bool fix5 = fixed_ok && R == 5 && nv <= 7 && geometry_matches(d, 5, 2 * 16 + 6);
-        plan_note(ctx, (long long)job.pairs * nbr * nbc * 64 * R, "k_exh_sea16p<%d,%d> tiles %dx%d persistent-%s%s grid %u lds %zu",
-                  R, fix3 ? 5 : fix5 ? 7 : nv <= 6 ? 6 : nv <= 8 ? 8 : nv <= 12 ? 12 : 16, d.tr, d.tc, pp.dynamic ? "dynamic" : "static", (fix3 || fix5) ? " geometry-fixed" : "", grid.x, lds);
-        if (fix3) {
-            hipLaunchKernelGGL((k_exh_sea16p<3, 5, 2 * 16 + 4>), grid, block, lds, ctx->stream, d);
-        } else if (fix5) {
-            hipLaunchKernelGGL((k_exh_sea16p<5, 7, 2 * 16 + 6>), grid, block, lds, ctx->stream, d);
-        } else
-#define SEA_LAUNCH_P(RR, NVV) hipLaunchKernelGGL((k_exh_sea16p<RR, NVV>), grid, block, lds, ctx->stream, d)
-#define SEA_LAUNCH_PN(RR) do { if (nv <= 6) SEA_LAUNCH_P(RR, 6); else if (nv <= 8) SEA_LAUNCH_P(RR, 8); \
-                               else if (nv <= 12) SEA_LAUNCH_P(RR, 12); else SEA_LAUNCH_P(RR, 16); } while (0)
-        switch (R) {
-        case 1: SEA_LAUNCH_PN(1); break;
-        case 2: SEA_LAUNCH_PN(2); break;
-        case 3: SEA_LAUNCH_PN(3); break;
-        case 4: SEA_LAUNCH_PN(4); break;
-        default: SEA_LAUNCH_PN(5); break;
-        }
-#undef SEA_LAUNCH_PN
-#undef SEA_LAUNCH_P
-    } else {
-    dim3 grid;
-    GME_REQUIRE(grid_for(d, &grid), GME_ERR_ARG, "too many workgroups in one launch");
-    plan_note(ctx, (long long)job.pairs * nbr * nbc * 64 * R, "k_exh_sea16<%d> tiles %dx%d one-tile grid %ux%ux%u lds %zu", R, d.tr, d.tc,
-              grid.x, grid.y, grid.z, lds);
-    // phase E with four lanes per patch (a quarter of the latency the other waves wait for): +11 % at
-    // sw 32, +3 % at sw 16 in the persistent kernel; GME_SEA_E4 = 0 / 1 overrides it for this one-tile kernel
-    const bool e4 = getenv("GME_SEA_E4") ? atoi(getenv("GME_SEA_E4")) != 0 : R >= 3;
-#define SEA_LAUNCH(RR) do { if (e4) hipLaunchKernelGGL((k_exh_sea16<RR, true>), grid, block, lds, ctx->stream, d); \
-                            else hipLaunchKernelGGL((k_exh_sea16<RR, false>), grid, block, lds, ctx->stream, d); } while (0)
-    switch (R) {
-    case 1: SEA_LAUNCH(1); break;
-    case 2: SEA_LAUNCH(2); break;
-    case 3: SEA_LAUNCH(3); break;
-    case 4: SEA_LAUNCH(4); break;
-    default: SEA_LAUNCH(5); break;
-    }
-#undef SEA_LAUNCH
-    }
-    GME_HIP_TRY(hipGetLastError());
-    *handled = true;
-    if (redo) return launch_exh_redo(ctx, job, R, d.tr, d.tc, d.wg_per_row, d.wg_per_pair, d.redo_list, d.status + GME_STATUS_REDO, d.status + GME_STATUS_REDO + 1);
-    return GME_OK;
+    return launch_sea<MaeLaunch>(ctx, job, handled);
 }

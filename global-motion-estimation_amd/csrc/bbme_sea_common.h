@@ -1,8 +1,7 @@
 // Shared pieces of the successive-elimination exhaustive kernels (bbme_sea.hip: MAE,
 // bbme_sea_mse.hip: MSE): launch descriptor, LDS layout, tile shapes, window staging, 8x8 box sums,
-// the persistent tile driver.
+// the one-tile and persistent tile drivers, the host launcher both norms share.
 #pragma once
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "gme_internal.h"
@@ -10,9 +9,7 @@
 namespace sea {
 
 // weight of window sharing in the tile-shape score (plan()); tuned by same-box sweeps
-#ifndef SEA_SHARE_WEIGHT
-#define SEA_SHARE_WEIGHT 0.5
-#endif
+constexpr double SHARE_WEIGHT = 0.5;
 
 struct SeaDev {
     const uint8_t* prev;
@@ -54,9 +51,6 @@ struct SeaDev {
     int xq;                       // S8 quads (4 columns each) per window row
     const uint32_t* sqbox;        // MSE only: 16x16 box sums of squares of `cur`, [pairs][H][pitch]
     long long sqbox_stride;
-#ifdef GME_SEA_STAMPS
-    long long* stamps;            // diagnostic build only (tools/microbench/sea_phases.hip): 8 per wave
-#endif
 };
 
 typedef uint64_t u64_a4 __attribute__((aligned(4)));
@@ -175,12 +169,12 @@ __device__ __forceinline__ void stage_window(const SeaDev& d, uint32_t* win, con
 // registers: S8(y) = S8(y-1) + r8(y+7) - r8(y-1).  s8[y][sq] = packed S8(y, 4sq .. 4sq+3).
 // CH = s8_rows / 8 is a template parameter so that the ring indices and the warm-up are resolved
 // at compile time (a run-time row count cost 5 % of the whole search in guards).
-template <int CH, int NCH = 8>
+template <int CH>
 __device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid)
 {
     typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
     const int XQ = d.xq;
-    for (int it = tid; it < NCH * XQ; it += blockDim.x) {
+    for (int it = tid; it < 8 * XQ; it += blockDim.x) {
         const int ch = div_small(it, d.magic_xq), sq = it - ch * XQ;
         int pi = (ch * CH) * d.pitch_dw + sq, oi = (ch * CH) * XQ + sq;     // running offsets: adds, no r * pitch multiplies
         u16x4 ring[8], sum = { 0, 0, 0, 0 };
@@ -204,20 +198,13 @@ __device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* wi
 }
 
 // s8_rows = 16R + 8 + 16 (tr - 1) is a multiple of 8 for every tile height: 8 chunks of 2R + 2 tr - 1 rows
-// (SEA_BOX_CHUNKS = 4: four chunks of twice the rows for two-row tiles -- 7 warm-up rows per chunk are 44 % of a 9-row
+// (four chunks of twice the rows for two-row tiles were measured too -- 7 warm-up rows per chunk are 44 % of a 9-row
 // chunk's work and 28 % of an 18-row one's, but half as many lanes share it; A/B in DESIGN.md)
-#ifndef SEA_BOX_CHUNKS
-#define SEA_BOX_CHUNKS 8
-#endif
 template <int R>
 __device__ __forceinline__ void box_sums8(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid)
 {
     if (d.tr == 1) box_sums8_ch<2 * R + 1>(d, win, s8, tid);
-    else if (d.tr == 2) {
-        constexpr int ROWS = 16 * R + 24;                  // s8_rows of a two-row tile
-        if (SEA_BOX_CHUNKS != 8 && ROWS % SEA_BOX_CHUNKS == 0) box_sums8_ch<ROWS / SEA_BOX_CHUNKS, SEA_BOX_CHUNKS>(d, win, s8, tid);
-        else box_sums8_ch<2 * R + 3>(d, win, s8, tid);
-    }
+    else if (d.tr == 2) box_sums8_ch<2 * R + 3>(d, win, s8, tid);
     else box_sums8_ch<2 * R + 7>(d, win, s8, tid);
 }
 
@@ -295,8 +282,7 @@ constexpr int pick_pitch(int need, int R)
 // shares more of the staged window and of the box-sum pass between its blocks (window bytes per
 // block: 1193 for 1 x 16, 864 for 2 x 8 at sw = 16), but LDS per workgroup grows.  The score is the
 // number of waves a CU keeps resident (160 KiB LDS, 32 waves), discounted by the idle waves of
-// ragged last tiles and by SIMD imbalance, with a bonus for the sharing.  GME_SEA_TILE = "TRxTC"
-// overrides it (A/B runs).  Returns false if nothing fits.
+// ragged last tiles and by SIMD imbalance, with a bonus for the sharing.  Returns false if nothing fits.
 // LDS geometry of a tile shape: depends on (R, tr, tc) only, so a kernel instantiated for one shape
 // (fix_geometry below) gets every stride, row count and division constant at compile time.
 struct Shape { int tr, tc, pitch, xq; size_t bytes; };
@@ -345,16 +331,12 @@ inline bool plan(int R, int nbr, int nbc, int sw, SeaDev* d, size_t* lds_bytes)
     auto shape = [&](int tr, int tc) { return shape_of(R, tr, tc); };
     Shape best = shape(1, 1);
     double best_score = -1.0;
-    int force_tr = 0, force_tc = 0;
-    if (const char* e = getenv("GME_SEA_TILE")) sscanf(e, "%dx%d", &force_tr, &force_tc);
-    if (const char* e = getenv("GME_SEA_NB")) { force_tr = 1; force_tc = atoi(e); }
     // resident waves per CU: 32 slots at <= 64 VGPRs (R <= 3); the R >= 4 kernels are held to 80 VGPRs -> 24
     const int wave_cap = R <= 3 ? 32 : 24;
     for (int pass = 0; pass < 2 && best_score < 0; ++pass)      // pass 0: SIMD-balanced wave counts only
         for (int tr = 1; tr <= 4; tr *= 2)
             for (int tc = 1; tc * tr <= 16; ++tc) {
-                if (force_tr > 0 && (tr != force_tr || tc != force_tc)) continue;
-                if (force_tr == 0 && (tc > nbc || (tr > 1 && tr > nbr) || (pass == 0 && (tr * tc) % 4 != 0))) continue;
+                if (tc > nbc || (tr > 1 && tr > nbr) || (pass == 0 && (tr * tc) % 4 != 0)) continue;
                 const Shape s = shape(tr, tc);
                 if (s.bytes > 160 * 1024 || s.pitch >= 256 || s.xq >= 256) continue;
                 const int nb = tr * tc;
@@ -371,7 +353,7 @@ inline bool plan(int R, int nbr, int nbc, int sw, SeaDev* d, size_t* lds_bytes)
                 // staged window bytes per block, relative to a block's own (16 + 2 sw + 15)^2 window
                 const double area = (double)(16 * tr + 2 * sw + 15) * (16 * tc + 2 * sw + 15) / nb;
                 const double own = (double)(2 * sw + 31) * (2 * sw + 31);
-                const double share = 1.0 + SEA_SHARE_WEIGHT * (1.0 - area / own);
+                const double share = 1.0 + SHARE_WEIGHT * (1.0 - area / own);
                 // a lone workgroup per CU has nobody to cover its barriers (measured 2-5 % at 1080p sw 32); four
                 // 8-wave workgroups interleave better than two 16-wave ones (2 x 4 vs 2 x 8 tiles: +4.5 % at sw 16)
                 const double together = wgs == 1 ? 0.93 : 1.0 + 0.03 * ((wgs > 4 ? 4 : wgs) - 2);
@@ -431,11 +413,46 @@ __device__ __forceinline__ int tile_number(const SeaDev& d, int pair, int trow, 
     return (pair >> 3) * d.wg_per_pair + trow * d.wg_per_row + div_small(bcol0, d.magic_tc);
 }
 
+// Kern (MaeTile in bbme_sea.hip, MseTile in bbme_sea_mse.hip) supplies what the two drivers below call per tile:
+//   Pre prep(d, lds, L, wave, lane, wave_ok, mine)          the wave's anchor dword -> LDS, per-wave anchor statistics
+//   bool phases(d, lds, L, pair, trow, bcol0, mine, pre, tid, tile_id)   phases A' .. F; true: the tile went to redo_list
+//   int probe_word(L, wave)                                 LDS word of the wave's third probe: the vector its block of the
+//                                                           previous tile ended with (one_tile seeds it with the zero
+//                                                           vector; the persistent kernels seed the same word themselves)
+// Count words (Layout::count) both drivers clear per tile and fold into the statistics (SeaDev::status, GME_STATUS_STATS):
+// [0] list length, [4] / [5] what phase C2 took off the list / scored, [7] MSE: length of the second list.
+
+// One-tile form of a search kernel: one workgroup per tile (grid_for, locate), the third probe seeded with the zero vector.
+template <class Kern>
+__device__ __forceinline__ void one_tile(const SeaDev& d, uint32_t* lds, const Layout L)
+{
+    int pair, trow, bcol0;
+    if (!locate(d, &pair, &trow, &bcol0)) return;          // whole workgroup
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    // ---- A: window, anchor
+    stage_window(d, lds + L.win, d.cur + (long long)pair * d.plane_stride, bcol0, trow * d.tr * 16);
+    uint32_t mine = 0;
+    const WaveBlock wb = wave_block(d, trow, bcol0, wave);
+    if (wb.ok) {
+        const uint8_t* aptr = d.prev + (long long)pair * d.plane_stride + (long long)(wb.brow * 16) * d.pitch + wb.bcol * 16;
+        mine = *(const uint32_t*)(aptr + (long long)(lane >> 2) * d.pitch + (lane & 3) * 4);
+    }
+    const typename Kern::Pre pre = Kern::prep(d, lds, L, wave, lane, wb.ok, mine);
+    if (lane == 0) lds[Kern::probe_word(L, wave)] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);      // no previous tile: the zero vector
+    if (threadIdx.x == 0) { lds[L.count] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0; }
+    __syncthreads();
+    Kern::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, pair, trow, bcol0));
+    if (threadIdx.x == 0) {                                // the counts are final behind phase D's barrier
+        atomicAdd(d.status + GME_STATUS_STATS + 16 * (blockIdx.x & 7), lds[L.count] + lds[L.count + 5]);
+        atomicAdd(d.status + GME_STATUS_STATS + 16 * (blockIdx.x & 7) + 2, lds[L.count] + lds[L.count + 4]);
+    }
+}
+
 // Persistent form of a search kernel: G workgroups (as many as fit on the chip at once) walk the
 // tiles of "their" XCD's pairs.  The window and anchor of the next tile are fetched into registers
 // while the current one is searched, so the HBM/L2 latency of phase A overlaps phases A' .. F
-// instead of idling the workgroup's waves.  Kern supplies prep() (anchor -> LDS, per-wave anchor
-// statistics) and phases() (A' .. F).
+// instead of idling the workgroup's waves.
 //
 // Schedule: static (tile += G/8) or, with d.dynamic, dynamic: after its first tile a workgroup
 // draws tile numbers G/8 + n from its XCD's counter.  Thread 0 asks one tile ahead, so the
@@ -528,9 +545,6 @@ __device__ __forceinline__ void persistent_tiles(const SeaDev& d, uint32_t* lds,
             fetch(tile);
             if (ctr && tid == 0) drawn = atomicInc(ctr, 0xFFFFFFFFu);
         }
-#ifdef SEA_NO_REDO
-        Kern::phases(d, lds, L, pair_c, trow_c, bcol0_c, mine, pre, tid, tile_c);
-#else
         // A hostile tile is handed to the redo kernel.  When the tile this workgroup processed just before was
         // hostile too (a scene cut, a noisy shot: not an isolated occlusion), thread 0's wave also draws the next
         // tile numbers of this XCD -- consecutive tiles of the same pairs -- and lists them unseen: 3 of them, then
@@ -552,15 +566,11 @@ __device__ __forceinline__ void persistent_tiles(const SeaDev& d, uint32_t* lds,
             }
             if (lane == 0) lds[L.count + 3] = (uint32_t)(streak + 1);
         }
-#endif
         if (!more) break;
         // No barrier here (round 4): every wave has passed phase D's barrier, and phase E's chunks end in one each, so
         // nobody still reads the window, the anchors, the box sums or the list when the next tile's staging overwrites them;
         // what is touched between here and the next tile's first barrier is per wave (best[], prev[]) or thread 0's
         // (the count words: a wave that has not read the list length yet can only be in a tile whose list is empty).
-#ifdef SEA_TILE_END_BARRIER
-        __syncthreads();
-#endif
     }
     // thread 0 has passed the barrier behind phase D: the last tile's counts are final
     if (threadIdx.x == 0) {
@@ -590,6 +600,89 @@ inline PersistPlan plan_persistent(const SeaDev& d, size_t lds_bytes, int pairs,
     p.dynamic = pm != 1;
     if (p.g > tiles_x) p.g = tiles_x;
     return p;
+}
+
+// The persistent instance <R, NV> for staging rows per thread nv <= NV (NV = 6, 8, 12, 16), or the one-tile instance <R>.
+template <class Norm, int R>
+inline void launch_class(bool persistent, int nv, dim3 grid, dim3 block, size_t lds, hipStream_t s, const SeaDev& d)
+{
+    if (!persistent) Norm::template one_tile<R>(grid, block, lds, s, d);
+    else if (nv <= 6) Norm::template persistent<R, 6>(grid, block, lds, s, d);
+    else if (nv <= 8) Norm::template persistent<R, 8>(grid, block, lds, s, d);
+    else if (nv <= 12) Norm::template persistent<R, 12>(grid, block, lds, s, d);
+    else Norm::template persistent<R, 16>(grid, block, lds, s, d);
+}
+
+// Host launcher of both norms, for a job the caller's gate accepted.  Norm (MaeLaunch in bbme_sea.hip, MseLaunch in
+// bbme_sea_mse.hip) supplies what differs between them:
+//   int no_plan()                        what a window plan() cannot fit returns (*handled stays false)
+//   void tables(SeaDev&, job)            the box-sum table of squares (MSE)
+//   void ordered(SeaDev&)                phase C2's quota / bisect / engage (SeaDev::quota)
+//   bool fits(R, nv)                     whether the persistent form holds the prefetched tile in registers
+//   persistent<R, NV[, GEO]>, one_tile<R>(grid, block, lds, stream, d)      kernel launches
+//   persistent_name, one_tile_name       the kernels' names in plan_note
+template <class Norm>
+int launch_sea(gme_ctx* ctx, const BbmeJob& job, bool* handled)
+{
+    *handled = false;
+    const int NC = 2 * job.sw + 16, R = (NC + 15) / 16;
+    const int nbr = job.H / 16, nbc = job.W / 16;
+    if (nbr == 0 || nbc == 0) return GME_OK;
+    SeaDev d;
+    d.status = (uint32_t*)ctx->status; d.dynamic = 0;
+    d.prev = job.prev; d.cur = job.cur; d.plane_stride = job.plane_stride;
+    d.pairs = job.pairs; d.H = job.H; d.W = job.W; d.pitch = job.pitch; d.sw = job.sw;
+    d.nbr = nbr; d.nbc = nbc; d.mf = job.mf;
+    Norm::tables(d, job);
+    size_t lds = 0;
+    if (!plan(R, nbr, nbc, job.sw, &d, &lds)) return Norm::no_plan();
+    const dim3 block(64 * d.nb);
+    // hostile tiles (bound prunes little) -> brute-force redo kernel behind this one; GME_SEA_REDO=0 switches it off,
+    // GME_SEA_REDO_FRAC sets the share of a tile's patches from which phase E costs more than evaluating everything
+    d.redo_list = nullptr; d.redo_threshold = 0x7FFFFFFF;
+    Norm::ordered(d);
+    const bool redo = !(getenv("GME_SEA_REDO") && atoi(getenv("GME_SEA_REDO")) == 0);
+    if (redo) {
+        int rc = ctx_redo_list(ctx, (size_t)job.pairs * d.wg_per_pair, &d.redo_list);
+        if (rc) return rc;
+        const double frac = getenv("GME_SEA_REDO_FRAC") ? atof(getenv("GME_SEA_REDO_FRAC")) : REDO_DEFAULT_FRAC;
+        d.redo_threshold = (int)(frac * d.nb * 64 * R);
+        if (!job.status_fresh) GME_HIP_TRY(hipMemsetAsync(d.status + GME_STATUS_REDO, 0, 2 * sizeof(uint32_t), ctx->stream));
+    }
+    const PersistPlan pp = plan_persistent(d, lds, job.pairs, ctx->prop.multiProcessorCount);
+    const int nv = pp.nv;
+    const long long patches = (long long)job.pairs * nbr * nbc * 64 * R;
+    const bool persistent = pp.use && Norm::fits(R, nv);
+    dim3 grid;
+    bool fix3 = false, fix5 = false;
+    if (persistent) {
+        grid = dim3((unsigned)(8 * pp.g));
+        if (pp.dynamic) {
+            d.dynamic = 1;
+            if (!job.status_fresh) GME_HIP_TRY(hipMemsetAsync(d.status + GME_STATUS_TILECTR, 0, 8 * 16 * sizeof(uint32_t), ctx->stream));
+        }
+        // the two BASELINE shapes (720x480 sw 16: 2x4 tiles; 1080p sw 32: 2x6 tiles) have instances with the tile
+        // geometry folded in at compile time
+        fix3 = R == 3 && nv <= 5 && geometry_matches(d, 3, 2 * 16 + 4);
+        fix5 = R == 5 && nv <= 7 && geometry_matches(d, 5, 2 * 16 + 6);
+        plan_note(ctx, patches, "%s<%d,%d> tiles %dx%d persistent-%s%s grid %u lds %zu", Norm::persistent_name,
+                  R, fix3 ? 5 : fix5 ? 7 : nv <= 6 ? 6 : nv <= 8 ? 8 : nv <= 12 ? 12 : 16, d.tr, d.tc, pp.dynamic ? "dynamic" : "static", (fix3 || fix5) ? " geometry-fixed" : "", grid.x, lds);
+    } else {
+        GME_REQUIRE(grid_for(d, &grid), GME_ERR_ARG, "too many workgroups in one launch");
+        plan_note(ctx, patches, "%s<%d> tiles %dx%d one-tile grid %ux%ux%u lds %zu", Norm::one_tile_name, R, d.tr, d.tc,
+                  grid.x, grid.y, grid.z, lds);
+    }
+    if (fix3) Norm::template persistent<3, 5, 2 * 16 + 4>(grid, block, lds, ctx->stream, d);
+    else if (fix5) Norm::template persistent<5, 7, 2 * 16 + 6>(grid, block, lds, ctx->stream, d);
+    else if (R == 1) launch_class<Norm, 1>(persistent, nv, grid, block, lds, ctx->stream, d);
+    else if (R == 2) launch_class<Norm, 2>(persistent, nv, grid, block, lds, ctx->stream, d);
+    else if (R == 3) launch_class<Norm, 3>(persistent, nv, grid, block, lds, ctx->stream, d);
+    else if (R == 4) launch_class<Norm, 4>(persistent, nv, grid, block, lds, ctx->stream, d);
+    else launch_class<Norm, 5>(persistent, nv, grid, block, lds, ctx->stream, d);
+    GME_HIP_TRY(hipGetLastError());
+    *handled = true;
+    if (redo) return launch_exh_redo(ctx, job, R, d.tr, d.tc, d.wg_per_row, d.wg_per_pair, d.redo_list, d.status + GME_STATUS_REDO, d.status + GME_STATUS_REDO + 1);
+    return GME_OK;
 }
 
 }  // namespace sea

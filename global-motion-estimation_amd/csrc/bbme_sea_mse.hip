@@ -9,7 +9,7 @@
 // UB of a good match, a few hundred, that let bounds up to 1.5 x the exact limit through.)  List entries keep 19 bits,
 // floor(LBx / 2^11), for the re-check against a tightened UB (UB >> 5).
 //
-// Same phases as k_exh_sea16 (bbme_sea.hip); what differs:
+// Same phases and the same two forms (one tile per workgroup / persistent) as k_exh_sea16 (bbme_sea.hip); what differs:
 //   B  dS_q by v_pk_sub_i16 on the packed quadrant sums, squares summed by v_dot2_i32_i16;
 //   C  UB from two cooperative SSDs (sum a^2 + sum b^2 - 2 sum ab with v_dot4_u32_u8 per lane);
 //   E  a listed patch costs 16*R*16 v_dot4_u32_u8 (three v_alignbyte copies per window dword) for
@@ -78,10 +78,8 @@ __device__ __forceinline__ void lower_bounds_mse(const uint64_t* sp0, int XQ, in
     }
 }
 
-#ifndef SEA_MSE_TWO_LEVEL_FROM
-#define SEA_MSE_TWO_LEVEL_FROM 4      // window classes R >= this use the two-level bound (R = 5, sw 32: +6 %; R = 3, sw 16: +-0, real frames -3 %)
-#endif
-// Level 1 of the two-level bound (R >= SEA_MSE_TWO_LEVEL_FROM): the MAE kernel's quadrant bound L1 = sum_q |dS_q| (5.7 instructions per
+constexpr int TWO_LEVEL_FROM = 4;     // window classes R >= this use the two-level bound (R = 5, sw 32: +6 %; R = 3, sw 16: +-0, real frames -3 %)
+// Level 1 of the two-level bound (R >= TWO_LEVEL_FROM): the MAE kernel's quadrant bound L1 = sum_q |dS_q| (5.7 instructions per
 // candidate against 8 for the squared form).  SSD >= SAD^2 / 256 >= L1^2 / 256 (Cauchy-Schwarz over the 256 pixels, then the
 // triangle inequality per quadrant), so a patch whose smallest L1 has L1^2 > 256 UB holds no winner; the squared form --
 // never weaker -- is applied as level 2 to the patches that pass, one lane per patch (bounds2_patch).
@@ -144,11 +142,11 @@ __device__ __forceinline__ uint32_t bounds2_patch(const uint64_t* sp, int XQ, in
 }
 
 // Phases A' .. F of one tile (entry conditions as tile_phases() of bbme_sea.hip, plus a2s[] filled).
-template <int R, int LPPT>
+template <int R>
 __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                 uint32_t mine, uint32_t a01, uint32_t a23, uint32_t mine2, int tid, int tile_id)
 {
-    constexpr bool TWO = R >= SEA_MSE_TWO_LEVEL_FROM;     // two-level bound: L1 form for every candidate, squared form for the listed patches
+    constexpr bool TWO = R >= TWO_LEVEL_FROM;     // two-level bound: L1 form for every candidate, squared form for the listed patches
     const int T = blockDim.x;
     const int NC = 2 * d.sw + 16, XQ = d.xq;
     uint32_t* win = lds + L.win;
@@ -294,14 +292,11 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
         }
     }
 
-    // ---- E: LPP lanes per listed patch; lane `sub` takes anchor rows AR*sub .. AR*sub+AR-1 (R+AR-1 window
-    // rows), the partial dot products are added inside the quad with DPP moves.  Four lanes per patch
-    // repeat some v_alignbyte work but put four times as many waves on the (long) evaluation.
-    constexpr int LPP = LPPT, AR = 16 / LPP;
+    // ---- E: one lane per listed patch (R + 15 window rows).  Four lanes per patch, four anchor rows each, would put four
+    // times as many waves on the (long) evaluation but repeat the v_alignbyte work: measured 9 % slower.
     const SqTable tab = sq_table(d.sqbox + (long long)pair * d.sqbox_stride, d.H, d.pitch);
-    for (int base = 0; base < n; base += T / LPP) {
-        const int e = base + tid / LPP;
-        const int sub = lane & (LPP - 1);
+    for (int base = 0; base < n; base += T) {
+        const int e = base + tid;
         bool active = e < n;
         uint32_t ent = 0;
         if (active) {
@@ -317,23 +312,23 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
 #pragma unroll
             for (int e4 = 0; e4 < 4; ++e4) acc[i][e4] = 0;
         if (active) {
-            const uint32_t* lrow = win + (16 * wr2 + prow2 * R + AR * sub) * d.pitch_dw + wc2 * 4 + q2 * R + k2;
-            const uint32_t* an = anchor + w2 * ANCHOR_STRIDE + AR * 4 * sub;
+            const uint32_t* lrow = win + (16 * wr2 + prow2 * R) * d.pitch_dw + wc2 * 4 + q2 * R + k2;
+            const uint32_t* an = anchor + w2 * ANCHOR_STRIDE;
             // anchor rows t - i meet window row t: each row is read ONCE, when it enters (i = 0), and stays in `keep` for the
             // R - 1 window rows that follow (round 4: the per-(t, i) reads were not merged by the compiler -- 48 b128 LDS
             // reads per patch, now 16)
             u32x4 keep[R];
 #pragma unroll
-            for (int t = 0; t < R + AR - 1; ++t) {
+            for (int t = 0; t < R + 15; ++t) {
                 uint32_t w[5];
 #pragma unroll
                 for (int s = 0; s < 5; ++s) w[s] = lrow[t * d.pitch_dw + s];
-                if (t <= AR - 1) keep[t % R] = *(const u32x4*)(an + t * 4);
+                if (t <= 15) keep[t % R] = *(const u32x4*)(an + t * 4);
                 u32x4 ar[R];                               // anchor rows t - i that meet this window row
 #pragma unroll
                 for (int i = 0; i < R; ++i) {
                     const int a = t - i;
-                    if (a >= 0 && a <= AR - 1) ar[i] = keep[a % R];
+                    if (a >= 0 && a <= 15) ar[i] = keep[a % R];
                 }
                 // one window dword at a time: its four byte alignments (bytes 4j+e4 .. 4j+e4+3) live in four
                 // registers and feed the R x 4 accumulators, then the next dword reuses them
@@ -346,7 +341,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
 #pragma unroll
                     for (int i = 0; i < R; ++i) {
                         const int a = t - i;
-                        if (a < 0 || a > AR - 1) continue;
+                        if (a < 0 || a > 15) continue;
 #pragma unroll
                         for (int e4 = 0; e4 < 4; ++e4) acc[i][e4] = __builtin_amdgcn_udot4(sh[e4], ar[i][j], acc[i][e4], false);
                     }
@@ -362,16 +357,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
                     for (int e4 = 0; e4 < 4; ++e4) asm volatile("" : "+v"(acc[i][e4]));
             }
         }
-        if (LPP > 1) {                                     // lane groups are uniform in `active` (one entry per group)
-#pragma unroll
-            for (int i = 0; i < R; ++i)
-#pragma unroll
-                for (int e4 = 0; e4 < 4; ++e4) {
-                    acc[i][e4] += SEA_DPP(acc[i][e4], 0xB1);                     // quad_perm [1,0,3,2]
-                    if (LPP > 2) acc[i][e4] += SEA_DPP(acc[i][e4], 0x4E);        // quad_perm [2,3,0,1]
-                }
-        }
-        if (active && sub == 0) {
+        if (active) {
             const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
             const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, d.W - 16 - c02 + d.sw);
             const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, d.H - 16 - r02 + d.sw);
@@ -422,7 +408,8 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
     return false;
 }
 
-template <int R, int LPPT>
+// What the shared tile drivers (bbme_sea_common.h: one_tile, persistent_tiles) need from this kernel.
+template <int R>
 struct MseTile {
     struct Pre { uint32_t a01, a23, mine2; };
     static __device__ __forceinline__ Pre prep(const SeaDev&, uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
@@ -443,41 +430,18 @@ struct MseTile {
     static __device__ __forceinline__ bool phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                   uint32_t mine, const Pre& p, int tid, int tile_id)
     {
-        return tile_phases_mse<R, LPPT>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id);
+        return tile_phases_mse<R>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id);
     }
+    static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.prev + wave; }
 };
 
-template <int R, int LPPT>
+template <int R>
 __global__ void __launch_bounds__(1024) k_exh_sea16_mse(SeaDev d)
 {
     extern __shared__ uint32_t lds[];
-    const Layout L = layout_of(d, R);
-    int pair, trow, bcol0;
-    if (!locate(d, &pair, &trow, &bcol0)) return;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    // ---- A
-    stage_window(d, lds + L.win, d.cur + (long long)pair * d.plane_stride, bcol0, trow * d.tr * 16);
-    uint32_t mine = 0;
-    const WaveBlock wb = wave_block(d, trow, bcol0, wave);
-    if (wb.ok) {
-        const uint8_t* aptr = d.prev + (long long)pair * d.plane_stride + (long long)(wb.brow * 16) * d.pitch + wb.bcol * 16;
-        mine = *(const uint32_t*)(aptr + (long long)(lane >> 2) * d.pitch + (lane & 3) * 4);
-    }
-    const typename MseTile<R, LPPT>::Pre pre = MseTile<R, LPPT>::prep(d, lds, L, wave, lane, wb.ok, mine);
-    if (lane == 0) lds[L.prev + wave] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);       // no previous tile: the zero vector
-    if (threadIdx.x == 0) { lds[L.count] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0; }
-    __syncthreads();
-    MseTile<R, LPPT>::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, pair, trow, bcol0));
-    if (threadIdx.x == 0) {                                // list length is final behind phase D
-        atomicAdd(d.status + GME_STATUS_STATS + 16 * (blockIdx.x & 7), lds[L.count]);
-        atomicAdd(d.status + GME_STATUS_STATS + 16 * (blockIdx.x & 7) + 2, lds[L.count]);
-    }
+    one_tile<MseTile<R>>(d, lds, layout_of(d, R));
 }
 
-#ifndef SEA_MSE_LPP
-#define SEA_MSE_LPP 1
-#endif
 template <int R, int NV, int GEO = 0>
 __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p_mse(SeaDev d)
 {
@@ -485,8 +449,34 @@ __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p_mse(SeaDe
     fix_geometry<R, GEO>(d);
     const Layout L = layout_of(d, R);
     if ((threadIdx.x & 63) == 0) lds[L.prev + (threadIdx.x >> 6)] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);    // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MseTile<R, SEA_MSE_LPP>>(d, lds, L);
+    persistent_tiles<NV, MseTile<R>>(d, lds, L);
 }
+
+// What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.
+struct MseLaunch {
+    static constexpr const char* persistent_name = "k_exh_sea16p_mse";
+    static constexpr const char* one_tile_name = "k_exh_sea16_mse";
+    static int no_plan() { return GME_OK; }                 // does not fit: the dot4 kernel takes it
+    static void tables(SeaDev& d, const BbmeJob& job) { d.sqbox = job.sqbox_cur; d.sqbox_stride = job.sqbox_stride; }
+    // No ordered evaluation (phase C2 of bbme_sea.hip) here: measured -6 % on every content (round 4, DESIGN.md): with one
+    // lane per patch a 720x480 tile's list is a single pass either way, and under MSE the quadrant bound is too weak for the
+    // tightened upper bound to prune much (pan240 x2: 30 -> 25 % of the patches).
+    static void ordered(SeaDev& d) { d.quota = 0; d.bisect = 0; d.engage = 0; }
+    // The persistent form must hold the prefetched tile in registers next to phase E's 4R accumulators
+    // inside the 64 VGPRs of 8 waves/SIMD: only R = 3 with 16 staging rows per thread does not fit
+    // (the compiler would spill the prefetch itself) and keeps the one-tile kernel.
+    static bool fits(int R, int nv) { return R != 3 || nv <= 12; }
+    template <int R, int NV, int GEO = 0>
+    static void persistent(dim3 grid, dim3 block, size_t lds, hipStream_t s, const SeaDev& d)
+    {
+        hipLaunchKernelGGL((k_exh_sea16p_mse<R, NV, GEO>), grid, block, lds, s, d);
+    }
+    template <int R>
+    static void one_tile(dim3 grid, dim3 block, size_t lds, hipStream_t s, const SeaDev& d)
+    {
+        hipLaunchKernelGGL((k_exh_sea16_mse<R>), grid, block, lds, s, d);
+    }
+};
 
 }  // namespace
 
@@ -498,90 +488,5 @@ int launch_bbme_sea_mse(gme_ctx* ctx, const BbmeJob& job, bool* handled)
     if (getenv("GME_FORCE_GENERIC") || getenv("GME_EXH_BRUTE")) return GME_OK;
     const int NC = 2 * job.sw + 16, R = (NC + 15) / 16;
     if (R < 1 || R > 5 || NC * NC > 8192) return GME_OK;
-    const int nbr = job.H / 16, nbc = job.W / 16;
-    if (nbr == 0 || nbc == 0) return GME_OK;
-    SeaDev d;
-    d.status = (uint32_t*)ctx->status; d.dynamic = 0;
-    d.prev = job.prev; d.cur = job.cur; d.plane_stride = job.plane_stride;
-    d.pairs = job.pairs; d.H = job.H; d.W = job.W; d.pitch = job.pitch; d.sw = job.sw;
-    d.nbr = nbr; d.nbc = nbc; d.mf = job.mf;
-    d.sqbox = job.sqbox_cur; d.sqbox_stride = job.sqbox_stride;
-#ifdef GME_SEA_STAMPS
-    d.stamps = nullptr;
-#endif
-    size_t lds = 0;
-    if (!plan(R, nbr, nbc, job.sw, &d, &lds)) return GME_OK;        // does not fit: the dot4 kernel takes it
-    const dim3 block(64 * d.nb);
-    // hostile tiles (bound prunes little) -> brute-force redo kernel behind this one; GME_SEA_REDO=0 switches it off,
-    // GME_SEA_REDO_FRAC sets the share of a tile's patches from which phase E costs more than evaluating everything
-    d.redo_list = nullptr; d.redo_threshold = 0x7FFFFFFF;
-    // No ordered evaluation (phase C2 of bbme_sea.hip) here: measured -6 % on every content (round 4, DESIGN.md): with one
-    // lane per patch a 720x480 tile's list is a single pass either way, and under MSE the quadrant bound is too weak for the
-    // tightened upper bound to prune much (pan240 x2: 30 -> 25 % of the patches).
-    d.quota = 0; d.bisect = 0; d.engage = 0;
-    const bool redo = !(getenv("GME_SEA_REDO") && atoi(getenv("GME_SEA_REDO")) == 0);
-    if (redo) {
-        int rc = ctx_redo_list(ctx, (size_t)job.pairs * d.wg_per_pair, &d.redo_list);
-        if (rc) return rc;
-        const double frac = getenv("GME_SEA_REDO_FRAC") ? atof(getenv("GME_SEA_REDO_FRAC")) : REDO_DEFAULT_FRAC;
-        d.redo_threshold = (int)(frac * d.nb * 64 * R);
-        if (!job.status_fresh) GME_HIP_TRY(hipMemsetAsync(d.status + GME_STATUS_REDO, 0, 2 * sizeof(uint32_t), ctx->stream));
-    }
-    const PersistPlan pp = plan_persistent(d, lds, job.pairs, ctx->prop.multiProcessorCount);
-    const int nv = pp.nv;
-    // The persistent form must hold the prefetched tile in registers next to phase E's 4R accumulators
-    // inside the 64 VGPRs of 8 waves/SIMD: only R = 3 with 16 staging rows per thread does not fit
-    // (the compiler would spill the prefetch itself) and keeps the one-tile kernel.
-    const bool fits = R != 3 || nv <= 12;
-    if (pp.use && fits) {
-        const dim3 grid((unsigned)(8 * pp.g));
-        if (pp.dynamic) {
-            d.dynamic = 1;
-            if (!job.status_fresh) GME_HIP_TRY(hipMemsetAsync(d.status + GME_STATUS_TILECTR, 0, 8 * 16 * sizeof(uint32_t), ctx->stream));
-        }
-        // the two BASELINE shapes (720x480 sw 16: 2x4 tiles; 1080p sw 32: 2x6 tiles) have instances with the tile
-        // geometry folded in at compile time; GME_SEA_GENERIC=1 keeps the run-time form (A/B, tests)
-        const bool fixed_ok = !getenv("GME_SEA_GENERIC");
-        const bool fix3 = fixed_ok && R == 3 && nv <= 5 && geometry_matches(d, 3, 2 * 16 + 4);
-        const bool fix5 = fixed_ok && R == 5 && nv <= 7 && geometry_matches(d, 5, 2 * 16 + 6);
-        plan_note(ctx, (long long)job.pairs * nbr * nbc * 64 * R, "k_exh_sea16p_mse<%d,%d> tiles %dx%d persistent-%s%s grid %u lds %zu",
-                  R, fix3 ? 5 : fix5 ? 7 : nv <= 6 ? 6 : nv <= 8 ? 8 : nv <= 12 ? 12 : 16, d.tr, d.tc, pp.dynamic ? "dynamic" : "static", (fix3 || fix5) ? " geometry-fixed" : "", grid.x, lds);
-        if (fix3) {
-            hipLaunchKernelGGL((k_exh_sea16p_mse<3, 5, 2 * 16 + 4>), grid, block, lds, ctx->stream, d);
-        } else if (fix5) {
-            hipLaunchKernelGGL((k_exh_sea16p_mse<5, 7, 2 * 16 + 6>), grid, block, lds, ctx->stream, d);
-        } else
-#define SEA_LAUNCH_P(RR, NVV) hipLaunchKernelGGL((k_exh_sea16p_mse<RR, NVV>), grid, block, lds, ctx->stream, d)
-#define SEA_LAUNCH_PN(RR) do { if (nv <= 6) SEA_LAUNCH_P(RR, 6); else if (nv <= 8) SEA_LAUNCH_P(RR, 8); \
-                               else if (nv <= 12) SEA_LAUNCH_P(RR, 12); else SEA_LAUNCH_P(RR, 16); } while (0)
-        switch (R) {
-        case 1: SEA_LAUNCH_PN(1); break;
-        case 2: SEA_LAUNCH_PN(2); break;
-        case 3: SEA_LAUNCH_PN(3); break;
-        case 4: SEA_LAUNCH_PN(4); break;
-        default: SEA_LAUNCH_PN(5); break;
-        }
-#undef SEA_LAUNCH_PN
-#undef SEA_LAUNCH_P
-    } else {
-        dim3 grid;
-        GME_REQUIRE(grid_for(d, &grid), GME_ERR_ARG, "too many workgroups in one launch");
-    plan_note(ctx, (long long)job.pairs * nbr * nbc * 64 * R, "k_exh_sea16_mse<%d> tiles %dx%d one-tile grid %ux%ux%u lds %zu", R, d.tr, d.tc,
-              grid.x, grid.y, grid.z, lds);
-        const bool e4 = getenv("GME_SEA_E4") ? atoi(getenv("GME_SEA_E4")) != 0 : false;   // measured: four lanes per patch lose 9 % here (repeated v_alignbyte work)
-#define SEA_LAUNCH(RR) do { if (e4) hipLaunchKernelGGL((k_exh_sea16_mse<RR, 4>), grid, block, lds, ctx->stream, d); \
-                            else hipLaunchKernelGGL((k_exh_sea16_mse<RR, 1>), grid, block, lds, ctx->stream, d); } while (0)
-        switch (R) {
-        case 1: SEA_LAUNCH(1); break;
-        case 2: SEA_LAUNCH(2); break;
-        case 3: SEA_LAUNCH(3); break;
-        case 4: SEA_LAUNCH(4); break;
-        default: SEA_LAUNCH(5); break;
-        }
-#undef SEA_LAUNCH
-    }
-    GME_HIP_TRY(hipGetLastError());
-    *handled = true;
-    if (redo) return launch_exh_redo(ctx, job, R, d.tr, d.tc, d.wg_per_row, d.wg_per_pair, d.redo_list, d.status + GME_STATUS_REDO, d.status + GME_STATUS_REDO + 1);
-    return GME_OK;
+    return launch_sea<MseLaunch>(ctx, job, handled);
 }

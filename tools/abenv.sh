@@ -1,6 +1,6 @@
 # usage: bash tools/abenv.sh "<variants>" "<bench configs>" [rounds] [extra bench args]
 # Same-box A/B of runtime switches of one build.  A variant is '-' (no switch) or comma-separated
-# assignments, e.g. bash tools/abenv.sh "- GME_SEA_PERSIST=2 GME_SEA_PERSIST=2,GME_SEA_NB=8" "exh720"
+# assignments, e.g. bash tools/abenv.sh "- GME_SEA_PERSIST=2 GME_SEA_PERSIST=2,GME_SEA_QUOTA=0" "exh720"
 # A config may carry a content after a colon: "exh720:pan240x2" = --config exh720 --content pan240x2.
 set -e
 cd ${GRAFT_REPO_ROOT:-/root/repo}
