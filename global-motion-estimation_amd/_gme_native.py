@@ -75,6 +75,10 @@ _SIGNATURES = {
     "gme_seq_gme_begin_fit": (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, _c_f32p, _c_f64p]),
     "gme_seq_gme_read_stage": (_i, [_vp, _i, _i, _c_i32p, _c_i16p, _c_u8p, _c_i64p]),
     "gme_seq_compensate": (_i, [_vp, _i, _i, _c_f64p, _c_i64p]),
+    "gme_model2_field": (_i, [_vp, _c_f64p, _i, _i, _c_i16p]),
+    "gme_seq_gme_begin_fit2": (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, _c_f32p, _c_f64p]),
+    "gme_seq_gme_fit2": (_i, [_vp, _i, _c_f64p, ctypes.c_double, _c_f64p]),
+    "gme_seq_compensate2": (_i, [_vp, _i, _i, _c_f64p, _c_i64p]),
     "gme_solve_fit_sums": (_i, [_vp, _c_f64p, _i, _i, _i, _i, _c_f64p, _c_i32p]),
     "gme_seq_gme_device_solve": (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, _c_f64p, _c_i64p, _c_i32p]),
     "gme_seq_read_compensated": (_i, [_vp, _i, _c_u8p]),
@@ -279,6 +283,13 @@ class Context:
         p = np.ascontiguousarray(np.asarray(params).astype(np.float64).reshape(6))
         out = np.zeros((h, w, 2), dtype=np.int16)
         _check(self.lib.gme_affine_field(self.handle, _p(p, _c_f64p), h, w, _p(out, _c_i16p)), self.lib)
+        return out
+
+    def model2_field(self, params, h, w):
+        """The second-order field of params float64[12] (roadmap.py) -> int16[h, w, 2]."""
+        p = np.ascontiguousarray(np.asarray(params).astype(np.float64).reshape(12))
+        out = np.zeros((h, w, 2), dtype=np.int16)
+        _check(self.lib.gme_model2_field(self.handle, _p(p, _c_f64p), h, w, _p(out, _c_i16p)), self.lib)
         return out
 
     def compensate(self, frame, mf):
@@ -504,6 +515,39 @@ class Sequence:
         _check(self.lib.gme_seq_gme_fit(self.handle, level, _p(p, _c_f64p), float(outlier_fraction), _p(sums, _c_f64p)),
                self.lib)
         return sums
+
+    # ---- second-order models (roadmap.py): params float64[P, 12], sums float64[P, 27]
+    def gme_begin_fit2(self, frame_distance, bbme_block_size, outlier_fraction, procedure=3, search_window=2):
+        """gme_begin_fit with the order-2 sums -> (first parameters float32[P, 6], level-1 sums float64[P, 27])."""
+        pairs = self.N - frame_distance
+        bbme_block_size = _block_size(bbme_block_size)
+        p0 = self._buffer("p0", (max(pairs, 0), 6), np.float32)
+        sums = self._buffer("sums2_1", (max(pairs, 0), 27), np.float64)
+        _check(self.lib.gme_seq_gme_begin_fit2(self.handle, frame_distance, bbme_block_size, procedure, search_window,
+                                               float(outlier_fraction), _p(p0, _c_f32p), _p(sums, _c_f64p)), self.lib)
+        self._gme = (frame_distance, bbme_block_size, pairs)
+        return p0, sums
+
+    def gme_fit2(self, level, params_in, outlier_fraction):
+        """gme_fit for params float64[P, 12] -> sums float64[P, 27] = moments (15) | Sx (6) | Sy (6)."""
+        pairs = self._gme[2] if level >= 0 else self._mv_shape[0]
+        p = self._buffer("fit2_in%d" % level, (pairs, 12), np.float64)
+        p[...] = np.asarray(params_in, dtype=np.float64).reshape(pairs, 12)
+        sums = self._buffer("sums2_%d" % level, (pairs, 27), np.float64)
+        _check(self.lib.gme_seq_gme_fit2(self.handle, level, _p(p, _c_f64p), float(outlier_fraction), _p(sums, _c_f64p)),
+               self.lib)
+        return sums
+
+    def compensate2(self, frame_distance, block_size, params):
+        """compensate() with the order-2 field of params float64[P, 12] -> sse int64[P]."""
+        pairs = self.N - frame_distance
+        block_size = _block_size(block_size)
+        p = self._buffer("comp2_in", (pairs, 12), np.float64)
+        p[...] = np.asarray(params, dtype=np.float64).reshape(pairs, 12)
+        sse = self._buffer("sse", (pairs,), np.int64)
+        _check(self.lib.gme_seq_compensate2(self.handle, frame_distance, block_size, _p(p, _c_f64p), _p(sse, _c_i64p)),
+               self.lib)
+        return sse
 
     def stage_shape(self, level):
         if level < 0:

@@ -466,6 +466,7 @@ static void free_fit(FitLevelBuf& f)
     if (f.list) hipFree(f.list);
     if (f.thr) hipFree(f.thr);
     if (f.sums) hipFree(f.sums);
+    if (f.sums2) hipFree(f.sums2);
     f = FitLevelBuf();
 }
 
@@ -487,6 +488,7 @@ extern "C" void gme_seq_destroy(gme_seq* s)
     if (s->solve_flags) hipFree(s->solve_flags);
     if (s->sse) hipFree(s->sse);
     if (s->comp_params) hipFree(s->comp_params);
+    if (s->comp_mf) hipFree(s->comp_mf);
     if (s->synth_canvas) hipFree(s->synth_canvas);
     if (s->summary) hipFree(s->summary);
     if (s->gathered) hipFree(s->gathered);
@@ -971,6 +973,7 @@ static int alloc_fit(FitLevelBuf& f, int pairs, int h, int w, bool full)
         if ((size_t)h * w * 16 > 40 * 1024) ok = ok && hipMalloc(&f.list, n * 16) == hipSuccess;
         ok = ok && hipMalloc((void**)&f.thr, (size_t)pairs * sizeof(int32_t)) == hipSuccess;
         ok = ok && hipMalloc((void**)&f.sums, (size_t)pairs * 15 * sizeof(double)) == hipSuccess;
+        ok = ok && hipMalloc((void**)&f.sums2, (size_t)pairs * 27 * sizeof(double)) == hipSuccess;
     }
     if (!ok) { gme_set_error("out of device memory (GME level buffers)"); return GME_ERR_NOMEM; }
     return GME_OK;
@@ -1060,7 +1063,7 @@ static int gme_begin_common(gme_seq* s, int fd, int bbme_bs, int procedure, int 
         s->params0 = nullptr; s->params_in = nullptr; s->solve_flags = nullptr;
         if (hipMalloc((void**)&s->params0, (size_t)cap_pairs * 6 * sizeof(float)) != hipSuccess ||
             hipMalloc((void**)&s->solve_flags, (size_t)(cap_pairs > 0 ? cap_pairs : 1) * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc((void**)&s->params_in, (size_t)cap_pairs * 6 * sizeof(double)) != hipSuccess) {
+            hipMalloc((void**)&s->params_in, (size_t)cap_pairs * 12 * sizeof(double)) != hipSuccess) {      // 12: gme_seq_gme_fit2
             gme_set_error("out of device memory (parameters)");
             return GME_ERR_NOMEM;
         }
@@ -1133,6 +1136,7 @@ static int ensure_fit_mv(gme_seq* s)
     if (f.list) hipFree(f.list);
     if (f.thr) hipFree(f.thr);
     if (f.sums) hipFree(f.sums);
+    if (f.sums2) hipFree(f.sums2);
     f = FitLevelBuf();
     f.h = s->mv_h; f.w = s->mv_w;
     const size_t n = (size_t)s->mv_pairs * f.h * f.w;
@@ -1140,7 +1144,8 @@ static int ensure_fit_mv(gme_seq* s)
         hipMalloc((void**)&f.diff, n * sizeof(int32_t)) != hipSuccess ||
         ((size_t)f.h * f.w * 16 > 40 * 1024 && hipMalloc(&f.list, n * 16) != hipSuccess) ||
         hipMalloc((void**)&f.thr, (size_t)s->mv_pairs * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&f.sums, (size_t)s->mv_pairs * 15 * sizeof(double)) != hipSuccess) {
+        hipMalloc((void**)&f.sums, (size_t)s->mv_pairs * 15 * sizeof(double)) != hipSuccess ||
+        hipMalloc((void**)&f.sums2, (size_t)s->mv_pairs * 27 * sizeof(double)) != hipSuccess) {
         gme_set_error("out of device memory (fit buffers)");
         return GME_ERR_NOMEM;
     }
@@ -1260,7 +1265,7 @@ static int ensure_comp(gme_seq* s, int fd, int pairs)
         if (s->comp_params) hipFree(s->comp_params);
         s->sse = nullptr; s->comp_params = nullptr;
         if (hipMalloc((void**)&s->sse, (size_t)cap_pairs * sizeof(unsigned long long)) != hipSuccess ||
-            hipMalloc((void**)&s->comp_params, (size_t)cap_pairs * 6 * sizeof(double)) != hipSuccess) {
+            hipMalloc((void**)&s->comp_params, (size_t)cap_pairs * 12 * sizeof(double)) != hipSuccess) {     // 12: gme_seq_compensate2
             gme_set_error("out of device memory");
             return GME_ERR_NOMEM;
         }
@@ -1395,4 +1400,141 @@ extern "C" int gme_seq_read_compensated(gme_seq* s, int pair, uint8_t* out)
     GME_REQUIRE(s->comp.ptr && pair >= 0 && pair < s->comp.count, GME_ERR_STATE, "gme_seq_read_compensated: no such pair");
     GME_HIP_TRY(hipMemcpy2DAsync(out, s->W, s->comp.at(pair), s->comp.pitch, s->W, s->H, hipMemcpyDeviceToHost, s->ctx->stream));
     return ctx_finish(s->ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Second-order motion models (roadmap.py: bilinear, pseudo-perspective, quadratic; kernels in gme_models.hip).  The calls
+// below are the order-1 calls above with params [P][12] = [a0 a1 a2 b0 b1 b2 | a3 a4 a5 b3 b4 b5] and sums [P][27]; same
+// staging, split-phase behaviour and state errors.  The stage buffers (model field, mask, threshold, compensated frames)
+// are shared with the order-1 calls, so gme_seq_gme_read_stage / gme_seq_read_compensated[_range] read whichever ran last.
+// ---------------------------------------------------------------------------
+extern "C" int gme_model2_field(gme_ctx* ctx, const double params[12], int h, int w, int16_t* mf_out)
+{
+    GME_ENTER(ctx);
+    int rc = GME_OK;
+    GME_REQUIRE(params && mf_out && h >= 0 && w >= 0, GME_ERR_ARG, "gme_model2_field: bad arguments");
+    if (h == 0 || w == 0) return GME_OK;
+    Carver c;
+    const size_t o_p = c.take(12 * sizeof(double)), o_f = c.take((size_t)h * w * 2 * sizeof(int16_t));
+    void* base = nullptr;
+    rc = ctx_scratch(ctx, c.off, &base);
+    if (rc) return rc;
+    uint8_t* b = (uint8_t*)base;
+    GME_HIP_TRY(hipMemcpyAsync(b + o_p, params, 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_model2_field(ctx, (const double*)(b + o_p), 1, h, w, (int16_t*)(b + o_f), nullptr);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(mf_out, b + o_f, (size_t)h * w * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
+// order-2 model field, mask and sums of level -1 (fit_mv), 1 or 2 from parameters already on the device (pstride doubles per
+// pair); result copy + event / wait.  The context is locked.
+static int fit2_level_launch(gme_seq* s, int level, const double* dparams, int pstride, double outlier_fraction, double* sums_out)
+{
+    gme_ctx* ctx = s->ctx;
+    const bool mv = level < 0;
+    const FitLevelBuf* f = mv ? &s->fit_mv : &s->fit[level];
+    const int pairs = mv ? s->mv_pairs : s->gme_pairs, n = f->h * f->w;
+    GME_REQUIRE(n > 0, GME_ERR_GEOMETRY, "level %d holds no block (motion.py:243 would index an empty list)", level);
+    // int(0.3 * len), motion.py:242; a negative fraction selects the unmasked fit (motion.py:33-88)
+    const int drop = outlier_fraction < 0 ? -1 : (int)(outlier_fraction * (double)n);
+    GME_REQUIRE(drop <= n, GME_ERR_ARG, "outlier fraction %g out of range", outlier_fraction);
+    const int level_H = mv ? s->H : s->level[level].H, level_W = mv ? s->W : s->level[level].W;
+    int rc = launch_fit_level2(ctx, f->gt, pairs, f->h, f->w, dparams, pstride, drop, level_H, level_W, f->model, f->mask, f->diff,
+                               f->thr, f->sums2, f->list);
+    if (rc) return rc;
+    rc = copy_small(ctx, sums_out, f->sums2, (size_t)pairs * 27 * sizeof(double), hipMemcpyDeviceToHost, s->split_phase);
+    if (rc) return rc;
+    if (s->split_phase) GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream));
+    else rc = ctx_finish(ctx);
+    return rc;
+}
+
+// gme_seq_gme_begin_fit with the order-2 sums at level 1: the level-1 field is that of the projected first parameters (a
+// translation), so mask and threshold are those of gme_seq_gme_begin_fit.
+extern "C" int gme_seq_gme_begin_fit2(gme_seq* s, int fd, int bbme_bs, int procedure, int sw, double outlier_fraction,
+                                      float* params0_out, double* sums1_out)
+{
+    GME_REQUIRE(s != nullptr && sums1_out != nullptr, GME_ERR_ARG, "gme_seq_gme_begin_fit2: null pointer");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = gme_begin_common(s, fd, bbme_bs, procedure, sw);
+    if (rc) return rc;
+    rc = launch_project_first(ctx, s->params0, s->gme_pairs, s->params_in);
+    if (rc) return rc;
+    if (params0_out)
+        { rc = copy_small(ctx, params0_out, s->params0, (size_t)s->gme_pairs * 6 * sizeof(float), hipMemcpyDeviceToHost, s->split_phase); if (rc) return rc; }
+    rc = gme_level_bbme(s, 1);
+    if (rc) return rc;
+    rc = fit2_level_launch(s, 1, s->params_in, 6, outlier_fraction, sums1_out);
+    if (rc) return rc;
+    return gme_level_bbme(s, 2);                           // searched while the caller solves level 1
+}
+
+extern "C" int gme_seq_gme_fit2(gme_seq* s, int level, const double* params_in, double outlier_fraction, double* sums_out)
+{
+    GME_REQUIRE(s != nullptr && params_in != nullptr && sums_out != nullptr, GME_ERR_ARG, "gme_seq_gme_fit2: null pointer");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = GME_OK;
+    GME_REQUIRE(level == 1 || level == 2 || level == -1, GME_ERR_ARG, "gme_seq_gme_fit2: level %d (1, 2 or -1)", level);
+    int pairs;
+    double* dparams;
+    if (level == -1) {
+        GME_REQUIRE(s->mv != nullptr && s->mv_pairs > 0, GME_ERR_STATE, "gme_seq_gme_fit2(level -1) before gme_seq_bbme");
+        rc = ensure_fit_mv(s);
+        if (rc) return rc;
+        pairs = s->mv_pairs;
+        size_t have = s->mv_params_bytes;
+        rc = ensure(&s->mv_params, &have, (size_t)pairs * 12 * sizeof(double));
+        s->mv_params_bytes = have;
+        if (rc) return rc;
+        dparams = s->mv_params;
+    } else {
+        GME_REQUIRE(s->gme_pairs > 0 && s->params_in, GME_ERR_STATE, "gme_seq_gme_fit2 before gme_seq_gme_begin");
+        rc = gme_flush_bbme(s, level);
+        if (rc) return rc;
+        pairs = s->gme_pairs;
+        dparams = s->params_in;
+    }
+    rc = copy_small(ctx, dparams, params_in, (size_t)pairs * 12 * sizeof(double), hipMemcpyHostToDevice, s->split_phase);
+    if (rc) return rc;
+    rc = fit2_level_launch(s, level, dparams, 12, outlier_fraction, sums_out);
+    if (rc) return rc;
+    if (level == 1) return gme_level_bbme(s, 2);           // searched while the caller solves level 1
+    return GME_OK;
+}
+
+// gme_seq_compensate with the order-2 field: k_model2_field writes the int32 field of every pair, the mf32 path of
+// k_compensate16 / k_compensate gathers from it and sums the squared error (results.py:52-59,109).
+extern "C" int gme_seq_compensate2(gme_seq* s, int fd, int bs, const double* params, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr && params != nullptr, GME_ERR_ARG, "gme_seq_compensate2: null pointer");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = GME_OK;
+    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "frame_distance %d needs at least %d frames", fd, fd + 1);
+    const int pairs = s->N - fd;
+    GME_REQUIRE(bs >= 1, GME_ERR_ARG, "block_size %d", bs);
+    const int h = s->H / bs, w = s->W / bs;
+    GME_REQUIRE(h > 0 && w > 0, GME_ERR_GEOMETRY, "block_size %d does not fit a %d x %d frame", bs, s->H, s->W);
+    rc = ensure_comp(s, fd, pairs);
+    if (rc) return rc;
+    rc = ensure(&s->comp_mf, &s->comp_mf_bytes, (size_t)pairs * h * w * 2 * sizeof(int32_t));
+    if (rc) return rc;
+    rc = copy_small(ctx, s->comp_params, params, (size_t)pairs * 12 * sizeof(double), hipMemcpyHostToDevice, s->split_phase);
+    if (rc) return rc;
+    rc = launch_model2_field(ctx, s->comp_params, pairs, h, w, nullptr, s->comp_mf);
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    rc = launch_compensate(ctx, p.at(0), p.stride, pairs, s->H, s->W, p.pitch, s->comp_mf, nullptr, h, w, s->comp.ptr,
+                           s->comp.stride, s->comp.pitch, p.at(fd), p.stride, s->sse);
+    if (rc) return rc;
+    if (sse_out) {
+        rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase);
+        if (rc) return rc;
+        if (s->split_phase) { GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream)); return GME_OK; }
+        return ctx_finish(ctx);
+    }
+    return GME_OK;
 }

@@ -83,6 +83,7 @@ struct FitLevelBuf {
     void* list = nullptr;         // [P][h][w] int4 inlier list, only for fields too large for LDS
     int32_t* thr = nullptr;       // [P]
     double* sums = nullptr;       // [P][15]
+    double* sums2 = nullptr;      // [P][27] order-2 sums (gme_seq_gme_fit2, gme_models.hip)
 };
 
 struct gme_seq {
@@ -109,15 +110,17 @@ struct gme_seq {
     FitLevelBuf fit[3];           // fit[0].gt = dense field
     FitLevelBuf fit_mv;           // stage buffers for fitting `mv` directly (gt not owned)
     int fit_mv_pairs = 0;
-    double* mv_params = nullptr;  // [P][6] parameters for fit_mv
+    double* mv_params = nullptr;  // [P][6] parameters for fit_mv ([P][12] after gme_seq_gme_fit2)
     size_t mv_params_bytes = 0;
     float* params0 = nullptr;     // [P][6]
-    double* params_in = nullptr;  // [P][6]
+    double* params_in = nullptr;  // [P][6], or [P][12] for gme_seq_gme_fit2 (room for 12 per pair)
     int32_t* solve_flags = nullptr;      // [P] gme_seq_gme_device_solve: pairs whose device solve must be redone on the host
     size_t gme_alloc_pairs = 0;
     // compensation
     Plane comp;                   // [P] compensated frames
-    double* comp_params = nullptr;       // [P][6]
+    double* comp_params = nullptr;       // [P][6], or [P][12] for gme_seq_compensate2 (room for 12 per pair)
+    int32_t* comp_mf = nullptr;          // [P][h][w][2] order-2 field gme_seq_compensate2 compensates with
+    size_t comp_mf_bytes = 0;
     unsigned long long* sse = nullptr;   // [P]
     // per-pair summary rows of `mv` (gme_seq_mv_summary) and their all-gather over the ranks (gme_seq_mv_summary_gather)
     double* summary = nullptr;           // [n_max][6], zero-padded behind mv_pairs rows
@@ -233,6 +236,14 @@ int launch_compensate(gme_ctx* ctx, const uint8_t* frames, int64_t frame_stride,
                       int64_t cur_stride, unsigned long long* sse);
 int launch_sse(gme_ctx* ctx, const uint8_t* a, int64_t a_stride, int a_pitch, const uint8_t* b,
                int64_t b_stride, int b_pitch, int pairs, int H, int W, unsigned long long* sse);
+
+// ---- gme_models.hip: second-order motion models (roadmap.py) ------------------
+// params [P][12]; exactly one of out16 / out32 is non-null
+int launch_model2_field(gme_ctx* ctx, const double* params, int pairs, int h, int w, int16_t* out16, int32_t* out32);
+// k_fit_level with the order-2 field and sums27 [P][27]; params hold pstride (6 or 12) doubles per pair
+int launch_fit_level2(gme_ctx* ctx, const int32_t* gt, int pairs, int h, int w, const double* params, int pstride, int drop,
+                      int level_H, int level_W, int16_t* model, uint8_t* mask, int32_t* diff, int32_t* thr, double* sums27,
+                      void* list);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -5,12 +5,17 @@ parameters and the usages of the various scripts").  EXTENSION: the reference ha
 argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as they are.
 
     python gme_cli.py bbme    -p <video|frame dir> -fi 13 -bs 16 -sw 16 -sp 0     # bbme.py main
-    python gme_cli.py results -v <name under resources/videos> -f 1 [--model similarity] [--suggest]   # results.py main
+    python gme_cli.py results -v <name under resources/videos> -f 1 [--model quadratic] [--suggest]    # results.py main
     python gme_cli.py suggest -p <video|frame dir> [-fi 1] [-f 1]                 # parameter heuristics
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
 import sys
+
+
+def _models():
+    import roadmap
+    return roadmap.MODELS
 
 
 def _parser():
@@ -29,7 +34,7 @@ def _parser():
     r.add_argument("-f", "--frame-distance", dest="fd", type=str, required=False)
     r.add_argument("--block-size", type=int, default=None, help="motion.BBME_BLOCK_SIZE for this run (the authors patched the constant by hand)")
     r.add_argument("--outlier-fraction", type=float, default=None, help="motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE for this run")
-    r.add_argument("--model", choices=("affine", "translation", "similarity"), default="affine",
+    r.add_argument("--model", choices=_models(), default="affine",
                    help="motion model fitted per level (roadmap.solve_model); affine is the reference")
     r.add_argument("--suggest", action="store_true",
                    help="pick block size and outlier fraction for this video with roadmap.suggest_parameters (middle pair); "

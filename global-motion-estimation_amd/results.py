@@ -44,10 +44,13 @@ def process_frames(frames, frame_distance=FRAME_DISTANCE, save_path=None, progre
     # the video stays in host memory and streams through a few lanes: one lane's upload runs beside the other lanes'
     # kernels, one host thread drives all of them (split-phase calls) and does their 3x3 solves in between; every device
     # object is released before this returns
-    solve = None
+    solve, stream_model, field = None, None, motion.get_motion_field_affine
     if model != "affine":
         import roadmap
-        solve = lambda sums: roadmap.solve_model(sums, model)       # noqa: E731
+        if model in roadmap.SECOND_ORDER:       # order-2 stages, params[P, 12] (sequence.StreamEstimator.run)
+            stream_model, field = model, roadmap.model_field
+        else:
+            solve = lambda sums: roadmap.solve_model(sums, model)       # noqa: E731
     field_shape = (int(shape[0] / bs), int(shape[1] / bs), 2)
     written = {}
 
@@ -59,7 +62,7 @@ def process_frames(frames, frame_distance=FRAME_DISTANCE, save_path=None, progre
         for k in range(p1 - p0):
             p, idx = p0 + k, p0 + k + fd
             previous, current, compensated = frames[p], frames[idx], comp[k]
-            model_motion_field = motion.get_motion_field_affine(field_shape, parameters=params[k])
+            model_motion_field = field(field_shape, params[k])
             write_image(os.path.join(save_path, "frames", "") + str(idx - 5) + ".png", previous)
             write_image(os.path.join(save_path, "compensated", "") + str(idx - 5) + ".png", compensated)
             diff_curr_prev = np.absolute(current.astype("int") - previous.astype("int")).astype("uint8")
@@ -76,7 +79,7 @@ def process_frames(frames, frame_distance=FRAME_DISTANCE, save_path=None, progre
     # kernels, one host thread drives all of them (split-phase calls) and does their 3x3 solves in between; every device
     # object is released before this returns
     params, psnr = estimate_stream(frames, fd, chunk_pairs=CHUNK_PAIRS, streams=STREAMS, solve=solve,
-                                   on_chunk=write_chunk if save_path is not None else None)
+                                   on_chunk=write_chunk if save_path is not None else None, model=stream_model)
     for idx in range(fd, len(frames)):
         p = idx - fd
         if progress:

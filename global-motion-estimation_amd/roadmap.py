@@ -21,6 +21,24 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    coordinate mismatch: the fit sees ``x = 4 i, y = 4 j`` (motion.py:254-255) while the model field is
    evaluated at the raw block indices (motion.py:139-157), so the linear terms of ANY model act with a
    quarter of their fitted strength downstream, exactly as in the reference's affine path.
+
+   **Second-order models.**  The paper the reference follows has second-order terms (motion.py:191-207 quotes its
+   projection rule); the 15 sums above cannot determine them, so these models have their own device fit
+   (``k_fit_level2``, gme_models.hip) leaving 27 sums: the 15 weighted moments ``sum w x^p y^q`` (p + q <= 4, in the
+   order ``1 x y x2 xy y2 x3 x2y xy2 y3 x4 x3y x2y2 xy3 y4``), then ``Sx = sum w phi dx`` and ``Sy = sum w phi dy`` over the
+   basis ``phi = [1, x, y, x^2, xy, y^2]``.  Parameters are float64[12] = ``[a0 a1 a2 b0 b1 b2 | a3 a4 a5 b3 b4 b5]``,
+   ``dx = a0 + a1 x + a2 y + a3 x^2 + a4 xy + a5 y^2``, ``dy`` likewise -- the first six are the affine layout:
+
+   * ``bilinear``            only ``xy`` among the second-order terms (two 4x4 systems)
+   * ``pseudo_perspective``  ``dx = a0 + a1 x + a2 y + c1 y^2 + c2 xy``, ``dy = b0 + b1 x + b2 y + c1 xy + c2 x^2`` in the
+     reference's axes, i.e. ``a4 = b3 = c2``, ``a5 = b4 = c1``, ``a3 = b5 = 0`` (one coupled 8x8 system)
+   * ``quadratic``           all twelve (two 6x6 systems)
+
+   The same coordinate quirk holds: downstream, linear terms act at 1/4 of their fitted strength and second-order terms
+   at 1/16 (``model_field`` evaluates at the raw block indices ``(i, j)``).  Projection between the levels doubles the
+   constants, keeps the linear terms and halves the second-order ones (``project``: x, y double per level).  The normal
+   matrices are Jacobi-equilibrated before the solve (raw condition number ~6e9 at 720p, ~3e11 at 1080p for the 6x6
+   quadratic system; ~6e2 scaled).  The projective model proper is nonlinear and not offered.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.
@@ -30,12 +48,104 @@ import numpy as np
 
 import motion
 
-MODELS = ("affine", "translation", "similarity")
+MODELS = ("affine", "translation", "similarity", "bilinear", "pseudo_perspective", "quadratic")
+SECOND_ORDER = ("bilinear", "pseudo_perspective", "quadratic")
+
+# moment index of x^p y^q in the 27 sums (M order: 1 x y x2 xy y2 x3 x2y xy2 y3 x4 x3y x2y2 xy3 y4)
+_MOMENT = {(0, 0): 0, (1, 0): 1, (0, 1): 2, (2, 0): 3, (1, 1): 4, (0, 2): 5, (3, 0): 6, (2, 1): 7, (1, 2): 8, (0, 3): 9,
+           (4, 0): 10, (3, 1): 11, (2, 2): 12, (1, 3): 13, (0, 4): 14}
+_PHI = ((0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2))          # exponents of phi = [1, x, y, x^2, xy, y^2]
+
+
+def affine_sums(sums27):
+    """float64[P, 27] order-2 sums -> the exact float64[P, 15] affine sums F (3x3) | Sx[0:3] | Sy[0:3] (the same values the
+    order-1 fit leaves: every term of both is one rounding of (integer) * w)."""
+    s = np.asarray(sums27, dtype=np.float64).reshape(-1, 27)
+    M = s[:, :15]
+    F = M[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]]
+    return np.concatenate([F, s[:, 15:18], s[:, 21:24]], axis=1)
+
+
+def project(params):
+    """motion.parameter_projection (motion.py:191-207) generalised to float64[..., 6 or 12]: constants doubled, linear
+    terms kept, second-order terms halved (x, y double per level).  Exact in float64.  Returns a new array."""
+    p = np.array(params, dtype=np.float64)
+    p[..., 0] = p[..., 0] * 2
+    p[..., 3] = p[..., 3] * 2
+    if p.shape[-1] == 12:
+        p[..., 6:12] = p[..., 6:12] * 0.5
+    return p
+
+
+def _jacobi_solve(N, rhs):
+    """Solve the stacked symmetric systems N x = rhs after Jacobi scaling (D N D) z = D rhs, x = D z.  Every step is an
+    elementwise operation or np.linalg.solve's per-matrix LAPACK call, so a stacked batch equals per-pair solves bit for bit."""
+    d = np.diagonal(N, axis1=1, axis2=2)
+    if np.any(~(d > 0)):
+        raise np.linalg.LinAlgError("Singular matrix")
+    D = 1.0 / np.sqrt(d)
+    A = N * D[:, :, None] * D[:, None, :]
+    z = np.linalg.solve(A, (rhs * D)[:, :, None])[:, :, 0]        # LinAlgError on a singular system
+    return z * D
+
+
+def _solve_second_order(sums, model):
+    s = np.asarray(sums, dtype=np.float64)
+    if s.ndim == 1:
+        s = s[None, :]
+    if s.shape[-1] != 27:
+        raise ValueError("model %r needs the 27 order-2 sums (gme_fit2), got %d per pair" % (model, s.shape[-1]))
+    P = len(s)
+    M, sx, sy = s[:, :15], s[:, 15:21], s[:, 21:27]
+    out = np.zeros((P, 12))
+    if P == 0:
+        return out
+    if model in ("quadratic", "bilinear"):
+        basis = (0, 1, 2, 3, 4, 5) if model == "quadratic" else (0, 1, 2, 4)
+        idx = [[_MOMENT[(_PHI[a][0] + _PHI[b][0], _PHI[a][1] + _PHI[b][1])] for b in basis] for a in basis]
+        N = M[:, np.array(idx)]
+        # both displacements share N: one stacked solve of 2P systems
+        th = _jacobi_solve(np.concatenate([N, N]), np.concatenate([sx[:, basis], sy[:, basis]]))
+        tx, ty = th[:P], th[P:]
+        slots = [0, 1, 2, 6, 7, 8]                                    # phi_k -> parameter slot of dx (dy: + 3)
+        for c, k in enumerate(basis):
+            out[:, slots[k]] = tx[:, c]
+            out[:, slots[k] + 3] = ty[:, c]
+        return out
+    if model == "pseudo_perspective":
+        # unknowns (a0 a1 a2 b0 b1 b2 c1 c2); rows r_x = [1 x y 0 0 0 y^2 xy] for dx, r_y = [0 0 0 1 x y xy x^2] for dy
+        rx = [(0, 0), (1, 0), (0, 1), None, None, None, (0, 2), (1, 1)]
+        ry = [None, None, None, (0, 0), (1, 0), (0, 1), (1, 1), (2, 0)]
+        N = np.zeros((P, 8, 8))
+        for a in range(8):
+            for b in range(8):
+                acc = None
+                for r in (rx, ry):
+                    if r[a] is not None and r[b] is not None:
+                        v = M[:, _MOMENT[(r[a][0] + r[b][0], r[a][1] + r[b][1])]]
+                        acc = v if acc is None else acc + v
+                if acc is not None:
+                    N[:, a, b] = acc
+        rhs = np.stack([sx[:, 0], sx[:, 1], sx[:, 2], sy[:, 0], sy[:, 1], sy[:, 2], sx[:, 5] + sy[:, 4], sx[:, 4] + sy[:, 3]], axis=1)
+        th = _jacobi_solve(N, rhs)
+        out[:, 0:6] = th[:, 0:6]
+        c1, c2 = th[:, 6], th[:, 7]
+        out[:, 7], out[:, 9] = c2, c2                                 # a4 = b3 = c2
+        out[:, 8], out[:, 10] = c1, c1                                # a5 = b4 = c1
+        return out
+    raise ValueError("unknown motion model %r (choose from %r)" % (model, MODELS))
 
 
 def solve_model(sums, model="affine"):
-    """float64[P, 15] normal-equation sums (F | Sx | Sy) -> float64[P, 6] parameters in affine layout."""
-    sums = np.asarray(sums, dtype=np.float64).reshape(-1, 15)
+    """Normal-equation sums -> parameters.  First-order models: float64[P, 15] (F | Sx | Sy; or the 27 order-2 sums,
+    reduced by affine_sums) -> float64[P, 6] in affine layout.  Second-order models (SECOND_ORDER): float64[P, 27] ->
+    float64[P, 12]; 15-wide sums raise ValueError."""
+    if model in SECOND_ORDER:
+        return _solve_second_order(sums, model)
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim >= 1 and sums.shape[-1] == 27:
+        sums = affine_sums(sums)
+    sums = sums.reshape(-1, 15)
     if model == "affine":
         return motion._solve_batch(sums)
     F = sums[:, :9].reshape(-1, 3, 3)
@@ -66,11 +176,28 @@ def solve_model(sums, model="affine"):
     raise ValueError("unknown motion model %r (choose from %r)" % (model, MODELS))
 
 
+def model_field(shape, params):
+    """motion.get_motion_field_affine (motion.py:139-157) for any model: float64[6] -> the affine field, float64[12] -> the
+    second-order field ``((p0 + p2 j) + p1 i) + ((a3 (i i) + a4 (i j)) + a5 (j j))`` -> int16[shape[0], shape[1], 2]."""
+    p = np.asarray(params, dtype=np.float64).reshape(-1)
+    if p.size == 6:
+        return motion.get_motion_field_affine(shape, p)
+    if p.size != 12:
+        raise ValueError("parameters of %d entries (6 or 12)" % p.size)
+    import _gme_native
+    return _gme_native.default_context().model2_field(p, int(shape[0]), int(shape[1]))
+
+
 def estimate_sequence(seq, frame_distance=1, model="affine", procedure=3, search_window=2):
-    """motion.estimate_sequence with a selectable motion model -> float64[P, 6] (affine layout)."""
+    """motion.estimate_sequence with a selectable motion model -> float64[P, 6] (affine layout), or float64[P, 12] for the
+    second-order models (order-2 device fits, gme_seq_gme_begin_fit2 / gme_seq_gme_fit2)."""
     if getattr(seq, "_split", False):
         raise RuntimeError("estimate_sequence needs blocking calls: the sequence is in split-phase mode")
     frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
+    if model in SECOND_ORDER:
+        _, sums = seq.gme_begin_fit2(frame_distance, int(motion.BBME_BLOCK_SIZE), frac, procedure, search_window)
+        params = project(solve_model(sums, model))
+        return solve_model(seq.gme_fit2(2, params, frac), model)
     _, sums = seq.gme_begin_fit(frame_distance, int(motion.BBME_BLOCK_SIZE), frac, procedure, search_window)
     params = solve_model(sums, model)
     params[:, 0] = params[:, 0] * 2

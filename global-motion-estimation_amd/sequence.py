@@ -646,13 +646,25 @@ class StreamEstimator:
             p0 += c
         return out
 
-    def run(self, frames, compensated=None, exact_psnr=True, solve=None, on_chunk=None):
+    def run(self, frames, compensated=None, exact_psnr=True, solve=None, on_chunk=None, model=None):
         """``on_chunk(p0, p1, comp, params, psnr)`` is called as each chunk finishes (chunks of different lanes may finish out
         of order) with its compensated frames uint8[p1 - p0, H, W] (one read for the chunk; the array is reused by the next
-        chunk of the same lane), parameters and PSNR: what results.py writes per pair, without a whole-video array on the host."""
+        chunk of the same lane), parameters and PSNR: what results.py writes per pair, without a whole-video array on the host.
+
+        ``model``: one of roadmap.MODELS (None: the reference's affine path, as without the argument).  The second-order
+        models (roadmap.SECOND_ORDER) run the order-2 stages (gme_begin_fit2 / gme_fit2 / compensate2) and return
+        params float64[P, 12]."""
         fd, H, W, cap = self.fd, self.H, self.W, self.cap
         P = max(0, len(frames) - fd)
-        params_out, sse_out = np.zeros((P, 6)), np.zeros(P, dtype=np.int64)
+        order2 = False
+        if model is not None:
+            import roadmap
+            if model not in roadmap.MODELS:
+                raise ValueError("unknown motion model %r (choose from %r)" % (model, roadmap.MODELS))
+            order2 = model in roadmap.SECOND_ORDER
+            if solve is None:
+                solve = lambda sums: roadmap.solve_model(sums, model)       # noqa: E731
+        params_out, sse_out = np.zeros((P, 12 if order2 else 6)), np.zeros(P, dtype=np.int64)
         if P == 0:
             return params_out, np.zeros(0)
         if tuple(np.asarray(frames[0]).shape) != (H, W):
@@ -687,19 +699,23 @@ class StreamEstimator:
             n = p1 - p0
             seq.wait()
             if lane.stage == 1:                  # the chunk is on the device: dense field, first parameters, level-1 fit
-                lane.pending = seq.gme_begin_fit(fd, bs, frac, self.procedure, self.search_window)[1]
+                begin = seq.gme_begin_fit2 if order2 else seq.gme_begin_fit
+                lane.pending = begin(fd, bs, frac, self.procedure, self.search_window)[1]
                 lane.stage = 2
                 return False
             if lane.stage == 2:                  # level-1 sums are back: solve, project (float64), ask for level 2
                 p = solve(lane.pending[:n])
-                p[:, 0] = p[:, 0] * 2
-                p[:, 3] = p[:, 3] * 2
-                lane.pending = seq.gme_fit(2, p, frac)
+                if order2:
+                    lane.pending = seq.gme_fit2(2, roadmap.project(p), frac)
+                else:
+                    p[:, 0] = p[:, 0] * 2
+                    p[:, 3] = p[:, 3] * 2
+                    lane.pending = seq.gme_fit(2, p, frac)
                 lane.stage = 3
                 return False
             if lane.stage == 3:
                 lane.params = solve(lane.pending[:n])
-                lane.pending = seq.compensate(fd, bs, lane.params)
+                lane.pending = (seq.compensate2 if order2 else seq.compensate)(fd, bs, lane.params)
                 lane.stage = 4
                 return False
             params_out[p0:p1] = lane.params
@@ -744,17 +760,21 @@ class StreamEstimator:
 
 
 def estimate_stream(frames, frame_distance=1, chunk_pairs=512, streams=2, ctx=None, compensated=None, procedure=3, on_chunk=None,
-                    search_window=2, exact_psnr=True, solve=None, min_chunk=64):
+                    search_window=2, exact_psnr=True, solve=None, min_chunk=64, model=None):
     """One-shot StreamEstimator: allocate the lanes, run `frames` through them, release them
-    -> (params float64[P, 6], psnr float64[P]).  Setting the lanes up costs a few milliseconds each; callers with
-    several videos of one size keep a StreamEstimator."""
+    -> (params float64[P, 6], psnr float64[P]); params float64[P, 12] for a second-order ``model`` (StreamEstimator.run).
+    Setting the lanes up costs a few milliseconds each; callers with several videos of one size keep a StreamEstimator."""
     n_frames = len(frames)
     P = max(0, n_frames - int(frame_distance))
     if P == 0:
-        return np.zeros((0, 6)), np.zeros(0)
+        width = 6
+        if model is not None:
+            import roadmap
+            width = 12 if model in roadmap.SECOND_ORDER else 6
+        return np.zeros((0, width)), np.zeros(0)
     H, W = np.asarray(frames[0]).shape
     chunk_pairs = max(1, min(int(chunk_pairs), P))
     n_chunks = (P + chunk_pairs - 1) // chunk_pairs
     with StreamEstimator(H, W, frame_distance, chunk_pairs, max(1, min(int(streams), n_chunks)), ctx, procedure, search_window,
                          min_chunk=min_chunk) as est:
-        return est.run(frames, compensated=compensated, exact_psnr=exact_psnr, solve=solve, on_chunk=on_chunk)
+        return est.run(frames, compensated=compensated, exact_psnr=exact_psnr, solve=solve, on_chunk=on_chunk, model=model)

@@ -192,6 +192,29 @@ GME_API int gme_seq_read_compensated(gme_seq *seq, int pair, uint8_t *out);
 /* the compensated frames of pairs first .. first+count-1 into out[count][H][W] (tight), one wait for all of them: a finished
  * chunk of a streamed video for results.py's writers (results.py:59-76) */
 GME_API int gme_seq_read_compensated_range(gme_seq *seq, int first, int count, uint8_t *out);
+
+/* Second-order motion models (EXTENSION: roadmap.py bilinear / pseudo_perspective / quadratic; the reference fits the affine
+ * part of the paper's model only, motion.py:191-207).  params[12] = [a0 a1 a2 b0 b1 b2 | a3 a4 a5 b3 b4 b5] with
+ * dx = a0 + a1 x + a2 y + a3 x^2 + a4 xy + a5 y^2 and dy likewise: the first six are the affine layout.  The fit sees
+ * x = 4 i, y = 4 j (motion.py:254-255); the field is evaluated at the raw block indices (motion.py:139-157) as
+ * d = ((p0 + p2 j) + p1 i) + ((a3 (i i) + a4 (i j)) + a5 (j j)), each product and sum rounded separately, round-half-even,
+ * int16 wrap -- with zero second-order terms the affine field bit for bit.
+ * sums[27] = the 15 weighted moments sum w x^p y^q, p + q <= 4, in the order 1 x y x2 xy y2 x3 x2y xy2 y3 x4 x3y x2y2 xy3 y4,
+ * then Sx[6] = sum w phi_k dx, Sy[6] = sum w phi_k dy with phi = [1 x y x2 xy y2]; each a sequential float64 sum over the
+ * inliers in row-major order (motion.py:248-261,266-279), so the entries M[0..5], Sx[0..2], Sy[0..2] equal the 15 sums of the
+ * order-1 calls bit for bit.  Staging, split-phase behaviour and state errors are those of the order-1 counterparts; the
+ * stage and compensated-frame read-backs work after them. */
+/* motion.get_motion_field_affine (motion.py:139-157) for params[12]: int16[h][w][2] */
+GME_API int gme_model2_field(gme_ctx *ctx, const double params[12], int h, int w, int16_t *mf_out);
+/* gme_seq_gme_begin_fit with sums1_out[P][27] (the level-1 field is the projected translation's: same field, mask and
+ * threshold as gme_seq_gme_begin_fit) */
+GME_API int gme_seq_gme_begin_fit2(gme_seq *seq, int frame_distance, int bbme_block_size, int procedure, int search_window,
+                                   double outlier_fraction, float *params0_out, double *sums1_out);
+/* gme_seq_gme_fit (motion.py:210-279) with params_in[P][12] and sums_out[P][27]; levels 1, 2 and -1 (the field of the last
+ * gme_seq_bbme, negative outlier_fraction: the unmasked fit of motion.py:33-88) */
+GME_API int gme_seq_gme_fit2(gme_seq *seq, int level, const double *params_in, double outlier_fraction, double *sums_out);
+/* gme_seq_compensate (motion.py:289-321, results.py:52-59,109) with the order-2 field of params[P][12] */
+GME_API int gme_seq_compensate2(gme_seq *seq, int frame_distance, int block_size, const double *params, int64_t *sse_out);
 /* Opt-in one-call form of begin_fit -> solve -> fit(2) -> solve -> compensate with the two 3x3 solves of
  * motion.py:262-264,280-282 on the device: one host round trip per estimate instead of three.  LAPACK's last bits are not
  * reproduced: params_out[P][6] is within rtol 1e-10 of the staged path's (motion.py:109-136); model fields, masks,
