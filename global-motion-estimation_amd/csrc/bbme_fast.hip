@@ -548,7 +548,7 @@ int launch_bbme_fast(gme_ctx* ctx, const BbmeJob& job, bool* handled)
     *handled = false;
     if (job.procedure != GME_SEARCH_EXHAUSTIVE || job.bs != 16) return GME_OK;
     const bool mse = job.pnorm == GME_NORM_MSE;
-    if (mse && (job.sqbox_cur == nullptr || getenv("GME_FORCE_GENERIC"))) return GME_OK;
+    if (mse && (job.sqbox_cur == nullptr || job.sqbox_kind != 1 || getenv("GME_FORCE_GENERIC"))) return GME_OK;     // sum(b^2) table only
     if (job.sw < 0 || job.sw % 4 != 0) return GME_OK;
     const int NC = 2 * job.sw + 16;
     const int R = (NC + 15) / 16;
@@ -666,13 +666,13 @@ int launch_sqbox16(gme_ctx* ctx, const uint8_t* src, long long src_stride, int c
     return GME_OK;
 }
 
-int bbme_aux_kind(int bs, int sw, int procedure, int pnorm)
+int bbme_aux_kind(int H, int W, int pitch, long long pairs, int bs, int sw, int procedure, int pnorm)
 {
     if (procedure != GME_SEARCH_EXHAUSTIVE || bs != 16 || pnorm != GME_NORM_MSE) return 0;
     if (sw < 0 || sw % 4 != 0) return 0;
     const int NC = 2 * sw + 16;
     if (!((NC + 15) / 16 <= 5 && NC * NC <= 8192 && !getenv("GME_FORCE_GENERIC"))) return 0;
-    return bbme_mfma_wanted(sw) ? 2 : 1;
+    return bbme_mfma_takes(H, W, pitch, bbme_pairs_per_launch(H, W, bs, pairs), sw) ? 2 : 1;
 }
 
 int launch_aux_table(gme_ctx* ctx, int kind, const uint8_t* src, long long src_stride, int count, int H, int W,

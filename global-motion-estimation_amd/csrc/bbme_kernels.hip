@@ -507,11 +507,24 @@ static bool needs_f32_order(int bs, int pnorm)
 
 static int launch_bbme_chunk(gme_ctx* ctx, const BbmeJob& job);
 
+long long bbme_pairs_per_launch(int H, int W, int bs, long long pairs)
+{
+    // long sequences: keep every launch below ~16 M blocks so grid sizes stay far from 2^31
+    const long long nblk = (long long)(H / bs) * (W / bs);
+    if (nblk == 0) return pairs;
+    long long cap = 1ll << 24;
+    if (const char* e = getenv("GME_BBME_CHUNK_BLOCKS")) {             // test hook: reach the chunked path with few pairs
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (1ll << 24)) cap = v;
+    }
+    const long long per = cap / nblk < 1 ? 1 : cap / nblk;
+    return pairs < per ? pairs : per;
+}
+
 int launch_bbme(gme_ctx* ctx, const BbmeJob& job)
 {
     int rc = bbme_check_args(job.H, job.W, job.bs, job.sw, job.procedure, job.pnorm);
     if (rc != GME_OK) return rc;
-    // long sequences: keep every launch below ~16 M blocks so grid sizes stay far from 2^31
     const long long nblk = (long long)(job.H / job.bs) * (job.W / job.bs);
     if (nblk == 0 || job.pairs == 0) return GME_OK;
     if (!job.chained) {
@@ -521,12 +534,7 @@ int launch_bbme(gme_ctx* ctx, const BbmeJob& job)
         // in front of a 3.7 ms launch)
         GME_HIP_TRY(hipMemsetAsync(ctx->status + GME_STATUS_TILECTR, 0, (GME_STATUS_REDO + 2 - GME_STATUS_TILECTR) * sizeof(int), ctx->stream));
     }
-    long long cap = 1ll << 24;
-    if (const char* e = getenv("GME_BBME_CHUNK_BLOCKS")) {             // test hook: reach the chunked path with few pairs
-        const long long v = atoll(e);
-        if (v >= 1 && v <= (1ll << 24)) cap = v;
-    }
-    const long long per = cap / nblk < 1 ? 1 : cap / nblk;
+    const long long per = bbme_pairs_per_launch(job.H, job.W, job.bs, job.pairs);
     for (long long first = 0; first < job.pairs; first += per) {
         BbmeJob part = job;
         part.status_fresh = first == 0 && !job.chained;

@@ -400,16 +400,24 @@ bool bbme_mfma_wanted(int sw)
     return e ? atoi(e) != 0 : sw <= GME_EXH_MFMA_AUTO_SW;
 }
 
+// One predicate for both sides of the table: bbme_aux_kind builds the signed table (kind 2) for exactly these jobs, and
+// launch_bbme_mfma takes exactly these.  A geometry it declines gets the vector kernels' table (kind 1) instead.
+bool bbme_mfma_takes(int H, int W, int pitch, long long pairs, int sw)
+{
+    if (!bbme_mfma_wanted(sw)) return false;
+    const int nbr = H / 16, nbc = W / 16;
+    if (nbr == 0 || nbc == 0 || nbr > 65535 || (pairs + 7) / 8 > 65535) return false;     // grid.y, grid.z
+    return (long long)(H + 64) * pitch * 4 < (1ll << 31);                                  // 32-bit table offsets
+}
+
 int launch_bbme_mfma(gme_ctx* ctx, const BbmeJob& job, bool* handled)
 {
     *handled = false;
     if (job.procedure != GME_SEARCH_EXHAUSTIVE || job.bs != 16 || job.pnorm != GME_NORM_MSE) return GME_OK;
-    if (job.sqbox_cur == nullptr || !bbme_mfma_wanted(job.sw)) return GME_OK;
-    if (bbme_aux_kind(job.bs, job.sw, job.procedure, job.pnorm) != 2) return GME_OK;
+    if (job.sqbox_cur == nullptr || job.sqbox_kind != 2) return GME_OK;                   // reads the signed table only
+    if (!bbme_mfma_takes(job.H, job.W, job.pitch, job.pairs, job.sw)) return GME_OK;
     const int NC = 2 * job.sw + 16, NT = NC / 16;
     const int nbr = job.H / 16, nbc = job.W / 16;
-    if (nbr == 0 || nbc == 0 || nbr > 65535 || (job.pairs + 7) / 8 > 65535) return GME_OK;
-    if ((long long)(job.H + 64) * job.pitch * 4 >= (1ll << 31)) return GME_OK;          // 32-bit table offsets
 
     MfmaDev d;
     d.prev = job.prev; d.cur = job.cur; d.plane_stride = job.plane_stride;

@@ -484,7 +484,7 @@ int launch_bbme_sea_mse(gme_ctx* ctx, const BbmeJob& job, bool* handled)
 {
     *handled = false;
     if (job.procedure != GME_SEARCH_EXHAUSTIVE || job.bs != 16 || job.pnorm != GME_NORM_MSE) return GME_OK;
-    if (job.sqbox_cur == nullptr || job.sw < 0 || job.sw % 4 != 0) return GME_OK;
+    if (job.sqbox_cur == nullptr || job.sqbox_kind != 1 || job.sw < 0 || job.sw % 4 != 0) return GME_OK;     // sum(b^2) table only
     if (getenv("GME_FORCE_GENERIC") || getenv("GME_EXH_BRUTE")) return GME_OK;
     const int NC = 2 * job.sw + 16, R = (NC + 15) / 16;
     if (R < 1 || R > 5 || NC * NC > 8192) return GME_OK;

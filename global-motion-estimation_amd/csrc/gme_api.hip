@@ -324,7 +324,7 @@ extern "C" int gme_bbme_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     Carver c;
     const size_t o_prev = c.take(plane + pitch), o_cur = c.take(plane + pitch);
     const size_t o_mf = c.take((size_t)h * w * 2 * sizeof(int32_t));
-    const int aux = bbme_aux_kind(block_size, search_window, procedure, pnorm);
+    const int aux = bbme_aux_kind(H, W, pitch, 1, block_size, search_window, procedure, pnorm);
     const bool want_sq = aux != 0;
     const size_t o_sq = c.take(want_sq ? plane * 4 : 0);
     void* base = nullptr;
@@ -343,6 +343,7 @@ extern "C" int gme_bbme_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
         rc = launch_aux_table(ctx, aux, b + o_cur, 0, 1, H, W, pitch, (uint32_t*)(b + o_sq), 0);
         if (rc) return rc;
         job.sqbox_cur = (const uint32_t*)(b + o_sq);
+        job.sqbox_kind = aux;
     }
     rc = launch_bbme(ctx, job);
     if (rc) return rc;
@@ -747,11 +748,12 @@ extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, i
     job.H = s->H; job.W = s->W; job.pitch = p.pitch;
     job.bs = bs; job.sw = sw; job.procedure = procedure; job.pnorm = pnorm;
     job.mf = s->mv; job.sqbox_cur = nullptr; job.sqbox_stride = 0;
-    if (const int aux = bbme_aux_kind(bs, sw, procedure, pnorm)) {
+    if (const int aux = bbme_aux_kind(s->H, s->W, p.pitch, pairs, bs, sw, procedure, pnorm)) {
         rc = seq_sqbox(s, 2, aux);
         if (rc) return rc;
         job.sqbox_cur = s->sqbox[2] + (size_t)fd * p.stride;
         job.sqbox_stride = p.stride;
+        job.sqbox_kind = aux;
     }
     return launch_bbme(s->ctx, job);
 }
@@ -792,7 +794,9 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     if (rc) return rc;
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
     const Plane& p = s->level[2];
-    const int aux = bbme_aux_kind(bs, sw, procedure, pnorm);
+    // one table kind for the whole call: every chunk's launches carry at most `pairs` pairs, so one that the matrix-core
+    // kernel would take at the largest also takes it at every chunk, and a smaller chunk of a declined call keeps kind 1
+    const int aux = bbme_aux_kind(s->H, s->W, p.pitch, pairs, bs, sw, procedure, pnorm);
     if (aux) {
         rc = ensure(&s->sqbox[2], &s->sqbox_bytes[2], (size_t)p.stride * p.count * sizeof(uint32_t));
         if (rc) return rc;
@@ -922,7 +926,7 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
                 const int t0 = tab_done;
                 rc = launch_aux_table(ctx, aux, p.at(t0), p.stride, f1 - t0, p.H, p.W, p.pitch, s->sqbox[2] + (size_t)t0 * p.stride, p.stride);
                 tab_done = f1;
-                if (rc == GME_OK) { job.sqbox_cur = s->sqbox[2] + (size_t)(p_done + fd) * p.stride; job.sqbox_stride = p.stride; }
+                if (rc == GME_OK) { job.sqbox_cur = s->sqbox[2] + (size_t)(p_done + fd) * p.stride; job.sqbox_stride = p.stride; job.sqbox_kind = aux; }
             }
             if (rc == GME_OK) rc = launch_bbme(ctx, job);
             if (rc != GME_OK) {
@@ -997,11 +1001,12 @@ static int gme_level_bbme(gme_seq* s, int l)
     job.pnorm = GME_NORM_MSE;
     job.mf = s->fit[l].gt; job.sqbox_cur = nullptr; job.sqbox_stride = 0;
     if (s->fit[l].h == 0 || s->fit[l].w == 0) return GME_OK;
-    if (const int aux = bbme_aux_kind(job.bs, job.sw, job.procedure, job.pnorm)) {      // BASELINE config 4
+    if (const int aux = bbme_aux_kind(p.H, p.W, p.pitch, job.pairs, job.bs, job.sw, job.procedure, job.pnorm)) {      // BASELINE config 4
         const int rc = seq_sqbox(s, l, aux);
         if (rc) return rc;
         job.sqbox_cur = s->sqbox[l] + (size_t)fd * p.stride;
         job.sqbox_stride = p.stride;
+        job.sqbox_kind = aux;
     }
     return launch_bbme(s->ctx, job);
 }

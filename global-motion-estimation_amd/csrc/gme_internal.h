@@ -143,10 +143,13 @@ struct BbmeJob {
     int32_t* mf;                  // [pairs][H/bs][W/bs][2]
     const uint32_t* sqbox_cur;    // optional, matches `cur` planes: [pairs][H][pitch] uint32 (SqTable)
     int64_t sqbox_stride;         // elements between consecutive planes
+    int sqbox_kind = 0;           // what sqbox_cur holds (bbme_aux_kind): each kernel that reads it declines the other kind
     bool chained = false;         // a later chunk of one streamed call: keep the plan text and the statistics
     bool status_fresh = false;    // launch_bbme has just cleared the tile counters and redo words (first chunk of a call)
 };
 int launch_bbme(gme_ctx* ctx, const BbmeJob& job);
+// the most pairs one kernel launch of launch_bbme carries for `pairs` pairs of H x W at block size bs
+long long bbme_pairs_per_launch(int H, int W, int bs, long long pairs);
 int launch_exh_redo(gme_ctx* ctx, const BbmeJob& job, int R, int tr, int tc, int tile_wg_per_row, int tile_wg_per_pair,
                     const uint32_t* list, const uint32_t* count, uint32_t* head);
 // The table of 16x16 box sums of squares (exhaustive MSE, bs 16): uint32 [H][pitch] per frame, positions are those of the
@@ -204,15 +207,19 @@ __device__ __forceinline__ void sq4(SqTable t, long long idx, uint32_t (&out)[4]
 #endif
 int launch_sqbox16(gme_ctx* ctx, const uint8_t* src, long long src_stride, int count, int H, int W, int pitch,
                    uint32_t* out, long long stride, bool sgn);
-// per-frame auxiliary table a fast exhaustive kernel wants for `cur` (BbmeJob::sqbox_cur):
+// per-frame auxiliary table a fast exhaustive kernel wants for `cur` (BbmeJob::sqbox_cur, BbmeJob::sqbox_kind) when
+// launch_bbme searches `pairs` pairs of H x W planes with row pitch `pitch`:
 // 0 none, 1 = 16x16 box sums of squares (MSE, k_exh_dot16 and the elimination kernels), 2 = 16x16 box sums of the squares
-// of (byte - 128) (MSE on the matrix cores, bbme_mfma.hip)
-int bbme_aux_kind(int bs, int sw, int procedure, int pnorm);
+// of (byte - 128) (MSE on the matrix cores, bbme_mfma.hip: exactly the jobs bbme_mfma_takes)
+int bbme_aux_kind(int H, int W, int pitch, long long pairs, int bs, int sw, int procedure, int pnorm);
 int launch_aux_table(gme_ctx* ctx, int kind, const uint8_t* src, long long src_stride, int count, int H, int W,
                      int pitch, uint32_t* out, long long stride);
 bool bbme_sea_applies(int bs, int sw, int procedure, int pnorm);
 // ---- bbme_mfma.hip: exhaustive MSE at bs 16 as an int8 correlation on the matrix cores
 bool bbme_mfma_wanted(int sw);                // search windows it takes (and GME_EXH_MFMA has not switched it off)
+// exhaustive MSE at bs 16 that k_exh_mfma16 searches: a wanted window and a geometry its grid and its 32-bit table offsets
+// hold; `pairs` = the most pairs one launch carries (bbme_pairs_per_launch)
+bool bbme_mfma_takes(int H, int W, int pitch, long long pairs, int sw);
 int launch_bbme_mfma(gme_ctx* ctx, const BbmeJob& job, bool* handled);
 
 int bbme_check_args(int H, int W, int bs, int sw, int procedure, int pnorm);

@@ -4,6 +4,7 @@ oracle on shapes the tile grid does not divide, at every frame edge, on pan / no
 the four search windows the kernel takes (sw 8 .. 32), at the benched sizes, and against the vector-unit kernels.
 Needs an MI355X."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -52,14 +53,20 @@ def _content(rng, kind, n, H, W):
     return np.ascontiguousarray(fr)
 
 
-@pytest.mark.parametrize("sw", [8, 16, 24, 32])
-def test_mfma_random_shapes_vs_oracle(native, sw):
+def _vector_plan(sw):
+    """the elimination kernel's plan for this window: k_exh_sea16p_mse<R,NV> (persistent) or k_exh_sea16_mse<R>"""
+    return re.compile(r"k_exh_sea16p?_mse<%d[,>]" % ((2 * sw + 31) // 16))
+
+
+# sw 0 is NT = 1 (one 16 x 16 tile, the narrowest staging); "0-vector" is the same window on the vector unit (R = 1)
+@pytest.mark.parametrize("sw,mfma", [pytest.param(sw, 1, id=str(sw)) for sw in (0, 8, 16, 24, 32)] + [pytest.param(0, 0, id="0-vector")])
+def test_mfma_random_shapes_vs_oracle(native, sw, mfma):
     co = c_oracle()
     rng = np.random.default_rng(900 + sw)
     ctx = native.default_context()
     shapes = [(16, 16), (17, 33), (31, 95), (48, 64), (64, 96), (100, 130), (97, 143), (80, 176)]
     checked = 0
-    with _env(GME_EXH_MFMA=1):
+    with _env(GME_EXH_MFMA=mfma):
         for H, W in shapes:
             for kind in ("pan", "noise", "flat", "mixed", "extremes"):
                 n = 3
@@ -70,7 +77,10 @@ def test_mfma_random_shapes_vs_oracle(native, sw):
                     seq.bbme(fd, 16, sw, 0, 1)
                     mv = seq.read_mv()
                     plan = ctx.last_bbme_info()["plan"]
-                    assert plan.startswith("k_exh_mfma16<%d>" % ((2 * sw + 16) // 16)), plan
+                    if mfma:
+                        assert plan.startswith("k_exh_mfma16<%d>" % ((2 * sw + 16) // 16)), plan
+                    else:
+                        assert _vector_plan(sw).match(plan), plan
                     for p in range(n - fd):
                         want = co.bbme(frames[p], frames[p + fd], 16, sw, 0, 1)
                         assert np.array_equal(mv[p], want), (H, W, kind, fd, sw, p, np.argwhere(mv[p] != want)[:4])
@@ -80,22 +90,51 @@ def test_mfma_random_shapes_vs_oracle(native, sw):
     assert checked >= 40
 
 
-@pytest.mark.parametrize("tile", ["1x1", "1x2", "1x3", "1x4"])
-def test_mfma_tile_shapes(native, tile):
+# sw 16 keeps the ids it always had; sw 8, 24 and 32 reach the <NT, XS, TC> instances of NT 2, 4 and 5
+@pytest.mark.parametrize("tile,sw", [pytest.param(t, sw, id=t if sw == 16 else "%s-sw%d" % (t, sw))
+                                     for sw in (16, 8, 24, 32) for t in ("1x1", "1x2", "1x3", "1x4")])
+def test_mfma_tile_shapes(native, tile, sw):
     """every tile shape the launcher may pick (and the ragged last tiles of each) gives the oracle's field"""
     co = c_oracle()
     rng = np.random.default_rng(77)
     ctx = native.default_context()
     frames = _content(rng, "mixed", 3, 112, 208)              # 7 x 13 blocks: no tile shape divides it
-    want = [co.bbme(frames[p], frames[p + 1], 16, 16, 0, 1) for p in range(2)]
+    want = [co.bbme(frames[p], frames[p + 1], 16, sw, 0, 1) for p in range(2)]
     with _env(GME_EXH_MFMA=1, GME_MFMA_TILE=tile):
         seq = native.Sequence.from_frames(ctx, frames)
         try:
-            seq.bbme(1, 16, 16, 0, 1)
+            seq.bbme(1, 16, sw, 0, 1)
             mv = seq.read_mv()
-            assert ("%s blocks per workgroup" % tile) in ctx.last_bbme_info()["plan"], ctx.last_bbme_info()
+            plan = ctx.last_bbme_info()["plan"]
+            assert plan.startswith("k_exh_mfma16<%d>" % ((2 * sw + 16) // 16)), plan
+            assert ("%s blocks per workgroup" % tile) in plan, ctx.last_bbme_info()
             for p in range(2):
-                assert np.array_equal(mv[p], want[p]), (tile, p)
+                assert np.array_equal(mv[p], want[p]), (tile, sw, p)
+        finally:
+            seq.close()
+
+
+@pytest.mark.parametrize("rows", [1, 4, 6, 40])
+@pytest.mark.parametrize("H,W,sw", [(112, 208, 16), (208, 112, 32)])
+def test_mfma_rows_per_workgroup(native, rows, H, W, sw):
+    """GME_MFMA_ROWS block rows per workgroup on 7 and 13 block rows: one row, remainders of 3 / 1 (4 rows), 1 / 1 (6 rows),
+    and more rows than the frame has (the launcher clamps to nbr: one workgroup row)"""
+    co = c_oracle()
+    rng = np.random.default_rng(rows * 1000 + H)
+    ctx = native.default_context()
+    frames = _content(rng, "mixed", 3, H, W)
+    nbr = H // 16
+    with _env(GME_EXH_MFMA=1, GME_MFMA_ROWS=rows):
+        seq = native.Sequence.from_frames(ctx, frames)
+        try:
+            seq.bbme(1, 16, sw, 0, 1)
+            mv = seq.read_mv()
+            plan = ctx.last_bbme_info()["plan"]
+            eff = min(rows, nbr)
+            assert plan.startswith("k_exh_mfma16<%d>" % ((2 * sw + 16) // 16)), plan
+            assert (" %d rows each, grid " % eff) in plan and ("x%dx1" % ((nbr + eff - 1) // eff)) in plan, plan
+            for p in range(2):
+                assert np.array_equal(mv[p], co.bbme(frames[p], frames[p + 1], 16, sw, 0, 1)), (rows, H, W, p)
         finally:
             seq.close()
 
