@@ -493,61 +493,65 @@ class Sequence:
         self._gme = (frame_distance, bbme_block_size, pairs)
         return p0
 
-    def gme_begin_fit(self, frame_distance, bbme_block_size, outlier_fraction, procedure=3, search_window=2):
-        """gme_begin + projection of the first parameters + gme_fit(level 1) without the trip to the host in between
-        -> (first parameters float32[P, 6], level-1 sums float64[P, 15]); the level-2 search is queued behind."""
+    # Model orders: 1 = affine (params float64[P, 6], sums float64[P, 15] = F (9) | Sx (3) | Sy (3)); 2 = the second-order
+    # models of roadmap.py (params float64[P, 12], sums float64[P, 27] = moments (15) | Sx (6) | Sy (6)).  Each order has
+    # its own C entry points and its own reused buffers (split-phase callers hold the returned arrays).
+    _ORDER = {1: (6, 15, ""), 2: (12, 27, "2")}          # order -> (parameters, sums, entry-point suffix)
+
+    def _begin_fit(self, order, frame_distance, bbme_block_size, outlier_fraction, procedure, search_window):
+        n_sums, suffix = self._ORDER[order][1:]
         pairs = self.N - frame_distance
         bbme_block_size = _block_size(bbme_block_size)
         p0 = self._buffer("p0", (max(pairs, 0), 6), np.float32)
-        sums = self._buffer("sums1", (max(pairs, 0), 15), np.float64)
-        _check(self.lib.gme_seq_gme_begin_fit(self.handle, frame_distance, bbme_block_size, procedure, search_window,
-                                              float(outlier_fraction), _p(p0, _c_f32p), _p(sums, _c_f64p)), self.lib)
+        sums = self._buffer("sums%d_1" % order, (max(pairs, 0), n_sums), np.float64)
+        _check(getattr(self.lib, "gme_seq_gme_begin_fit" + suffix)(self.handle, frame_distance, bbme_block_size, procedure,
+                                                                   search_window, float(outlier_fraction), _p(p0, _c_f32p),
+                                                                   _p(sums, _c_f64p)), self.lib)
         self._gme = (frame_distance, bbme_block_size, pairs)
         return p0, sums
+
+    def _fit(self, order, level, params_in, outlier_fraction):
+        n_params, n_sums, suffix = self._ORDER[order]
+        pairs = self._gme[2] if level >= 0 else self._mv_shape[0]
+        p = self._buffer("fit%d_in%d" % (order, level), (pairs, n_params), np.float64)
+        p[...] = np.asarray(params_in, dtype=np.float64).reshape(pairs, n_params)
+        sums = self._buffer("sums%d_%d" % (order, level), (pairs, n_sums), np.float64)
+        _check(getattr(self.lib, "gme_seq_gme_fit" + suffix)(self.handle, level, _p(p, _c_f64p), float(outlier_fraction),
+                                                             _p(sums, _c_f64p)), self.lib)
+        return sums
+
+    def _compensate(self, order, frame_distance, block_size, params):
+        n_params, _, suffix = self._ORDER[order]
+        pairs = self.N - frame_distance
+        block_size = _block_size(block_size)
+        p = self._buffer("comp%d_in" % order, (pairs, n_params), np.float64)
+        p[...] = np.asarray(params, dtype=np.float64).reshape(pairs, n_params)
+        sse = self._buffer("sse", (pairs,), np.int64)
+        _check(getattr(self.lib, "gme_seq_compensate" + suffix)(self.handle, frame_distance, block_size, _p(p, _c_f64p),
+                                                                _p(sse, _c_i64p)), self.lib)
+        return sse
+
+    def gme_begin_fit(self, frame_distance, bbme_block_size, outlier_fraction, procedure=3, search_window=2):
+        """gme_begin + projection of the first parameters + gme_fit(level 1) without the trip to the host in between
+        -> (first parameters float32[P, 6], level-1 sums float64[P, 15]); the level-2 search is queued behind."""
+        return self._begin_fit(1, frame_distance, bbme_block_size, outlier_fraction, procedure, search_window)
 
     def gme_fit(self, level, params_in, outlier_fraction):
         """-> sums float64[P, 15] = F (9) | Sx (3) | Sy (3).  level -1 fits the field of the
         last bbme() call against the full-resolution frame size."""
-        pairs = self._gme[2] if level >= 0 else self._mv_shape[0]
-        p = self._buffer("fit_in%d" % level, (pairs, 6), np.float64)
-        p[...] = np.asarray(params_in, dtype=np.float64).reshape(pairs, 6)
-        sums = self._buffer("sums%d" % level, (pairs, 15), np.float64)
-        _check(self.lib.gme_seq_gme_fit(self.handle, level, _p(p, _c_f64p), float(outlier_fraction), _p(sums, _c_f64p)),
-               self.lib)
-        return sums
+        return self._fit(1, level, params_in, outlier_fraction)
 
-    # ---- second-order models (roadmap.py): params float64[P, 12], sums float64[P, 27]
     def gme_begin_fit2(self, frame_distance, bbme_block_size, outlier_fraction, procedure=3, search_window=2):
         """gme_begin_fit with the order-2 sums -> (first parameters float32[P, 6], level-1 sums float64[P, 27])."""
-        pairs = self.N - frame_distance
-        bbme_block_size = _block_size(bbme_block_size)
-        p0 = self._buffer("p0", (max(pairs, 0), 6), np.float32)
-        sums = self._buffer("sums2_1", (max(pairs, 0), 27), np.float64)
-        _check(self.lib.gme_seq_gme_begin_fit2(self.handle, frame_distance, bbme_block_size, procedure, search_window,
-                                               float(outlier_fraction), _p(p0, _c_f32p), _p(sums, _c_f64p)), self.lib)
-        self._gme = (frame_distance, bbme_block_size, pairs)
-        return p0, sums
+        return self._begin_fit(2, frame_distance, bbme_block_size, outlier_fraction, procedure, search_window)
 
     def gme_fit2(self, level, params_in, outlier_fraction):
         """gme_fit for params float64[P, 12] -> sums float64[P, 27] = moments (15) | Sx (6) | Sy (6)."""
-        pairs = self._gme[2] if level >= 0 else self._mv_shape[0]
-        p = self._buffer("fit2_in%d" % level, (pairs, 12), np.float64)
-        p[...] = np.asarray(params_in, dtype=np.float64).reshape(pairs, 12)
-        sums = self._buffer("sums2_%d" % level, (pairs, 27), np.float64)
-        _check(self.lib.gme_seq_gme_fit2(self.handle, level, _p(p, _c_f64p), float(outlier_fraction), _p(sums, _c_f64p)),
-               self.lib)
-        return sums
+        return self._fit(2, level, params_in, outlier_fraction)
 
     def compensate2(self, frame_distance, block_size, params):
         """compensate() with the order-2 field of params float64[P, 12] -> sse int64[P]."""
-        pairs = self.N - frame_distance
-        block_size = _block_size(block_size)
-        p = self._buffer("comp2_in", (pairs, 12), np.float64)
-        p[...] = np.asarray(params, dtype=np.float64).reshape(pairs, 12)
-        sse = self._buffer("sse", (pairs,), np.int64)
-        _check(self.lib.gme_seq_compensate2(self.handle, frame_distance, block_size, _p(p, _c_f64p), _p(sse, _c_i64p)),
-               self.lib)
-        return sse
+        return self._compensate(2, frame_distance, block_size, params)
 
     def stage_shape(self, level):
         if level < 0:
@@ -570,14 +574,8 @@ class Sequence:
 
     # ---- compensation + squared error
     def compensate(self, frame_distance, block_size, params):
-        pairs = self.N - frame_distance
-        block_size = _block_size(block_size)
-        p = self._buffer("comp_in", (pairs, 6), np.float64)
-        p[...] = np.asarray(params, dtype=np.float64).reshape(pairs, 6)
-        sse = self._buffer("sse", (pairs,), np.int64)
-        _check(self.lib.gme_seq_compensate(self.handle, frame_distance, block_size, _p(p, _c_f64p), _p(sse, _c_i64p)),
-               self.lib)
-        return sse
+        """Compensated frames of the affine params float64[P, 6] -> sse int64[P]."""
+        return self._compensate(1, frame_distance, block_size, params)
 
     def gme_device_solve(self, frame_distance, bbme_block_size, outlier_fraction, procedure=3, search_window=2):
         """The whole estimate + compensation with the 3x3 solves on the device (gme_seq_gme_device_solve): one round trip

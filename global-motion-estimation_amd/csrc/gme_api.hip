@@ -963,18 +963,22 @@ extern "C" int gme_seq_read_mv(gme_seq* s, int first_pair, int count, int32_t* m
     return ctx_finish(s->ctx);
 }
 
-static int alloc_fit(FitLevelBuf& f, int pairs, int h, int w, bool full)
+// gt: the level's own field, or (borrowed_gt) one the fit only reads -- then never allocated or freed here.
+// full: also the stage buffers of the fit (model field, mask, sums, ...); the dense level needs gt only.
+static int alloc_fit(FitLevelBuf& f, int pairs, int h, int w, bool full, int32_t* borrowed_gt = nullptr)
 {
     free_fit(f);
     f.h = h; f.w = w;
     const size_t n = (size_t)pairs * h * w;
     if (n == 0) return GME_OK;
-    bool ok = hipMalloc((void**)&f.gt, n * 2 * sizeof(int32_t)) == hipSuccess;
+    bool ok = true;
+    if (borrowed_gt) f.gt = borrowed_gt;
+    else ok = hipMalloc((void**)&f.gt, n * 2 * sizeof(int32_t)) == hipSuccess;
     if (full) {
         ok = ok && hipMalloc((void**)&f.model, n * 2 * sizeof(int16_t)) == hipSuccess;
         ok = ok && hipMalloc((void**)&f.mask, n) == hipSuccess;
         ok = ok && hipMalloc((void**)&f.diff, n * sizeof(int32_t)) == hipSuccess;
-        if ((size_t)h * w * 16 > 40 * 1024) ok = ok && hipMalloc(&f.list, n * 16) == hipSuccess;
+        if ((size_t)h * w * 16 > FIT_LIST_LDS_BYTES) ok = ok && hipMalloc(&f.list, n * 16) == hipSuccess;
         ok = ok && hipMalloc((void**)&f.thr, (size_t)pairs * sizeof(int32_t)) == hipSuccess;
         ok = ok && hipMalloc((void**)&f.sums, (size_t)pairs * 15 * sizeof(double)) == hipSuccess;
         ok = ok && hipMalloc((void**)&f.sums2, (size_t)pairs * 27 * sizeof(double)) == hipSuccess;
@@ -1106,15 +1110,44 @@ extern "C" int gme_seq_gme_begin(gme_seq* s, int fd, int bbme_bs, int procedure,
     return gme_flush_bbme(s, 2);
 }
 
-static int fit_level_launch(gme_seq* s, int level, const double* dparams, double outlier_fraction, double* sums_out);
+// Model orders: 1 = affine (params [P][6], sums [P][15] = F (9) | Sx (3) | Sy (3)); 2 = the second-order models
+// (params [P][12], sums [P][27], see the section at the end of this file).
+static int order_params(int order) { return order == 1 ? 6 : 12; }
+static int order_sums(int order) { return order == 1 ? 15 : 27; }
+
+// model field, mask and sums of level -1 (fit_mv), 1 or 2 from parameters already on the device (pstride doubles per
+// pair); result copy + event / wait.  The context is locked.
+static int fit_launch(gme_seq* s, int order, int level, const double* dparams, int pstride, double outlier_fraction, double* sums_out)
+{
+    gme_ctx* ctx = s->ctx;
+    const bool mv = level < 0;
+    const FitLevelBuf& f = mv ? s->fit_mv : s->fit[level];
+    const int pairs = mv ? s->mv_pairs : s->gme_pairs, n = f.h * f.w;
+    GME_REQUIRE(n > 0, GME_ERR_GEOMETRY, "level %d holds no block (motion.py:243 would index an empty list)", level);
+    // int(0.3 * len), motion.py:242; a negative fraction selects the unmasked fit (motion.py:33-88)
+    const int drop = outlier_fraction < 0 ? -1 : (int)(outlier_fraction * (double)n);
+    GME_REQUIRE(drop <= n, GME_ERR_ARG, "outlier fraction %g out of range", outlier_fraction);
+    const int level_H = mv ? s->H : s->level[level].H, level_W = mv ? s->W : s->level[level].W;
+    int rc = launch_fit_level(ctx, f, order, pairs, dparams, pstride, drop, level_H, level_W);
+    if (rc) return rc;
+    if (!sums_out) return GME_OK;                          // gme_seq_gme_device_solve: the sums stay on the device
+    rc = copy_small(ctx, sums_out, order == 1 ? f.sums : f.sums2, (size_t)pairs * order_sums(order) * sizeof(double),
+                    hipMemcpyDeviceToHost, s->split_phase);
+    if (rc) return rc;
+    if (s->split_phase) GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream));
+    else rc = ctx_finish(ctx);
+    return rc;
+}
 
 // gme_seq_gme_begin + the projection of the first parameters (motion.py:191-207 on the float32 vector: two exact doublings)
 // + gme_seq_gme_fit(level 1) without the trip to the host in between: the first parameters never leave the device on the
 // way to the level-1 fit, so a staged run has three dependent host round trips instead of four.  params0_out may be NULL.
-extern "C" int gme_seq_gme_begin_fit(gme_seq* s, int fd, int bbme_bs, int procedure, int sw, double outlier_fraction,
-                                     float* params0_out, double* sums1_out)
+// At order 2 the level-1 field is that of the projected first parameters (a translation, six doubles per pair), so mask
+// and threshold are those of order 1.
+static int seq_begin_fit(gme_seq* s, int order, const char* who, int fd, int bbme_bs, int procedure, int sw,
+                         double outlier_fraction, float* params0_out, double* sums1_out)
 {
-    GME_REQUIRE(s != nullptr && sums1_out != nullptr, GME_ERR_ARG, "gme_seq_gme_begin_fit: null pointer");
+    GME_REQUIRE(s != nullptr && sums1_out != nullptr, GME_ERR_ARG, "%s: null pointer", who);
     gme_ctx* ctx = s->ctx;
     GME_ENTER(ctx);
     int rc = gme_begin_common(s, fd, bbme_bs, procedure, sw);
@@ -1125,110 +1158,71 @@ extern "C" int gme_seq_gme_begin_fit(gme_seq* s, int fd, int bbme_bs, int proced
         { rc = copy_small(ctx, params0_out, s->params0, (size_t)s->gme_pairs * 6 * sizeof(float), hipMemcpyDeviceToHost, s->split_phase); if (rc) return rc; }
     rc = gme_level_bbme(s, 1);
     if (rc) return rc;
-    rc = fit_level_launch(s, 1, s->params_in, outlier_fraction, sums1_out);
+    rc = fit_launch(s, order, 1, s->params_in, 6, outlier_fraction, sums1_out);
     if (rc) return rc;
     return gme_level_bbme(s, 2);                           // searched while the caller solves level 1
 }
 
+extern "C" int gme_seq_gme_begin_fit(gme_seq* s, int fd, int bbme_bs, int procedure, int sw, double outlier_fraction,
+                                     float* params0_out, double* sums1_out)
+{
+    return seq_begin_fit(s, 1, "gme_seq_gme_begin_fit", fd, bbme_bs, procedure, sw, outlier_fraction, params0_out, sums1_out);
+}
+
+// stage buffers for fitting `mv` (gme_seq_bbme's field) at level -1; its gt is s->mv, borrowed
 static int ensure_fit_mv(gme_seq* s)
 {
     FitLevelBuf& f = s->fit_mv;
-    if (f.h == s->mv_h && f.w == s->mv_w && s->fit_mv_pairs == s->mv_pairs && f.model) { f.gt = s->mv; return GME_OK; }
-    f.gt = nullptr;                       // borrowed from s->mv, never freed here
-    if (f.model) hipFree(f.model);
-    if (f.mask) hipFree(f.mask);
-    if (f.diff) hipFree(f.diff);
-    if (f.list) hipFree(f.list);
-    if (f.thr) hipFree(f.thr);
-    if (f.sums) hipFree(f.sums);
-    if (f.sums2) hipFree(f.sums2);
-    f = FitLevelBuf();
-    f.h = s->mv_h; f.w = s->mv_w;
-    const size_t n = (size_t)s->mv_pairs * f.h * f.w;
-    if (hipMalloc((void**)&f.model, n * 2 * sizeof(int16_t)) != hipSuccess || hipMalloc((void**)&f.mask, n) != hipSuccess ||
-        hipMalloc((void**)&f.diff, n * sizeof(int32_t)) != hipSuccess ||
-        ((size_t)f.h * f.w * 16 > 40 * 1024 && hipMalloc(&f.list, n * 16) != hipSuccess) ||
-        hipMalloc((void**)&f.thr, (size_t)s->mv_pairs * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&f.sums, (size_t)s->mv_pairs * 15 * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&f.sums2, (size_t)s->mv_pairs * 27 * sizeof(double)) != hipSuccess) {
-        gme_set_error("out of device memory (fit buffers)");
-        return GME_ERR_NOMEM;
+    if (!(f.h == s->mv_h && f.w == s->mv_w && s->fit_mv_pairs == s->mv_pairs && f.model)) {
+        f.gt = nullptr;                       // borrowed, never freed here
+        const int rc = alloc_fit(f, s->mv_pairs, s->mv_h, s->mv_w, true, s->mv);
+        if (rc) return rc;
+        s->fit_mv_pairs = s->mv_pairs;
     }
     f.gt = s->mv;
-    s->fit_mv_pairs = s->mv_pairs;
+    return GME_OK;
+}
+
+static int seq_fit(gme_seq* s, int order, const char* who, int level, const double* params_in, double outlier_fraction,
+                   double* sums_out)
+{
+    GME_REQUIRE(s != nullptr && params_in != nullptr && sums_out != nullptr, GME_ERR_ARG, "%s: null pointer", who);
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = GME_OK;
+    GME_REQUIRE(level == 1 || level == 2 || level == -1, GME_ERR_ARG, "%s: level %d (1, 2 or -1)", who, level);
+    const int width = order_params(order);
+    int pairs;
+    double* dparams;
+    if (level == -1) {
+        GME_REQUIRE(s->mv != nullptr && s->mv_pairs > 0, GME_ERR_STATE, "%s(level -1) before gme_seq_bbme", who);
+        rc = ensure_fit_mv(s);
+        if (rc) return rc;
+        pairs = s->mv_pairs;
+        size_t have = s->mv_params_bytes;
+        rc = ensure(&s->mv_params, &have, (size_t)pairs * width * sizeof(double));
+        s->mv_params_bytes = have;
+        if (rc) return rc;
+        dparams = s->mv_params;
+    } else {
+        GME_REQUIRE(s->gme_pairs > 0 && s->params_in, GME_ERR_STATE, "%s before gme_seq_gme_begin", who);
+        rc = gme_flush_bbme(s, level);
+        if (rc) return rc;
+        pairs = s->gme_pairs;
+        dparams = s->params_in;
+    }
+    rc = copy_small(ctx, dparams, params_in, (size_t)pairs * width * sizeof(double), hipMemcpyHostToDevice, s->split_phase);
+    if (rc) return rc;
+    rc = fit_launch(s, order, level, dparams, width, outlier_fraction, sums_out);
+    if (rc) return rc;
+    if (level == 1) return gme_level_bbme(s, 2);           // searched while the caller solves level 1
     return GME_OK;
 }
 
 extern "C" int gme_seq_gme_fit(gme_seq* s, int level, const double* params_in, double outlier_fraction,
                                double* sums_out)
 {
-    GME_REQUIRE(s != nullptr && params_in != nullptr && sums_out != nullptr, GME_ERR_ARG, "gme_seq_gme_fit: null pointer");
-    gme_ctx* ctx = s->ctx;
-    GME_ENTER(ctx);
-    int rc = GME_OK;
-    GME_REQUIRE(level == 1 || level == 2 || level == -1, GME_ERR_ARG, "gme_seq_gme_fit: level %d (1, 2 or -1)", level);
-    int pairs, level_H, level_W;
-    const FitLevelBuf* f;
-    double* dparams;
-    if (level == -1) {
-        GME_REQUIRE(s->mv != nullptr && s->mv_pairs > 0, GME_ERR_STATE, "gme_seq_gme_fit(level -1) before gme_seq_bbme");
-        rc = ensure_fit_mv(s);
-        if (rc) return rc;
-        f = &s->fit_mv; pairs = s->mv_pairs; level_H = s->H; level_W = s->W;
-        size_t have = s->mv_params_bytes;
-        rc = ensure(&s->mv_params, &have, (size_t)pairs * 6 * sizeof(double));
-        s->mv_params_bytes = have;
-        if (rc) return rc;
-        dparams = s->mv_params;
-    } else {
-        GME_REQUIRE(s->gme_pairs > 0 && s->params_in, GME_ERR_STATE, "gme_seq_gme_fit before gme_seq_gme_begin");
-        rc = gme_flush_bbme(s, level);
-        if (rc) return rc;
-        f = &s->fit[level]; pairs = s->gme_pairs; level_H = s->level[level].H; level_W = s->level[level].W;
-        dparams = s->params_in;
-    }
-    if (level == -1) {
-        const int n = f->h * f->w;
-        GME_REQUIRE(n > 0, GME_ERR_GEOMETRY, "level %d holds no block (motion.py:243 would index an empty list)", level);
-        // int(0.3 * len), motion.py:242; a negative fraction selects the unmasked fit (motion.py:33-88)
-        const int drop = outlier_fraction < 0 ? -1 : (int)(outlier_fraction * (double)n);
-        GME_REQUIRE(drop <= n, GME_ERR_ARG, "outlier fraction %g out of range", outlier_fraction);
-        GME_HIP_TRY(hipMemcpyAsync(dparams, params_in, (size_t)pairs * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        rc = launch_fit_level(ctx, f->gt, pairs, f->h, f->w, dparams, drop, level_H, level_W, f->model, f->mask, f->diff,
-                              f->thr, f->sums, f->list);
-        if (rc) return rc;
-        GME_HIP_TRY(hipMemcpyAsync(sums_out, f->sums, (size_t)pairs * 15 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        if (s->split_phase) GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream));
-        else rc = ctx_finish(ctx);
-        return rc;
-    }
-    rc = copy_small(ctx, dparams, params_in, (size_t)pairs * 6 * sizeof(double), hipMemcpyHostToDevice, s->split_phase);
-    if (rc) return rc;
-    rc = fit_level_launch(s, level, dparams, outlier_fraction, sums_out);
-    if (rc) return rc;
-    if (level == 1) return gme_level_bbme(s, 2);           // searched while the caller solves level 1
-    return GME_OK;
-}
-
-// model field, mask and sums of GME level 1 or 2 from parameters already on the device; result copy + event / wait
-static int fit_level_launch(gme_seq* s, int level, const double* dparams, double outlier_fraction, double* sums_out)
-{
-    gme_ctx* ctx = s->ctx;
-    const FitLevelBuf* f = &s->fit[level];
-    const int pairs = s->gme_pairs, n = f->h * f->w;
-    GME_REQUIRE(n > 0, GME_ERR_GEOMETRY, "level %d holds no block (motion.py:243 would index an empty list)", level);
-    // int(0.3 * len), motion.py:242; a negative fraction selects the unmasked fit (motion.py:33-88)
-    const int drop = outlier_fraction < 0 ? -1 : (int)(outlier_fraction * (double)n);
-    GME_REQUIRE(drop <= n, GME_ERR_ARG, "outlier fraction %g out of range", outlier_fraction);
-    int rc = launch_fit_level(ctx, f->gt, pairs, f->h, f->w, dparams, drop, s->level[level].H, s->level[level].W, f->model, f->mask,
-                              f->diff, f->thr, f->sums, f->list);
-    if (rc) return rc;
-    if (!sums_out) return GME_OK;                          // gme_seq_gme_device_solve: the sums stay on the device
-    rc = copy_small(ctx, sums_out, f->sums, (size_t)pairs * 15 * sizeof(double), hipMemcpyDeviceToHost, s->split_phase);
-    if (rc) return rc;
-    if (s->split_phase) GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream));
-    else rc = ctx_finish(ctx);
-    return rc;
+    return seq_fit(s, 1, "gme_seq_gme_fit", level, params_in, outlier_fraction, sums_out);
 }
 
 extern "C" int gme_seq_gme_read_stage(gme_seq* s, int level, int pair, int32_t* gt, int16_t* model, uint8_t* mask,
@@ -1278,9 +1272,11 @@ static int ensure_comp(gme_seq* s, int fd, int pairs)
     return GME_OK;
 }
 
-extern "C" int gme_seq_compensate(gme_seq* s, int fd, int bs, const double* params, int64_t* sse_out)
+// Order 1 evaluates the affine field per block inside k_compensate16 / k_compensate; order 2 first writes the int32 field
+// of every pair with k_model2_field, then takes their mf32 path.  Both sum the squared error (results.py:52-59,109).
+static int seq_compensate(gme_seq* s, int order, const char* who, int fd, int bs, const double* params, int64_t* sse_out)
 {
-    GME_REQUIRE(s != nullptr && params != nullptr, GME_ERR_ARG, "gme_seq_compensate: null pointer");
+    GME_REQUIRE(s != nullptr && params != nullptr, GME_ERR_ARG, "%s: null pointer", who);
     gme_ctx* ctx = s->ctx;
     GME_ENTER(ctx);
     int rc = GME_OK;
@@ -1291,11 +1287,21 @@ extern "C" int gme_seq_compensate(gme_seq* s, int fd, int bs, const double* para
     GME_REQUIRE(h > 0 && w > 0, GME_ERR_GEOMETRY, "block_size %d does not fit a %d x %d frame", bs, s->H, s->W);
     rc = ensure_comp(s, fd, pairs);
     if (rc) return rc;
-    rc = copy_small(ctx, s->comp_params, params, (size_t)pairs * 6 * sizeof(double), hipMemcpyHostToDevice, s->split_phase);
+    if (order == 2) {
+        rc = ensure(&s->comp_mf, &s->comp_mf_bytes, (size_t)pairs * h * w * 2 * sizeof(int32_t));
+        if (rc) return rc;
+    }
+    rc = copy_small(ctx, s->comp_params, params, (size_t)pairs * order_params(order) * sizeof(double), hipMemcpyHostToDevice,
+                    s->split_phase);
     if (rc) return rc;
+    if (order == 2) {
+        rc = launch_model2_field(ctx, s->comp_params, pairs, h, w, nullptr, s->comp_mf);
+        if (rc) return rc;
+    }
     const Plane& p = s->level[2];
-    rc = launch_compensate(ctx, p.at(0), p.stride, pairs, s->H, s->W, p.pitch, nullptr, s->comp_params, h, w, s->comp.ptr,
-                           s->comp.stride, s->comp.pitch, p.at(fd), p.stride, s->sse);
+    rc = launch_compensate(ctx, p.at(0), p.stride, pairs, s->H, s->W, p.pitch, order == 2 ? s->comp_mf : nullptr,
+                           order == 2 ? nullptr : s->comp_params, h, w, s->comp.ptr, s->comp.stride, s->comp.pitch, p.at(fd),
+                           p.stride, s->sse);
     if (rc) return rc;
     if (sse_out) {
         rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase);
@@ -1304,6 +1310,11 @@ extern "C" int gme_seq_compensate(gme_seq* s, int fd, int bs, const double* para
         return ctx_finish(ctx);
     }
     return GME_OK;
+}
+
+extern "C" int gme_seq_compensate(gme_seq* s, int fd, int bs, const double* params, int64_t* sse_out)
+{
+    return seq_compensate(s, 1, "gme_seq_compensate", fd, bs, params, sse_out);
 }
 
 // `count` compensated frames starting at pair `first` into out[count][H][W] (tight) with ONE wait: what results.py's
@@ -1376,12 +1387,12 @@ extern "C" int gme_seq_gme_device_solve(gme_seq* s, int fd, int bbme_bs, int pro
     if (rc) return rc;
     rc = gme_level_bbme(s, 2);                             // independent of the parameters: queued ahead of the level-1 fit
     if (rc) return rc;
-    rc = fit_level_launch(s, 1, s->params_in, outlier_fraction, nullptr);
+    rc = fit_launch(s, 1, 1, s->params_in, 6, outlier_fraction, nullptr);
     if (rc) return rc;
     // level-1 solution, projected (motion.py:191-207), used for the level-2 model field: flag bit 1 where that rounds near a tie
     rc = launch_solve3(ctx, s->fit[1].sums, pairs, 1, s->fit[2].h, s->fit[2].w, s->params_in, s->solve_flags, 1);
     if (rc) return rc;
-    rc = fit_level_launch(s, 2, s->params_in, outlier_fraction, nullptr);
+    rc = fit_launch(s, 1, 2, s->params_in, 6, outlier_fraction, nullptr);
     if (rc) return rc;
     rc = launch_solve3(ctx, s->fit[2].sums, pairs, 0, h, w, s->comp_params, s->solve_flags, 2);
     if (rc) return rc;
@@ -1408,7 +1419,7 @@ extern "C" int gme_seq_read_compensated(gme_seq* s, int pair, uint8_t* out)
 }
 
 // ---------------------------------------------------------------------------
-// Second-order motion models (roadmap.py: bilinear, pseudo-perspective, quadratic; kernels in gme_models.hip).  The calls
+// Second-order motion models (roadmap.py: bilinear, pseudo-perspective, quadratic; kernels in gme_kernels.hip).  The calls
 // below are the order-1 calls above with params [P][12] = [a0 a1 a2 b0 b1 b2 | a3 a4 a5 b3 b4 b5] and sums [P][27]; same
 // staging, split-phase behaviour and state errors.  The stage buffers (model field, mask, threshold, compensated frames)
 // are shared with the order-1 calls, so gme_seq_gme_read_stage / gme_seq_read_compensated[_range] read whichever ran last.
@@ -1432,114 +1443,18 @@ extern "C" int gme_model2_field(gme_ctx* ctx, const double params[12], int h, in
     return ctx_finish(ctx);
 }
 
-// order-2 model field, mask and sums of level -1 (fit_mv), 1 or 2 from parameters already on the device (pstride doubles per
-// pair); result copy + event / wait.  The context is locked.
-static int fit2_level_launch(gme_seq* s, int level, const double* dparams, int pstride, double outlier_fraction, double* sums_out)
-{
-    gme_ctx* ctx = s->ctx;
-    const bool mv = level < 0;
-    const FitLevelBuf* f = mv ? &s->fit_mv : &s->fit[level];
-    const int pairs = mv ? s->mv_pairs : s->gme_pairs, n = f->h * f->w;
-    GME_REQUIRE(n > 0, GME_ERR_GEOMETRY, "level %d holds no block (motion.py:243 would index an empty list)", level);
-    // int(0.3 * len), motion.py:242; a negative fraction selects the unmasked fit (motion.py:33-88)
-    const int drop = outlier_fraction < 0 ? -1 : (int)(outlier_fraction * (double)n);
-    GME_REQUIRE(drop <= n, GME_ERR_ARG, "outlier fraction %g out of range", outlier_fraction);
-    const int level_H = mv ? s->H : s->level[level].H, level_W = mv ? s->W : s->level[level].W;
-    int rc = launch_fit_level2(ctx, f->gt, pairs, f->h, f->w, dparams, pstride, drop, level_H, level_W, f->model, f->mask, f->diff,
-                               f->thr, f->sums2, f->list);
-    if (rc) return rc;
-    rc = copy_small(ctx, sums_out, f->sums2, (size_t)pairs * 27 * sizeof(double), hipMemcpyDeviceToHost, s->split_phase);
-    if (rc) return rc;
-    if (s->split_phase) GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream));
-    else rc = ctx_finish(ctx);
-    return rc;
-}
-
-// gme_seq_gme_begin_fit with the order-2 sums at level 1: the level-1 field is that of the projected first parameters (a
-// translation), so mask and threshold are those of gme_seq_gme_begin_fit.
 extern "C" int gme_seq_gme_begin_fit2(gme_seq* s, int fd, int bbme_bs, int procedure, int sw, double outlier_fraction,
                                       float* params0_out, double* sums1_out)
 {
-    GME_REQUIRE(s != nullptr && sums1_out != nullptr, GME_ERR_ARG, "gme_seq_gme_begin_fit2: null pointer");
-    gme_ctx* ctx = s->ctx;
-    GME_ENTER(ctx);
-    int rc = gme_begin_common(s, fd, bbme_bs, procedure, sw);
-    if (rc) return rc;
-    rc = launch_project_first(ctx, s->params0, s->gme_pairs, s->params_in);
-    if (rc) return rc;
-    if (params0_out)
-        { rc = copy_small(ctx, params0_out, s->params0, (size_t)s->gme_pairs * 6 * sizeof(float), hipMemcpyDeviceToHost, s->split_phase); if (rc) return rc; }
-    rc = gme_level_bbme(s, 1);
-    if (rc) return rc;
-    rc = fit2_level_launch(s, 1, s->params_in, 6, outlier_fraction, sums1_out);
-    if (rc) return rc;
-    return gme_level_bbme(s, 2);                           // searched while the caller solves level 1
+    return seq_begin_fit(s, 2, "gme_seq_gme_begin_fit2", fd, bbme_bs, procedure, sw, outlier_fraction, params0_out, sums1_out);
 }
 
 extern "C" int gme_seq_gme_fit2(gme_seq* s, int level, const double* params_in, double outlier_fraction, double* sums_out)
 {
-    GME_REQUIRE(s != nullptr && params_in != nullptr && sums_out != nullptr, GME_ERR_ARG, "gme_seq_gme_fit2: null pointer");
-    gme_ctx* ctx = s->ctx;
-    GME_ENTER(ctx);
-    int rc = GME_OK;
-    GME_REQUIRE(level == 1 || level == 2 || level == -1, GME_ERR_ARG, "gme_seq_gme_fit2: level %d (1, 2 or -1)", level);
-    int pairs;
-    double* dparams;
-    if (level == -1) {
-        GME_REQUIRE(s->mv != nullptr && s->mv_pairs > 0, GME_ERR_STATE, "gme_seq_gme_fit2(level -1) before gme_seq_bbme");
-        rc = ensure_fit_mv(s);
-        if (rc) return rc;
-        pairs = s->mv_pairs;
-        size_t have = s->mv_params_bytes;
-        rc = ensure(&s->mv_params, &have, (size_t)pairs * 12 * sizeof(double));
-        s->mv_params_bytes = have;
-        if (rc) return rc;
-        dparams = s->mv_params;
-    } else {
-        GME_REQUIRE(s->gme_pairs > 0 && s->params_in, GME_ERR_STATE, "gme_seq_gme_fit2 before gme_seq_gme_begin");
-        rc = gme_flush_bbme(s, level);
-        if (rc) return rc;
-        pairs = s->gme_pairs;
-        dparams = s->params_in;
-    }
-    rc = copy_small(ctx, dparams, params_in, (size_t)pairs * 12 * sizeof(double), hipMemcpyHostToDevice, s->split_phase);
-    if (rc) return rc;
-    rc = fit2_level_launch(s, level, dparams, 12, outlier_fraction, sums_out);
-    if (rc) return rc;
-    if (level == 1) return gme_level_bbme(s, 2);           // searched while the caller solves level 1
-    return GME_OK;
+    return seq_fit(s, 2, "gme_seq_gme_fit2", level, params_in, outlier_fraction, sums_out);
 }
 
-// gme_seq_compensate with the order-2 field: k_model2_field writes the int32 field of every pair, the mf32 path of
-// k_compensate16 / k_compensate gathers from it and sums the squared error (results.py:52-59,109).
 extern "C" int gme_seq_compensate2(gme_seq* s, int fd, int bs, const double* params, int64_t* sse_out)
 {
-    GME_REQUIRE(s != nullptr && params != nullptr, GME_ERR_ARG, "gme_seq_compensate2: null pointer");
-    gme_ctx* ctx = s->ctx;
-    GME_ENTER(ctx);
-    int rc = GME_OK;
-    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "frame_distance %d needs at least %d frames", fd, fd + 1);
-    const int pairs = s->N - fd;
-    GME_REQUIRE(bs >= 1, GME_ERR_ARG, "block_size %d", bs);
-    const int h = s->H / bs, w = s->W / bs;
-    GME_REQUIRE(h > 0 && w > 0, GME_ERR_GEOMETRY, "block_size %d does not fit a %d x %d frame", bs, s->H, s->W);
-    rc = ensure_comp(s, fd, pairs);
-    if (rc) return rc;
-    rc = ensure(&s->comp_mf, &s->comp_mf_bytes, (size_t)pairs * h * w * 2 * sizeof(int32_t));
-    if (rc) return rc;
-    rc = copy_small(ctx, s->comp_params, params, (size_t)pairs * 12 * sizeof(double), hipMemcpyHostToDevice, s->split_phase);
-    if (rc) return rc;
-    rc = launch_model2_field(ctx, s->comp_params, pairs, h, w, nullptr, s->comp_mf);
-    if (rc) return rc;
-    const Plane& p = s->level[2];
-    rc = launch_compensate(ctx, p.at(0), p.stride, pairs, s->H, s->W, p.pitch, s->comp_mf, nullptr, h, w, s->comp.ptr,
-                           s->comp.stride, s->comp.pitch, p.at(fd), p.stride, s->sse);
-    if (rc) return rc;
-    if (sse_out) {
-        rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase);
-        if (rc) return rc;
-        if (s->split_phase) { GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream)); return GME_OK; }
-        return ctx_finish(ctx);
-    }
-    return GME_OK;
+    return seq_compensate(s, 2, "gme_seq_compensate2", fd, bs, params, sse_out);
 }

@@ -83,8 +83,10 @@ struct FitLevelBuf {
     void* list = nullptr;         // [P][h][w] int4 inlier list, only for fields too large for LDS
     int32_t* thr = nullptr;       // [P]
     double* sums = nullptr;       // [P][15]
-    double* sums2 = nullptr;      // [P][27] order-2 sums (gme_seq_gme_fit2, gme_models.hip)
+    double* sums2 = nullptr;      // [P][27] order-2 sums (gme_seq_gme_fit2)
 };
+// the fit kernels keep a level's inlier list in LDS up to this size (two workgroups per CU), in `list` above it
+constexpr size_t FIT_LIST_LDS_BYTES = 40 * 1024;
 
 struct gme_seq {
     gme_ctx* ctx = nullptr;
@@ -231,10 +233,13 @@ int launch_repack(gme_ctx* ctx, hipStream_t stream, const uint8_t* src, int coun
 int launch_pyrdown(gme_ctx* ctx, const Plane& src, const Plane& dst);
 int launch_first_params(gme_ctx* ctx, const int32_t* dense, int pairs, int n_blocks, float* params0);
 int launch_project_first(gme_ctx* ctx, const float* params0, int pairs, double* params_in);
-int launch_fit_level(gme_ctx* ctx, const int32_t* gt, int pairs, int h, int w, const double* params,
-                     int drop_count, int level_H, int level_W, int16_t* model, uint8_t* mask,
-                     int32_t* diff, int32_t* thr, double* sums, void* list);
+// model field, mask, threshold and sums of one level's fit, into f: order 1 -> f.sums [P][15] (params [P][6]), order 2 ->
+// f.sums2 [P][27] (params of pstride doubles per pair: 12, or 6 for the affine layout with zero second-order terms)
+int launch_fit_level(gme_ctx* ctx, const FitLevelBuf& f, int order, int pairs, const double* params, int pstride, int drop,
+                     int level_H, int level_W);
 int launch_affine_field(gme_ctx* ctx, const double* params, int pairs, int h, int w, int16_t* out);
+// order-2 field, params [P][12]; exactly one of out16 / out32 is non-null
+int launch_model2_field(gme_ctx* ctx, const double* params, int pairs, int h, int w, int16_t* out16, int32_t* out32);
 int launch_solve3(gme_ctx* ctx, const double* sums, int pairs, int project, int h, int w, double* params_out, int32_t* flags, int flag_bit);
 int launch_mv_summary(gme_ctx* ctx, const int32_t* mf, int pairs, int n_blocks, double* rows);
 int launch_compensate(gme_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int pairs, int H,
@@ -243,14 +248,6 @@ int launch_compensate(gme_ctx* ctx, const uint8_t* frames, int64_t frame_stride,
                       int64_t cur_stride, unsigned long long* sse);
 int launch_sse(gme_ctx* ctx, const uint8_t* a, int64_t a_stride, int a_pitch, const uint8_t* b,
                int64_t b_stride, int b_pitch, int pairs, int H, int W, unsigned long long* sse);
-
-// ---- gme_models.hip: second-order motion models (roadmap.py) ------------------
-// params [P][12]; exactly one of out16 / out32 is non-null
-int launch_model2_field(gme_ctx* ctx, const double* params, int pairs, int h, int w, int16_t* out16, int32_t* out32);
-// k_fit_level with the order-2 field and sums27 [P][27]; params hold pstride (6 or 12) doubles per pair
-int launch_fit_level2(gme_ctx* ctx, const int32_t* gt, int pairs, int h, int w, const double* params, int pstride, int drop,
-                      int level_H, int level_W, int16_t* model, uint8_t* mask, int32_t* diff, int32_t* thr, double* sums27,
-                      void* list);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -24,7 +24,7 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
 
    **Second-order models.**  The paper the reference follows has second-order terms (motion.py:191-207 quotes its
    projection rule); the 15 sums above cannot determine them, so these models have their own device fit
-   (``k_fit_level2``, gme_models.hip) leaving 27 sums: the 15 weighted moments ``sum w x^p y^q`` (p + q <= 4, in the
+   (``k_fit_level2``, gme_kernels.hip) leaving 27 sums: the 15 weighted moments ``sum w x^p y^q`` (p + q <= 4, in the
    order ``1 x y x2 xy y2 x3 x2y xy2 y3 x4 x3y x2y2 xy3 y4``), then ``Sx = sum w phi dx`` and ``Sy = sum w phi dy`` over the
    basis ``phi = [1, x, y, x^2, xy, y^2]``.  Parameters are float64[12] = ``[a0 a1 a2 b0 b1 b2 | a3 a4 a5 b3 b4 b5]``,
    ``dx = a0 + a1 x + a2 y + a3 x^2 + a4 xy + a5 y^2``, ``dy`` likewise -- the first six are the affine layout:
@@ -194,15 +194,9 @@ def estimate_sequence(seq, frame_distance=1, model="affine", procedure=3, search
     if getattr(seq, "_split", False):
         raise RuntimeError("estimate_sequence needs blocking calls: the sequence is in split-phase mode")
     frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
-    if model in SECOND_ORDER:
-        _, sums = seq.gme_begin_fit2(frame_distance, int(motion.BBME_BLOCK_SIZE), frac, procedure, search_window)
-        params = project(solve_model(sums, model))
-        return solve_model(seq.gme_fit2(2, params, frac), model)
-    _, sums = seq.gme_begin_fit(frame_distance, int(motion.BBME_BLOCK_SIZE), frac, procedure, search_window)
-    params = solve_model(sums, model)
-    params[:, 0] = params[:, 0] * 2
-    params[:, 3] = params[:, 3] * 2
-    return solve_model(seq.gme_fit(2, params, frac), model)
+    begin, fit = (seq.gme_begin_fit2, seq.gme_fit2) if model in SECOND_ORDER else (seq.gme_begin_fit, seq.gme_fit)
+    _, sums = begin(frame_distance, int(motion.BBME_BLOCK_SIZE), frac, procedure, search_window)
+    return solve_model(fit(2, project(solve_model(sums, model)), frac), model)
 
 
 def global_motion_estimation(previous, current, model="affine"):

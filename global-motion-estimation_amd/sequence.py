@@ -21,6 +21,7 @@ import numpy as np
 
 import _gme_native as _native
 import motion
+import roadmap
 
 
 def shard_range(n_pairs, rank, world):
@@ -532,9 +533,7 @@ class ShardedSequence:
             pending = [lane.seq.gme_begin_fit(self.fd, bs, frac, procedure, search_window)[1] for lane in lanes]
             for k, lane in enumerate(lanes):
                 lane.seq.wait()
-                p = motion._solve_batch(pending[k])        # level 1 solved, projected in float64, level 2 asked for
-                p[:, 0] = p[:, 0] * 2
-                p[:, 3] = p[:, 3] * 2
+                p = roadmap.project(motion._solve_batch(pending[k]))     # level 1 solved, projected in float64, level 2 asked for
                 pending[k] = lane.seq.gme_fit(2, p, frac)
             params, sse = [None] * len(lanes), [None] * len(lanes)
             for k, lane in enumerate(lanes):
@@ -658,7 +657,6 @@ class StreamEstimator:
         P = max(0, len(frames) - fd)
         order2 = False
         if model is not None:
-            import roadmap
             if model not in roadmap.MODELS:
                 raise ValueError("unknown motion model %r (choose from %r)" % (model, roadmap.MODELS))
             order2 = model in roadmap.SECOND_ORDER
@@ -704,13 +702,8 @@ class StreamEstimator:
                 lane.stage = 2
                 return False
             if lane.stage == 2:                  # level-1 sums are back: solve, project (float64), ask for level 2
-                p = solve(lane.pending[:n])
-                if order2:
-                    lane.pending = seq.gme_fit2(2, roadmap.project(p), frac)
-                else:
-                    p[:, 0] = p[:, 0] * 2
-                    p[:, 3] = p[:, 3] * 2
-                    lane.pending = seq.gme_fit(2, p, frac)
+                p = roadmap.project(solve(lane.pending[:n]))
+                lane.pending = (seq.gme_fit2 if order2 else seq.gme_fit)(2, p, frac)
                 lane.stage = 3
                 return False
             if lane.stage == 3:
@@ -769,7 +762,6 @@ def estimate_stream(frames, frame_distance=1, chunk_pairs=512, streams=2, ctx=No
     if P == 0:
         width = 6
         if model is not None:
-            import roadmap
             width = 12 if model in roadmap.SECOND_ORDER else 6
         return np.zeros((0, width)), np.zeros(0)
     H, W = np.asarray(frames[0]).shape

@@ -1,5 +1,5 @@
-"""Second-order motion models on the device (gme_models.hip through gme_seq_gme_begin_fit2 / gme_seq_gme_fit2 /
-gme_seq_compensate2 / gme_model2_field): reduction to the affine path, the exact order-2 stage against NumPy
+"""Second-order motion models on the device (k_fit_level2 / k_model2_field of gme_kernels.hip through gme_seq_gme_begin_fit2 /
+gme_seq_gme_fit2 / gme_seq_compensate2 / gme_model2_field): reduction to the affine path, the exact order-2 stage against NumPy
 restatements, recovery of a known quadratic field, the streamed batch against per-pair calls, and the CLI.  Needs an MI355X."""
 import os
 
