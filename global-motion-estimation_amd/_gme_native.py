@@ -16,6 +16,17 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgme_hip.so")
 
 GME_OK, ERR_ARG, ERR_GEOMETRY, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -3, -4, -5, -6
+# GME_MODEL_* of include/gme_hip.h: the second-order models by their index in roadmap.MODELS
+MODEL_IDS = {"bilinear": 3, "pseudo_perspective": 4, "quadratic": 5}
+
+
+def model_id(model):
+    """A second-order model name (roadmap.SECOND_ORDER) -> its GME_MODEL_* id; an int passes through (the library checks it)."""
+    if isinstance(model, str):
+        if model not in MODEL_IDS:
+            raise ValueError("no device solve for motion model %r (choose from %r)" % (model, tuple(MODEL_IDS)))
+        return MODEL_IDS[model]
+    return int(model)
 
 
 class GmeError(RuntimeError):
@@ -81,6 +92,8 @@ _SIGNATURES = {
     "gme_seq_compensate2": (_i, [_vp, _i, _i, _c_f64p, _c_i64p]),
     "gme_solve_fit_sums": (_i, [_vp, _c_f64p, _i, _i, _i, _i, _c_f64p, _c_i32p]),
     "gme_seq_gme_device_solve": (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, _c_f64p, _c_i64p, _c_i32p]),
+    "gme_solve_model2_sums": (_i, [_vp, _i, _c_f64p, _i, _i, _i, _i, _c_f64p, _c_i32p]),
+    "gme_seq_gme_device_solve2": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_double, _c_f64p, _c_i64p, _c_i32p]),
     "gme_seq_read_compensated": (_i, [_vp, _i, _c_u8p]),
     "gme_seq_read_compensated_range": (_i, [_vp, _i, _i, _c_u8p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
@@ -247,6 +260,16 @@ class Context:
         flags = np.empty(len(sums), np.int32)
         _check(self.lib.gme_solve_fit_sums(self.handle, _p(sums, _c_f64p), len(sums), int(bool(project)), int(h), int(w),
                                            _p(params, _c_f64p), _p(flags, _c_i32p)), self.lib)
+        return params, flags
+
+    def solve_model2_sums(self, sums, model, h, w, project=False):
+        """gme_solve_model2_sums: float64[P, 27] order-2 sums of a second-order `model` (name or GME_MODEL_* id)
+        -> (params float64[P, 12], flags int32[P]); the tie check runs on the h x w field."""
+        sums = np.ascontiguousarray(np.asarray(sums, dtype=np.float64).reshape(-1, 27))
+        params = np.empty((len(sums), 12), np.float64)
+        flags = np.empty(len(sums), np.int32)
+        _check(self.lib.gme_solve_model2_sums(self.handle, model_id(model), _p(sums, _c_f64p), len(sums), int(bool(project)), int(h),
+                                              int(w), _p(params, _c_f64p), _p(flags, _c_i32p)), self.lib)
         return params, flags
 
     def timer_start(self):
@@ -587,6 +610,21 @@ class Sequence:
         flags = self._buffer("dev_flags", (max(pairs, 0),), np.int32)
         _check(self.lib.gme_seq_gme_device_solve(self.handle, frame_distance, bbme_block_size, procedure, search_window,
                                                  float(outlier_fraction), _p(params, _c_f64p), _p(sse, _c_i64p), _p(flags, _c_i32p)), self.lib)
+        self._gme = (frame_distance, bbme_block_size, pairs)
+        return params, sse, flags
+
+    def gme_device_solve2(self, model, frame_distance, bbme_block_size, outlier_fraction, procedure=3, search_window=2):
+        """gme_device_solve for a second-order `model` (gme_seq_gme_device_solve2) -> (params float64[P, 12], sse int64[P],
+        flags int32[P]); pairs with a non-zero flag must be redone by the staged order-2 calls."""
+        mid = model_id(model)
+        pairs = self.N - frame_distance
+        bbme_block_size = _block_size(bbme_block_size)
+        params = self._buffer("dev2_params", (max(pairs, 0), 12), np.float64)
+        sse = self._buffer("dev_sse", (max(pairs, 0),), np.int64)
+        flags = self._buffer("dev_flags", (max(pairs, 0),), np.int32)
+        _check(self.lib.gme_seq_gme_device_solve2(self.handle, mid, frame_distance, bbme_block_size, procedure, search_window,
+                                                  float(outlier_fraction), _p(params, _c_f64p), _p(sse, _c_i64p),
+                                                  _p(flags, _c_i32p)), self.lib)
         self._gme = (frame_distance, bbme_block_size, pairs)
         return params, sse, flags
 

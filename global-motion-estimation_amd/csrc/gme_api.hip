@@ -1274,6 +1274,19 @@ static int ensure_comp(gme_seq* s, int fd, int pairs)
 
 // Order 1 evaluates the affine field per block inside k_compensate16 / k_compensate; order 2 first writes the int32 field
 // of every pair with k_model2_field, then takes their mf32 path.  Both sum the squared error (results.py:52-59,109).
+// compensate_launch takes the parameters from s->comp_params (and, order 2, s->comp_mf sized for the h x w fields).
+static int compensate_launch(gme_seq* s, int order, int fd, int pairs, int h, int w)
+{
+    if (order == 2) {
+        const int rc = launch_model2_field(s->ctx, s->comp_params, pairs, h, w, nullptr, s->comp_mf);
+        if (rc) return rc;
+    }
+    const Plane& p = s->level[2];
+    return launch_compensate(s->ctx, p.at(0), p.stride, pairs, s->H, s->W, p.pitch, order == 2 ? s->comp_mf : nullptr,
+                             order == 2 ? nullptr : s->comp_params, h, w, s->comp.ptr, s->comp.stride, s->comp.pitch, p.at(fd),
+                             p.stride, s->sse);
+}
+
 static int seq_compensate(gme_seq* s, int order, const char* who, int fd, int bs, const double* params, int64_t* sse_out)
 {
     GME_REQUIRE(s != nullptr && params != nullptr, GME_ERR_ARG, "%s: null pointer", who);
@@ -1294,14 +1307,7 @@ static int seq_compensate(gme_seq* s, int order, const char* who, int fd, int bs
     rc = copy_small(ctx, s->comp_params, params, (size_t)pairs * order_params(order) * sizeof(double), hipMemcpyHostToDevice,
                     s->split_phase);
     if (rc) return rc;
-    if (order == 2) {
-        rc = launch_model2_field(ctx, s->comp_params, pairs, h, w, nullptr, s->comp_mf);
-        if (rc) return rc;
-    }
-    const Plane& p = s->level[2];
-    rc = launch_compensate(ctx, p.at(0), p.stride, pairs, s->H, s->W, p.pitch, order == 2 ? s->comp_mf : nullptr,
-                           order == 2 ? nullptr : s->comp_params, h, w, s->comp.ptr, s->comp.stride, s->comp.pitch, p.at(fd),
-                           p.stride, s->sse);
+    rc = compensate_launch(s, order, fd, pairs, h, w);
     if (rc) return rc;
     if (sse_out) {
         rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase);
@@ -1333,19 +1339,31 @@ extern "C" int gme_seq_read_compensated_range(gme_seq* s, int first, int count, 
     return GME_OK;
 }
 
-// The device solve on its own (what gme_seq_gme_device_solve runs between its stages), for callers and tests that hold
-// normal-equation sums: sums[P][15] = F | Sx | Sy -> params_out[P][6] (first components doubled if `project`,
-// motion.py:191-207) and flags_out[P]: bit 1 where a displacement of the h x w model field of those parameters lies within
-// 1e-9 of a rounding tie, bit 4 for a singular system.
-extern "C" int gme_solve_fit_sums(gme_ctx* ctx, const double* sums, int pairs, int project, int h, int w, double* params_out,
-                                  int32_t* flags_out)
+static bool model2_known(int model)
+{
+    return model == GME_MODEL_BILINEAR || model == GME_MODEL_PSEUDO_PERSPECTIVE || model == GME_MODEL_QUADRATIC;
+}
+
+// the device solve between two stages: order 1 the two 3x3 systems (k_solve3), order 2 the model's system (k_solve_model2)
+static int solve_launch(gme_ctx* ctx, int order, int model, const double* sums, int pairs, int project, int h, int w,
+                        double* params_out, int32_t* flags, int flag_bit)
+{
+    if (order == 1) return launch_solve3(ctx, sums, pairs, project, h, w, params_out, flags, flag_bit);
+    return launch_solve_model2(ctx, sums, model, pairs, project, h, w, params_out, flags, flag_bit);
+}
+
+static int solve_sums(gme_ctx* ctx, int order, int model, const char* who, const double* sums, int pairs, int project, int h, int w,
+                      double* params_out, int32_t* flags_out)
 {
     GME_ENTER(ctx);
     GME_REQUIRE(sums != nullptr && params_out != nullptr && flags_out != nullptr && pairs >= 0 && h >= 0 && w >= 0, GME_ERR_ARG,
-                "gme_solve_fit_sums: bad arguments");
+                "%s: bad arguments", who);
+    GME_REQUIRE(order == 1 || model2_known(model), GME_ERR_ARG, "%s: model %d is not a second-order model (%d, %d or %d)", who,
+                model, GME_MODEL_BILINEAR, GME_MODEL_PSEUDO_PERSPECTIVE, GME_MODEL_QUADRATIC);
     if (pairs == 0) return GME_OK;
     void* buf = nullptr;
-    const size_t b_sums = (size_t)pairs * 15 * sizeof(double), b_par = (size_t)pairs * 6 * sizeof(double), b_fl = (size_t)pairs * sizeof(int32_t);
+    const size_t b_sums = (size_t)pairs * order_sums(order) * sizeof(double), b_par = (size_t)pairs * order_params(order) * sizeof(double);
+    const size_t b_fl = (size_t)pairs * sizeof(int32_t);
     int rc = ctx_scratch(ctx, b_sums + b_par + b_fl, &buf);
     if (rc) return rc;
     double* d_sums = (double*)buf;
@@ -1353,10 +1371,71 @@ extern "C" int gme_solve_fit_sums(gme_ctx* ctx, const double* sums, int pairs, i
     int32_t* d_fl = (int32_t*)((char*)buf + b_sums + b_par);
     GME_HIP_TRY(hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, ctx->stream));
     GME_HIP_TRY(hipMemsetAsync(d_fl, 0, b_fl, ctx->stream));
-    rc = launch_solve3(ctx, d_sums, pairs, project, h, w, d_par, d_fl, 1);
+    rc = solve_launch(ctx, order, model, d_sums, pairs, project, h, w, d_par, d_fl, 1);
     if (rc) return rc;
     GME_HIP_TRY(hipMemcpyAsync(params_out, d_par, b_par, hipMemcpyDeviceToHost, ctx->stream));
     GME_HIP_TRY(hipMemcpyAsync(flags_out, d_fl, b_fl, hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
+// The device solve on its own (what gme_seq_gme_device_solve runs between its stages), for callers and tests that hold
+// normal-equation sums: sums[P][15] = F | Sx | Sy -> params_out[P][6] (first components doubled if `project`,
+// motion.py:191-207) and flags_out[P]: bit 1 where a displacement of the h x w model field of those parameters lies within
+// 1e-9 of a rounding tie, bit 4 for a singular system.
+extern "C" int gme_solve_fit_sums(gme_ctx* ctx, const double* sums, int pairs, int project, int h, int w, double* params_out,
+                                  int32_t* flags_out)
+{
+    return solve_sums(ctx, 1, 0, "gme_solve_fit_sums", sums, pairs, project, h, w, params_out, flags_out);
+}
+
+// begin + level-1 fit, solve + projection, level-2 fit, solve, field + compensation, all queued on the stream; the solves of
+// `order` write their flags into s->solve_flags.  The context is locked by the entry points below.
+static int seq_device_solve(gme_seq* s, int order, int model, const char* who, int fd, int bbme_bs, int procedure, int sw,
+                            double outlier_fraction, double* params_out, int64_t* sse_out, int32_t* flags_out)
+{
+    GME_REQUIRE(s != nullptr && params_out != nullptr && flags_out != nullptr, GME_ERR_ARG, "%s: null pointer", who);
+    GME_REQUIRE(order == 1 || model2_known(model), GME_ERR_ARG, "%s: model %d is not a second-order model (%d, %d or %d)", who,
+                model, GME_MODEL_BILINEAR, GME_MODEL_PSEUDO_PERSPECTIVE, GME_MODEL_QUADRATIC);
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = gme_begin_common(s, fd, bbme_bs, procedure, sw);
+    if (rc) return rc;
+    const int pairs = s->gme_pairs;
+    const int h = s->H / bbme_bs, w = s->W / bbme_bs;
+    GME_REQUIRE(h > 0 && w > 0, GME_ERR_GEOMETRY, "block_size %d does not fit a %d x %d frame", bbme_bs, s->H, s->W);
+    rc = ensure_comp(s, fd, pairs);
+    if (rc) return rc;
+    if (order == 2) {
+        rc = ensure(&s->comp_mf, &s->comp_mf_bytes, (size_t)pairs * h * w * 2 * sizeof(int32_t));
+        if (rc) return rc;
+    }
+    GME_HIP_TRY(hipMemsetAsync(s->solve_flags, 0, (size_t)(pairs > 0 ? pairs : 1) * sizeof(int32_t), ctx->stream));
+    rc = launch_project_first(ctx, s->params0, pairs, s->params_in);
+    if (rc) return rc;
+    rc = gme_level_bbme(s, 1);
+    if (rc) return rc;
+    rc = gme_level_bbme(s, 2);                             // independent of the parameters: queued ahead of the level-1 fit
+    if (rc) return rc;
+    rc = fit_launch(s, order, 1, s->params_in, 6, outlier_fraction, nullptr);
+    if (rc) return rc;
+    // level-1 solution, projected (motion.py:191-207), used for the level-2 model field: flag bit 1 where that rounds near a tie
+    rc = solve_launch(ctx, order, model, order == 1 ? s->fit[1].sums : s->fit[1].sums2, pairs, 1, s->fit[2].h, s->fit[2].w,
+                      s->params_in, s->solve_flags, 1);
+    if (rc) return rc;
+    rc = fit_launch(s, order, 2, s->params_in, order_params(order), outlier_fraction, nullptr);
+    if (rc) return rc;
+    rc = solve_launch(ctx, order, model, order == 1 ? s->fit[2].sums : s->fit[2].sums2, pairs, 0, h, w, s->comp_params,
+                      s->solve_flags, 2);
+    if (rc) return rc;
+    rc = compensate_launch(s, order, fd, pairs, h, w);
+    if (rc) return rc;
+    rc = copy_small(ctx, params_out, s->comp_params, (size_t)pairs * order_params(order) * sizeof(double), hipMemcpyDeviceToHost,
+                    s->split_phase);
+    if (rc) return rc;
+    if (sse_out) { rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase); if (rc) return rc; }
+    rc = copy_small(ctx, flags_out, s->solve_flags, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, s->split_phase);
+    if (rc) return rc;
+    if (s->split_phase) { GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream)); return GME_OK; }
     return ctx_finish(ctx);
 }
 
@@ -1370,43 +1449,8 @@ extern "C" int gme_solve_fit_sums(gme_ctx* ctx, const double* sums, int pairs, i
 extern "C" int gme_seq_gme_device_solve(gme_seq* s, int fd, int bbme_bs, int procedure, int sw, double outlier_fraction,
                                         double* params_out, int64_t* sse_out, int32_t* flags_out)
 {
-    GME_REQUIRE(s != nullptr && params_out != nullptr && flags_out != nullptr, GME_ERR_ARG, "gme_seq_gme_device_solve: null pointer");
-    gme_ctx* ctx = s->ctx;
-    GME_ENTER(ctx);
-    int rc = gme_begin_common(s, fd, bbme_bs, procedure, sw);
-    if (rc) return rc;
-    const int pairs = s->gme_pairs;
-    const int h = s->H / bbme_bs, w = s->W / bbme_bs;
-    GME_REQUIRE(h > 0 && w > 0, GME_ERR_GEOMETRY, "block_size %d does not fit a %d x %d frame", bbme_bs, s->H, s->W);
-    rc = ensure_comp(s, fd, pairs);
-    if (rc) return rc;
-    GME_HIP_TRY(hipMemsetAsync(s->solve_flags, 0, (size_t)(pairs > 0 ? pairs : 1) * sizeof(int32_t), ctx->stream));
-    rc = launch_project_first(ctx, s->params0, pairs, s->params_in);
-    if (rc) return rc;
-    rc = gme_level_bbme(s, 1);
-    if (rc) return rc;
-    rc = gme_level_bbme(s, 2);                             // independent of the parameters: queued ahead of the level-1 fit
-    if (rc) return rc;
-    rc = fit_launch(s, 1, 1, s->params_in, 6, outlier_fraction, nullptr);
-    if (rc) return rc;
-    // level-1 solution, projected (motion.py:191-207), used for the level-2 model field: flag bit 1 where that rounds near a tie
-    rc = launch_solve3(ctx, s->fit[1].sums, pairs, 1, s->fit[2].h, s->fit[2].w, s->params_in, s->solve_flags, 1);
-    if (rc) return rc;
-    rc = fit_launch(s, 1, 2, s->params_in, 6, outlier_fraction, nullptr);
-    if (rc) return rc;
-    rc = launch_solve3(ctx, s->fit[2].sums, pairs, 0, h, w, s->comp_params, s->solve_flags, 2);
-    if (rc) return rc;
-    const Plane& p = s->level[2];
-    rc = launch_compensate(ctx, p.at(0), p.stride, pairs, s->H, s->W, p.pitch, nullptr, s->comp_params, h, w, s->comp.ptr,
-                           s->comp.stride, s->comp.pitch, p.at(fd), p.stride, s->sse);
-    if (rc) return rc;
-    rc = copy_small(ctx, params_out, s->comp_params, (size_t)pairs * 6 * sizeof(double), hipMemcpyDeviceToHost, s->split_phase);
-    if (rc) return rc;
-    if (sse_out) { rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase); if (rc) return rc; }
-    rc = copy_small(ctx, flags_out, s->solve_flags, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, s->split_phase);
-    if (rc) return rc;
-    if (s->split_phase) { GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream)); return GME_OK; }
-    return ctx_finish(ctx);
+    return seq_device_solve(s, 1, 0, "gme_seq_gme_device_solve", fd, bbme_bs, procedure, sw, outlier_fraction, params_out,
+                            sse_out, flags_out);
 }
 
 extern "C" int gme_seq_read_compensated(gme_seq* s, int pair, uint8_t* out)
@@ -1457,4 +1501,18 @@ extern "C" int gme_seq_gme_fit2(gme_seq* s, int level, const double* params_in, 
 extern "C" int gme_seq_compensate2(gme_seq* s, int fd, int bs, const double* params, int64_t* sse_out)
 {
     return seq_compensate(s, 2, "gme_seq_compensate2", fd, bs, params, sse_out);
+}
+
+// The order-2 device solves (k_solve_model2): the contract is the header's.
+extern "C" int gme_solve_model2_sums(gme_ctx* ctx, int model, const double* sums, int pairs, int project, int h, int w,
+                                     double* params_out, int32_t* flags_out)
+{
+    return solve_sums(ctx, 2, model, "gme_solve_model2_sums", sums, pairs, project, h, w, params_out, flags_out);
+}
+
+extern "C" int gme_seq_gme_device_solve2(gme_seq* s, int model, int fd, int bbme_bs, int procedure, int sw,
+                                         double outlier_fraction, double* params_out, int64_t* sse_out, int32_t* flags_out)
+{
+    return seq_device_solve(s, 2, model, "gme_seq_gme_device_solve2", fd, bbme_bs, procedure, sw, outlier_fraction, params_out,
+                            sse_out, flags_out);
 }

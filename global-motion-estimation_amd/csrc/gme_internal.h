@@ -241,6 +241,10 @@ int launch_affine_field(gme_ctx* ctx, const double* params, int pairs, int h, in
 // order-2 field, params [P][12]; exactly one of out16 / out32 is non-null
 int launch_model2_field(gme_ctx* ctx, const double* params, int pairs, int h, int w, int16_t* out16, int32_t* out32);
 int launch_solve3(gme_ctx* ctx, const double* sums, int pairs, int project, int h, int w, double* params_out, int32_t* flags, int flag_bit);
+// order-2 counterpart: sums [P][27] of one of the GME_MODEL_* second-order models -> params_out [P][12] (projected if
+// `project`), flags |= 4 (singular), 8 (ill-conditioned), flag_bit (a displacement of the h x w field near a rounding tie)
+int launch_solve_model2(gme_ctx* ctx, const double* sums, int model, int pairs, int project, int h, int w, double* params_out,
+                        int32_t* flags, int flag_bit);
 int launch_mv_summary(gme_ctx* ctx, const int32_t* mf, int pairs, int n_blocks, double* rows);
 int launch_compensate(gme_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int pairs, int H,
                       int W, int pitch, const int32_t* mf32, const double* params, int h, int w,

@@ -434,12 +434,18 @@ __global__ void __launch_bounds__(256) k_affine_field(const double* params, int 
 //              row-major order of terms (exact integer) * w, k_fit_level's discipline; so M[0..5], Sx[0..2], Sy[0..2] equal
 //              k_fit_level's 15 affine sums bit for bit.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int16_t model2_component(double p0, double p1, double p2, double q0, double q1, double q2, int i, int j)
+// the displacement before rounding: k_solve_model2's tie check evaluates exactly what the field rounds
+__device__ __forceinline__ double model2_value(double p0, double p1, double p2, double q0, double q1, double q2, int i, int j)
 {
     const double di = (double)i, dj = (double)j;
     const double aff = __dadd_rn(__dadd_rn(p0, __dmul_rn(p2, dj)), __dmul_rn(p1, di));
     const double sec = __dadd_rn(__dadd_rn(__dmul_rn(q0, __dmul_rn(di, di)), __dmul_rn(q1, __dmul_rn(di, dj))), __dmul_rn(q2, __dmul_rn(dj, dj)));
-    return (int16_t)(long long)rint(__dadd_rn(aff, sec));      // round-half-even, int16 store wraps
+    return __dadd_rn(aff, sec);
+}
+
+__device__ __forceinline__ int16_t model2_component(double p0, double p1, double p2, double q0, double q1, double q2, int i, int j)
+{
+    return (int16_t)(long long)rint(model2_value(p0, p1, p2, q0, q1, q2, i, j));      // round-half-even, int16 store wraps
 }
 
 // The order-2 field of every pair: int16 for gme_model2_field, int32 (the int16 value, widened) for the mf32 path of
@@ -455,6 +461,151 @@ __global__ void __launch_bounds__(256) k_model2_field(const double* params, int 
     const int i = k / w, j = k - i * w;
     o[2 * k] = (T)model2_component(p[0], p[1], p[2], p[6], p[7], p[8], i, j);
     o[2 * k + 1] = (T)model2_component(p[3], p[4], p[5], p[9], p[10], p[11], i, j);
+}
+
+// ---------------------------------------------------------------------------
+// Opt-in (GME_DEVICE_SOLVE=1, gme_seq_gme_device_solve2): k_solve3's contract for the second-order models.  The normal
+// matrix is roadmap._solve_second_order's, entry for entry (quadratic 6x6 and bilinear 4x4 over the basis 1 x y [x2] xy [y2]
+// with two right-hand sides; pseudo-perspective one coupled 8x8 whose entries add the r_x moment, then the r_y one), then
+// Jacobi equilibration (D = 1 / sqrt(diag)), Gaussian elimination with partial pivoting and x = D z, every product and sum
+// rounded separately.  LAPACK's last bits are not reproduced, so the pair is flagged for the host path:
+//   4         a non-positive diagonal entry (roadmap raises LinAlgError there) or a zero pivot;
+//   8         min |pivot| / max |pivot| of the equilibrated system below 1e-12: the parameters may then be further from
+//             LAPACK's than the contract allows;
+//   flag_bit  a displacement of the h x w order-2 field of the output (model2_value: k_model2_field's arithmetic) within
+//             tol = 1e-9 max(1, sum_k |p_k| m_k) of k + 0.5, m_k = max |phi_k(i, j)| over the field, or |d| >= 30000, or NaN.
+//             The parameters are promised to |dp_k| m_k <= 1e-10 max(1, sum_k |p_k| m_k), so the six terms of a displacement
+//             move it by less than tol: an unflagged field rounds as the host's does.
+// One workgroup per pair.  The augmented system lives in LDS (runtime pivot rows: a private array would go to scratch);
+// one thread per element runs each elimination step, all threads scan the field.
+// ---------------------------------------------------------------------------
+constexpr int SOLVE2_ROWS = 8, SOLVE2_COLS = 10;     // pseudo-perspective: 8 unknowns; quadratic: 6 + two right-hand sides
+
+__device__ __forceinline__ int phi_degree(int k) { return k == 0 ? 0 : k < 3 ? 1 : 2; }        // phi = [1 x y x2 xy y2]
+__device__ __forceinline__ int phi_ypow(int k) { const int d = phi_degree(k); return k - d * (d + 1) / 2; }
+__device__ __forceinline__ int phi_xpow(int k) { return phi_degree(k) - phi_ypow(k); }
+// index of the moment of phi_a phi_b among the 15 (order 1 x y x2 xy y2 x3 x2y xy2 y3 x4 x3y x2y2 xy3 y4)
+__device__ __forceinline__ int moment_of(int a, int b)
+{
+    const int px = phi_xpow(a) + phi_xpow(b), py = phi_ypow(a) + phi_ypow(b), d = px + py;
+    return d * (d + 1) / 2 + py;
+}
+
+__global__ void __launch_bounds__(256) k_solve_model2(const double* sums, int model, int project, int h, int w,
+                                                      double* params_out, int32_t* flags, int flag_bit)
+{
+    __shared__ double a[SOLVE2_ROWS][SOLVE2_COLS];   // [N | rhs], equilibrated and eliminated in place
+    __shared__ double dsc[SOLVE2_ROWS];
+    __shared__ double z[2][SOLVE2_ROWS];
+    __shared__ double p[12];
+    __shared__ int bad;
+    const int pair = blockIdx.x, t = threadIdx.x;
+    const double* M = sums + (long long)pair * 27;
+    const double *sx = M + 15, *sy = M + 21;
+    const bool pp = model == GME_MODEL_PSEUDO_PERSPECTIVE;
+    const int n = pp ? 8 : model == GME_MODEL_QUADRATIC ? 6 : 4, nrhs = pp ? 1 : 2, ncol = n + nrhs;
+    const int tr = t / ncol, tc = t - tr * ncol;                 // this thread's element of the augmented system
+
+    // normal matrix and right-hand sides (roadmap._solve_second_order)
+    if (t == 0) bad = 0;
+    if (tr < n) {
+        double v;
+        if (pp) {
+            // unknowns a0 a1 a2 b0 b1 b2 c1 c2: phi index of row r of r_x (dx) and of r_y (dy), -1 where the row has no term
+            const auto kx = [](int r) { return r < 3 ? r : r == 6 ? 5 : r == 7 ? 4 : -1; };
+            const auto ky = [](int r) { return r >= 3 && r < 6 ? r - 3 : r == 6 ? 4 : r == 7 ? 3 : -1; };
+            const int xa = kx(tr), ya = ky(tr);
+            if (tc < n) {
+                const int xb = kx(tc), yb = ky(tc);
+                const bool hx = xa >= 0 && xb >= 0, hy = ya >= 0 && yb >= 0;
+                const double vx = hx ? M[moment_of(xa, xb)] : 0.0, vy = hy ? M[moment_of(ya, yb)] : 0.0;
+                v = hx && hy ? __dadd_rn(vx, vy) : hx ? vx : vy;
+            } else {
+                v = xa >= 0 && ya >= 0 ? __dadd_rn(sx[xa], sy[ya]) : xa >= 0 ? sx[xa] : sy[ya];
+            }
+        } else {
+            const auto kb = [&](int r) { return model == GME_MODEL_BILINEAR && r == 3 ? 4 : r; };     // bilinear: 1 x y xy
+            v = tc < n ? M[moment_of(kb(tr), kb(tc))] : tc == n ? sx[kb(tr)] : sy[kb(tr)];
+        }
+        a[tr][tc] = v;
+    }
+    __syncthreads();
+    if (t < n) {
+        const double d = a[t][t];
+        if (!(d > 0.0)) atomicOr(&bad, 4);
+        dsc[t] = __ddiv_rn(1.0, __dsqrt_rn(d));
+    }
+    __syncthreads();
+    if (tr < n) a[tr][tc] = tc < n ? __dmul_rn(__dmul_rn(a[tr][tc], dsc[tr]), dsc[tc]) : __dmul_rn(a[tr][tc], dsc[tr]);
+    __syncthreads();
+
+    double pmin = INFINITY, pmax = 0.0;                          // |pivots| (thread 0's copy is used)
+    for (int k = 0; k < n; ++k) {
+        int piv = k;                                             // the first largest |a[r][k]|, as LAPACK's idamax
+        double big = fabs(a[k][k]);
+        for (int r = k + 1; r < n; ++r) {
+            const double v = fabs(a[r][k]);
+            if (v > big) { big = v; piv = r; }
+        }
+        pmin = fmin(pmin, big);
+        pmax = fmax(pmax, big);
+        __syncthreads();                                         // column k read by all before rows move
+        if (piv != k && t < ncol) { const double u = a[k][t]; a[k][t] = a[piv][t]; a[piv][t] = u; }
+        __syncthreads();
+        // row k + 1 + tr: only columns > k change; column k and row k are read, never written, in this step
+        const int r = k + 1 + tr;
+        if (r < n && tc > k) a[r][tc] = __dsub_rn(a[r][tc], __dmul_rn(__ddiv_rn(a[r][k], a[k][k]), a[k][tc]));
+        __syncthreads();
+    }
+    if (t < nrhs) {
+        for (int k = n - 1; k >= 0; --k) {
+            double u = a[k][n + t];
+            for (int c = k + 1; c < n; ++c) u = __dsub_rn(u, __dmul_rn(a[k][c], z[t][c]));
+            z[t][k] = __ddiv_rn(u, a[k][k]);
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        int b = bad;
+        if (pmin == 0.0) b |= 4;
+        if (!(__ddiv_rn(pmin, pmax) >= 1e-12)) b |= 8;
+        for (int k = 0; k < 12; ++k) p[k] = 0.0;
+        if (pp) {
+            for (int k = 0; k < 6; ++k) p[k] = __dmul_rn(z[0][k], dsc[k]);
+            const double c1 = __dmul_rn(z[0][6], dsc[6]), c2 = __dmul_rn(z[0][7], dsc[7]);
+            p[7] = c2; p[9] = c2;                                // a4 = b3 = c2
+            p[8] = c1; p[10] = c1;                               // a5 = b4 = c1
+        } else {
+            for (int r = 0; r < n; ++r) {
+                const int k = model == GME_MODEL_BILINEAR && r == 3 ? 4 : r, slot = k < 3 ? k : k + 3;
+                p[slot] = __dmul_rn(z[0][r], dsc[r]);
+                p[slot + 3] = __dmul_rn(z[1][r], dsc[r]);
+            }
+        }
+        if (project) {                                           // roadmap.project: x, y double per level
+            p[0] = __dmul_rn(p[0], 2.0); p[3] = __dmul_rn(p[3], 2.0);
+            for (int k = 6; k < 12; ++k) p[k] = __dmul_rn(p[k], 0.5);
+        }
+        for (int k = 0; k < 12; ++k) params_out[(long long)pair * 12 + k] = p[k];
+        bad = b;
+    }
+    __syncthreads();
+    const double hm = (double)(h - 1), wm = (double)(w - 1);
+    int near_half = 0;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const double p0 = p[3 * c], p1 = p[3 * c + 1], p2 = p[3 * c + 2], q0 = p[6 + 3 * c], q1 = p[7 + 3 * c], q2 = p[8 + 3 * c];
+        const double scale = fabs(p0) + fabs(p1) * hm + fabs(p2) * wm + fabs(q0) * (hm * hm) + fabs(q1) * (hm * wm) + fabs(q2) * (wm * wm);
+        const double tol = 1e-9 * fmax(1.0, scale);
+        for (int e = t; e < h * w; e += blockDim.x) {
+            const int i = e / w, j = e - i * w;
+            const double d = model2_value(p0, p1, p2, q0, q1, q2, i, j);
+            if (fabs(d - floor(d) - 0.5) <= tol || !(fabs(d) < 30000.0)) near_half = 1;
+        }
+    }
+    if (near_half) atomicOr(&bad, flag_bit);
+    __syncthreads();
+    if (t == 0 && bad) atomicOr(flags + pair, bad);
 }
 
 // ---------------------------------------------------------------------------
@@ -1121,6 +1272,16 @@ int launch_solve3(gme_ctx* ctx, const double* sums, int pairs, int project, int 
 {
     if (pairs == 0) return GME_OK;
     hipLaunchKernelGGL(k_solve3, dim3((unsigned)pairs), dim3(256), 0, ctx->stream, sums, pairs, project, h, w, 1e-9, params_out, flags, flag_bit);
+    GME_HIP_TRY(hipGetLastError());
+    return GME_OK;
+}
+
+int launch_solve_model2(gme_ctx* ctx, const double* sums, int model, int pairs, int project, int h, int w, double* params_out,
+                        int32_t* flags, int flag_bit)
+{
+    if (pairs == 0) return GME_OK;
+    hipLaunchKernelGGL(k_solve_model2, dim3((unsigned)pairs), dim3(256), 0, ctx->stream, sums, model, project, h, w, params_out,
+                       flags, flag_bit);
     GME_HIP_TRY(hipGetLastError());
     return GME_OK;
 }

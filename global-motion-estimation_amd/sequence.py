@@ -449,12 +449,26 @@ class ShardedSequence:
             return lane.seq.read_mv(0, lane.hi - lane.lo)
         return np.concatenate(self._each(run), axis=0)
 
-    def estimate(self, procedure=3, search_window=2):
-        """motion.global_motion_estimation for every local pair -> float64[P_local, 6]."""
+    @staticmethod
+    def _model(model):
+        """None for the reference's affine path (model None or "affine"), else the roadmap.MODELS name; ValueError otherwise."""
+        if model is None or model == "affine":
+            return None
+        if model not in roadmap.MODELS:
+            raise ValueError("unknown motion model %r (choose from %r)" % (model, roadmap.MODELS))
+        return model
+
+    def estimate(self, procedure=3, search_window=2, model=None):
+        """motion.global_motion_estimation for every local pair -> float64[P_local, 6].  ``model``: one of roadmap.MODELS
+        (roadmap.estimate_sequence per lane); the second-order models return float64[P_local, 12]."""
+        model = self._model(model)
         if not self.lanes:
-            return np.zeros((0, 6))
+            return np.zeros((0, 12 if model in roadmap.SECOND_ORDER else 6))
         if self.interleave and len(self.lanes) > 1:
-            return self._interleaved(procedure, search_window, False)[0]
+            return self._interleaved(procedure, search_window, False, model=model)[0]
+        if model is not None:
+            return np.concatenate(self._each(
+                lambda lane: roadmap.estimate_sequence(lane.seq, self.fd, model, procedure, search_window)[:lane.hi - lane.lo]), axis=0)
         return np.concatenate(self._each(
             lambda lane: motion.estimate_sequence(lane.seq, self.fd, procedure, search_window)[:lane.hi - lane.lo]), axis=0)
 
@@ -470,39 +484,54 @@ class ShardedSequence:
                                                           params[lane.lo:lane.hi])[:lane.hi - lane.lo])
         return self._psnr(np.concatenate(sse))
 
-    def estimate_and_compensate(self, procedure=3, search_window=2, exact_psnr=False):
-        """estimate() then compensate() per stream without a join in between -> (params[P,6], psnr[P])."""
-        if not self.lanes:
-            return np.zeros((0, 6)), np.zeros(0)
+    def estimate_and_compensate(self, procedure=3, search_window=2, exact_psnr=False, model=None):
+        """estimate() then compensate() per stream without a join in between -> (params[P,6], psnr[P]).
 
-        if os.environ.get("GME_DEVICE_SOLVE") == "1":
-            got = self._device_solved(procedure, search_window, exact_psnr)
+        ``model``: one of roadmap.MODELS (None or "affine": the reference's path).  The others run the staged calls of their
+        order with roadmap.solve_model / roadmap.project; the second-order models return params[P, 12] and, under
+        GME_DEVICE_SOLVE=1, solve on the device (gme_device_solve2) unless a pair is flagged."""
+        model = self._model(model)
+        order2 = model in roadmap.SECOND_ORDER
+        if not self.lanes:
+            return np.zeros((0, 12 if order2 else 6)), np.zeros(0)
+
+        if os.environ.get("GME_DEVICE_SOLVE") == "1" and (model is None or order2):
+            got = self._device_solved(procedure, search_window, exact_psnr, model=model)
             if got is not None:
-                return got                        # else: a pair sat on a rounding tie (or was singular): the host path below
+                return got                        # else: a pair sat on a rounding tie (or was singular / ill-conditioned): the host path below
 
         if self.interleave and len(self.lanes) > 1:
-            return self._interleaved(procedure, search_window, True, exact_psnr)
+            return self._interleaved(procedure, search_window, True, exact_psnr, model=model)
 
         def run(lane):
             n = lane.hi - lane.lo
+            if model is not None:
+                p = roadmap.estimate_sequence(lane.seq, self.fd, model, procedure, search_window)[:n]
+                comp = lane.seq.compensate2 if order2 else lane.seq.compensate
+                return p, comp(self.fd, int(motion.BBME_BLOCK_SIZE), p)[:n]
             p = motion.estimate_sequence(lane.seq, self.fd, procedure, search_window)[:n]
             return p, lane.seq.compensate(self.fd, int(motion.BBME_BLOCK_SIZE), p)[:n]
         parts = self._each(run)
         return np.concatenate([p for p, _ in parts], axis=0), self._psnr(np.concatenate([s for _, s in parts]), exact_psnr)
 
-    def _device_solved(self, procedure, search_window, exact_psnr=False):
+    def _device_solved(self, procedure, search_window, exact_psnr=False, model=None):
         """estimate_and_compensate() with the 3x3 solves on the device (GME_DEVICE_SOLVE=1, gme_seq_gme_device_solve): every
         lane's whole estimate is queued in one call, one wait per lane.  Parameters are within rtol 1e-10 of the host
         path's (LAPACK's last bits are not reproduced); model fields, masks, compensated frames and PSNR are bit-equal to
         it -- unless the library flags a pair (a model displacement within 1e-9 of a rounding tie, or a singular system):
-        then nothing is returned and the caller runs the host path, which also raises upstream's LinAlgError."""
+        then nothing is returned and the caller runs the host path, which also raises upstream's LinAlgError.
+        A second-order ``model`` solves its own system instead (gme_seq_gme_device_solve2, whose header states the contract;
+        it also flags ill-conditioned systems)."""
         frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
         bs = int(motion.BBME_BLOCK_SIZE)
         lanes = self.lanes
         for lane in lanes:
             lane.seq.set_split_phase(True)
         try:
-            pending = [lane.seq.gme_device_solve(self.fd, bs, frac, procedure, search_window) for lane in lanes]
+            if model is None:
+                pending = [lane.seq.gme_device_solve(self.fd, bs, frac, procedure, search_window) for lane in lanes]
+            else:
+                pending = [lane.seq.gme_device_solve2(model, self.fd, bs, frac, procedure, search_window) for lane in lanes]
             params, sse, clean = [], [], True
             for lane, (p, e, f) in zip(lanes, pending):
                 lane.seq.wait()
@@ -518,29 +547,33 @@ class ShardedSequence:
             return None
         return np.concatenate(params, axis=0), self._psnr(np.concatenate(sse), exact_psnr)
 
-    def _interleaved(self, procedure, search_window, compensate, exact_psnr=False):
+    def _interleaved(self, procedure, search_window, compensate, exact_psnr=False, model=None):
         """estimate() / estimate_and_compensate() for several ranges from one host thread: every stage is queued on
         all streams before the first result is awaited, so range k's projection and 3x3 solves (motion.py:191-207,
         262-282, the same arithmetic as motion.estimate_sequence) run while the other ranges' searches do.
-        -> (params[P, 6], psnr[P] or None)"""
+        ``model`` (roadmap.MODELS, None: affine) selects the stages' order and roadmap.solve_model's solve.
+        -> (params[P, 6] (12 for a second-order model), psnr[P] or None)"""
         frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
         bs = int(motion.BBME_BLOCK_SIZE)
         lanes = self.lanes
+        solve = motion._solve_batch if model is None else (lambda sums: roadmap.solve_model(sums, model))
+        order2 = model in roadmap.SECOND_ORDER
         for lane in lanes:
             lane.seq.set_split_phase(True)
         try:
             # first parameters, their projection and the level-1 fit in one queued call (gme_seq_gme_begin_fit)
-            pending = [lane.seq.gme_begin_fit(self.fd, bs, frac, procedure, search_window)[1] for lane in lanes]
+            pending = [(lane.seq.gme_begin_fit2 if order2 else lane.seq.gme_begin_fit)(self.fd, bs, frac, procedure, search_window)[1]
+                       for lane in lanes]
             for k, lane in enumerate(lanes):
                 lane.seq.wait()
-                p = roadmap.project(motion._solve_batch(pending[k]))     # level 1 solved, projected in float64, level 2 asked for
-                pending[k] = lane.seq.gme_fit(2, p, frac)
+                p = roadmap.project(solve(pending[k]))                    # level 1 solved, projected in float64, level 2 asked for
+                pending[k] = (lane.seq.gme_fit2 if order2 else lane.seq.gme_fit)(2, p, frac)
             params, sse = [None] * len(lanes), [None] * len(lanes)
             for k, lane in enumerate(lanes):
                 lane.seq.wait()
-                params[k] = motion._solve_batch(pending[k])
+                params[k] = solve(pending[k])
                 if compensate:
-                    sse[k] = lane.seq.compensate(self.fd, bs, params[k])
+                    sse[k] = (lane.seq.compensate2 if order2 else lane.seq.compensate)(self.fd, bs, params[k])
             out_sse = []
             for k, lane in enumerate(lanes):
                 if compensate:

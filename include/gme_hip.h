@@ -215,6 +215,30 @@ GME_API int gme_seq_gme_begin_fit2(gme_seq *seq, int frame_distance, int bbme_bl
 GME_API int gme_seq_gme_fit2(gme_seq *seq, int level, const double *params_in, double outlier_fraction, double *sums_out);
 /* gme_seq_compensate (motion.py:289-321, results.py:52-59,109) with the order-2 field of params[P][12] */
 GME_API int gme_seq_compensate2(gme_seq *seq, int frame_distance, int block_size, const double *params, int64_t *sse_out);
+/* Second-order model ids of gme_solve_model2_sums / gme_seq_gme_device_solve2: the indices of roadmap.MODELS.  Any other id
+ * is GME_ERR_ARG. */
+enum { GME_MODEL_BILINEAR = 3, GME_MODEL_PSEUDO_PERSPECTIVE = 4, GME_MODEL_QUADRATIC = 5 };
+/* Opt-in device solve of the second-order normal equations (the order-2 counterpart of gme_solve_fit_sums, below):
+ * sums[P][27] -> params_out[P][12] in the layout above (pseudo-perspective: a4 = b3 = c2, a5 = b4 = c1; if `project`,
+ * roadmap.project: constants x2, second-order terms x1/2) and flags_out[P].  The system is roadmap._solve_second_order's,
+ * Jacobi-equilibrated and solved by Gaussian elimination with partial pivoting.  LAPACK's last bits are not reproduced; with
+ * m_k = max |phi_k(i, j)| over the h x w field (1, h-1, w-1, (h-1)^2, (h-1)(w-1), (w-1)^2) and S = sum_k |p_k| m_k over the six
+ * terms of one displacement, every parameter of an unflagged pair satisfies |p_dev - p_host| m_k <= 1e-10 max(1, S).
+ * flags_out: bit 1 -- a displacement of the h x w order-2 field of the output within 1e-9 max(1, S) of k + 0.5 (or
+ * |d| >= 30000, or NaN); bit 4 -- singular (a non-positive diagonal entry: LinAlgError in roadmap; or a zero pivot); bit 8 --
+ * ill-conditioned (min / max |pivot| of the equilibrated system below 1e-12).  Host pointers. */
+GME_API int gme_solve_model2_sums(gme_ctx *ctx, int model, const double *sums, int pairs, int project, int h, int w,
+                                  double *params_out, int32_t *flags_out);
+/* gme_seq_gme_device_solve for a second-order model: begin_fit2 -> device solve + projection -> fit2(2) -> device solve ->
+ * compensate2 in one call with one host round trip.  params_out[P][12] meets the parameter bound of gme_solve_model2_sums
+ * against the staged path (gme_seq_gme_begin_fit2 -> roadmap.solve_model -> roadmap.project -> gme_seq_gme_fit2(2) ->
+ * roadmap.solve_model -> gme_seq_compensate2) over the final H/bs x W/bs field; for every pair whose flags_out[p] is 0 the
+ * level-2 model field, mask and threshold, the compensated frame and sse_out[p] (may be NULL) are bit-equal to that path's.
+ * flags_out[p]: bit 1 / 2 -- a displacement near a rounding tie in the level-2 field / the final field; bit 4 singular,
+ * bit 8 ill-conditioned, as above: redo that pair through the staged calls.  Split-phase like gme_seq_gme_device_solve. */
+GME_API int gme_seq_gme_device_solve2(gme_seq *seq, int model, int frame_distance, int bbme_block_size, int procedure,
+                                      int search_window, double outlier_fraction, double *params_out, int64_t *sse_out,
+                                      int32_t *flags_out);
 /* Opt-in one-call form of begin_fit -> solve -> fit(2) -> solve -> compensate with the two 3x3 solves of
  * motion.py:262-264,280-282 on the device: one host round trip per estimate instead of three.  LAPACK's last bits are not
  * reproduced: params_out[P][6] is within rtol 1e-10 of the staged path's (motion.py:109-136); model fields, masks,
