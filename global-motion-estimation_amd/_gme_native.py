@@ -94,6 +94,9 @@ _SIGNATURES = {
     "gme_seq_gme_device_solve": (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, _c_f64p, _c_i64p, _c_i32p]),
     "gme_solve_model2_sums": (_i, [_vp, _i, _c_f64p, _i, _i, _i, _i, _c_f64p, _c_i32p]),
     "gme_seq_gme_device_solve2": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_double, _c_f64p, _c_i64p, _c_i32p]),
+    "gme_seq_direct_eval": (_i, [_vp, _i, _i, _c_f64p, ctypes.c_double, _c_f64p, _c_i64p, _c_f64p, _c_f64p]),
+    "gme_seq_refine_projective": (_i, [_vp, _i, _c_f64p, ctypes.c_double, _i, _c_f64p, _c_i32p]),
+    "gme_seq_compensate_projective": (_i, [_vp, _i, _c_f64p, _c_i64p]),
     "gme_seq_read_compensated": (_i, [_vp, _i, _c_u8p]),
     "gme_seq_read_compensated_range": (_i, [_vp, _i, _i, _c_u8p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
@@ -627,6 +630,45 @@ class Sequence:
                                                   _p(flags, _c_i32p)), self.lib)
         self._gme = (frame_distance, bbme_block_size, pairs)
         return params, sse, flags
+
+    # ---- direct projective refinement (gme_direct.hip, direct.py)
+    def _projective(self, frame_distance, params):
+        if getattr(self, "_split", False):
+            raise RuntimeError("the projective calls are blocking: the sequence is in split-phase mode")
+        pairs = self.N - int(frame_distance)
+        if pairs < 0:
+            raise IndexError("frame_distance %d needs at least %d frames" % (frame_distance, frame_distance + 1))
+        return pairs, np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(pairs, 8))
+
+    def direct_eval(self, frame_distance, level, params, outlier_fraction=0.1):
+        """One evaluation per pair at params float64[P, 8] in level-`level` coordinates with a fresh threshold
+        (gme_seq_direct_eval) -> dict(threshold float64[P], counts int64[P, 2] = n_valid, n_in, cost float64[P],
+        sums float64[P, 44] = JtJ upper triangle | Jte)."""
+        pairs, p = self._projective(frame_distance, params)
+        out = {"threshold": np.zeros(pairs), "counts": np.zeros((pairs, 2), np.int64), "cost": np.zeros(pairs),
+               "sums": np.zeros((pairs, 44))}
+        _check(self.lib.gme_seq_direct_eval(self.handle, int(frame_distance), int(level), _p(p, _c_f64p), float(outlier_fraction),
+                                            _p(out["threshold"], _c_f64p), _p(out["counts"], _c_i64p), _p(out["cost"], _c_f64p),
+                                            _p(out["sums"], _c_f64p)), self.lib)
+        return out
+
+    def refine_projective(self, frame_distance, init, outlier_fraction=0.1, max_iters=10):
+        """Direct projective refinement of every pair from init float64[P, 8] (full resolution; gme_seq_refine_projective)
+        -> (params float64[P, 8], flags int32[P])."""
+        pairs, p = self._projective(frame_distance, init)
+        params = np.zeros((pairs, 8))
+        flags = np.zeros(pairs, np.int32)
+        _check(self.lib.gme_seq_refine_projective(self.handle, int(frame_distance), _p(p, _c_f64p), float(outlier_fraction),
+                                                  int(max_iters), _p(params, _c_f64p), _p(flags, _c_i32p)), self.lib)
+        return params, flags
+
+    def compensate_projective(self, frame_distance, params):
+        """Dense compensation under params float64[P, 8] (gme_seq_compensate_projective) -> sse int64[P]; the frames are
+        read with read_compensated(_range)."""
+        pairs, p = self._projective(frame_distance, params)
+        sse = np.zeros(pairs, np.int64)
+        _check(self.lib.gme_seq_compensate_projective(self.handle, int(frame_distance), _p(p, _c_f64p), _p(sse, _c_i64p)), self.lib)
+        return sse
 
     def read_compensated(self, pair):
         out = np.empty((self.H, self.W), dtype=np.uint8)

@@ -491,6 +491,7 @@ extern "C" void gme_seq_destroy(gme_seq* s)
     if (s->comp_params) hipFree(s->comp_params);
     if (s->comp_mf) hipFree(s->comp_mf);
     if (s->synth_canvas) hipFree(s->synth_canvas);
+    if (s->direct) hipFree(s->direct);
     if (s->summary) hipFree(s->summary);
     if (s->gathered) hipFree(s->gathered);
     if (s->ready) hipEventDestroy(s->ready);
@@ -1025,6 +1026,35 @@ static int gme_flush_bbme(gme_seq* s, int level)
     return GME_OK;
 }
 
+// pyramid planes (utils.py:34-51): level 1 = pyrDown(level 2), level 0 = pyrDown(level 1), sized for the sequence
+static int seq_levels(gme_seq* s)
+{
+    for (int l = 1; l >= 0; --l) {
+        const Plane& src = s->level[l + 1];
+        if (!s->level[l].ptr) {
+            const int rc = plane_alloc(s->ctx, &s->level[l], s->N_cap, (src.H + 1) / 2, (src.W + 1) / 2);
+            if (rc) return rc;
+        }
+    }
+    return GME_OK;
+}
+
+// ... and their contents, unless they are current
+static int seq_pyramids(gme_seq* s)
+{
+    if (!s->pyramids_valid) {
+        for (int l = 1; l >= 0; --l) {
+            Plane src = s->level[l + 1], dst = s->level[l];       // views over the frames in use (gme_seq_set_frames)
+            src.count = dst.count = s->N;
+            const int rc = launch_pyrdown(s->ctx, src, dst);
+            if (rc) return rc;
+        }
+        s->pyramids_valid = true;
+        s->sqbox_valid[0] = s->sqbox_valid[1] = false;
+    }
+    return GME_OK;
+}
+
 // pyramids, buffers, dense field and first parameters (motion.py:123-128,160-188) of a staged run; the context is locked
 static int gme_begin_common(gme_seq* s, int fd, int bbme_bs, int procedure, int sw)
 {
@@ -1033,14 +1063,8 @@ static int gme_begin_common(gme_seq* s, int fd, int bbme_bs, int procedure, int 
     GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "frame_distance %d needs at least %d frames", fd, fd + 1);
     GME_REQUIRE(bbme_bs >= 1, GME_ERR_ARG, "block_size %d", bbme_bs);
     const int pairs = s->N - fd;
-    // pyramids (utils.py:34-51): level 1 = pyrDown(level 2), level 0 = pyrDown(level 1)
-    for (int l = 1; l >= 0; --l) {
-        const Plane& src = s->level[l + 1];
-        if (!s->level[l].ptr) {
-            rc = plane_alloc(ctx, &s->level[l], s->N_cap, (src.H + 1) / 2, (src.W + 1) / 2);
-            if (rc) return rc;
-        }
-    }
+    rc = seq_levels(s);
+    if (rc) return rc;
     // argument checks for the three BBME runs before anything is launched
     rc = bbme_check_args(s->level[0].H, s->level[0].W, 2, 2, GME_SEARCH_DIAMOND, GME_NORM_MSE);
     if (rc) return rc;
@@ -1048,16 +1072,8 @@ static int gme_begin_common(gme_seq* s, int fd, int bbme_bs, int procedure, int 
         rc = bbme_check_args(s->level[l].H, s->level[l].W, bbme_bs, sw, procedure, GME_NORM_MSE);
         if (rc) return rc;
     }
-    if (!s->pyramids_valid) {
-        for (int l = 1; l >= 0; --l) {
-            Plane src = s->level[l + 1], dst = s->level[l];       // views over the frames in use (gme_seq_set_frames)
-            src.count = dst.count = s->N;
-            rc = launch_pyrdown(ctx, src, dst);
-            if (rc) return rc;
-        }
-        s->pyramids_valid = true;
-        s->sqbox_valid[0] = s->sqbox_valid[1] = false;
-    }
+    rc = seq_pyramids(s);
+    if (rc) return rc;
     const int cap_pairs = s->N_cap - fd;                   // buffers hold the sequence's full count: gme_seq_set_frames never reallocates
     if (s->gme_alloc_pairs < (size_t)cap_pairs || s->gme_bs != bbme_bs) {
         rc = alloc_fit(s->fit[0], cap_pairs, s->level[0].H / 2, s->level[0].W / 2, false);
@@ -1515,4 +1531,102 @@ extern "C" int gme_seq_gme_device_solve2(gme_seq* s, int model, int fd, int bbme
 {
     return seq_device_solve(s, 2, model, "gme_seq_gme_device_solve2", fd, bbme_bs, procedure, sw, outlier_fraction, params_out,
                             sse_out, flags_out);
+}
+
+// ---------------------------------------------------------------------------
+// Direct projective refinement (gme_direct.hip): pyramids if stale, parameters up, every launch
+// queued, results down, one wait.
+// ---------------------------------------------------------------------------
+static int direct_begin(gme_seq* s, const char* who, int fd, const double* params)
+{
+    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "%s: frame_distance %d needs at least %d frames", who, fd, fd + 1);
+    int rc = seq_levels(s);
+    if (rc) return rc;
+    rc = seq_pyramids(s);
+    if (rc) return rc;
+    const int pairs = s->N - fd;
+    double *in, *out, *ev;
+    int32_t* fl;
+    rc = direct_io(s, pairs, &in, &out, &fl, &ev);
+    if (rc) return rc;
+    if (pairs > 0) GME_HIP_TRY(hipMemcpyAsync(in, params, (size_t)pairs * 8 * sizeof(double), hipMemcpyHostToDevice, s->ctx->stream));
+    return GME_OK;
+}
+
+extern "C" int gme_seq_direct_eval(gme_seq* s, int fd, int level, const double* params_in, double outlier_fraction,
+                                   double* threshold_out, int64_t* counts_out, double* cost_out, double* sums_out)
+{
+    GME_REQUIRE(s != nullptr && params_in != nullptr, GME_ERR_ARG, "gme_seq_direct_eval: null pointer");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(level >= 0 && level <= 2, GME_ERR_ARG, "gme_seq_direct_eval: level %d (0 .. 2)", level);
+    GME_REQUIRE(outlier_fraction >= 0.0 && outlier_fraction < 1.0, GME_ERR_ARG, "gme_seq_direct_eval: outlier_fraction %g", outlier_fraction);
+    int rc = direct_begin(s, "gme_seq_direct_eval", fd, params_in);
+    if (rc) return rc;
+    const int pairs = s->N - fd;
+    if (pairs == 0) return GME_OK;
+    rc = launch_direct_eval(s, fd, level, pairs, outlier_fraction);
+    if (rc) return rc;
+    double *in, *out, *ev;
+    int32_t* fl;
+    rc = direct_io(s, pairs, &in, &out, &fl, &ev);
+    if (rc) return rc;
+    std::vector<double> rows((size_t)pairs * 48);
+    GME_HIP_TRY(hipMemcpyAsync(rows.data(), ev, rows.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    rc = ctx_finish(ctx);
+    if (rc) return rc;
+    for (int p = 0; p < pairs; ++p) {
+        const double* r = rows.data() + (size_t)p * 48;
+        if (threshold_out) threshold_out[p] = r[0];
+        if (counts_out) { counts_out[2 * p] = (int64_t)r[1]; counts_out[2 * p + 1] = (int64_t)r[2]; }
+        if (cost_out) cost_out[p] = r[3];
+        if (sums_out) memcpy(sums_out + (size_t)p * 44, r + 4, 44 * sizeof(double));
+    }
+    return GME_OK;
+}
+
+extern "C" int gme_seq_refine_projective(gme_seq* s, int fd, const double* init, double outlier_fraction, int max_iters,
+                                         double* params_out, int32_t* flags_out)
+{
+    GME_REQUIRE(s != nullptr && init != nullptr && params_out != nullptr && flags_out != nullptr, GME_ERR_ARG,
+                "gme_seq_refine_projective: null pointer");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(outlier_fraction >= 0.0 && outlier_fraction < 1.0, GME_ERR_ARG, "gme_seq_refine_projective: outlier_fraction %g",
+                outlier_fraction);
+    GME_REQUIRE(max_iters >= 1 && max_iters <= 1000, GME_ERR_ARG, "gme_seq_refine_projective: max_iters %d (1 .. 1000)", max_iters);
+    int rc = direct_begin(s, "gme_seq_refine_projective", fd, init);
+    if (rc) return rc;
+    const int pairs = s->N - fd;
+    if (pairs == 0) return GME_OK;
+    rc = launch_direct_refine(s, fd, pairs, outlier_fraction, max_iters);
+    if (rc) return rc;
+    double *in, *out, *ev;
+    int32_t* fl;
+    rc = direct_io(s, pairs, &in, &out, &fl, &ev);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(params_out, out, (size_t)pairs * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(flags_out, fl, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
+extern "C" int gme_seq_compensate_projective(gme_seq* s, int fd, const double* params, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr && params != nullptr, GME_ERR_ARG, "gme_seq_compensate_projective: null pointer");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = direct_begin(s, "gme_seq_compensate_projective", fd, params);
+    if (rc) return rc;
+    const int pairs = s->N - fd;
+    rc = ensure_comp(s, fd, pairs);
+    if (rc) return rc;
+    if (pairs == 0) return GME_OK;
+    double *in, *out, *ev;
+    int32_t* fl;
+    rc = direct_io(s, pairs, &in, &out, &fl, &ev);
+    if (rc) return rc;
+    rc = launch_compensate_proj(s, fd, pairs, in);
+    if (rc) return rc;
+    if (sse_out) GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
 }

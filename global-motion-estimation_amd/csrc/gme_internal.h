@@ -129,6 +129,8 @@ struct gme_seq {
     size_t summary_bytes = 0;
     double* gathered = nullptr;          // [world][n_max][6]
     size_t gathered_bytes = 0;
+    void* direct = nullptr;              // gme_direct.hip: per-pair refinement state, histograms, slabs and parameters
+    size_t direct_bytes = 0;
     uint8_t* synth_canvas = nullptr;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -198,6 +200,57 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 #endif
 }
 
+// The small symmetric systems of the device solves (k_solve_model2, gme_kernels.hip; k_direct_state, gme_direct.hip): the n x n
+// normal matrix in a[0:n][0:n] with nrhs <= 2 right-hand sides in columns n .. n + nrhs - 1, held in LDS, solved by the
+// threads t = threadIdx.x of one workgroup (at least n * (n + nrhs) of them).  Jacobi equilibration D N D z = D rhs with
+// dsc = D = 1 / sqrt(diag) (a non-positive diagonal ORs 4 into *bad), then Gaussian elimination with partial pivoting (the
+// first largest |a[r][k]|, as LAPACK's idamax) and back substitution into z[rhs][0:n]; x = z * dsc.  *pmin / *pmax: the
+// smallest and largest |pivot|.  Every operation is rounded on its own (*_rn).  Ends with a barrier.
+constexpr int SOLVE2_ROWS = 8, SOLVE2_COLS = 10;     // pseudo-perspective / projective: 8 unknowns; quadratic: 6 + two right-hand sides
+__device__ __forceinline__ void equilibrated_solve(double (&a)[SOLVE2_ROWS][SOLVE2_COLS], double (&dsc)[SOLVE2_ROWS],
+                                                   double (&z)[2][SOLVE2_ROWS], int n, int nrhs, int t, int* bad,
+                                                   double* pmin_out, double* pmax_out)
+{
+    const int ncol = n + nrhs, tr = t / ncol, tc = t - tr * ncol;  // this thread's element of the augmented system
+    if (t < n) {
+        const double d = a[t][t];
+        if (!(d > 0.0)) atomicOr(bad, 4);
+        dsc[t] = __ddiv_rn(1.0, __dsqrt_rn(d));
+    }
+    __syncthreads();
+    if (tr < n) a[tr][tc] = tc < n ? __dmul_rn(__dmul_rn(a[tr][tc], dsc[tr]), dsc[tc]) : __dmul_rn(a[tr][tc], dsc[tr]);
+    __syncthreads();
+
+    double pmin = INFINITY, pmax = 0.0;
+    for (int k = 0; k < n; ++k) {
+        int piv = k;
+        double big = fabs(a[k][k]);
+        for (int r = k + 1; r < n; ++r) {
+            const double v = fabs(a[r][k]);
+            if (v > big) { big = v; piv = r; }
+        }
+        pmin = fmin(pmin, big);
+        pmax = fmax(pmax, big);
+        __syncthreads();                                         // column k read by all before rows move
+        if (piv != k && t < ncol) { const double u = a[k][t]; a[k][t] = a[piv][t]; a[piv][t] = u; }
+        __syncthreads();
+        // row k + 1 + tr: only columns > k change; column k and row k are read, never written, in this step
+        const int r = k + 1 + tr;
+        if (r < n && tc > k) a[r][tc] = __dsub_rn(a[r][tc], __dmul_rn(__ddiv_rn(a[r][k], a[k][k]), a[k][tc]));
+        __syncthreads();
+    }
+    if (t < nrhs) {
+        for (int k = n - 1; k >= 0; --k) {
+            double u = a[k][n + t];
+            for (int c = k + 1; c < n; ++c) u = __dsub_rn(u, __dmul_rn(a[k][c], z[t][c]));
+            z[t][k] = __ddiv_rn(u, a[k][k]);
+        }
+    }
+    __syncthreads();
+    *pmin_out = pmin;
+    *pmax_out = pmax;
+}
+
 typedef const uint32_t* SqTable;
 __device__ __forceinline__ SqTable sq_table(const uint32_t* slot, int, int) { return slot; }
 __device__ __forceinline__ uint32_t sq1(SqTable t, long long idx) { return t[idx]; }
@@ -252,6 +305,17 @@ int launch_compensate(gme_ctx* ctx, const uint8_t* frames, int64_t frame_stride,
                       int64_t cur_stride, unsigned long long* sse);
 int launch_sse(gme_ctx* ctx, const uint8_t* a, int64_t a_stride, int a_pitch, const uint8_t* b,
                int64_t b_stride, int b_pitch, int pairs, int H, int W, unsigned long long* sse);
+
+// ---- gme_direct.hip: direct projective refinement ---------------------------------------------
+// device blocks of the sequence's workspace for `pairs` pairs: in[P][8] (parameters the calls below read), out[P][8],
+// flags[P] (refinement results), eval[P][48] = threshold, n_valid, n_in, cost, sums[44] (gme_seq_direct_eval)
+int direct_io(gme_seq* s, int pairs, double** in, double** out, int32_t** flags, double** eval);
+// the whole refinement of in[] (full-resolution start) into out[] / flags[], every launch queued, no wait
+int launch_direct_refine(gme_seq* s, int fd, int pairs, double outlier_fraction, int max_iters);
+// one evaluation of in[] (level-`level` coordinates) with a fresh threshold into eval[]
+int launch_direct_eval(gme_seq* s, int fd, int level, int pairs, double outlier_fraction);
+// compensation of every pair under params[P][8] (device) into s->comp, squared errors into s->sse
+int launch_compensate_proj(gme_seq* s, int fd, int pairs, const double* params);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -479,7 +479,6 @@ __global__ void __launch_bounds__(256) k_model2_field(const double* params, int 
 // One workgroup per pair.  The augmented system lives in LDS (runtime pivot rows: a private array would go to scratch);
 // one thread per element runs each elimination step, all threads scan the field.
 // ---------------------------------------------------------------------------
-constexpr int SOLVE2_ROWS = 8, SOLVE2_COLS = 10;     // pseudo-perspective: 8 unknowns; quadratic: 6 + two right-hand sides
 
 __device__ __forceinline__ int phi_degree(int k) { return k == 0 ? 0 : k < 3 ? 1 : 2; }        // phi = [1 x y x2 xy y2]
 __device__ __forceinline__ int phi_ypow(int k) { const int d = phi_degree(k); return k - d * (d + 1) / 2; }
@@ -530,41 +529,8 @@ __global__ void __launch_bounds__(256) k_solve_model2(const double* sums, int mo
         a[tr][tc] = v;
     }
     __syncthreads();
-    if (t < n) {
-        const double d = a[t][t];
-        if (!(d > 0.0)) atomicOr(&bad, 4);
-        dsc[t] = __ddiv_rn(1.0, __dsqrt_rn(d));
-    }
-    __syncthreads();
-    if (tr < n) a[tr][tc] = tc < n ? __dmul_rn(__dmul_rn(a[tr][tc], dsc[tr]), dsc[tc]) : __dmul_rn(a[tr][tc], dsc[tr]);
-    __syncthreads();
-
-    double pmin = INFINITY, pmax = 0.0;                          // |pivots| (thread 0's copy is used)
-    for (int k = 0; k < n; ++k) {
-        int piv = k;                                             // the first largest |a[r][k]|, as LAPACK's idamax
-        double big = fabs(a[k][k]);
-        for (int r = k + 1; r < n; ++r) {
-            const double v = fabs(a[r][k]);
-            if (v > big) { big = v; piv = r; }
-        }
-        pmin = fmin(pmin, big);
-        pmax = fmax(pmax, big);
-        __syncthreads();                                         // column k read by all before rows move
-        if (piv != k && t < ncol) { const double u = a[k][t]; a[k][t] = a[piv][t]; a[piv][t] = u; }
-        __syncthreads();
-        // row k + 1 + tr: only columns > k change; column k and row k are read, never written, in this step
-        const int r = k + 1 + tr;
-        if (r < n && tc > k) a[r][tc] = __dsub_rn(a[r][tc], __dmul_rn(__ddiv_rn(a[r][k], a[k][k]), a[k][tc]));
-        __syncthreads();
-    }
-    if (t < nrhs) {
-        for (int k = n - 1; k >= 0; --k) {
-            double u = a[k][n + t];
-            for (int c = k + 1; c < n; ++c) u = __dsub_rn(u, __dmul_rn(a[k][c], z[t][c]));
-            z[t][k] = __ddiv_rn(u, a[k][k]);
-        }
-    }
-    __syncthreads();
+    double pmin, pmax;                                           // |pivots| (thread 0's copy is used)
+    equilibrated_solve(a, dsc, z, n, nrhs, t, &bad, &pmin, &pmax);
     if (t == 0) {
         int b = bad;
         if (pmin == 0.0) b |= 4;

@@ -7,6 +7,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py bbme    -p <video|frame dir> -fi 13 -bs 16 -sw 16 -sp 0     # bbme.py main
     python gme_cli.py results -v <name under resources/videos> -f 1 [--model quadratic] [--suggest]    # results.py main
     python gme_cli.py suggest -p <video|frame dir> [-fi 1] [-f 1]                 # parameter heuristics
+    python gme_cli.py projective -p <video|frame dir> -fi 1 [-f 1]                # direct projective refinement of one pair
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -43,8 +44,39 @@ def _parser():
     s.add_argument("-p", "--video-path", dest="path", type=str, required=True)
     s.add_argument("-fi", "--frame-index", dest="fi", type=int, default=1)
     s.add_argument("-f", "--frame-distance", dest="fd", type=int, default=1)
+    j = sub.add_parser("projective", help="direct projective refinement of one frame pair (roadmap.refine_projective, DESIGN.md 7b)")
+    j.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    j.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the current frame")
+    j.add_argument("-f", "--frame-distance", dest="fd", type=int, default=1)
+    j.add_argument("--outlier-fraction", type=float, default=0.1)
+    j.add_argument("--max-iters", type=int, default=10)
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
+
+
+def _projective(args):
+    """h, flags and the PSNR of the block-affine and of the projective compensation of one pair."""
+    import numpy as np
+    import _gme_native
+    import motion
+    import roadmap
+    import sequence
+    import utils
+    frames = utils.get_video_frames(args.path)
+    prev, cur = _gme_native.as_frame(frames[args.fi - args.fd]), _gme_native.as_frame(frames[args.fi])
+    seq = motion._pair_sequence(prev, cur)
+    bs = int(motion.BBME_BLOCK_SIZE)
+    affine = motion.estimate_sequence(seq, 1)
+    sse_affine = seq.compensate(1, bs, affine)
+    h, flags = roadmap.refine_sequence(seq, 1, roadmap.affine_to_projective(affine, bs), args.outlier_fraction, args.max_iters)
+    sse_proj = seq.compensate_projective(1, h)
+    psnr = sequence.psnr_from_sse(np.concatenate([sse_affine, sse_proj]), *prev.shape)
+    print("frames {} -> {} of shape {}".format(args.fi - args.fd, args.fi, prev.shape))
+    print("h: {}".format(" ".join("%.9g" % x for x in h[0])))
+    print("flags: {}".format(int(flags[0])))
+    print("psnr block-affine: {:.4f} dB".format(psnr[0]))
+    print("psnr projective:   {:.4f} dB".format(psnr[1]))
+    return {"h": h[0], "flags": int(flags[0]), "psnr_affine": float(psnr[0]), "psnr_projective": float(psnr[1])}
 
 
 def main(argv=None):
@@ -84,6 +116,8 @@ def main(argv=None):
         for k, v in out.items():
             print("{}: {}".format(k, v))
         return out
+    if args.command == "projective":
+        return _projective(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")

@@ -38,7 +38,13 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    at 1/16 (``model_field`` evaluates at the raw block indices ``(i, j)``).  Projection between the levels doubles the
    constants, keeps the linear terms and halves the second-order ones (``project``: x, y double per level).  The normal
    matrices are Jacobi-equilibrated before the solve (raw condition number ~6e9 at 720p, ~3e11 at 1080p for the 6x6
-   quadratic system; ~6e2 scaled).  The projective model proper is nonlinear and not offered.
+   quadratic system; ~6e2 scaled).  The projective model is nonlinear and is not one of these indirect models: it has its
+   own direct estimator below.
+
+   **Projective (direct).**  ``refine_projective`` / ``refine_sequence`` start from the indirect affine estimate
+   (``affine_to_projective``) and refine an 8-parameter perspective warp on the pixels of the pyramids, coarse to fine, by
+   Gauss-Newton under a truncated quadratic (k_direct_sums / k_direct_state, csrc/gme_direct.hip; host definition
+   direct.py), with dense sub-pixel compensation under it.  It is a separate estimator, not an entry of ``MODELS``.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.
@@ -202,6 +208,39 @@ def estimate_sequence(seq, frame_distance=1, model="affine", procedure=3, search
 def global_motion_estimation(previous, current, model="affine"):
     """motion.global_motion_estimation (motion.py:109-136) with a selectable model."""
     return estimate_sequence(motion._pair_sequence(previous, current), 1, model)[0]      # the cached two-frame sequence of motion.py
+
+
+def affine_to_projective(params, block_size=16):
+    """The indirect affine estimate float64[..., 6] (or a second-order model's 12, of which the first six are used) ->
+    the projective start float64[..., 8] of the same displacement field (direct.affine_to_projective)."""
+    import direct
+    return direct.affine_to_projective(params, block_size)
+
+
+def projective_to_level(h, level):
+    """Full-resolution projective parameters -> those of pyramid level ``level`` (0 coarsest, 2 full resolution): h2, h5
+    scaled by 2^-(2-level), h6, h7 by its inverse.  Exact in float64."""
+    import direct
+    return direct.projective_to_level(h, level)
+
+
+def refine_sequence(seq, frame_distance=1, init=None, outlier_fraction=0.1, max_iters=10, procedure=3, search_window=2):
+    """Direct projective refinement of every pair of a device-resident sequence (gme_seq_refine_projective) ->
+    (h float64[P, 8], flags int32[P]).  ``init`` float64[P, 8] defaults to the indirect affine estimate
+    (motion.estimate_sequence, affine_to_projective at motion.BBME_BLOCK_SIZE)."""
+    if init is None:
+        init = affine_to_projective(motion.estimate_sequence(seq, frame_distance, procedure, search_window),
+                                    int(motion.BBME_BLOCK_SIZE))
+    return seq.refine_projective(frame_distance, init, outlier_fraction, max_iters)
+
+
+def refine_projective(previous, current, init=None, outlier_fraction=0.1, max_iters=10):
+    """One pair: the projective warp from ``current`` back into ``previous`` -> (h float64[8], flags).  ``init`` float64[8]
+    defaults to the indirect affine estimate."""
+    seq = motion._pair_sequence(previous, current)
+    h, flags = refine_sequence(seq, 1, None if init is None else np.asarray(init, dtype=np.float64).reshape(1, 8),
+                               outlier_fraction, max_iters)
+    return h[0], int(flags[0])
 
 
 def suggest_parameters(previous, current):

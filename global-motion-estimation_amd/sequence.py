@@ -586,6 +586,21 @@ class ShardedSequence:
         p_all = np.concatenate([p[:lane.hi - lane.lo] for p, lane in zip(params, lanes)], axis=0)
         return p_all, (self._psnr(np.concatenate(out_sse), exact_psnr) if compensate else None)
 
+    def estimate_projective(self, procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10, exact_psnr=False):
+        """Direct projective refinement of every local pair from its indirect affine estimate, and the
+        dense compensation under the result -> (h float64[P_local, 8], flags int32[P_local], psnr float64[P_local]).  One
+        host thread per lane; the rows gather like any other (gather, k = 8)."""
+        if not self.lanes:
+            return np.zeros((0, 8)), np.zeros(0, np.int32), np.zeros(0)
+
+        def run(lane):
+            n = lane.hi - lane.lo
+            h, flags = roadmap.refine_sequence(lane.seq, self.fd, None, outlier_fraction, max_iters, procedure, search_window)
+            return h[:n], flags[:n], lane.seq.compensate_projective(self.fd, h)[:n]
+        parts = self._each(run)
+        return (np.concatenate([h for h, _, _ in parts], axis=0), np.concatenate([f for _, f, _ in parts]),
+                self._psnr(np.concatenate([e for _, _, e in parts]), exact_psnr))
+
     def read_compensated(self, pair):
         lane, k = self._lane_of(pair)
         return lane.seq.read_compensated(k)

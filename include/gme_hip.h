@@ -239,6 +239,38 @@ GME_API int gme_solve_model2_sums(gme_ctx *ctx, int model, const double *sums, i
 GME_API int gme_seq_gme_device_solve2(gme_seq *seq, int model, int frame_distance, int bbme_block_size, int procedure,
                                       int search_window, double outlier_fraction, double *params_out, int64_t *sse_out,
                                       int32_t *flags_out);
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Direct projective refinement (host definition: direct.py).  An opt-in estimator beside the
+ * indirect models, working on the pixels of the resident pyramids.  Parameters are float64[8] h, H = [[h0 h1 h2] [h3 h4 h5]
+ * [h6 h7 1]]: the pixel (u = column, v = row) of the CURRENT frame samples the PREVIOUS frame at u' = (h0 u + h1 v + h2) / d,
+ * v' = (h3 u + h4 v + h5) / d, d = h6 u + h7 v + 1 (OpenCV's warpPerspective with WARP_INVERSE_MAP) -- image axes, not the
+ * reference's "x = row".  Identity [1 0 0 0 1 0 0 0].  At pyramid level L, h2 and h5 are scaled by s = 2^-(2-L) and h6, h7
+ * by 1/s.  Prediction: prev sampled bilinearly at (u', v') where 0 <= u' <= W_L-1 and 0 <= v' <= H_L-1 (valid pixels), the
+ * far tap clamped on the last row / column; warp, weights and residual e = cur - prediction in float64, one rounding per
+ * operation, bit-identical to direct.py.  Objective of a level: a truncated quadratic with threshold t fixed at the level's
+ * start (the upper edge of the first 1/16-wide bin of the |e| histogram at which the count reaches
+ * ceil((1 - outlier_fraction) n_valid)); cost = (sum over |e| < t of e^2 + (n_valid - n_in) t^2) / n_valid.  These calls
+ * build the pyramids if they are stale and cover the pairs (p, p + frame_distance) of the frames in use.  Host pointers.
+ * ------------------------------------------------------------------------------------------------------------------- */
+/* One evaluation per pair at params_in[P][8] in level-`level` coordinates (0 coarsest .. 2 full resolution) with a fresh
+ * threshold: threshold_out[P], counts_out[P][2] = n_valid, n_in, cost_out[P], sums_out[P][44] = the upper triangle of JtJ
+ * row by row (36) then Jte (8) over the inliers, J the derivative of the prediction.  threshold and
+ * counts are exact; cost and sums are float64 sums in another order than direct.py's (relative 1e-9 of the sums of absolute
+ * terms).  Any output pointer may be NULL. */
+GME_API int gme_seq_direct_eval(gme_seq *seq, int frame_distance, int level, const double *params_in, double outlier_fraction,
+                                double *threshold_out, int64_t *counts_out, double *cost_out, double *sums_out);
+/* Gauss-Newton with step halving (at most 4 halvings, at most max_iters steps per level, a level ends when a step moves no
+ * corner by more than 1e-3 level pixels) over levels 0 -> 1 -> 2 from init[P][8] (full resolution), every launch queued in
+ * this call, one wait -> params_out[P][8], flags_out[P]: 1 singular / ill-conditioned system, 2 fewer than a quarter of a
+ * level's pixels valid, 4 d <= 0 at a frame corner, 8 no improvement over init at full resolution, 16 max_iters reached at
+ * level 2 (informational).  Under 1, 2, 4 or 8 params_out is init.  Deterministic; a pair's result does not depend on the
+ * other pairs of the call.  0 <= outlier_fraction < 1, 1 <= max_iters <= 1000. */
+GME_API int gme_seq_refine_projective(gme_seq *seq, int frame_distance, const double *init, double outlier_fraction,
+                                      int max_iters, double *params_out, int32_t *flags_out);
+/* Dense compensation under params[P][8]: comp[v][u] = floor(bilinear(prev)(u', v') + 0.5) at valid pixels, prev[v][u]
+ * elsewhere (the reference keeps the previous frame's pixel, motion.py:289-321); the frames are read back with
+ * gme_seq_read_compensated(_range); sse_out[P] = sum (cur - comp)^2 (may be NULL). */
+GME_API int gme_seq_compensate_projective(gme_seq *seq, int frame_distance, const double *params, int64_t *sse_out);
 /* Opt-in one-call form of begin_fit -> solve -> fit(2) -> solve -> compensate with the two 3x3 solves of
  * motion.py:262-264,280-282 on the device: one host round trip per estimate instead of three.  LAPACK's last bits are not
  * reproduced: params_out[P][6] is within rtol 1e-10 of the staged path's (motion.py:109-136); model fields, masks,
