@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W            # N=1 directly (no torch in the process)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py ... --dump-outputs DIR                  # also writes what the last timed step returned (timed_outputs)
+    python bench.py ... --full                              # also every check and secondary figure listed below
 
 One "step" = one pass of the hot path over this rank's batch of frame pairs, frames already resident
 in HBM.  Default workload = BASELINE.json configs[1]: 720x480 synthetic luma, bs=16, sw=16, exhaustive
@@ -15,7 +16,9 @@ search runs behind the collective), and the GME sequence config gathers its para
 (gme_shard_gather).  Barriers and the max-over-ranks time go through the same communicator
 (gme_comm_*, include/gme_hip.h).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes the outputs if asked and prints
+the headline (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) with the `config` it ran; nothing else
+runs.  With --full the line also carries these objects (oracle checks, extra launches, baselines, other configs):
   roofline      HBM view of the dominant kernel: algorithmic bytes / HIP-event kernel time, measured live
   issue         the same kernel against its real bound, the VALU issue rate: busy fraction and
                 instructions per wave from the committed PMC profile of this command (labelled as such)
@@ -23,7 +26,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
   content_sweep the same kernel on other content (real frames, noise, flat): pairs/s and the share of
                 candidate patches the elimination bound left for exact evaluation; content_sweep_mse likewise
   secondary     (default command only) the other BASELINE configs at a handful of steps each, so that the one
-                driver-run line carries configs[2] and configs[3] too: pairs/s, ms/step, sampled oracle parity
+                default --full line carries configs[2] and configs[3] too: pairs/s, ms/step, sampled oracle parity
   cpu_baseline  the NumPy oracle (reference loop structure) on one host core over a bounded sample
 """
 import argparse
@@ -547,8 +550,9 @@ def rank_report(comm, rate_local, gather_s, steps):
 
 
 def measure(opt, ctx, comm, rank, world):
-    """One bench line: set the workload up, time `opt.steps` steps, check parity; -> dict on rank 0, None elsewhere.
-    `opt`: config, content, pairs, steps, warmup, cpu_baseline, content_sweep, pcie, parity_budget_s."""
+    """One bench line: set the workload up, time `opt.steps` steps; with `opt.full` also check parity and add the secondary
+    figures -> dict on rank 0, None elsewhere.
+    `opt`: config, content, pairs, steps, warmup, full, cpu_baseline, content_sweep, pcie, parity_budget_s."""
     import _gme_native as native
     cfg = CONFIGS[opt.config]
     H, W, bs, sw, proc, pnorm, seed, label = cfg
@@ -682,10 +686,10 @@ def measure(opt, ctx, comm, rank, world):
         kernel_ms = 1e3 * elapsed / max(opt.steps, 1)     # several streams: the whole step on the wall clock
     # N > 1: the slowest and the fastest rank (their own pairs over their own clock between the two barriers), and what the
     # step's exchange costs: host-timed around the gather where it blocks; where it is queued behind the search (RCCL,
-    # block matching) five gathers are timed alone after the loop
+    # block matching) five gathers are timed alone after the loop (--full)
     rep = rank_report(comm, B * opt.steps / elapsed, last.get("gather_s"), opt.steps)
     per_rank, gather_ms = rep["per_rank_pairs_per_s"], rep["gather_ms_per_step"]
-    if seq is not None and distributed and comm.rccl:
+    if seq is not None and distributed and comm.rccl and opt.full:
         comm.barrier()
         t_g = time.perf_counter()
         for k in range(5):
@@ -714,6 +718,39 @@ def measure(opt, ctx, comm, rank, world):
     dumped = None
     if getattr(opt, "dump_outputs", None):         # read back before anything below launches on the same buffers
         dumped = dump_outputs(opt.dump_outputs, timed_outputs(seq, shard, last, proc))
+
+    total_pairs = (shard.n_pairs_total if proc == -3 else world * B) * opt.steps
+    value = total_pairs / elapsed
+    if proc == -3:
+        exchange = "all-gather of float64[7] rows (6 parameters + PSNR) per pair at the end of a step (gme_shard_gather)"
+    elif distributed and not gme:
+        exchange = ("all-gather of one float64[6] summary row per pair at the end of every step, device to device, queued behind "
+                    "the search (gme_seq_mv_summary_gather)" if comm.rccl else
+                    "all-gather of one float64[6] summary row per pair at the end of every step, through the host (gme_seq_mv_summary)")
+    else:
+        exchange = "none in this run"
+    out = {
+        "metric": "frame-pairs/s + achieved HBM GB/s, 720x480 bs=16 sw=16 exhaustive"
+                  if opt.config == "exh720" else "frame-pairs/s, " + opt.config,
+        "value": value, "unit": "frame-pairs/s", "n_gpus": world, "steps": opt.steps, "warmup": opt.warmup,
+        "ms_per_step": 1e3 * elapsed / opt.steps, "higher_is_better": True,
+        "scaling": "strong" if proc == -3 else "weak",
+        "vs_baseline": None, "dtype": "u8", "data": extra.get("content") or ("synthetic" if opt.content == "synthetic" else opt.content),
+        "config": {"workload": label, "pairs_per_step_per_gpu": B, "frame_distance": fd,
+                   "sharding": "frame pairs across ranks, no data-path collective",
+                   "streams_per_gpu": len(shard.lanes) if shard is not None else 1,
+                   "collective": comm.kind, "exchange": exchange, "rccl_reports": comm.rccl_reports,
+                   "per_rank_pairs_per_s": per_rank, "gather_ms_per_step": gather_ms,
+                   "multi_gpu_measured_by_builder": False},
+    }
+    if dumped:
+        out["outputs_dumped"] = dumped
+    if comm.degraded:
+        out["degraded"] = comm.degraded             # `value` then is NOT the product path's exchange; bench.py exits non-zero
+    if not opt.full:
+        release()
+        return out
+
     sys.path.insert(0, os.path.join(REPO, "tests"))
     from helpers import c_oracle, mv_summary_rows, oracle_results_flow
 
@@ -796,41 +833,13 @@ def measure(opt, ctx, comm, rank, world):
             parity["ok"] = parity["ok"] and parity["pair0_equals_reference_golden"]
     parity["seconds"] = round(time.perf_counter() - t_par, 2)
 
-    total_pairs = (shard.n_pairs_total if proc == -3 else world * B) * opt.steps
-    value = total_pairs / elapsed
     abytes = algorithmic_bytes(H, W, bs, gme) * B
     achieved = abytes / (kernel_ms * 1e-3) / 1e9
-    if proc == -3:
-        exchange = "all-gather of float64[7] rows (6 parameters + PSNR) per pair at the end of a step (gme_shard_gather)"
-    elif distributed and not gme:
-        exchange = ("all-gather of one float64[6] summary row per pair at the end of every step, device to device, queued behind "
-                    "the search (gme_seq_mv_summary_gather)" if comm.rccl else
-                    "all-gather of one float64[6] summary row per pair at the end of every step, through the host (gme_seq_mv_summary)")
-    else:
-        exchange = "none in this run"
-    out = {
-        "metric": "frame-pairs/s + achieved HBM GB/s, 720x480 bs=16 sw=16 exhaustive"
-                  if opt.config == "exh720" else "frame-pairs/s, " + opt.config,
-        "value": value, "unit": "frame-pairs/s", "n_gpus": world, "steps": opt.steps, "warmup": opt.warmup,
-        "ms_per_step": 1e3 * elapsed / opt.steps, "higher_is_better": True,
-        "scaling": "strong" if proc == -3 else "weak",
-        "vs_baseline": None, "dtype": "u8", "data": extra.get("content") or ("synthetic" if opt.content == "synthetic" else opt.content),
-        "config": {"workload": label, "pairs_per_step_per_gpu": B, "frame_distance": fd,
-                   "sharding": "frame pairs across ranks, no data-path collective",
-                   "streams_per_gpu": len(shard.lanes) if shard is not None else 1,
-                   "collective": comm.kind, "exchange": exchange, "rccl_reports": comm.rccl_reports,
-                   "per_rank_pairs_per_s": per_rank, "gather_ms_per_step": gather_ms,
-                   "multi_gpu_measured_by_builder": False},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                     "kernel": info["plan"] if not gme else "whole step (all kernels + host solves)",
-                     "kernel_ms_per_launch": kernel_ms, "algorithmic_bytes_per_launch": abytes},
-        "parity": parity,
-    }
-    if dumped:
-        out["outputs_dumped"] = dumped
-    if comm.degraded:
-        out["degraded"] = comm.degraded             # `value` then is NOT the product path's exchange; bench.py exits non-zero
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                       "kernel": info["plan"] if not gme else "whole step (all kernels + host solves)",
+                       "kernel_ms_per_launch": kernel_ms, "algorithmic_bytes_per_launch": abytes}
+    out["parity"] = parity
     if distributed and not gme:
         out["roofline"]["note"] = "kernel_ms_per_launch spans the step's search, summary kernel and all-gather (HIP events on the stream)"
     if gme:
@@ -1059,12 +1068,12 @@ def measure(opt, ctx, comm, rank, world):
 
 
 def secondary_block(ctx, comm):
-    """The other BASELINE configs at a handful of steps each (same code path as `--config <name>`, fewer steps, a
-    smaller parity sample, no CPU baseline): the driver's one default run then carries configs[2] / configs[3] numbers."""
+    """The other BASELINE configs at a handful of steps each (same code path as `--config <name> --full`, fewer steps, a
+    smaller parity sample, no CPU baseline): the one default --full run then carries configs[2] / configs[3] numbers."""
     block = {}
     t0 = time.perf_counter()
     for name, pairs, steps, warmup, par_s, par_min in SECONDARY:
-        opt = types.SimpleNamespace(config=name, content="synthetic", pairs=pairs, steps=steps, warmup=warmup,
+        opt = types.SimpleNamespace(config=name, content="synthetic", pairs=pairs, steps=steps, warmup=warmup, full=True,
                                     cpu_baseline=False, content_sweep=False, pcie=False, parity_budget_s=par_s, parity_min_pairs=par_min)
         t1 = time.perf_counter()
         comm1 = comm
@@ -1113,10 +1122,13 @@ def main():
     ap.add_argument("--config", default="exh720", choices=sorted(CONFIGS))
     ap.add_argument("--content", default="synthetic", choices=["synthetic", "race", "pan240seq", "pan240x2", "noise", "flat"],
                     help="frame content of the exhaustive / walk configs (uploaded from the host unless synthetic)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also check parity against the C oracle and add the roofline, issue, content sweep, "
+                         "PCIe, CPU baseline and (default command) secondary figures; --no-* below leave some of them out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-content-sweep", action="store_true")
     ap.add_argument("--no-pcie", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs the default line also times")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs the default --full line also times")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, at most "
                          "%d MB in all; seeded inputs, so two builds can be compared output for output)" % (DUMP_LIMIT_BYTES // 10 ** 6))
@@ -1138,13 +1150,13 @@ def main():
     ctx = native.Context(local % max(ndev, 1))          # rehearsals may put several ranks on one card
     comm = Comm(ctx, rank, world, local % max(ndev, 1))
     opt = types.SimpleNamespace(config=args.config, content=args.content, pairs=args.pairs, steps=args.steps, warmup=args.warmup,
-                                cpu_baseline=not args.no_cpu_baseline, content_sweep=not args.no_content_sweep,
+                                full=args.full, cpu_baseline=not args.no_cpu_baseline, content_sweep=not args.no_content_sweep,
                                 pcie=not args.no_pcie, parity_budget_s=PARITY_BUDGET_S, dump_outputs=args.dump_outputs)
     out = measure(opt, ctx, comm, rank, world)
     if rank == 0:
         default_command = (args.config == "exh720" and args.content == "synthetic" and world == 1 and args.pairs is None
                            and comm.kind == "none")
-        if default_command and not args.no_secondary:
+        if default_command and args.full and not args.no_secondary:
             out["secondary"] = secondary_block(ctx, comm)
         print(json.dumps(out), flush=True)
     degraded = comm.degraded

@@ -11,7 +11,7 @@ for v in $1; do
   cp tools/microbench/libgme_$v.so $L
   for cc in $2; do
     c=${cc%%:*}; content=""; [ "$cc" != "$c" ] && content="--content ${cc#*:}"
-    echo -n "$v $cc $4 "; timeout -k 10 200 python3 bench.py --config $c $content --no-cpu-baseline --no-pcie --no-content-sweep --no-secondary $4 2>/dev/null | python3 -c "
+    echo -n "$v $cc $4 "; timeout -k 10 200 python3 bench.py --full --config $c $content --no-cpu-baseline --no-pcie --no-content-sweep --no-secondary $4 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); e=d.get('elimination',{})
 print(round(d['value']), d['parity']['ok'], 'surviving', e.get('surviving_fraction'), 'listed', e.get('listed_fraction_before_ordered_rounds'), 'redo', e.get('tiles_redone_by_brute_force'))"

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in $V; do
   cp $ROOT/tools/microbench/libgme_$v.so $L
   rm -rf /tmp/abt_$v
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abt_$v -- python3 $ROOT/bench.py --no-cpu-baseline --no-pcie --no-content-sweep "$@" > /tmp/abt_$v.log 2>&1 || echo "$v: run failed"
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abt_$v -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-pcie --no-content-sweep "$@" > /tmp/abt_$v.log 2>&1 || echo "$v: run failed"
   python3 - <<PY
 import csv,glob,re
 for f in glob.glob("/tmp/abt_$v/*/*kernel_stats.csv"):

@@ -9,7 +9,7 @@ for v in $1; do
   for cc in $2; do
     c=${cc%%:*}; content=""; [ "$cc" != "$c" ] && content="--content ${cc#*:}"
     echo -n "$v $cc $4 "
-    if [ "$v" = "-" ]; then timeout -k 10 200 python3 bench.py --config $c $content --no-cpu-baseline --no-secondary --no-pcie --no-content-sweep $4 2>/dev/null > /tmp/o.json; else env ${v//,/ } timeout -k 10 200 python3 bench.py --config $c $content --no-cpu-baseline --no-secondary --no-pcie --no-content-sweep $4 2>/dev/null > /tmp/o.json; fi
+    if [ "$v" = "-" ]; then timeout -k 10 200 python3 bench.py --full --config $c $content --no-cpu-baseline --no-secondary --no-pcie --no-content-sweep $4 2>/dev/null > /tmp/o.json; else env ${v//,/ } timeout -k 10 200 python3 bench.py --full --config $c $content --no-cpu-baseline --no-secondary --no-pcie --no-content-sweep $4 2>/dev/null > /tmp/o.json; fi
     python3 -c "
 import json
 d=json.loads(open('/tmp/o.json').read()); e=d.get('elimination',{})

@@ -3,7 +3,7 @@ TAG=$1; O=gpurun_out/$TAG
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $O
 for c in $2; do
-  timeout -k 10 400 python3 bench.py --config $c --no-secondary 2>$O/${c}_bench.err > $O/${TAG}_${c}_bench.json || { echo "$c failed"; tail -3 $O/${c}_bench.err; continue; }
+  timeout -k 10 400 python3 bench.py --full --config $c --no-secondary 2>$O/${c}_bench.err > $O/${TAG}_${c}_bench.json || { echo "$c failed"; tail -3 $O/${c}_bench.err; continue; }
   python3 - <<PY
 import json
 d = json.loads(open("$O/${TAG}_${c}_bench.json").read())

@@ -3,7 +3,7 @@ TAG=${1:-r04_final}; O=gpurun_out/$TAG
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $O
 t0=$(date +%s)
-timeout -k 10 600 python3 bench.py > $O/${TAG}_default_bench.json 2> $O/default_bench.err || { echo "default bench failed"; tail -5 $O/default_bench.err; }
+timeout -k 10 600 python3 bench.py --full > $O/${TAG}_default_bench.json 2> $O/default_bench.err || { echo "default bench failed"; tail -5 $O/default_bench.err; }
 echo "default bench: $(( $(date +%s) - t0 )) s"
 python3 - <<PY
 import json

@@ -21,7 +21,7 @@ PY
 }
 if [ "$PART" = tests ]; then
   timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; tail -2 $O/pytest_gpu.log
-  timeout -k 10 600 python3 bench.py > $O/${TAG}_default_bench.json 2> $O/default_bench.err || { echo "default bench failed"; tail -5 $O/default_bench.err; }
+  timeout -k 10 600 python3 bench.py --full > $O/${TAG}_default_bench.json 2> $O/default_bench.err || { echo "default bench failed"; tail -5 $O/default_bench.err; }
   line default $O/${TAG}_default_bench.json
   python3 - <<PY
 import json
@@ -35,10 +35,10 @@ print("  cpu_baseline", {k: v for k, v in d["cpu_baseline"].items() if k != "sam
 print("  pcie", {k: v for k, v in d.get("pcie_inclusive", {}).items() if k != "note"})
 PY
   echo "== rehearsals: 2 gloo ranks on one GPU (rows through the host); 1 rank over the C ABI's RCCL (device-to-device gather per step)"
-  GME_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 1 2>$O/gloo2.err | tail -1 > $O/${TAG}_gloo2_bench.json
-  GME_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29544 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-content-sweep --no-pcie 2>$O/rccl1.err > $O/${TAG}_rccl1_bench.json
+  GME_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 1 2>$O/gloo2.err | tail -1 > $O/${TAG}_gloo2_bench.json
+  GME_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29544 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-content-sweep --no-pcie 2>$O/rccl1.err > $O/${TAG}_rccl1_bench.json
   for c in exh720 seq1080; do
-    GME_BENCH_FORCE_DIST=1 GME_BENCH_FRAMES=400 MASTER_ADDR=127.0.0.1 MASTER_PORT=29545 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout -k 10 300 python3 bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-content-sweep --no-pcie 2>/dev/null > $O/rccl1_$c.json; line rccl1_$c $O/rccl1_$c.json
+    GME_BENCH_FORCE_DIST=1 GME_BENCH_FRAMES=400 MASTER_ADDR=127.0.0.1 MASTER_PORT=29545 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout -k 10 300 python3 bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-content-sweep --no-pcie 2>/dev/null > $O/rccl1_$c.json; line rccl1_$c $O/rccl1_$c.json
   done
   python3 - <<PY
 import json
@@ -54,16 +54,16 @@ PY
   bash tools/scale_run.sh exh720 20 3 $O/scale 2>&1 | tail -3
 elif [ "$PART" = benches ]; then
   for c in exh720mse exh720mse_vec exh1080 exh1080mse exh1080mse_mfma dia720 dia720mse tss720 tdl720 gme720 gme720dev gme1080 gme1080exh seq1080 tss_bs4sw2 gme_pan240_bs12fd5; do
-    timeout -k 10 400 python3 bench.py --config $c --no-secondary 2>$O/${c}_bench.err > $O/${TAG}_${c}_bench.json || { echo "$c failed"; tail -3 $O/${c}_bench.err; continue; }
+    timeout -k 10 400 python3 bench.py --full --config $c --no-secondary 2>$O/${c}_bench.err > $O/${TAG}_${c}_bench.json || { echo "$c failed"; tail -3 $O/${c}_bench.err; continue; }
     line $c $O/${TAG}_${c}_bench.json
   done
-  GME_BENCH_STREAMS=1 timeout -k 10 300 python3 bench.py --config gme720 --no-secondary --no-cpu-baseline --no-pcie 2>/dev/null > $O/${TAG}_gme720_1stream_bench.json; line gme720_1stream $O/${TAG}_gme720_1stream_bench.json
-  GME_EXH_BRUTE=1 timeout -k 10 300 python3 bench.py --no-secondary --no-cpu-baseline --no-content-sweep --no-pcie 2>/dev/null > $O/${TAG}_exh720_brute_bench.json; line exh720_brute $O/${TAG}_exh720_brute_bench.json
-  GME_BENCH_STREAMS=1 GME_DEVICE_SOLVE=1 timeout -k 10 300 python3 bench.py --config gme720 --no-secondary --no-cpu-baseline --no-pcie 2>/dev/null > $O/${TAG}_gme720_1stream_devsolve_bench.json; line gme720_1stream_devsolve $O/${TAG}_gme720_1stream_devsolve_bench.json
-  GME_SEA_QUOTA=0 timeout -k 10 300 python3 bench.py --content pan240x2 --no-secondary --no-cpu-baseline --no-pcie --no-content-sweep 2>/dev/null > $O/${TAG}_exh720_pan240x2_noc2_bench.json; line exh720_pan240x2_noc2 $O/${TAG}_exh720_pan240x2_noc2_bench.json
+  GME_BENCH_STREAMS=1 timeout -k 10 300 python3 bench.py --full --config gme720 --no-secondary --no-cpu-baseline --no-pcie 2>/dev/null > $O/${TAG}_gme720_1stream_bench.json; line gme720_1stream $O/${TAG}_gme720_1stream_bench.json
+  GME_EXH_BRUTE=1 timeout -k 10 300 python3 bench.py --full --no-secondary --no-cpu-baseline --no-content-sweep --no-pcie 2>/dev/null > $O/${TAG}_exh720_brute_bench.json; line exh720_brute $O/${TAG}_exh720_brute_bench.json
+  GME_BENCH_STREAMS=1 GME_DEVICE_SOLVE=1 timeout -k 10 300 python3 bench.py --full --config gme720 --no-secondary --no-cpu-baseline --no-pcie 2>/dev/null > $O/${TAG}_gme720_1stream_devsolve_bench.json; line gme720_1stream_devsolve $O/${TAG}_gme720_1stream_devsolve_bench.json
+  GME_SEA_QUOTA=0 timeout -k 10 300 python3 bench.py --full --content pan240x2 --no-secondary --no-cpu-baseline --no-pcie --no-content-sweep 2>/dev/null > $O/${TAG}_exh720_pan240x2_noc2_bench.json; line exh720_pan240x2_noc2 $O/${TAG}_exh720_pan240x2_noc2_bench.json
   for c in noise flat race pan240x2 pan240seq; do
     for cfg in exh720 exh720mse exh720mse_vec; do
-      timeout -k 10 300 python3 bench.py --config $cfg --content $c --no-secondary --no-cpu-baseline --no-pcie 2>/dev/null > $O/${TAG}_${cfg}_${c}_bench.json; line ${cfg}_$c $O/${TAG}_${cfg}_${c}_bench.json
+      timeout -k 10 300 python3 bench.py --full --config $cfg --content $c --no-secondary --no-cpu-baseline --no-pcie 2>/dev/null > $O/${TAG}_${cfg}_${c}_bench.json; line ${cfg}_$c $O/${TAG}_${cfg}_${c}_bench.json
     done
   done
 else

@@ -4,7 +4,7 @@
 O=${1:-gpurun_out/gloo2_seq1080}; mkdir -p $O
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 GME_BENCH_BACKEND=gloo GME_BENCH_FRAMES=${GME_BENCH_FRAMES:-401} timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29588 bench.py --gpus 2 --config seq1080 --steps 3 --warmup 1 2>$O/stderr.log | tail -1 > $O/gloo2_seq1080_bench.json
+  --master-addr 127.0.0.1 --master-port 29588 bench.py --full --gpus 2 --config seq1080 --steps 3 --warmup 1 2>$O/stderr.log | tail -1 > $O/gloo2_seq1080_bench.json
 python3 - <<PY
 import json
 d = json.loads(open("$O/gloo2_seq1080_bench.json").read())

@@ -14,7 +14,7 @@ for v in $LIBS; do
     O=$ROOT/gpurun_out/$TAG/${v}_${cc/:/_}; mkdir -p $O
     for C in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU"; do
       N=$(echo $C | tr ' ' '_' | cut -c1-30)
-      timeout -k 10 200 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$N -- python3 $ROOT/bench.py --config $c $content --no-cpu-baseline --no-content-sweep --no-pcie --no-secondary --steps 3 --warmup 1 > $O/pmc_$N.log 2>&1 || echo "pmc failed $v $cc"
+      timeout -k 10 200 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$N -- python3 $ROOT/bench.py --full --config $c $content --no-cpu-baseline --no-content-sweep --no-pcie --no-secondary --steps 3 --warmup 1 > $O/pmc_$N.log 2>&1 || echo "pmc failed $v $cc"
     done
     echo "== $v $cc"; python3 $ROOT/tools/pmc_summary.py $O "$KERN" | grep -v "^#" | awk '{print $(NF-2), $NF}' | tr '\n' ' '; echo
   done

@@ -17,10 +17,10 @@ for N in 1 2 4 8; do
   PORT=$((PORT + 1))
   F="$OUT/scale_${CONFIG}_N${N}.json"
   if [ "$N" = 1 ]; then
-    timeout -k 10 900 python3 bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --config $CONFIG --no-secondary > "$F" 2> "$F.err"
+    timeout -k 10 900 python3 bench.py --full --gpus 1 --steps $STEPS --warmup $WARMUP --config $CONFIG --no-secondary > "$F" 2> "$F.err"
   else
     timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT \
-      bench.py --gpus $N --steps $STEPS --warmup $WARMUP --config $CONFIG > "$F" 2> "$F.err"
+      bench.py --full --gpus $N --steps $STEPS --warmup $WARMUP --config $CONFIG > "$F" 2> "$F.err"
   fi
   rc=$?
   [ $rc -ne 0 ] && { echo "N=$N failed (rc $rc): $(tail -3 "$F.err")"; break; }
