@@ -406,17 +406,14 @@ __global__ void __launch_bounds__(384) k_exh_dot16(FastDev d)
     dot16_block<R>(d, win, pair, brow, bcol0, (int)threadIdx.x);
 }
 
-#ifndef REDO_KS5
-// column groups per pass of the R = 5 MSE body: 2 -> 128 VGPRs, 4 waves per SIMD; 1 -> 96 VGPRs, 5 waves (both: no spill, no scratch).
+// Column groups per pass of the R = 5 MSE body: 2 -> 128 VGPRs, 4 waves per SIMD; 1 -> 96 VGPRs, 5 waves (both: no spill, no scratch).
 // Same box, 128 pairs of 1080p noise, sw 32: 6.29 k pairs/s with 2, 6.01 k with 1 (the fifth wave does not pay for three more
 // passes over the window), 4.37 k for round 3's one-pass body (215 VGPRs spilled to 192 bytes of scratch per lane).
-#define REDO_KS5 2
-#endif
 // The work-loop form of the two bodies above.  The anchors stay scalar here too (constant address space, see
 // as_constant): with plain global loads the compiler moved them to VGPRs inside the loop (86-128 per wave), round 2
 // staged them in LDS instead (82 / 117 VGPRs: 5 / 4 waves per SIMD).
 template <int R, bool MSE>
-__global__ void __launch_bounds__(1024, (MSE && (R == 4 || (R == 5 && REDO_KS5 == 1)) ? 5 : 4)) k_exh_redo16(FastDev d, RedoDev r)
+__global__ void __launch_bounds__(1024, (MSE && R == 4 ? 5 : 4)) k_exh_redo16(FastDev d, RedoDev r)
 {
     extern __shared__ uint32_t win[];
     __shared__ uint32_t item_s;
@@ -442,7 +439,7 @@ __global__ void __launch_bounds__(1024, (MSE && (R == 4 || (R == 5 && REDO_KS5 =
         if (ok) stage_window(d, win, d.cur + (long long)pair * d.plane_stride, bcol0, brow * 16, tid);
         __syncthreads();
         if (ok) {
-            if (MSE) dot16_block<R, (R >= 5 ? REDO_KS5 : R >= 3 ? 2 : R)>(d, win, pair, brow, bcol0, tid);
+            if (MSE) dot16_block<R, (R >= 3 ? 2 : R)>(d, win, pair, brow, bcol0, tid);
             else qsad16_block<R>(d, win, pair, brow, bcol0, tid);
         }
         __syncthreads();                                   // the next item restages `win` and redraws item_s
@@ -457,10 +454,7 @@ __global__ void __launch_bounds__(1024, (MSE && (R == 4 || (R == 5 && REDO_KS5 =
 //   S(y)   = S(y-1) + h(y+15) - h(y-1), the last 16 h vectors held in a register ring (the row
 //            loop is unrolled in groups of 16 so that the ring indices are compile-time).
 // Each chunk re-walks 15 warm-up rows (1 byte per pixel, cheap next to the 4-byte outputs).
-#ifndef SQ_CHUNK_ROWS
-#define SQ_CHUNK_ROWS 64
-#endif
-constexpr int SQ_CHUNK = SQ_CHUNK_ROWS;
+constexpr int SQ_CHUNK = 64;
 
 // SGN: the squares of (b - 128) instead of b -- the table of the MFMA search (bbme_mfma.hip), whose int8 operands are
 // the frames' bytes with the top bit flipped

@@ -37,49 +37,11 @@
 // search windows the kernel takes without being asked (GME_EXH_MFMA unset): up to this one.  At sw 32 it is content-independent
 // (31 k pairs/s at 1080p on noise against 6.3 k) but 8 % behind the elimination kernel on the synthetic pan of configs[3]
 // (31.5 k against 34.4 k): opt-in there (GME_EXH_MFMA=1).
-#ifndef GME_EXH_MFMA_AUTO_SW
-#define GME_EXH_MFMA_AUTO_SW 16
-#endif
-// blocks per workgroup (sw <= 16 / wider), see the sweep in DESIGN.md
-#ifndef MFMA_TC_SMALL
-#define MFMA_TC_SMALL 4
-#endif
-#ifndef MFMA_TC_LARGE
-#define MFMA_TC_LARGE 4
-#endif
-// table reads of a pass's first tile column before the correlation (costs 12-20 registers = a wave per SIMD: slower, measured)
-#ifndef MFMA_EARLY_TABLE
-#define MFMA_EARLY_TABLE 0
-#endif
-// the next anchor row group's B-operand dwords read a row group ahead: 10 registers, 88-95 VGPRs instead of 78-81 = 5
-// instead of 6 waves per SIMD at sw 16 (same box, 1x4 tiles: 397.8 k against 428.9 k pairs/s with it off)
-#ifndef MFMA_BOP_PREFETCH
-#define MFMA_BOP_PREFETCH 0
-#endif
-// Waves per SIMD decide this kernel (the unified file holds VGPRs + AGPRs; the accumulators live in AGPRs).  At sw <= 16:
-// window operands single-buffered and the accumulator tiles pinned by an empty asm after every step -> 45 + 48 registers =
-// 5 waves (double-buffered, unpinned: 77 + 48 = 4 waves; same box 415.4 k -> 429.1 k pairs/s).  At sw 32 neither form gets
-// under the 128 registers of 4 waves and double buffering is worth 5 % (32.7 k against 31.1 k): -1 = that choice by NT.
-#ifndef MFMA_PIN_ACC
-#define MFMA_PIN_ACC -1
-#endif
-#ifndef MFMA_WQ_DOUBLE
-#define MFMA_WQ_DOUBLE -1
-#endif
-#ifndef MFMA_STAGE_PREFETCH
-#define MFMA_STAGE_PREFETCH 1
-#endif
-// tile columns per pass (XS) at sw <= 16 / wider
-#ifndef MFMA_XS_SMALL
-#define MFMA_XS_SMALL 3
-#endif
-#ifndef MFMA_XS_LARGE
-#define MFMA_XS_LARGE 2
-#endif
-// block rows a workgroup walks (1: 386 k, 6: 404-421 k, 30: 409-421 k pairs/s at 720x480, same box)
-#ifndef MFMA_ROWS_PER_WG
-#define MFMA_ROWS_PER_WG 6
-#endif
+constexpr int AUTO_SW = 16;
+// blocks per workgroup at every window, see the sweep in DESIGN.md (GME_MFMA_TILE=1xC overrides)
+constexpr int TC_DEFAULT = 4;
+// block rows a workgroup walks (1: 386 k, 6: 404-421 k, 30: 409-421 k pairs/s at 720x480, same box; GME_MFMA_ROWS overrides)
+constexpr int ROWS_PER_WG = 6;
 
 namespace {
 
@@ -168,10 +130,12 @@ __device__ __forceinline__ void mfma_pass(const MfmaBlock& k, const __amdgpu_buf
                 out[i] = __builtin_amdgcn_raw_buffer_load_b32(rs, k.tlane + ((16 * ty + i) * k.pitch + 16 * (TX0 + tx)) * 4, 0, 0);
         }
     };
-    if (MFMA_EARLY_TABLE) table_reads(0, tb[0]);
     constexpr int STEPS = 4 * NT;
-    constexpr bool WQ_DOUBLE = MFMA_WQ_DOUBLE < 0 ? NT > 3 : MFMA_WQ_DOUBLE != 0;
-    constexpr bool PIN_ACC = MFMA_PIN_ACC < 0 ? NT <= 3 : MFMA_PIN_ACC != 0;
+    // Waves per SIMD decide this kernel (the unified file holds VGPRs + AGPRs; the accumulators live in AGPRs).  At sw <= 16:
+    // window operands single-buffered and the accumulator tiles pinned by an empty asm after every step -> 45 + 48 registers =
+    // 5 waves (double-buffered, unpinned: 77 + 48 = 4 waves; same box 415.4 k -> 429.1 k pairs/s).  At sw 32 neither form
+    // gets under the 128 registers of 4 waves and double buffering is worth 5 % (32.7 k against 31.1 k).
+    constexpr bool PIN_ACC = NT <= 3, WQ_DOUBLE = NT > 3;
     v4i acc[NT][TXN];
 #pragma unroll
     for (int ty = 0; ty < NT; ++ty)
@@ -200,7 +164,6 @@ __device__ __forceinline__ void mfma_pass(const MfmaBlock& k, const __amdgpu_buf
             const uint8_t* wrow = wcol + 4 * (4 * ty1 + rg1) * PITCH;
 #pragma unroll
             for (int xi = 0; xi <= TXN; ++xi) wq[(st + 1) & 1][xi] = *(const u32x4*)(wrow + 16 * xi);
-            if (MFMA_BOP_PREFETCH && ty == 0 && rg + 1 < 4) { bop_read(k, 0, rg + 1, raw[0]); bop_read(k, 1, rg + 1, raw[1]); }
         }
         if (WQ_DOUBLE) __builtin_amdgcn_sched_barrier(0);             // the next step's reads are in flight before this one's MFMAs
 #pragma unroll
@@ -214,8 +177,10 @@ __device__ __forceinline__ void mfma_pass(const MfmaBlock& k, const __amdgpu_buf
 #pragma unroll
             for (int xi = 0; xi < TXN; ++xi) asm volatile("" : "+a"(acc[ty][xi]));
         }
+        // the next row group's B operand is read here, not a row group ahead: that prefetch held 10 more registers, 88-95
+        // VGPRs instead of 78-81 = 5 instead of 6 waves per SIMD at sw 16 (same box, 1x4 tiles: 397.8 k against 428.9 k pairs/s)
         if (ty == NT - 1 && rg + 1 < 4) {
-            if (!MFMA_BOP_PREFETCH) { bop_read(k, 0, rg + 1, raw[0]); bop_read(k, 1, rg + 1, raw[1]); }
+            bop_read(k, 0, rg + 1, raw[0]); bop_read(k, 1, rg + 1, raw[1]);
             bop[0] = bop_cut(k, 0, raw[0]); bop[1] = bop_cut(k, 1, raw[1]);
         }
     }
@@ -227,7 +192,7 @@ __device__ __forceinline__ void mfma_pass(const MfmaBlock& k, const __amdgpu_buf
     inner = k.interior ? 1 : 0;
     asm volatile("" : "+s"(inner));
     const bool interior = inner != 0;
-    if (!MFMA_EARLY_TABLE) table_reads(0, tb[0]);
+    table_reads(0, tb[0]);                // here, not before the correlation: that cost 12-20 registers = a wave per SIMD (measured)
 #pragma unroll
     for (int t = 0; t < TXN * NT; ++t) {
         const int tx = t / NT, ty = t - tx * NT;
@@ -262,7 +227,7 @@ __device__ __forceinline__ void mfma_pass(const MfmaBlock& k, const __amdgpu_buf
 // Registers decide this kernel's speed (latencies are covered by waves, not by one wave's schedule).  An occupancy
 // attribute does not help -- asked for 5 or 6 waves the scheduler first builds its usual pressure and then spills 33-67
 // registers; what keeps the count down is in the code: row groups outer (two B operands live), no operand prefetch, the
-// opaque lane indices of the row loop, one tile's table reads at a time, pinned accumulators (see MFMA_PIN_ACC).
+// opaque lane indices of the row loop, one tile's table reads at a time, pinned accumulators (see PIN_ACC in mfma_pass).
 // tests/test_host.py holds the sw 16 instance to 5 waves.
 template <int NT, int XS, int TC>
 __global__ void __launch_bounds__(64 * TC) k_exh_mfma16(MfmaDev d)
@@ -334,7 +299,7 @@ __global__ void __launch_bounds__(64 * TC) k_exh_mfma16(MfmaDev d)
             a2 = wave_sum_u32(__builtin_amdgcn_udot4(a8 ^ FLIP, a8 ^ FLIP, 0u, false)) - 256u * wave_sum_u32(__builtin_amdgcn_udot4(a8 ^ FLIP, 0x01010101u, 0u, false)) + 256u * 16384u;
         }
         __syncthreads();
-        if (MFMA_STAGE_PREFETCH && it + 1 < nrows) stage_load(brow + 1);     // in flight while this row is searched
+        if (it + 1 < nrows) stage_load(brow + 1);     // in flight while this row is searched
         if (mine) {
             // opaque per row: everything derived from the lane's (n, g) -- LDS addresses, shift amounts, table offsets, some
             // 40 registers -- would otherwise be hoisted out of the row loop and held across it (136 VGPRs instead of ~80)
@@ -372,10 +337,7 @@ __global__ void __launch_bounds__(64 * TC) k_exh_mfma16(MfmaDev d)
                 o[1] = ri - d.sw;
             }
         }
-        if (it + 1 < nrows) {
-            __syncthreads();                                          // every wave has read the window before it is overwritten
-            if (!MFMA_STAGE_PREFETCH) stage_load(brow + 1);
-        }
+        if (it + 1 < nrows) __syncthreads();                          // every wave has read the window before it is overwritten
     }
 }
 
@@ -391,13 +353,13 @@ void mfma_launch(gme_ctx* ctx, const MfmaDev& d)
 
 // Search windows the matrix-core kernel takes: NC = 2 sw + 16 a multiple of 16, at most 5 tiles per axis.
 // GME_EXH_MFMA=0 keeps exhaustive MSE on the vector unit (the elimination kernels of bbme_sea_mse.hip), =1 takes every
-// window this kernel can, unset: windows up to GME_EXH_MFMA_AUTO_SW.
+// window this kernel can, unset: windows up to AUTO_SW.
 bool bbme_mfma_wanted(int sw)
 {
     if (sw < 0 || sw % 8 != 0 || sw > 32) return false;
     if (getenv("GME_FORCE_GENERIC") || getenv("GME_EXH_BRUTE")) return false;
     const char* e = getenv("GME_EXH_MFMA");
-    return e ? atoi(e) != 0 : sw <= GME_EXH_MFMA_AUTO_SW;
+    return e ? atoi(e) != 0 : sw <= AUTO_SW;
 }
 
 // One predicate for both sides of the table: bbme_aux_kind builds the signed table (kind 2) for exactly these jobs, and
@@ -424,10 +386,10 @@ int launch_bbme_mfma(gme_ctx* ctx, const BbmeJob& job, bool* handled)
     d.pairs = job.pairs; d.H = job.H; d.W = job.W; d.pitch = job.pitch; d.sw = job.sw;
     d.nbr = nbr; d.nbc = nbc; d.mf = job.mf;
     d.sq = job.sqbox_cur; d.sq_stride = job.sqbox_stride;
-    d.rpw = getenv("GME_MFMA_ROWS") ? atoi(getenv("GME_MFMA_ROWS")) : MFMA_ROWS_PER_WG;
+    d.rpw = getenv("GME_MFMA_ROWS") ? atoi(getenv("GME_MFMA_ROWS")) : ROWS_PER_WG;
     if (d.rpw < 1) d.rpw = 1;
     if (d.rpw > nbr) d.rpw = nbr;
-    int tc = NT <= 3 ? MFMA_TC_SMALL : MFMA_TC_LARGE;
+    int tc = TC_DEFAULT;
     if (const char* e = getenv("GME_MFMA_TILE")) { int a = 0, c = 0; if (sscanf(e, "%dx%d", &a, &c) == 2 && a == 1 && c >= 1 && c <= 4) tc = c; }
 #define MFMA_CASE(NTV, XSV) \
     case NTV: if (tc == 1) mfma_launch<NTV, XSV, 1>(ctx, d); else if (tc == 2) mfma_launch<NTV, XSV, 2>(ctx, d); \
@@ -435,9 +397,9 @@ int launch_bbme_mfma(gme_ctx* ctx, const BbmeJob& job, bool* handled)
     switch (NT) {
     MFMA_CASE(1, 1);
     MFMA_CASE(2, 2);
-    MFMA_CASE(3, MFMA_XS_SMALL);
+    MFMA_CASE(3, 3);
     MFMA_CASE(4, 2);
-    default: MFMA_CASE(5, MFMA_XS_LARGE);
+    default: MFMA_CASE(5, 2);
     }
 #undef MFMA_CASE
     GME_HIP_TRY(hipGetLastError());

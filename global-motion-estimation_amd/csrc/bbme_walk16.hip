@@ -120,15 +120,6 @@ constexpr int WIN_ALLOC = 43 * WIN_PITCH;      // staging moves 128 sixteen-byte
 // lane, pitch 17 dwords: odd, so the 8 lanes of a group still hit 8 banks) hold a pattern of span 32 -- the first step
 // of both searches at sw = 16 -- so that round is served from the LDS as well instead of reading global memory through
 // unaligned loads, and the later, narrower rounds usually fall inside the same window: one staging per block.
-// which FITS searches fetch their first window ahead (bit PROC): it costs 12 VGPRs per prefetch buffer
-#ifndef WALK_FITS_PREFETCH
-#define WALK_FITS_PREFETCH (1 << GME_SEARCH_THREESTEP)
-#endif
-#ifndef WALK_SMALLWIN
-constexpr bool WALK_BIG = true;
-#else
-constexpr bool WALK_BIG = false;
-#endif
 template <bool BIG> struct Win {
     static constexpr int ROWS = BIG ? 48 : WIN_ROWS, DW = BIG ? 16 : WIN_DW, PITCH = BIG ? 17 : WIN_PITCH;
     static constexpr int SPAN = 4 * (DW - 5) + 3;
@@ -374,9 +365,10 @@ __device__ __forceinline__ void first_window_span(const WalkDev& d, int r0, int 
     wc0 = max(0, (cmin - ((WS::SPAN - 3 - (cmax - cmin)) >> 1)) & ~3);
 }
 
+// of the FITS searches only three-step fetches its first window ahead: it costs 12 VGPRs per prefetch buffer
 template <int PROC, bool FITS> constexpr int walk_pre()
 {
-    return PROC == GME_SEARCH_DIAMOND ? 1 : FITS && ((WALK_FITS_PREFETCH >> PROC) & 1) ? 2 : 0;
+    return PROC == GME_SEARCH_DIAMOND ? 1 : FITS && PROC == GME_SEARCH_THREESTEP ? 2 : 0;
 }
 
 // PRE = 0: anchors only; 1: + the diamond's first window; 2: + the first window of a three-step / 2-D log walk (FITS)
@@ -414,7 +406,7 @@ __device__ __forceinline__ void walk_block(const WalkDev& d, const int pair, con
                                            WalkPre<NW>& nxt, const bool more, const int brow_n, const int bcol_n)
 {
     constexpr bool DIA = PROC == GME_SEARCH_DIAMOND;
-    constexpr bool SBIG = !DIA && WALK_BIG;                      // window geometry of this search (Win<>)
+    constexpr bool SBIG = !DIA;                                  // window geometry of this search (Win<>)
     typedef Win<SBIG> WS;
     const long long gid = (long long)pair * nblk + blk;
     const int r0 = brow * 16, c0 = bcol * 16;
@@ -437,10 +429,6 @@ __device__ __forceinline__ void walk_block(const WalkDev& d, const int pair, con
     // bounding box) and, if the pattern is wider than the window (!FITS: sw > 16), the round reads global memory directly.
     int wr0 = -(1 << 20), wc0 = 0;                  // far away: nothing staged yet (the diamond and FITS walks set their first window themselves)
     bool round_lds = FITS;                          // the last EVALV round was served from the LDS window
-#if defined(WALK_ABLATE) && WALK_ABLATE == 1      // timing experiments only (tools/build_variant.sh): anchors loaded, nothing else
-    if (lane == 0) { int32_t* o = d.mf + gid * 2; o[0] = (int)(a[0] + a[7] + aa) >> 30; o[1] = 0; }
-    return;
-#endif
     // cost of this lane's group's candidate (RR, CC, OK: per-lane values, equal inside a group) -> COST in every lane of
     // the group (INF32 if !OK).  [RMIN, RMAX] x [CMIN, CMAX] is a wave-uniform box that holds the round's valid
     // candidates (RMIN > RMAX: none): when it fits, the round is served from the LDS window, which is moved (centred on
@@ -552,10 +540,6 @@ __device__ __forceinline__ void walk_block(const WalkDev& d, const int pair, con
             // pattern round that would keep 7 of the 8 groups idle.  The prefetched window is built around it.
             centre_cost = wave_eval_lds<PNORM, WIN_PITCH>(pre.mine, sbase, qr, qc, lane);
         }
-#if defined(WALK_ABLATE) && WALK_ABLATE == 2      // first window staged + centre evaluated
-        if (lane == 0) { int32_t* o = d.mf + gid * 2; o[0] = (int)centre_cost >> 30; o[1] = 0; }
-        return;
-#endif
         int it = 0;
         bool again;
         do {
@@ -580,10 +564,6 @@ __device__ __forceinline__ void walk_block(const WalkDev& d, const int pair, con
             pr = qr; pc = qc;                                  // from here on the origin is a clamped position
         } while (again && ++it <= cap);
         overrun = again;
-#if defined(WALK_ABLATE) && WALK_ABLATE == 3      // large-pattern rounds done, small pattern skipped
-        if (lane == 0) { int32_t* o = d.mf + gid * 2; o[0] = pc - c0; o[1] = pr - r0; }
-        return;
-#endif
         {   // small pattern around the final centre
             RESTAGE_IF_OUTSIDE();
             int br = pr, bc = pc;
@@ -738,7 +718,7 @@ __device__ __forceinline__ void walk16_workgroup(const WalkDev& d, uint32_t (&wi
 {
     constexpr bool DIA = PROC == GME_SEARCH_DIAMOND;
     constexpr int PRE = walk_pre<PROC, FITS>(), NW = PRE == 1 ? Win<false>::SEGS_LANE : PRE == 2 ? Win<true>::SEGS_LANE : 1;
-    static_assert(!FITS || (!DIA && WALK_BIG), "FITS is a property of the 48 x 64 window");
+    static_assert(!FITS || !DIA, "FITS is a property of the 48 x 64 window");
     const int wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nblk = d.nbr * d.nbc;
     // XCD-aware: workgroups are dealt round-robin over the 8 XCDs, so workgroup b serves pair
@@ -775,16 +755,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
 }
 
 // waves per SIMD the register allocation aims at: 8, or 6 for an instance that holds a prefetched window (80 VGPRs)
-#ifndef WALK16S_WAVES_PRE
-#define WALK16S_WAVES_PRE 6
-#endif
+constexpr int WAVES_PRE = 6;
 // FITS: first step (three-step) / sw (2-D log) <= 16 -- every search the pipeline and the benches run; wider searches
 // take the instance with the global-memory path
 template <int PNORM, int PROC, bool FITS>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(!(FITS && WALK_BIG) ? 1 : walk_pre<PROC, true>() == 2 ? WALK16S_WAVES_PRE : 8, walk_pre<PROC, FITS && WALK_BIG>() == 2 ? WALK16S_WAVES_PRE : 8))) k_walk16s(WalkDev d)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(!FITS ? 1 : walk_pre<PROC, FITS>() == 2 ? WAVES_PRE : 8, walk_pre<PROC, FITS>() == 2 ? WAVES_PRE : 8))) k_walk16s(WalkDev d)
 {
-    __shared__ uint32_t win_all[4][Win<WALK_BIG>::ALLOC];
-    walk16_workgroup<PNORM, PROC, FITS && WALK_BIG, Win<WALK_BIG>::ALLOC>(d, win_all);
+    __shared__ uint32_t win_all[4][Win<true>::ALLOC];
+    walk16_workgroup<PNORM, PROC, FITS, Win<true>::ALLOC>(d, win_all);
 }
 
 // ---------------------------------------------------------------------------
@@ -862,8 +840,7 @@ int launch_bbme_walk_fast(gme_ctx* ctx, const BbmeJob& job, bool* handled)
     d.st1 = (int)(span / 3.0); d.st2 = (int)(span / 5.0); d.st3 = (int)(span / 10.0);
     const long long total = (long long)nbr * nbc * job.pairs;
     if (job.bs == 16) {
-        static const int bpw_env = getenv("GME_WALK_BPW") ? atoi(getenv("GME_WALK_BPW")) : 0;
-        d.bpw = bpw_env >= 1 && bpw_env <= 64 ? bpw_env : 8;
+        d.bpw = 8;                                             // blocks per wave, see walk16_workgroup
         const long long wpp = ((long long)nbr * nbc + 4 * d.bpw - 1) / (4 * d.bpw);
         const long long groups = (long long)((job.pairs + 7) / 8) * 8 * wpp;
         GME_REQUIRE(groups < (1ll << 31), GME_ERR_ARG, "too many workgroups in one launch");
@@ -876,7 +853,7 @@ int launch_bbme_walk_fast(gme_ctx* ctx, const BbmeJob& job, bool* handled)
         } else {
             const bool tss = job.procedure == GME_SEARCH_THREESTEP;
             // the widest round's span (2 x first step / 2 x sw) must fit the window's 32 rows of slack (Win<true>)
-            const bool fits = WALK_BIG && (tss ? d.st1 : d.sw) <= (Win<true>::ROWS - 16) / 2;
+            const bool fits = (tss ? d.st1 : d.sw) <= (Win<true>::ROWS - 16) / 2;
             plan_note(ctx, 0, "k_walk16s<%d,%d,%s> (%s) grid %u blocks/wave %d", job.pnorm, job.procedure, fits ? "true" : "false", tss ? "three-step" : "2-D log", (unsigned)grid, d.bpw);
 #define LAUNCH_WALK16S(P, S)                                                                                     \
     do {                                                                                                         \

@@ -92,7 +92,6 @@ extern "C" void gme_destroy(gme_ctx* ctx)
     if (ctx->stage) hipFree(ctx->stage);
     if (ctx->status) hipFree(ctx->status);
     if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
-    if (ctx->copy_stream2) hipStreamDestroy(ctx->copy_stream2);
     if (ctx->back_stream) hipStreamDestroy(ctx->back_stream);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
@@ -811,24 +810,7 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     gme_drop_run(s);
     // tight frames (the usual NumPy stack) whose rows are narrower than the plane pitch: linear copy + repack
     const bool tight = row_stride == s->W && frame_stride == (int64_t)s->W * s->H && p.pitch != s->W;
-    // page-locked source (gme_host_alloc / hipHostMalloc)?  GME_UPLOAD_ZEROCOPY=1 lets the repack kernel read it across
-    // the link itself instead of the copy engines (measured slower: 34 vs 40 GB/s)
-    bool host_mapped = false;
-    const uint8_t* dev_view = nullptr;
-    if (tight && getenv("GME_UPLOAD_ZEROCOPY")) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, frames) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer != nullptr) {
-            host_mapped = true;
-            dev_view = (const uint8_t*)at.devicePointer;
-        } else {
-            (void)hipGetLastError();                           // pageable memory: not an error
-        }
-    }
-    // GME_UPLOAD_ENGINES=2 splits every chunk over two streams (two copy engines); measured slower on MI355X boxes of
-    // this pool (22-25 GB/s against 38-39 GB/s for one stream), so one is the default
-    const bool two_engines = getenv("GME_UPLOAD_ENGINES") && atoi(getenv("GME_UPLOAD_ENGINES")) >= 2;
-    if (tight && two_engines && !ctx->copy_stream2) GME_HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream2, hipStreamNonBlocking));
-    if (tight && !host_mapped) {
+    if (tight) {
         const size_t want = (size_t)(chunk_frames < count ? chunk_frames : count) * s->H * s->W;
         if (want > ctx->stage_bytes) {
             GME_HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
@@ -870,25 +852,13 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
         LTRY(hipEventCreateWithFlags(&up[c], hipEventDisableTiming));
         LTRY(hipEventCreateWithFlags(&done[c], hipEventDisableTiming));
         // upload of chunk c on the copy stream: it runs while the compute stream still searches chunk c - 1
-        if (tight && host_mapped) {
-            // page-locked frames are mapped into the device's address space: the repack kernel reads them across the
-            // link itself (thousands of loads in flight instead of one DMA queue) and writes the pitched planes
-            if (launch_repack(ctx, ctx->copy_stream, dev_view + (int64_t)f0 * frame_stride, f1 - f0, s->H, s->W, p.at(f0), p.pitch, p.stride) != GME_OK) return false;
-        } else if (tight) {
+        if (tight) {
             // one linear copy (link speed), then spread into the pitched planes on the same stream: the next chunk's
-            // copy into the staging buffer is ordered behind this repack
+            // copy into the staging buffer is ordered behind this repack.  Measured against the two alternatives: the
+            // repack kernel reading page-locked frames across the link itself (34 against 40 GB/s) and the chunk split
+            // over two copy engines (22-25 against 38-39 GB/s) were both slower.
             const size_t bytes = (size_t)(f1 - f0) * s->H * s->W;
-            size_t head = bytes;
-            if (two_engines && bytes >= (1u << 20)) {
-                // second half through a second stream: two copy engines share the link (one alone moved ~40 GB/s)
-                head = (bytes / 2) & ~(size_t)4095;
-                if (c > 0) LTRY(hipStreamWaitEvent(ctx->copy_stream2, up[c - 1], 0));      // staging buffer free again
-                LTRY(hipMemcpyAsync(ctx->stage + head, frames + (int64_t)f0 * frame_stride + head, bytes - head,
-                                          hipMemcpyHostToDevice, ctx->copy_stream2));
-                LTRY(hipEventRecord(done[c], ctx->copy_stream2));                          // done[c] is re-recorded behind the kernel below
-            }
-            LTRY(hipMemcpyAsync(ctx->stage, frames + (int64_t)f0 * frame_stride, head, hipMemcpyHostToDevice, ctx->copy_stream));
-            if (head != bytes) LTRY(hipStreamWaitEvent(ctx->copy_stream, done[c], 0));
+            LTRY(hipMemcpyAsync(ctx->stage, frames + (int64_t)f0 * frame_stride, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
             if (launch_repack(ctx, ctx->copy_stream, ctx->stage, f1 - f0, s->H, s->W, p.at(f0), p.pitch, p.stride) != GME_OK) return false;
         } else if (p.stride == (int64_t)p.pitch * s->H && frame_stride == (int64_t)row_stride * s->H) {
             LTRY(hipMemcpy2DAsync(p.at(f0), p.pitch, frames + (int64_t)f0 * frame_stride, row_stride, s->W,
@@ -943,7 +913,6 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     if (!read_back()) { STREAM_TRY(hipErrorUnknown); }
 #undef STREAM_TRY
     hipError_t e1 = hipStreamSynchronize(ctx->copy_stream), e2 = hipStreamSynchronize(ctx->back_stream);
-    if (ctx->copy_stream2 && hipStreamSynchronize(ctx->copy_stream2) != hipSuccess) e1 = hipErrorUnknown;
     rc = ctx_finish(ctx);
     cleanup();
     if (aux) { s->sqbox_valid[2] = (count == s->N && tab_done == count); s->sqbox_kind[2] = aux; }

@@ -56,7 +56,7 @@ struct gme_ctx {
                                   // [GME_STATUS_STATS ..] per-XCD statistics of the last block-matching call (16 words apart)
     void* comm = nullptr;         // RCCL communicator (gme_comm.hip), one per context = per rank
     int comm_rank = 0, comm_world = 0;
-    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr, back_stream = nullptr;   // gme_seq_bbme_streamed: uploads / read-backs beside the kernels
+    hipStream_t copy_stream = nullptr, back_stream = nullptr;   // gme_seq_bbme_streamed: uploads / read-backs beside the kernels
     uint8_t* stage = nullptr;        // device staging of tight host frames (gme_seq_bbme_streamed), repacked into the planes
     size_t stage_bytes = 0;
     uint32_t* redo_list = nullptr;   // tiles the elimination kernels hand to the brute-force redo kernel (grown on demand)
@@ -173,15 +173,9 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
     v = min(v, GME_DPP(v, 0x4E));                          // quad_perm [2,3,0,1]
     v = min(v, GME_DPP(v, 0x141));                         // row_half_mirror
     v = min(v, GME_DPP(v, 0x140));                         // row_mirror
-#ifdef GME_WAVE_REDUCE_READLANES
-    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-    return min(min(r0, r1), min(r2, r3));
-#else
     v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xA, 0xF, false));     // row_bcast:15 -> rows 1, 3
     v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xC, 0xF, false));     // row_bcast:31 -> rows 2, 3
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-#endif
 }
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
@@ -190,14 +184,9 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
     v += GME_DPP(v, 0x4E);
     v += GME_DPP(v, 0x141);
     v += GME_DPP(v, 0x140);
-#ifdef GME_WAVE_REDUCE_READLANES
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
-           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-#else
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);             // row_bcast:15 -> rows 1, 3
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);             // row_bcast:31 -> rows 2, 3
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-#endif
 }
 
 // The small symmetric systems of the device solves (k_solve_model2, gme_kernels.hip; k_direct_state, gme_direct.hip): the n x n

@@ -1077,7 +1077,7 @@ int launch_pyrdown(gme_ctx* ctx, const Plane& src, const Plane& dst)
     const size_t lds = (size_t)PYR_ROWS * lpitch;
     const int pyr_per_row = (src.W + 15) / 16, pyr_quads = dst.W / 4;
     if (src.W % 8 == 0 && src.W >= 8 && src.pitch % 16 == 0 && lds <= 64 * 1024 && PYR_ROWS * pyr_per_row < 4096 && pyr_per_row < 256 &&
-        (PYR_T / 2) * pyr_quads < 4096 && pyr_quads < 256 && !getenv("GME_FORCE_GENERIC") && !getenv("GME_PYR_NOLDS")) {
+        (PYR_T / 2) * pyr_quads < 4096 && pyr_quads < 256 && !getenv("GME_FORCE_GENERIC")) {
         const uint32_t magic_row = (1u << 20) / (uint32_t)pyr_per_row + 1u, magic_quads = (1u << 20) / (uint32_t)pyr_quads + 1u;
         for (int first = 0; first < src.count; first += step) {
             const int n = src.count - first < step ? src.count - first : step;

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/build_variant.sh <name> "<extra hipcc flags, e.g. -DREDO_KS5=1>"
+# usage: tools/build_variant.sh <name> "<extra hipcc flags, e.g. -O2>"
 # Builds global-motion-estimation_amd/csrc into tools/microbench/libgme_<name>.so (same C ABI as the tree's
 # library) for same-box A/B runs with tools/ab.sh.
 set -e
