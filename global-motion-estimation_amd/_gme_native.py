@@ -99,6 +99,9 @@ _SIGNATURES = {
     "gme_seq_compensate_projective": (_i, [_vp, _i, _c_f64p, _c_i64p]),
     "gme_seq_read_compensated": (_i, [_vp, _i, _c_u8p]),
     "gme_seq_read_compensated_range": (_i, [_vp, _i, _i, _c_u8p]),
+    "gme_seq_warp_frames": (_i, [_vp, _i, _i, _c_f64p, _i, _i, _c_i64p]),
+    "gme_seq_read_warped_range": (_i, [_vp, _i, _i, _c_u8p]),
+    "gme_seq_frame_sse": (_i, [_vp, _i, _i, _i, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -683,6 +686,30 @@ class Sequence:
             raise ValueError("out must be a contiguous uint8[%d, %d, %d]" % (count, self.H, self.W))
         _check(self.lib.gme_seq_read_compensated_range(self.handle, int(first), int(count), _p(out, _c_u8p)), self.lib)
         return out
+
+    # ---- video stabilization (gme_stab.hip, stabilize.py)
+    def warp_frames(self, first, warps, border=0, fill=0):
+        """Frames first .. first+count-1 warped by warps float64[count, 8] (gme_seq_warp_frames; border 0 constant `fill`,
+        1 replicate) into the sequence's warped frames -> valid int64[count], the in-frame samples per frame."""
+        if getattr(self, "_split", False):
+            raise RuntimeError("the stabilization calls are blocking: the sequence is in split-phase mode")
+        w = np.ascontiguousarray(np.asarray(warps, dtype=np.float64).reshape(-1, 8))
+        valid = np.zeros(len(w), np.int64)
+        _check(self.lib.gme_seq_warp_frames(self.handle, int(first), len(w), _p(w, _c_f64p), int(border), int(fill),
+                                            _p(valid, _c_i64p)), self.lib)
+        return valid
+
+    def read_warped_range(self, first, count):
+        """Warped frames first .. first+count-1 -> uint8[count, H, W] with one wait."""
+        out = np.empty((int(count), self.H, self.W), dtype=np.uint8)
+        _check(self.lib.gme_seq_read_warped_range(self.handle, int(first), int(count), _p(out, _c_u8p)), self.lib)
+        return out
+
+    def frame_sse(self, warped, first, count):
+        """sum (f[first+k+1] - f[first+k])^2 for k < count, of the resident (warped=0) or warped (1) frames -> int64[count]."""
+        sse = np.zeros(int(count), np.int64)
+        _check(self.lib.gme_seq_frame_sse(self.handle, int(warped), int(first), int(count), _p(sse, _c_i64p)), self.lib)
+        return sse
 
 
 _default = None

@@ -491,6 +491,9 @@ extern "C" void gme_seq_destroy(gme_seq* s)
     if (s->comp_mf) hipFree(s->comp_mf);
     if (s->synth_canvas) hipFree(s->synth_canvas);
     if (s->direct) hipFree(s->direct);
+    plane_free(&s->warped);
+    if (s->warp_params) hipFree(s->warp_params);
+    if (s->warp_counts) hipFree(s->warp_counts);
     if (s->summary) hipFree(s->summary);
     if (s->gathered) hipFree(s->gathered);
     if (s->ready) hipEventDestroy(s->ready);
@@ -1597,5 +1600,90 @@ extern "C" int gme_seq_compensate_projective(gme_seq* s, int fd, const double* p
     rc = launch_compensate_proj(s, fd, pairs, in);
     if (rc) return rc;
     if (sse_out) GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Video stabilization (gme_stab.hip): blocking calls on the resident frames.
+// ---------------------------------------------------------------------------
+static int stab_buffers(gme_seq* s)
+{
+    if (s->warped.ptr) return GME_OK;
+    int rc = plane_alloc(s->ctx, &s->warped, s->N_cap, s->H, s->W);
+    if (rc) return rc;
+    if (hipMalloc((void**)&s->warp_params, (size_t)s->N_cap * 8 * sizeof(double)) != hipSuccess ||
+        hipMalloc((void**)&s->warp_counts, (size_t)s->N_cap * sizeof(unsigned long long)) != hipSuccess) {
+        plane_free(&s->warped);
+        gme_set_error("out of device memory (stabilization buffers)");
+        return GME_ERR_NOMEM;
+    }
+    s->warped_written.assign((size_t)s->N_cap, 0);
+    return GME_OK;
+}
+
+static bool stab_written(const gme_seq* s, int first, int count)
+{
+    if (!s->warped.ptr) return count == 0;
+    for (int k = first; k < first + count; ++k)
+        if (!s->warped_written[(size_t)k]) return false;
+    return true;
+}
+
+extern "C" int gme_seq_warp_frames(gme_seq* s, int first, int count, const double* params, int border, int fill,
+                                   int64_t* valid_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_warp_frames: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->N, GME_ERR_ARG, "gme_seq_warp_frames: frames [%d, %d) outside [0, %d)",
+                first, first + count, s->N);
+    GME_REQUIRE(params != nullptr || count == 0, GME_ERR_ARG, "gme_seq_warp_frames: null parameters");
+    GME_REQUIRE(border == 0 || border == 1, GME_ERR_ARG, "gme_seq_warp_frames: border %d (0 constant, 1 replicate)", border);
+    GME_REQUIRE(fill >= 0 && fill <= 255, GME_ERR_ARG, "gme_seq_warp_frames: fill %d (0 .. 255)", fill);
+    if (count == 0) return GME_OK;
+    int rc = stab_buffers(s);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(s->warp_params, params, (size_t)count * 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_warp_frames(ctx, s->level[2], s->warped, first, count, s->warp_params, border, fill, s->warp_counts);
+    if (rc) return rc;
+    if (valid_out)
+        GME_HIP_TRY(hipMemcpyAsync(valid_out, s->warp_counts, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+    rc = ctx_finish(ctx);
+    if (rc) return rc;
+    for (int k = first; k < first + count; ++k) s->warped_written[(size_t)k] = 1;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_warped_range(gme_seq* s, int first, int count, uint8_t* out)
+{
+    GME_REQUIRE(s != nullptr && out != nullptr, GME_ERR_ARG, "gme_seq_read_warped_range: null pointer");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->N, GME_ERR_ARG,
+                "gme_seq_read_warped_range: frames [%d, %d) outside [0, %d)", first, first + count, s->N);
+    GME_REQUIRE(stab_written(s, first, count), GME_ERR_ARG, "gme_seq_read_warped_range: frames [%d, %d) were never warped",
+                first, first + count);
+    for (int k = 0; k < count; ++k)
+        GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * s->H * s->W, s->W, s->warped.at(first + k), s->warped.pitch, s->W, s->H,
+                                     hipMemcpyDeviceToHost, s->ctx->stream));
+    return ctx_finish(s->ctx);
+}
+
+extern "C" int gme_seq_frame_sse(gme_seq* s, int warped, int first, int count, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr && sse_out != nullptr, GME_ERR_ARG, "gme_seq_frame_sse: null pointer");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(warped == 0 || warped == 1, GME_ERR_ARG, "gme_seq_frame_sse: warped %d (0 resident, 1 warped frames)", warped);
+    GME_REQUIRE(first >= 0 && count >= 0 && first + count + 1 <= s->N, GME_ERR_ARG,
+                "gme_seq_frame_sse: frames [%d, %d] outside [0, %d)", first, first + count, s->N);
+    if (count == 0) return GME_OK;
+    GME_REQUIRE(!warped || stab_written(s, first, count + 1), GME_ERR_ARG, "gme_seq_frame_sse: frames [%d, %d] were never warped",
+                first, first + count);
+    int rc = stab_buffers(s);
+    if (rc) return rc;
+    rc = launch_frame_sse(ctx, warped ? s->warped : s->level[2], first, count, s->warp_counts);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(sse_out, s->warp_counts, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
 }

@@ -131,6 +131,12 @@ struct gme_seq {
     size_t gathered_bytes = 0;
     void* direct = nullptr;              // gme_direct.hip: per-pair refinement state, histograms, slabs and parameters
     size_t direct_bytes = 0;
+    // stabilization (gme_stab.hip): the warped frames (N_cap, allocated by the first gme_seq_warp_frames), which of them a
+    // warp has written, and N_cap rows of parameters and counts
+    Plane warped;
+    std::vector<uint8_t> warped_written;
+    double* warp_params = nullptr;       // [N_cap][8]
+    unsigned long long* warp_counts = nullptr;   // [N_cap] valid samples, or squared errors of gme_seq_frame_sse
     uint8_t* synth_canvas = nullptr;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -305,6 +311,14 @@ int launch_direct_refine(gme_seq* s, int fd, int pairs, double outlier_fraction,
 int launch_direct_eval(gme_seq* s, int fd, int level, int pairs, double outlier_fraction);
 // compensation of every pair under params[P][8] (device) into s->comp, squared errors into s->sse
 int launch_compensate_proj(gme_seq* s, int fd, int pairs, const double* params);
+
+// ---- gme_stab.hip: video stabilization -------------------------------------------------------
+// frames first .. first + count - 1 of src warped by params[count][8] (device; border 0 constant fill, 1 replicate) into the
+// same frames of dst, in-frame samples per frame into valid[count] (device)
+int launch_warp_frames(gme_ctx* ctx, const Plane& src, const Plane& dst, int first, int count, const double* params, int border,
+                       int fill, unsigned long long* valid);
+// sse[k] = sum (p[first + k + 1] - p[first + k])^2, k < count (device)
+int launch_frame_sse(gme_ctx* ctx, const Plane& p, int first, int count, unsigned long long* sse);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -8,6 +8,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py results -v <name under resources/videos> -f 1 [--model quadratic] [--suggest]    # results.py main
     python gme_cli.py suggest -p <video|frame dir> [-fi 1] [-f 1]                 # parameter heuristics
     python gme_cli.py projective -p <video|frame dir> -fi 1 [-f 1]                # direct projective refinement of one pair
+    python gme_cli.py stabilize -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--radius 15]   # video stabilization
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -50,8 +51,50 @@ def _parser():
     j.add_argument("-f", "--frame-distance", dest="fd", type=int, default=1)
     j.add_argument("--outlier-fraction", type=float, default=0.1)
     j.add_argument("--max-iters", type=int, default=10)
+    st = sub.add_parser("stabilize", help="stabilize a whole video from its estimated camera path (stabilize.py, DESIGN.md 7c)")
+    st.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    st.add_argument("-o", "--output", dest="outdir", type=str, required=True,
+                    help="directory for stabilized/%%04d.png and stabilize.json")
+    st.add_argument("--estimator", choices=("projective", "affine"), default="projective")
+    st.add_argument("--radius", type=int, default=15, help="half-width of the Gaussian path filter, frames")
+    st.add_argument("--sigma", type=float, default=None, help="its standard deviation (default radius / 3)")
+    st.add_argument("--crop", type=_crop, default="auto", help="auto, or a fixed crop fraction in [0, 1)")
+    st.add_argument("--max-crop", type=float, default=0.25, help="cap of the auto crop")
+    st.add_argument("--border", choices=("constant", "replicate"), default="constant")
+    st.add_argument("--fill", type=int, default=0, help="value of border pixels under --border constant")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
+
+
+def _crop(text):
+    return text if text == "auto" else float(text)
+
+
+def _stabilize(args):
+    """Stabilized frames into OUTDIR/stabilized/%04d.png and the run's record into OUTDIR/stabilize.json."""
+    import json
+    import os
+    import numpy as np
+    import stabilize
+    import utils
+    frames = np.stack([np.asarray(f, dtype=np.uint8) for f in utils.get_video_frames(args.path)])
+    out, res = stabilize.stabilize(frames, estimator=args.estimator, radius=args.radius, sigma=args.sigma, crop=args.crop,
+                                   max_crop=args.max_crop, border=args.border, fill=args.fill)
+    d = os.path.join(args.outdir, "stabilized")
+    os.makedirs(d, exist_ok=True)
+    for k, f in enumerate(out):
+        utils.write_image(os.path.join(d, "%04d.png" % k), f)
+    record = {"options": {"path": args.path, "estimator": args.estimator, "radius": args.radius, "sigma": args.sigma,
+                          "crop": args.crop, "max_crop": args.max_crop, "border": args.border, "fill": args.fill},
+              "frames": int(len(out)), "crop": res["crop"], "itf_before": res["itf_before"], "itf_after": res["itf_after"],
+              "pair_params": res["h"].tolist(), "pair_flags": res["pair_flags"].tolist(), "W": res["W"].tolist(),
+              "frame_flags": res["flags"].tolist(), "valid": res["valid"].tolist()}
+    with open(os.path.join(args.outdir, "stabilize.json"), "w") as f:
+        json.dump(record, f, indent=1)
+    print("{} frames of shape {}, crop {:.4f}".format(len(out), out.shape[1:], res["crop"]))
+    print("itf before: {:.4f} dB".format(res["itf_before"]))
+    print("itf after:  {:.4f} dB".format(res["itf_after"]))
+    return res
 
 
 def _projective(args):
@@ -118,6 +161,8 @@ def main(argv=None):
         return out
     if args.command == "projective":
         return _projective(args)
+    if args.command == "stabilize":
+        return _stabilize(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")

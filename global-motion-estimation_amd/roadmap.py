@@ -45,6 +45,8 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    (``affine_to_projective``) and refine an 8-parameter perspective warp on the pixels of the pyramids, coarse to fine, by
    Gauss-Newton under a truncated quadratic (k_direct_sums / k_direct_state, csrc/gme_direct.hip; host definition
    direct.py), with dense sub-pixel compensation under it.  It is a separate estimator, not an entry of ``MODELS``.
+   **Stabilization.**  ``stabilize.stabilize`` chains the pair warps of either estimator into a camera path, smooths it and
+   warps every frame on the device (k_warp_frames, csrc/gme_stab.hip).
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

@@ -339,6 +339,25 @@ def psnr_from_sse(sse, height, width, exact=True):
     return out
 
 
+def lane_ranges(n_local_pairs, streams):
+    """The local pair ranges [lo, hi) of a shard's lanes: ``streams`` contiguous pieces, at most one per pair, at least one."""
+    k = max(1, min(int(streams), n_local_pairs))
+    return [shard_range(n_local_pairs, j, k) for j in range(k)]
+
+
+def stabilized_owners(n_frames, rank, world, streams=1):
+    """The global frames [a, b) whose stabilized form each lane of ``rank`` reads out (ShardedSequence.read_stabilized):
+    lane j owns the frames of its pairs, [lo, hi); the last lane of the last rank also owns frame N-1.  Frame distance 1."""
+    n_pairs = max(0, int(n_frames) - 1)
+    start, stop = shard_range(n_pairs, rank, world)
+    if stop == start:
+        return []
+    out = [(start + lo, start + hi) for lo, hi in lane_ranges(stop - start, streams)]
+    if rank == world - 1:
+        out[-1] = (out[-1][0], out[-1][1] + 1)
+    return out
+
+
 class _Lane:
     """One stream's part of a shard: its own context (HIP stream) and resident frames."""
 
@@ -372,9 +391,9 @@ class ShardedSequence:
         self.first_frame, n_local = shard_frames(self.n_pairs_total, self.fd, rank, world)
         self.lanes = []
         n_loc = self.pair_stop - self.pair_start
-        k = max(1, min(int(streams), n_loc))
-        for j in range(k if n_local else 0):
-            lo, hi = shard_range(n_loc, j, k)
+        ranges = lane_ranges(n_loc, streams)
+        k = len(ranges)
+        for j, (lo, hi) in enumerate(ranges if n_local else []):
             c = self.ctx if j == 0 else _native.Context(self.ctx.device)
             n_fr = (hi - lo) + self.fd if k > 1 else max(n_local, self.fd + 1)
             self.lanes.append(_Lane(c, _native.Sequence(c, n_fr, self.H, self.W), lo, hi))
@@ -604,6 +623,76 @@ class ShardedSequence:
     def read_compensated(self, pair):
         lane, k = self._lane_of(pair)
         return lane.seq.read_compensated(k)
+
+    # ---- video stabilization (stabilize.py, gme_stab.hip)
+    def stabilize(self, estimator="projective", radius=15, sigma=None, crop="auto", max_crop=0.25, border="constant", fill=0,
+                  procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10):
+        """Stabilize the whole video from its estimated camera path -> result dict (stabilize.stabilize).  Each lane estimates
+        its pairs; the pair warps are all-gathered (gather, k = 8), so every rank and lane computes the same path, crop and
+        corrections in host float64; each lane then warps all of its resident frames lo .. hi (the frame shared at a lane
+        boundary twice, identically) and the consecutive-frame squared errors of its pairs.  read_stabilized reads the
+        frames.  Results do not depend on ``streams``."""
+        import stabilize as stab
+        if self.fd != 1:
+            raise ValueError("stabilize needs frame_distance 1 (this sequence has %d)" % self.fd)
+        if estimator not in stab.ESTIMATORS:
+            raise ValueError("estimator %r (choose from %r)" % (estimator, stab.ESTIMATORS))
+        bid = stab.border_id(border)
+        if not 0 <= int(fill) <= 255:
+            raise ValueError("fill %d outside 0 .. 255" % fill)
+        bs = int(motion.BBME_BLOCK_SIZE)
+
+        def estimate(lane):
+            n = lane.hi - lane.lo
+            if estimator == "affine":
+                h = roadmap.affine_to_projective(motion.estimate_sequence(lane.seq, 1, procedure, search_window), bs)
+                return h[:n], np.zeros(n, np.int32)
+            h, flags = roadmap.refine_sequence(lane.seq, 1, None, outlier_fraction, max_iters, procedure, search_window)
+            return h[:n], flags[:n]
+        parts = self._each(estimate)
+        h_loc = np.concatenate([h for h, _ in parts], axis=0) if parts else np.zeros((0, 8))
+        f_loc = np.concatenate([f for _, f in parts]) if parts else np.zeros(0, np.int32)
+        h = self.gather(h_loc)
+        out = stab.plan(h, self.H, self.W, radius, sigma, crop, max_crop)
+        Wt = out["W"]
+
+        def warp(lane):
+            n = lane.hi - lane.lo
+            g0 = self.first_frame + lane.lo
+            valid = lane.seq.warp_frames(0, Wt[g0:g0 + n + 1], bid, int(fill))
+            return np.stack([lane.seq.frame_sse(0, 0, n).astype(np.float64), lane.seq.frame_sse(1, 0, n).astype(np.float64),
+                             valid[:n].astype(np.float64), valid[1:n + 1].astype(np.float64)], axis=1)
+        rows = self._each(warp)
+        local = np.concatenate(rows, axis=0) if rows else np.zeros((0, 4))
+        rows = self.gather(np.concatenate([f_loc.astype(np.float64)[:, None], local], axis=1).reshape(-1, 5))
+        out.update(h=h, pair_flags=rows[:, 0].astype(np.int32), estimator=estimator,
+                   valid=np.concatenate([rows[:, 3], rows[-1:, 4]]).astype(np.int64),
+                   itf_before=stab.itf(rows[:, 1].astype(np.int64), self.H, self.W),
+                   itf_after=stab.itf(rows[:, 2].astype(np.int64), self.H, self.W))
+        return out
+
+    def _owner(self, frame):
+        owners = stabilized_owners(self.n_frames_total, self.rank, self.world, len(self.lanes))
+        for lane, (a, b) in zip(self.lanes, owners):
+            if a <= frame < b:
+                return lane, frame - self.first_frame - lane.lo, b - frame
+        raise IndexError("frame %d is not read out by this rank" % frame)
+
+    def read_stabilized(self, frame):
+        """Stabilized frame ``frame`` (global index) from the lane that owns it (stabilized_owners) -> uint8[H, W]."""
+        lane, k, _ = self._owner(frame)
+        return lane.seq.read_warped_range(k, 1)[0]
+
+    def read_stabilized_range(self, first, count):
+        """Stabilized frames first .. first+count-1, all owned by this rank -> uint8[count, H, W]."""
+        out = np.empty((int(count), self.H, self.W), np.uint8)
+        k = 0
+        while k < count:
+            lane, j, left = self._owner(first + k)
+            n = min(count - k, left)
+            out[k:k + n] = lane.seq.read_warped_range(j, n)
+            k += n
+        return out
 
     def gather(self, local_rows):
         """All-gather of this shard's per-pair rows (float64[P_local, k]) -> float64[P_total, k] on every rank, over the

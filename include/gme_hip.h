@@ -300,6 +300,18 @@ GME_API int gme_seq_wait(gme_seq *seq);
 /* 1: the result of the last split-phase call has arrived (gme_seq_wait would not block), 0: not yet, < 0: error */
 GME_API int gme_seq_poll(gme_seq *seq);
 
+/* Video stabilization (host definition stabilize.py).  Blocking calls on the resident frames.
+ * Out frame first+k = frames[first+k] warped by params[k][8]: output pixel (u, v) samples the frame at direct.warp(params[k],
+ * u, v) bilinearly, rounded to nearest, where that point lies in the frame; elsewhere border 0 (constant) writes `fill`,
+ * border 1 (replicate) clamps the point into the frame first.  valid_out[count] (may be NULL): the in-frame samples per
+ * frame.  Output kept in the sequence (allocated on first use, N_cap frames).  A range outside [0, N), a bad border or
+ * fill, or a read of warped frames that were never written is GME_ERR_ARG. */
+GME_API int gme_seq_warp_frames(gme_seq *seq, int first, int count, const double *params, int border, int fill,
+                                int64_t *valid_out);
+GME_API int gme_seq_read_warped_range(gme_seq *seq, int first, int count, uint8_t *out);
+/* sse_out[k] = sum (f[first+k+1] - f[first+k])^2, k < count; warped 0: the resident frames, 1: the warped ones */
+GME_API int gme_seq_frame_sse(gme_seq *seq, int warped, int first, int count, int64_t *sse_out);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
