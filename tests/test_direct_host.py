@@ -41,6 +41,61 @@ def corner_error(a, b, H, W):
     return float(max(np.abs(ua - ub).max(), np.abs(va - vb).max()))
 
 
+def flag_cases(H=99, W=131):
+    """Inputs that reach each outcome of direct.refine on an odd-sized frame: name -> (prev, cur, init,
+    refine keyword arguments, flags).  prev / cur is a 2 % zoom with 0.5 degrees of rotation rendered by warp_canvas.
+
+    FLAG_NO_GAIN is reached by identical frames at the identity: the cost is 0 at the start and at the end, and 0 < 0 fails.
+    The exact warp of a rendered pair does not reach it: rounding the rendering to uint8 leaves a warp near the exact one
+    whose cost is a little lower, and the refinement finds it."""
+    import direct
+    prev, cur = warp_canvas(known_warps(W)["zoom_rotation"], H, W)
+    flat = np.full((H, W), 128, np.uint8)
+    ident = direct.IDENTITY
+    return {
+        "singular": (flat, flat, ident, {}, direct.FLAG_SINGULAR),                           # no gradient: JtJ = 0
+        "denominator": (prev, cur, np.array([1, 0, 0, 0, 1, 0, -2.0 / W, 0]), {}, direct.FLAG_DENOMINATOR),  # d < 0 at u = W-1
+        "few_valid": (prev, cur, np.array([1, 0, 0.8 * W, 0, 1, 0, 0, 0]), {}, direct.FLAG_FEW_VALID),  # ~20 % samples inside
+        "max_iters_1": (prev, cur, ident, {"max_iters": 1}, direct.FLAG_MAX_ITERS),
+        "max_iters_2": (prev, cur, ident, {"max_iters": 2, "outlier_fraction": 0.3}, direct.FLAG_MAX_ITERS),
+        "no_gain": (prev, prev, ident, {}, direct.FLAG_NO_GAIN),
+        "converged": (prev, cur, ident, {}, 0),
+        "converged_f0": (prev, cur, ident, {"outlier_fraction": 0.0, "max_iters": 20}, 0),
+        "converged_f05": (prev, cur, ident, {"outlier_fraction": 0.5, "max_iters": 60}, 0),         # 42 iterations at level 2
+    }
+
+
+def full_hd_case():
+    """A 1080 x 1920 rendering of the perspective warp (h6 scaled to the width) and a start 1.5 px / 0.2 % off it: the
+    refinement ends without a flag."""
+    w = known_warps(1920)["perspective"]
+    prev, cur = warp_canvas(w, 1080, 1920, seed=7, y0=300, x0=500)
+    init = w + np.array([0.002, 0, -1.5, 0, -0.002, 1.0, 0, 0])
+    return prev, cur, init, {}, 0
+
+
+def test_flag_cases_reach_their_flags():
+    """Each constructed case reaches exactly its flag; a flagged result is the start itself."""
+    import direct
+    from oracle import gme_oracle
+    for name, (prev, cur, init, kw, want) in flag_cases().items():
+        h, flags = direct.refine(gme_oracle.get_pyramids(prev), gme_oracle.get_pyramids(cur), init, **kw)
+        assert flags == want, (name, flags, want)
+        if flags & ~direct.FLAG_MAX_ITERS:
+            assert np.array_equal(h, init), name
+        else:
+            assert np.all(np.isfinite(h)) and not np.array_equal(h, init), name
+
+
+@pytest.mark.slow
+def test_full_hd_case_converges():
+    import direct
+    from oracle import gme_oracle
+    prev, cur, init, kw, want = full_hd_case()
+    h, flags = direct.refine(gme_oracle.get_pyramids(prev), gme_oracle.get_pyramids(cur), init, **kw)
+    assert flags == want and corner_error(h, known_warps(1920)["perspective"], 1080, 1920) < 0.05, (flags, h)
+
+
 def test_affine_start_matches_block_field():
     """At every block centre the warp's displacement is the affine block field's pre-rounding displacement
     (d0 columns, d1 rows at block (i, j), motion.py:139-157)."""

@@ -5,7 +5,7 @@ determinism, real frames, the sharded surface and the CLI.  Needs an MI355X."""
 import numpy as np
 import pytest
 
-from test_direct_host import corner_error, known_warps, warp_canvas
+from test_direct_host import corner_error, flag_cases, full_hd_case, known_warps, warp_canvas
 
 pytestmark = pytest.mark.gpu
 
@@ -64,9 +64,22 @@ def test_compensation_equals_host(native, g9, source):
     seq.close()
 
 
+def check_eval(got, p, want, what):
+    """One pair of direct_eval against direct.evaluate: threshold, n_valid and n_in bit-equal; cost and sums within 1e-9
+    of the sums of absolute values, bounded by Cauchy-Schwarz from the diagonal."""
+    import direct
+    assert got["threshold"][p] == want["threshold"], what
+    assert tuple(got["counts"][p]) == (want["n_valid"], want["n_in"]), what
+    assert abs(got["cost"][p] - want["cost"]) <= 1e-9 * want["cost"], what
+    N, rhs = direct.normal_matrix(want["sums"])
+    d = np.sqrt(np.diag(N))
+    se2 = want["cost"] * want["n_valid"]                               # >= sum of e^2 over the inliers
+    scale = np.concatenate([np.outer(d, d)[np.triu_indices(8)], d * np.sqrt(se2)])
+    assert np.all(np.abs(got["sums"][p] - want["sums"]) <= 1e-9 * scale), what
+
+
 def test_eval_equals_host(native, g9):
-    """Threshold, n_valid and n_in bit-equal; cost and sums within the documented tolerance (1e-9 of the sums of
-    absolute values, bounded by Cauchy-Schwarz from the diagonal)."""
+    """Threshold, n_valid and n_in bit-equal; cost and sums within the documented tolerance (check_eval)."""
     import direct
     import synth
     for frames in (g9[20:25], synth.sequence(77, 0, 3, 480, 720)):
@@ -80,15 +93,121 @@ def test_eval_equals_host(native, g9):
                 for p in range(P):
                     prev, cur = seq.read_frame(p, level), seq.read_frame(p + 1, level)
                     want = direct.evaluate(prev, cur, h[p], f)
-                    assert got["threshold"][p] == want["threshold"]
-                    assert tuple(got["counts"][p]) == (want["n_valid"], want["n_in"])
-                    assert abs(got["cost"][p] - want["cost"]) <= 1e-9 * want["cost"]
-                    N, rhs = direct.normal_matrix(want["sums"])
-                    d = np.sqrt(np.diag(N))
-                    se2 = want["cost"] * want["n_valid"]               # >= sum of e^2 over the inliers
-                    scale = np.concatenate([np.outer(d, d)[np.triu_indices(8)], d * np.sqrt(se2)])
-                    assert np.all(np.abs(got["sums"][p] - want["sums"]) <= 1e-9 * scale), (level, p)
+                    check_eval(got, p, want, (level, p))
         seq.close()
+
+
+DIRECT_TILE = 256 * 32                 # gme_direct.hip: pixels per hist / sums workgroup
+# odd and ragged sizes (odd level widths from (n + 1) / 2; level 0 of 37 x 53 is 10 x 14), full-resolution levels of
+# 2 DIRECT_TILE + 1 and 2 DIRECT_TILE - 1 pixels, and full HD (254 tiles per pass)
+EDGE_SHAPES = [(37, 53), (101, 203), (479, 719), (113, 145), (127, 129), (1080, 1920)]
+
+
+def edge_frames(H, W, n):
+    import synth
+    return synth.sequence(2024, 1, n, H, W)
+
+
+def test_edge_shapes_reach_their_geometry():
+    assert 113 * 145 == 2 * DIRECT_TILE + 1 and 127 * 129 == 2 * DIRECT_TILE - 1
+    assert (37 + 3) // 4 * ((53 + 3) // 4) < 200                          # level 0 of 37 x 53: 10 x 14 pixels
+    assert all(W % 2 for _, W in EDGE_SHAPES[:3])
+    assert -(-1080 * 1920 // DIRECT_TILE) == 254
+
+
+@pytest.mark.parametrize("shape", EDGE_SHAPES)
+def test_eval_edge_shapes(native, shape):
+    """direct_eval against direct.evaluate on every level of the edge shapes, fractions 0.0, 0.1 and 0.5."""
+    import direct
+    H, W = shape
+    frames = edge_frames(H, W, 3)
+    seq = sequence_of(native, frames)
+    for level in range(3):
+        h_l, w_l = seq.level_shape(level)
+        h = random_warps(np.random.default_rng(level + W), 2, h_l, w_l)
+        h[1, [2, 5]] = [0.3 * w_l, -0.2 * h_l]                           # part of the frame pushed out
+        prev = None
+        for f in (0.0, 0.1, 0.5):
+            got = seq.direct_eval(1, level, h, f)
+            prev = prev or [seq.read_frame(p, level) for p in range(3)]          # the pyramid exists after the first call
+            for p in range(2):
+                want = direct.evaluate(prev[p], prev[p + 1], h[p], f)
+                assert want["n_valid"] > 0
+                check_eval(got, p, want, (shape, level, f, p))
+    seq.close()
+
+
+def edge_compensation_warps(H, W):
+    """name -> warp: near-identity, part of the frame pushed out (the previous pixel is kept there), a horizon crossing the
+    frame (d <= 0 on its right part)."""
+    return {"near": random_warps(np.random.default_rng(W), 1, H, W)[0],
+            "pushed_out": np.array([1.01, 0.02, 0.4 * W, -0.01, 0.99, -0.3 * H, 0, 0]),
+            "horizon": np.array([1, 0.05, 1.5, 0.02, 1, -2.0, -1.6 / W, 0.2 / H])}
+
+
+@pytest.mark.parametrize("shape", EDGE_SHAPES)
+def test_compensation_edge_shapes(native, shape):
+    """compensate_projective against direct.compensate bit for bit, frames and SSE, on the edge shapes."""
+    import direct
+    H, W = shape
+    warps = edge_compensation_warps(H, W)
+    names = sorted(warps)
+    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    with np.errstate(all="ignore"):
+        d = direct.warp(warps["horizon"], u, v)[2]
+    assert np.any(d <= 0.0) and np.any(d > 0.0), shape                     # the horizon crosses the frame
+    _, valid = direct.residual(np.zeros((H, W), np.uint8), np.zeros((H, W), np.uint8), warps["pushed_out"])[:2]
+    assert 0 < valid.sum() < H * W, shape
+    frames = edge_frames(H, W, len(names) + 1)
+    seq = sequence_of(native, frames)
+    h = np.stack([warps[n] for n in names])
+    sse = seq.compensate_projective(1, h)
+    comp = seq.read_compensated_range(0, len(names))
+    for p, n in enumerate(names):
+        want, want_sse = direct.compensate(frames[p], frames[p + 1], h[p])
+        assert np.array_equal(comp[p], want), (shape, n)
+        assert sse[p] == want_sse, (shape, n)
+    seq.close()
+
+
+def refine_parity(native, cases):
+    """Device refinement against direct.refine on the device's own pyramids for cases name -> (prev, cur, init, kwargs,
+    flags): the host reaches the case's flag, the flags are identical, the corners within 0.01 px, a flagged start comes
+    back unchanged.  One sequence of pairs (2k, 2k + 1); one call per distinct set of keyword arguments."""
+    import direct
+    names = sorted(cases)
+    frames = np.stack([f for n in names for f in cases[n][:2]])
+    H, W = frames.shape[1:]
+    seq = sequence_of(native, frames)
+    init = np.tile(direct.IDENTITY, (len(frames) - 1, 1))
+    for k, n in enumerate(names):
+        init[2 * k] = cases[n][2]
+    groups = {}
+    for k, n in enumerate(names):
+        groups.setdefault(tuple(sorted(cases[n][3].items())), []).append(k)
+    for kw, ks in groups.items():
+        h, flags = seq.refine_projective(1, init, **dict(kw))
+        for k in ks:
+            n = names[k]
+            want, want_flags = direct.refine(pyramids(seq, 2 * k), pyramids(seq, 2 * k + 1), init[2 * k], **dict(kw))
+            assert want_flags == cases[n][4], (n, want_flags)
+            assert flags[2 * k] == want_flags, (n, flags[2 * k], want_flags)
+            assert corner_error(h[2 * k], want, H, W) < 0.01, (n, h[2 * k], want)
+            if want_flags & ~direct.FLAG_MAX_ITERS:
+                assert np.array_equal(h[2 * k], init[2 * k]), n
+    seq.close()
+
+
+def test_refine_flag_paths(native):
+    """Every outcome of the state machine on an odd-sized pair (test_direct_host.flag_cases): FLAG_SINGULAR, FLAG_DENOMINATOR,
+    FLAG_FEW_VALID, FLAG_MAX_ITERS at max_iters 1 and 2, FLAG_NO_GAIN and no flag at fractions 0.0, 0.1 and 0.5."""
+    refine_parity(native, flag_cases())
+
+
+def test_refine_full_hd(native):
+    """One 1080 x 1920 pair (254 slabs per pass through k_direct_state's ordered reduction) ends without a flag, as on the
+    host, and recovers the rendered warp."""
+    refine_parity(native, {"full_hd": full_hd_case()})
 
 
 def test_recovers_known_warps_full_size(native):

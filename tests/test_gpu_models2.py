@@ -45,7 +45,8 @@ def field2_np(params, h, w):
 
 
 def stage_np(gt, model, frac, level_hw):
-    """Threshold, mask (motion.py:240-244) and the 27 sequential sums over the ordered inliers."""
+    """Threshold, mask (motion.py:240-244) and the 27 sequential sums over the ordered inliers, each started at +0.0 (so that
+    a chain of -0.0 terms sums to +0.0, as the reference's accumulators do)."""
     h, w = gt.shape[:2]
     n = h * w
     diff = (np.abs(gt[:, :, 0].astype(np.int64) - model[:, :, 0]) + np.abs(gt[:, :, 1].astype(np.int64) - model[:, :, 1])).ravel()
@@ -60,7 +61,7 @@ def stage_np(gt, model, frac, level_hw):
     g0, g1 = gt.reshape(-1, 2)[k, 0].astype(np.float64), gt.reshape(-1, 2)[k, 1].astype(np.float64)
     wgt = 1.0 / (float(level_hw[0]) * float(level_hw[1]))
     cols = [x ** p * y ** q for p, q in MOMENTS] + [x ** p * y ** q * g0 for p, q in PHI] + [x ** p * y ** q * g1 for p, q in PHI]
-    sums = np.array([np.cumsum(c * wgt)[-1] if len(c) else 0.0 for c in cols])
+    sums = np.array([np.cumsum(np.concatenate([[0.0], c * wgt]))[-1] for c in cols])      # from +0.0, as the reference
     return thr, mask.reshape(h, w), sums
 
 
@@ -165,6 +166,66 @@ def test_exact_second_order_stage(golden, native):
             want = co.compensate(frames[0], want_field.astype(np.int32))
             assert np.array_equal(comp, want), (name, k)
             assert sse == co.sse(frames[1], want), (name, k)
+        seq.close()
+
+
+FIT_LIST_LDS_BYTES = 40 * 1024        # gme_internal.h: larger inlier lists (16 bytes per block) live in global memory
+
+
+def global_list_stages():
+    """(name, frames uint8[3, H, W], begin_fit block size or None, [(bbme block size for level -1)]) whose stages all hold
+    more than FIT_LIST_LDS_BYTES / 16 = 2560 blocks: full HD and a ragged size at levels 2 and 1 (bs 8) and -1 (bs 16),
+    480 x 720 at level -1 after small-block searches."""
+    import synth
+    return [("hd", synth.sequence(31, 0, 3, 1080, 1920), 8, [16]),
+            ("ragged", synth.sequence(32, 4, 3, 1078, 1918), 8, [16]),
+            ("synth720", synth.sequence(1234, 5, 3, 480, 720), None, [8, 4])]
+
+
+def check_stage_pair(seq, order, level, pair, p12, frac, lvl_hw, sums, what):
+    """One pair's stage against field2_np / stage_np bit for bit; order 1 against the affine part of the order-2 sums."""
+    import roadmap
+    st = seq.gme_read_stage(level, pair)
+    hh, ww = st["gt"].shape[:2]
+    assert hh * ww * 16 > FIT_LIST_LDS_BYTES, (what, hh, ww)                 # the global inlier list
+    model = field2_np(p12, hh, ww)
+    assert np.array_equal(st["model"], model), what
+    thr, mask, want = stage_np(st["gt"], model, frac, lvl_hw)
+    assert st["thr"] == thr and np.array_equal(st["mask"], mask), what
+    if order == 1:
+        want = roadmap.affine_sums(want)[0]
+    assert np.array_equal(bits(sums), bits(want)), (what, sums - want)
+
+
+def test_second_order_stage_global_list(native):
+    """test_exact_second_order_stage where the inlier list does not fit in LDS (k_fit_level2 / k_fit_level with the global
+    list): field, threshold, mask and all 27 sums bit for bit against the NumPy restatements for every SECOND parameter set
+    and fractions 0.3, 0.0 and -1, two pairs with different parameters per call (the per-pair list offset); the order-1
+    fit's 15 sums at the same stages against the affine part of the restated 27."""
+    ctx = native.default_context()
+    for name, frames, fit_bs, mv_bs in global_list_stages():
+        H, W = frames.shape[1:]
+        seq = native.Sequence(ctx, 3, H, W)
+        seq.upload(0, frames)
+        stages = []
+        if fit_bs:
+            seq.gme_begin_fit2(1, fit_bs, 0.3)
+            stages += [(2, None), (1, None)]
+        stages += [(-1, b) for b in mv_bs]
+        for level, bs in stages:
+            if bs:
+                seq.bbme(1, bs, 2, 3, 1)
+            lvl_hw = seq.level_shape(1) if level == 1 else (H, W)
+            for k in range(len(SECOND)):
+                p12 = np.stack([SECOND[k], SECOND[(k + 1) % len(SECOND)]])
+                for frac in (0.3, 0.0, -1.0):
+                    s27 = np.array(seq.gme_fit2(level, p12, frac))
+                    for pair in range(2):
+                        check_stage_pair(seq, 2, level, pair, p12[pair], frac, lvl_hw, s27[pair], (name, level, bs, k, frac, pair))
+                    s15 = np.array(seq.gme_fit(level, p12[:, :6], frac))
+                    for pair in range(2):
+                        check_stage_pair(seq, 1, level, pair, pad12(p12[pair, :6])[0], frac, lvl_hw, s15[pair],
+                                         (name, level, bs, k, frac, pair, "order 1"))
         seq.close()
 
 

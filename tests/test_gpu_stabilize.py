@@ -68,6 +68,72 @@ def test_warp_equals_host(native, shape, n):
     seq.close()
 
 
+def degenerate_warps(H, W):
+    """name -> (warp, branch) for the warps random_warps never makes.  branch names what the warp must reach on an H x W
+    frame: "edge" a valid sample point exactly on u' = W-1 or v' = H-1 (the far tap clamped), "horizon" pixels with d <= 0,
+    "behind" valid samples where d < 0, "d0" d == 0 exactly on a row, "nonfinite" non-finite coordinates."""
+    nan, inf = float("nan"), float("inf")
+    return {
+        "shift_small": ([1, 0, 3, 0, 1, -2, 0, 0], "edge"),
+        "shift_half": ([1, 0, -(W // 2), 0, 1, H // 3, 0, 0], "edge"),
+        "shift_to_last_column": ([1, 0, W - 1, 0, 1, 0, 0, 0], "edge"),            # only u = 0 samples, on u' = W-1
+        "mirror_horizontal": ([-1, 0, W - 1, 0, 1, 0, 0, 0], "edge"),
+        "mirror_vertical": ([1, 0, 0, 0, -1, H - 1, 0, 0], "edge"),
+        "horizon_behind": ([1, 0, -W, 0, 1, -H, -2.0 / W, 0], "behind"),         # d < 0 past u = W/2, and u', v' land inside
+        "horizon_tilted": ([1, 0.1, 2.0, -0.05, 1, 1.0, -2.5 / W, 0.3 / H], "horizon"),
+        "d_zero_row": ([1, 0, 0, 0, 1, 0, 0, -1.0 / 32], "d0"),                     # d = 1 - v / 32: exactly 0 on row 32
+        "nan_shift": ([1, 0, nan, 0, 1, 0, 0, 0], "nonfinite"),
+        "inf_shift": ([1, 0, 0, 0, 1, inf, 0, 0], "nonfinite"),
+        "minus_inf_perspective": ([1, 0, 0, 0, 1, 0, -inf, 0], "nonfinite"),        # u' = -0.0, v' = -0.0 for u > 0
+    }
+
+
+def reaches(h, branch, H, W):
+    import direct
+    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    with np.errstate(all="ignore"):
+        up, vp, d = direct.warp(np.asarray(h, np.float64), u.ravel(), v.ravel())
+        ins = (up >= 0.0) & (up <= W - 1.0) & (vp >= 0.0) & (vp <= H - 1.0)
+    if branch == "edge":
+        return bool(np.any(ins & ((up == W - 1.0) | (vp == H - 1.0))))
+    if branch == "horizon":
+        return bool(np.any(d <= 0.0))
+    if branch == "behind":
+        return bool(np.any(ins & (d < 0.0)))
+    if branch == "d0":
+        return bool(np.any(d == 0.0))
+    return not bool(np.all(np.isfinite(up)) and np.all(np.isfinite(vp)))
+
+
+@pytest.mark.parametrize("shape", [(41, 53), (96, 131), (540, 1918)])
+def test_degenerate_warps_equal_host(native, shape):
+    """Integer shifts onto the last column / row, mirror flips, horizons crossing the frame, d == 0 on a row, NaN and +-inf
+    parameters: warped frames and valid counts bit for bit with stabilize.warp_frames in the three
+    border / fill modes, and frame_sse of the warped planes (width not a multiple of 64: the padding must stay zero)
+    equal to the int64 squared errors of the host frames."""
+    import stabilize
+    import synth
+    H, W = shape
+    warps = degenerate_warps(H, W)
+    names = sorted(warps)
+    for n in names:
+        assert reaches(warps[n][0], warps[n][1], H, W), (shape, n)
+    h = np.array([warps[n][0] for n in names], np.float64)
+    N = len(names)
+    frames = synth.sequence(77, 0, N, H, W) if H > 64 else np.random.default_rng(W).integers(0, 256, (N, H, W), dtype=np.uint8)
+    seq = sequence_of(native, frames)
+    for border, fill in (("constant", 0), ("constant", 201), ("replicate", 0)):
+        valid = seq.warp_frames(0, h, stabilize.border_id(border), fill)
+        want, want_valid = stabilize.warp_frames(frames, h, border, fill)
+        got = seq.read_warped_range(0, N)
+        for k, n in enumerate(names):
+            assert np.array_equal(got[k], want[k]), (shape, border, fill, n)
+            assert valid[k] == want_valid[k], (shape, border, fill, n, valid[k], want_valid[k])
+        w = want.astype(np.int64)
+        assert np.array_equal(seq.frame_sse(1, 0, N - 1), ((w[1:] - w[:-1]) ** 2).sum(axis=(1, 2))), (shape, border, fill)
+    seq.close()
+
+
 def test_grid_chunks_give_the_same_bytes(native, monkeypatch):
     import stabilize
     import synth
