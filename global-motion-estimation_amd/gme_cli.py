@@ -109,8 +109,7 @@ def _projective(args):
     prev, cur = _gme_native.as_frame(frames[args.fi - args.fd]), _gme_native.as_frame(frames[args.fi])
     seq = motion._pair_sequence(prev, cur)
     bs = int(motion.BBME_BLOCK_SIZE)
-    affine = motion.estimate_sequence(seq, 1)
-    sse_affine = seq.compensate(1, bs, affine)
+    affine, sse_affine = roadmap.estimate_blocking(seq, 1, compensate=True)
     h, flags = roadmap.refine_sequence(seq, 1, roadmap.affine_to_projective(affine, bs), args.outlier_fraction, args.max_iters)
     sse_proj = seq.compensate_projective(1, h)
     psnr = sequence.psnr_from_sse(np.concatenate([sse_affine, sse_proj]), *prev.shape)

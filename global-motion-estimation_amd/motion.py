@@ -122,19 +122,10 @@ def estimate_sequence(seq, frame_distance=1, procedure=3, search_window=2):
     """motion.global_motion_estimation for every pair of a device-resident sequence.
 
     Returns float64[P, 6].  Three device phases (begin, fit level 1, fit level 2) with the
-    per-pair 3x3 solves on the host in between, exactly the order of motion.py:123-136.
+    per-pair 3x3 solves on the host in between, exactly the order of motion.py:123-136 (roadmap.stages).
     """
-    if getattr(seq, "_split", False):
-        raise RuntimeError("estimate_sequence needs blocking calls: the sequence is in split-phase mode "
-                           "(set_split_phase(False) first, or drive it with wait() like sequence._interleaved)")
-    frac = float(MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
-    # first parameters -> projection -> level-1 fit stay on the device (gme_seq_gme_begin_fit); the host solves level 1,
-    # projects (in float64, the solution's dtype) and asks for level 2
-    _, sums = seq.gme_begin_fit(frame_distance, int(BBME_BLOCK_SIZE), frac, procedure, search_window)
-    params = _solve_batch(sums)
-    params[:, 0] = params[:, 0] * 2                # parameter_projection
-    params[:, 3] = params[:, 3] * 2
-    return _solve_batch(seq.gme_fit(2, params, frac))
+    import roadmap                                 # roadmap imports this module
+    return roadmap.estimate_blocking(seq, frame_distance, "affine", procedure, search_window)[0]
 
 
 def global_motion_estimation(previous, current):

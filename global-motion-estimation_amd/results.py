@@ -15,6 +15,7 @@ from json import dump
 import numpy as np
 
 import motion
+import roadmap
 from sequence import estimate_stream
 from utils import draw_motion_field, get_video_frames, write_image
 
@@ -41,16 +42,7 @@ def process_frames(frames, frame_distance=FRAME_DISTANCE, save_path=None, progre
     psnr_dict = {}
     if len(frames) <= fd:
         return psnr_dict
-    # the video stays in host memory and streams through a few lanes: one lane's upload runs beside the other lanes'
-    # kernels, one host thread drives all of them (split-phase calls) and does their 3x3 solves in between; every device
-    # object is released before this returns
-    solve, stream_model, field = None, None, motion.get_motion_field_affine
-    if model != "affine":
-        import roadmap
-        if model in roadmap.SECOND_ORDER:       # order-2 stages, params[P, 12] (sequence.StreamEstimator.run)
-            stream_model, field = model, roadmap.model_field
-        else:
-            solve = lambda sums: roadmap.solve_model(sums, model)       # noqa: E731
+    field = roadmap.model_field if roadmap.normalize_model(model)[1] == 2 else motion.get_motion_field_affine
     field_shape = (int(shape[0] / bs), int(shape[1] / bs), 2)
     written = {}
 
@@ -78,8 +70,8 @@ def process_frames(frames, frame_distance=FRAME_DISTANCE, save_path=None, progre
     # the video stays in host memory and streams through a few lanes: one lane's upload runs beside the other lanes'
     # kernels, one host thread drives all of them (split-phase calls) and does their 3x3 solves in between; every device
     # object is released before this returns
-    params, psnr = estimate_stream(frames, fd, chunk_pairs=CHUNK_PAIRS, streams=STREAMS, solve=solve,
-                                   on_chunk=write_chunk if save_path is not None else None, model=stream_model)
+    params, psnr = estimate_stream(frames, fd, chunk_pairs=CHUNK_PAIRS, streams=STREAMS,
+                                   on_chunk=write_chunk if save_path is not None else None, model=model)
     for idx in range(fd, len(frames)):
         p = idx - fd
         if progress:

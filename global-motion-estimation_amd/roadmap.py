@@ -196,15 +196,69 @@ def model_field(shape, params):
     return _gme_native.default_context().model2_field(p, int(shape[0]), int(shape[1]))
 
 
+def normalize_model(model):
+    """A motion model name -> (name, order, parameters per pair): None and "affine" give ("affine", 1, 6), the other
+    first-order models order 1 and 6 parameters, SECOND_ORDER order 2 and 12; ValueError for a name not in MODELS."""
+    if model is None:
+        model = "affine"
+    if model not in MODELS:
+        raise ValueError("unknown motion model %r (choose from %r)" % (model, MODELS))
+    return (model, 2, 12) if model in SECOND_ORDER else (model, 1, 6)
+
+
+def stages(seq, frame_distance, model="affine", procedure=3, search_window=2, compensate=False):
+    """The staged estimate of every pair of ``seq`` (motion.py:123-136), as a generator that queues each device call and
+    yields when the next step needs its result: begin-fit (dense field, first parameters, projection, level-1 fit) ->
+    host solve -> ``project`` -> level-2 fit -> host solve, then optionally compensation.  Returns (params, sse int64[P] or
+    None).  A blocking sequence has the result at the yield already; a split-phase one once wait() returns.  Block size and
+    outlier fraction are read from ``motion`` here, at call time."""
+    model, order, _ = normalize_model(model)
+    frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
+    bs = int(motion.BBME_BLOCK_SIZE)
+    _, sums = seq._begin_fit(order, frame_distance, bs, frac, procedure, search_window)
+    yield
+    sums = seq._fit(order, 2, project(solve_model(sums, model)), frac)      # projected in float64, the solution's dtype
+    yield
+    params = solve_model(sums, model)
+    if not compensate:
+        return params, None
+    sse = seq._compensate(order, frame_distance, bs, params)
+    yield
+    return params, np.array(sse)                 # a split-phase call's buffer is reused by the next call of its kind
+
+
+def device_stages(seq, frame_distance, model="affine", procedure=3, search_window=2):
+    """The whole estimate + compensation with the solves on the device (gme_device_solve, or gme_device_solve2 for a
+    second-order model) as a one-step chain like ``stages`` -> (params, sse, flags).  Pairs with a non-zero flag must be
+    redone by ``stages``."""
+    model, order, _ = normalize_model(model)
+    frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
+    bs = int(motion.BBME_BLOCK_SIZE)
+    if model == "affine":
+        params, sse, flags = seq.gme_device_solve(frame_distance, bs, frac, procedure, search_window)
+    else:
+        params, sse, flags = seq.gme_device_solve2(model, frame_distance, bs, frac, procedure, search_window)
+    yield
+    return np.array(params), np.array(sse), np.array(flags)
+
+
+def estimate_blocking(seq, frame_distance, model="affine", procedure=3, search_window=2, compensate=False):
+    """``stages`` run to its end with blocking calls -> (params, sse or None)."""
+    if getattr(seq, "_split", False):
+        raise RuntimeError("estimate_sequence needs blocking calls: the sequence is in split-phase mode (set_split_phase(False) "
+                           "first, or drive roadmap.stages with wait() like sequence.ShardedSequence._round_robin)")
+    chain = stages(seq, frame_distance, model, procedure, search_window, compensate)
+    while True:
+        try:
+            next(chain)
+        except StopIteration as done:
+            return done.value
+
+
 def estimate_sequence(seq, frame_distance=1, model="affine", procedure=3, search_window=2):
     """motion.estimate_sequence with a selectable motion model -> float64[P, 6] (affine layout), or float64[P, 12] for the
     second-order models (order-2 device fits, gme_seq_gme_begin_fit2 / gme_seq_gme_fit2)."""
-    if getattr(seq, "_split", False):
-        raise RuntimeError("estimate_sequence needs blocking calls: the sequence is in split-phase mode")
-    frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
-    begin, fit = (seq.gme_begin_fit2, seq.gme_fit2) if model in SECOND_ORDER else (seq.gme_begin_fit, seq.gme_fit)
-    _, sums = begin(frame_distance, int(motion.BBME_BLOCK_SIZE), frac, procedure, search_window)
-    return solve_model(fit(2, project(solve_model(sums, model)), frac), model)
+    return estimate_blocking(seq, frame_distance, model, procedure, search_window)[0]
 
 
 def global_motion_estimation(previous, current, model="affine"):

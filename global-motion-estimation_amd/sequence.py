@@ -370,14 +370,14 @@ class ShardedSequence:
 
     ``streams`` > 1 cuts the slice once more into that many contiguous pair ranges, each with
     its own context (= HIP stream) on the same GPU and driven by its own host thread.  The
-    staged estimate (motion.estimate_sequence) has the host solve 3x3 systems between device
+    staged estimate (roadmap.stages) has the host solve 3x3 systems between device
     stages; with several streams one range's solves and launch latencies are covered by the
     other ranges' kernels.  Results do not depend on ``streams``.
 
     ``interleave=True`` drives the ranges from ONE host thread instead, through the split-phase calls
     of the C ABI (gme_seq_set_split_phase / gme_seq_wait): stage s of every range is queued, then each
     range's result is awaited and solved in turn while the other ranges' kernels run.  No host threads
-    contend for the interpreter or the BLAS; estimate_and_compensate() is the call that uses it.
+    contend for the interpreter or the BLAS; estimate() and estimate_and_compensate() use it.
     """
 
     def __init__(self, height, width, n_frames, frame_distance=1, rank=0, world=1, ctx=None, streams=1, interleave=False):
@@ -468,28 +468,13 @@ class ShardedSequence:
             return lane.seq.read_mv(0, lane.hi - lane.lo)
         return np.concatenate(self._each(run), axis=0)
 
-    @staticmethod
-    def _model(model):
-        """None for the reference's affine path (model None or "affine"), else the roadmap.MODELS name; ValueError otherwise."""
-        if model is None or model == "affine":
-            return None
-        if model not in roadmap.MODELS:
-            raise ValueError("unknown motion model %r (choose from %r)" % (model, roadmap.MODELS))
-        return model
-
     def estimate(self, procedure=3, search_window=2, model=None):
         """motion.global_motion_estimation for every local pair -> float64[P_local, 6].  ``model``: one of roadmap.MODELS
-        (roadmap.estimate_sequence per lane); the second-order models return float64[P_local, 12]."""
-        model = self._model(model)
+        (roadmap.stages per lane); the second-order models return float64[P_local, 12]."""
+        model, _, width = roadmap.normalize_model(model)
         if not self.lanes:
-            return np.zeros((0, 12 if model in roadmap.SECOND_ORDER else 6))
-        if self.interleave and len(self.lanes) > 1:
-            return self._interleaved(procedure, search_window, False, model=model)[0]
-        if model is not None:
-            return np.concatenate(self._each(
-                lambda lane: roadmap.estimate_sequence(lane.seq, self.fd, model, procedure, search_window)[:lane.hi - lane.lo]), axis=0)
-        return np.concatenate(self._each(
-            lambda lane: motion.estimate_sequence(lane.seq, self.fd, procedure, search_window)[:lane.hi - lane.lo]), axis=0)
+            return np.zeros((0, width))
+        return self._join(self._stages(procedure, search_window, model, False))[0]
 
     def _psnr(self, sse, exact=True):
         return psnr_from_sse(sse, self.H, self.W, exact)
@@ -507,103 +492,70 @@ class ShardedSequence:
         """estimate() then compensate() per stream without a join in between -> (params[P,6], psnr[P]).
 
         ``model``: one of roadmap.MODELS (None or "affine": the reference's path).  The others run the staged calls of their
-        order with roadmap.solve_model / roadmap.project; the second-order models return params[P, 12] and, under
-        GME_DEVICE_SOLVE=1, solve on the device (gme_device_solve2) unless a pair is flagged."""
-        model = self._model(model)
-        order2 = model in roadmap.SECOND_ORDER
-        if not self.lanes:
-            return np.zeros((0, 12 if order2 else 6)), np.zeros(0)
+        order with roadmap.solve_model / roadmap.project; the second-order models return params[P, 12].
 
-        if os.environ.get("GME_DEVICE_SOLVE") == "1" and (model is None or order2):
+        Under GME_DEVICE_SOLVE=1 the affine and second-order models try the device solve first (_device_solved)."""
+        model, order, width = roadmap.normalize_model(model)
+        if not self.lanes:
+            return np.zeros((0, width)), np.zeros(0)
+        if os.environ.get("GME_DEVICE_SOLVE") == "1" and (model == "affine" or order == 2):
             got = self._device_solved(procedure, search_window, exact_psnr, model=model)
             if got is not None:
-                return got                        # else: a pair sat on a rounding tie (or was singular / ill-conditioned): the host path below
+                return got
+        return self._join(self._stages(procedure, search_window, model, True), exact_psnr)
 
-        if self.interleave and len(self.lanes) > 1:
-            return self._interleaved(procedure, search_window, True, exact_psnr, model=model)
-
-        def run(lane):
-            n = lane.hi - lane.lo
-            if model is not None:
-                p = roadmap.estimate_sequence(lane.seq, self.fd, model, procedure, search_window)[:n]
-                comp = lane.seq.compensate2 if order2 else lane.seq.compensate
-                return p, comp(self.fd, int(motion.BBME_BLOCK_SIZE), p)[:n]
-            p = motion.estimate_sequence(lane.seq, self.fd, procedure, search_window)[:n]
-            return p, lane.seq.compensate(self.fd, int(motion.BBME_BLOCK_SIZE), p)[:n]
-        parts = self._each(run)
-        return np.concatenate([p for p, _ in parts], axis=0), self._psnr(np.concatenate([s for _, s in parts]), exact_psnr)
-
-    def _device_solved(self, procedure, search_window, exact_psnr=False, model=None):
-        """estimate_and_compensate() with the 3x3 solves on the device (GME_DEVICE_SOLVE=1, gme_seq_gme_device_solve): every
-        lane's whole estimate is queued in one call, one wait per lane.  Parameters are within rtol 1e-10 of the host
-        path's (LAPACK's last bits are not reproduced); model fields, masks, compensated frames and PSNR are bit-equal to
-        it -- unless the library flags a pair (a model displacement within 1e-9 of a rounding tie, or a singular system):
-        then nothing is returned and the caller runs the host path, which also raises upstream's LinAlgError.
-        A second-order ``model`` solves its own system instead (gme_seq_gme_device_solve2, whose header states the contract;
-        it also flags ill-conditioned systems)."""
-        frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
-        bs = int(motion.BBME_BLOCK_SIZE)
-        lanes = self.lanes
-        for lane in lanes:
-            lane.seq.set_split_phase(True)
-        try:
-            if model is None:
-                pending = [lane.seq.gme_device_solve(self.fd, bs, frac, procedure, search_window) for lane in lanes]
-            else:
-                pending = [lane.seq.gme_device_solve2(model, self.fd, bs, frac, procedure, search_window) for lane in lanes]
-            params, sse, clean = [], [], True
-            for lane, (p, e, f) in zip(lanes, pending):
-                lane.seq.wait()
-                n = lane.hi - lane.lo
-                clean = clean and not np.any(f[:n])
-                params.append(np.array(p[:n]))
-                sse.append(np.array(e[:n]))
-                lane.ctx.sync()                   # drains the stream and reports a walk that overran its guard
-        finally:
-            for lane in lanes:
-                lane.seq.set_split_phase(False)
-        if not clean:
+    def _device_solved(self, procedure, search_window, exact_psnr=False, model="affine"):
+        """estimate_and_compensate() with the solves on the device (roadmap.device_stages, round robin): one call and one
+        wait per lane -> (params, psnr), or None when the library flags a pair (near a rounding tie, singular or
+        ill-conditioned) and the caller must run the host path.  Affine parameters are within rtol 1e-10 of the host path's;
+        model fields, masks, compensated frames and PSNR are bit-equal to it (the order-2 contract:
+        gme_seq_gme_device_solve2 in the header)."""
+        parts = self._round_robin(lambda lane: roadmap.device_stages(lane.seq, self.fd, model, procedure, search_window))
+        if any(np.any(f[:lane.hi - lane.lo]) for lane, (_, _, f) in zip(self.lanes, parts)):
             return None
-        return np.concatenate(params, axis=0), self._psnr(np.concatenate(sse), exact_psnr)
+        return self._join(parts, exact_psnr)
 
-    def _interleaved(self, procedure, search_window, compensate, exact_psnr=False, model=None):
-        """estimate() / estimate_and_compensate() for several ranges from one host thread: every stage is queued on
-        all streams before the first result is awaited, so range k's projection and 3x3 solves (motion.py:191-207,
-        262-282, the same arithmetic as motion.estimate_sequence) run while the other ranges' searches do.
-        ``model`` (roadmap.MODELS, None: affine) selects the stages' order and roadmap.solve_model's solve.
-        -> (params[P, 6] (12 for a second-order model), psnr[P] or None)"""
-        frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
-        bs = int(motion.BBME_BLOCK_SIZE)
+    def _stages(self, procedure, search_window, model, compensate):
+        """roadmap.stages on every lane -> [(params, sse or None)] in lane order: driven round robin from one host thread
+        (``interleave`` and several lanes), else with blocking calls, one host thread per lane."""
+        if self.interleave and len(self.lanes) > 1:
+            return self._round_robin(lambda lane: roadmap.stages(lane.seq, self.fd, model, procedure, search_window, compensate))
+        return self._each(lambda lane: roadmap.estimate_blocking(lane.seq, self.fd, model, procedure, search_window, compensate))
+
+    def _round_robin(self, chain):
+        """``chain(lane)`` (roadmap.stages) of every lane driven from ONE host thread through the split-phase calls
+        (gme_seq_set_split_phase / gme_seq_wait) -> what each chain returns, in lane order.  Stage s is queued on every lane
+        before the first wait; each lane in turn is then awaited, solved and its stage s + 1 queued, so one lane's host
+        solves run while the other lanes' kernels do."""
         lanes = self.lanes
-        solve = motion._solve_batch if model is None else (lambda sums: roadmap.solve_model(sums, model))
-        order2 = model in roadmap.SECOND_ORDER
         for lane in lanes:
             lane.seq.set_split_phase(True)
         try:
-            # first parameters, their projection and the level-1 fit in one queued call (gme_seq_gme_begin_fit)
-            pending = [(lane.seq.gme_begin_fit2 if order2 else lane.seq.gme_begin_fit)(self.fd, bs, frac, procedure, search_window)[1]
-                       for lane in lanes]
-            for k, lane in enumerate(lanes):
-                lane.seq.wait()
-                p = roadmap.project(solve(pending[k]))                    # level 1 solved, projected in float64, level 2 asked for
-                pending[k] = (lane.seq.gme_fit2 if order2 else lane.seq.gme_fit)(2, p, frac)
-            params, sse = [None] * len(lanes), [None] * len(lanes)
-            for k, lane in enumerate(lanes):
-                lane.seq.wait()
-                params[k] = solve(pending[k])
-                if compensate:
-                    sse[k] = (lane.seq.compensate2 if order2 else lane.seq.compensate)(self.fd, bs, params[k])
-            out_sse = []
-            for k, lane in enumerate(lanes):
-                if compensate:
-                    lane.seq.wait()
-                    out_sse.append(np.array(sse[k][:lane.hi - lane.lo]))
-                lane.ctx.sync()                   # drains the stream and reports a walk that overran its guard
+            chains = [chain(lane) for lane in lanes]
+            for c in chains:
+                next(c)
+            out, left = [None] * len(lanes), list(range(len(lanes)))
+            while left:
+                for k in list(left):
+                    lanes[k].seq.wait()
+                    try:
+                        next(chains[k])                   # the lane's solve, and its next stage queued
+                    except StopIteration as done:
+                        out[k] = done.value
+                        left.remove(k)
+                        lanes[k].ctx.sync()       # drains the stream and reports a walk that overran its guard
         finally:
             for lane in lanes:
                 lane.seq.set_split_phase(False)   # the other methods of the class use the blocking calls
-        p_all = np.concatenate([p[:lane.hi - lane.lo] for p, lane in zip(params, lanes)], axis=0)
-        return p_all, (self._psnr(np.concatenate(out_sse), exact_psnr) if compensate else None)
+        return out
+
+    def _join(self, parts, exact_psnr=False):
+        """Per-lane (params, sse or None, ...) -> (params[P_local, k], psnr[P_local] or None)."""
+        n = [lane.hi - lane.lo for lane in self.lanes]
+        params = np.concatenate([part[0][:m] for part, m in zip(parts, n)], axis=0)
+        if parts[0][1] is None:
+            return params, None
+        return params, self._psnr(np.concatenate([part[1][:m] for part, m in zip(parts, n)]), exact_psnr)
 
     def estimate_projective(self, procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10, exact_psnr=False):
         """Direct projective refinement of every local pair from its indirect affine estimate, and the
@@ -721,8 +673,6 @@ class StreamEstimator:
     ``frames``: uint8[N, H, W] (page-locked memory from _gme_native.pinned_empty crosses at link speed and never holds
     the host thread) or a list of 2-D uint8 arrays (gathered chunk by chunk into a page-locked buffer per lane).
     ``compensated``: optional uint8[P, H, W] array that receives every compensated frame (results.py:59 writes them out).
-    ``solve``: float64[n, 15] normal-equation sums -> float64[n, 6] parameters; default motion._solve_batch (the
-    reference's two 3x3 systems), roadmap.solve_model for the other motion models.
     Results equal the resident path bit for bit (tests/test_gpu_round3.py)."""
 
     def __init__(self, height, width, frame_distance=1, chunk_pairs=512, streams=2, ctx=None, procedure=3, search_window=2,
@@ -739,7 +689,7 @@ class StreamEstimator:
                 c = self.ctx if j == 0 else _native.Context(self.ctx.device)
                 seq = _native.Sequence(c, self.cap, self.H, self.W)
                 seq.set_split_phase(True)
-                self.lanes.append(types.SimpleNamespace(ctx=c, seq=seq, host=None, chunk=None, stage=0, pending=None, params=None))
+                self.lanes.append(types.SimpleNamespace(ctx=c, seq=seq, host=None, comp_host=None, chain=None, steps=0))
         except BaseException:
             self.close(check=False)
             raise
@@ -782,37 +732,26 @@ class StreamEstimator:
             p0 += c
         return out
 
-    def run(self, frames, compensated=None, exact_psnr=True, solve=None, on_chunk=None, model=None):
+    def run(self, frames, compensated=None, exact_psnr=True, on_chunk=None, model=None):
         """``on_chunk(p0, p1, comp, params, psnr)`` is called as each chunk finishes (chunks of different lanes may finish out
         of order) with its compensated frames uint8[p1 - p0, H, W] (one read for the chunk; the array is reused by the next
         chunk of the same lane), parameters and PSNR: what results.py writes per pair, without a whole-video array on the host.
 
         ``model``: one of roadmap.MODELS (None: the reference's affine path, as without the argument).  The second-order
-        models (roadmap.SECOND_ORDER) run the order-2 stages (gme_begin_fit2 / gme_fit2 / compensate2) and return
-        params float64[P, 12]."""
+        models (roadmap.SECOND_ORDER) run the order-2 stages and return params float64[P, 12]."""
         fd, H, W, cap = self.fd, self.H, self.W, self.cap
         P = max(0, len(frames) - fd)
-        order2 = False
-        if model is not None:
-            if model not in roadmap.MODELS:
-                raise ValueError("unknown motion model %r (choose from %r)" % (model, roadmap.MODELS))
-            order2 = model in roadmap.SECOND_ORDER
-            if solve is None:
-                solve = lambda sums: roadmap.solve_model(sums, model)       # noqa: E731
-        params_out, sse_out = np.zeros((P, 12 if order2 else 6)), np.zeros(P, dtype=np.int64)
+        model, _, width = roadmap.normalize_model(model)
+        params_out, sse_out = np.zeros((P, width)), np.zeros(P, dtype=np.int64)
         if P == 0:
             return params_out, np.zeros(0)
         if tuple(np.asarray(frames[0]).shape) != (H, W):
             raise ValueError("frames of %r do not fit this estimator's %r" % (np.asarray(frames[0]).shape, (H, W)))
         chunks = self.schedule(P)
         stacked = isinstance(frames, np.ndarray) and frames.ndim == 3 and frames.dtype == np.uint8 and frames.flags.c_contiguous
-        frac = float(motion.MOTION_VECTOR_ERROR_THRESHOLD_PERCENTAGE)
-        bs = int(motion.BBME_BLOCK_SIZE)
-        solve = solve or motion._solve_batch
 
-        def start(lane, chunk):
-            lane.chunk, lane.stage = chunk, 1
-            p0, p1 = chunk
+        def chunk(lane, p0, p1):
+            """One chunk on one lane, a stage chain like roadmap.stages: the upload, the staged estimate, the results."""
             n = p1 - p0 + fd
             if stacked:
                 src = frames[p0:p0 + n]
@@ -826,42 +765,25 @@ class StreamEstimator:
             lane.seq.upload(0, src)              # queued; `src` stays alive (lane.host / the caller's array)
             # Nothing else is queued on the lane yet: a kernel launch behind a cross-stream wait on a copy holds the calling
             # thread until that copy is done (measured: one gme_begin_fit call of 7.6 ms, the upload of two chunks), and the
-            # one host thread must stay free for the other lanes.  Stage 1 ends when the upload's event has arrived.
-
-        def advance(lane):
-            """Take the lane's result (it has arrived) and queue its next stage -> True when the chunk is finished."""
-            seq, (p0, p1) = lane.seq, lane.chunk
-            n = p1 - p0
-            seq.wait()
-            if lane.stage == 1:                  # the chunk is on the device: dense field, first parameters, level-1 fit
-                begin = seq.gme_begin_fit2 if order2 else seq.gme_begin_fit
-                lane.pending = begin(fd, bs, frac, self.procedure, self.search_window)[1]
-                lane.stage = 2
-                return False
-            if lane.stage == 2:                  # level-1 sums are back: solve, project (float64), ask for level 2
-                p = roadmap.project(solve(lane.pending[:n]))
-                lane.pending = (seq.gme_fit2 if order2 else seq.gme_fit)(2, p, frac)
-                lane.stage = 3
-                return False
-            if lane.stage == 3:
-                lane.params = solve(lane.pending[:n])
-                lane.pending = (seq.compensate2 if order2 else seq.compensate)(fd, bs, lane.params)
-                lane.stage = 4
-                return False
-            params_out[p0:p1] = lane.params
-            sse_out[p0:p1] = lane.pending[:n]
+            # one host thread must stay free for the other lanes.  The stages follow once the upload's event has arrived.
+            yield
+            params, sse = yield from roadmap.stages(lane.seq, fd, model, self.procedure, self.search_window, compensate=True)
+            params_out[p0:p1] = params
+            sse_out[p0:p1] = sse
             if compensated is not None:
-                seq.read_compensated_range(0, n, compensated[p0:p1])      # one wait for the chunk, not one per pair
+                lane.seq.read_compensated_range(0, p1 - p0, compensated[p0:p1])      # one wait for the chunk, not one per pair
             if on_chunk is not None:
                 if compensated is not None:
                     comp = compensated[p0:p1]
                 else:
-                    if getattr(lane, "comp_host", None) is None:
+                    if lane.comp_host is None:
                         lane.comp_host = np.empty((cap, H, W), np.uint8)
-                    comp = seq.read_compensated_range(0, n, lane.comp_host[:n])
-                on_chunk(p0, p1, comp, lane.params[:n], psnr_from_sse(lane.pending[:n], H, W, exact_psnr))
-            lane.stage = 0
-            return True
+                    comp = lane.seq.read_compensated_range(0, p1 - p0, lane.comp_host[:p1 - p0])
+                on_chunk(p0, p1, comp, params, psnr_from_sse(sse, H, W, exact_psnr))
+
+        def start(lane, p0_p1):
+            lane.chain, lane.steps = chunk(lane, *p0_p1), 1
+            next(lane.chain)
 
         todo = list(reversed(chunks))
         busy = []
@@ -873,10 +795,14 @@ class StreamEstimator:
             # serve whichever lane has its result: a lane that waits for its frames must not hold up one whose sums are
             # back; the lanes furthest along go first, so that their next chunk's upload is queued as early as possible
             progressed = False
-            for lane in sorted(busy, key=lambda l: -l.stage):
+            for lane in sorted(busy, key=lambda l: -l.steps):
                 if lane.seq.poll():
                     progressed = True
-                    if advance(lane):
+                    lane.seq.wait()
+                    try:
+                        next(lane.chain)         # the lane's solve, and its next stage queued
+                        lane.steps += 1
+                    except StopIteration:        # the chunk is finished
                         if todo:
                             start(lane, todo.pop())
                         else:
@@ -890,20 +816,17 @@ class StreamEstimator:
 
 
 def estimate_stream(frames, frame_distance=1, chunk_pairs=512, streams=2, ctx=None, compensated=None, procedure=3, on_chunk=None,
-                    search_window=2, exact_psnr=True, solve=None, min_chunk=64, model=None):
+                    search_window=2, exact_psnr=True, min_chunk=64, model=None):
     """One-shot StreamEstimator: allocate the lanes, run `frames` through them, release them
     -> (params float64[P, 6], psnr float64[P]); params float64[P, 12] for a second-order ``model`` (StreamEstimator.run).
     Setting the lanes up costs a few milliseconds each; callers with several videos of one size keep a StreamEstimator."""
     n_frames = len(frames)
     P = max(0, n_frames - int(frame_distance))
     if P == 0:
-        width = 6
-        if model is not None:
-            width = 12 if model in roadmap.SECOND_ORDER else 6
-        return np.zeros((0, width)), np.zeros(0)
+        return np.zeros((0, roadmap.normalize_model(model)[2])), np.zeros(0)
     H, W = np.asarray(frames[0]).shape
     chunk_pairs = max(1, min(int(chunk_pairs), P))
     n_chunks = (P + chunk_pairs - 1) // chunk_pairs
     with StreamEstimator(H, W, frame_distance, chunk_pairs, max(1, min(int(streams), n_chunks)), ctx, procedure, search_window,
                          min_chunk=min_chunk) as est:
-        return est.run(frames, compensated=compensated, exact_psnr=exact_psnr, solve=solve, on_chunk=on_chunk, model=model)
+        return est.run(frames, compensated=compensated, exact_psnr=exact_psnr, on_chunk=on_chunk, model=model)
