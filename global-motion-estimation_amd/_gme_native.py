@@ -35,6 +35,7 @@ class GmeError(RuntimeError):
 
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
 _c_i16p = ctypes.POINTER(ctypes.c_int16)
+_c_u16p = ctypes.POINTER(ctypes.c_uint16)
 _c_i32p = ctypes.POINTER(ctypes.c_int32)
 _c_i64p = ctypes.POINTER(ctypes.c_int64)
 _c_f32p = ctypes.POINTER(ctypes.c_float)
@@ -102,6 +103,10 @@ _SIGNATURES = {
     "gme_seq_warp_frames": (_i, [_vp, _i, _i, _c_f64p, _i, _i, _c_i64p]),
     "gme_seq_read_warped_range": (_i, [_vp, _i, _i, _c_u8p]),
     "gme_seq_frame_sse": (_i, [_vp, _i, _i, _i, _c_i64p]),
+    "gme_seq_mosaic": (_i, [_vp, _i, _i, _c_f64p, _c_u8p, _i, _i, _i, _i, _i, _i]),
+    "gme_seq_read_mosaic": (_i, [_vp, _c_u8p, _c_u16p]),
+    "gme_seq_moving_masks": (_i, [_vp, _i, _i, _c_f64p, _c_u8p, _i, _i, _i, _i, _c_i64p, _c_i64p]),
+    "gme_seq_read_masks_range": (_i, [_vp, _i, _i, _c_u8p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -710,6 +715,47 @@ class Sequence:
         sse = np.zeros(int(count), np.int64)
         _check(self.lib.gme_seq_frame_sse(self.handle, int(warped), int(first), int(count), _p(sse, _c_i64p)), self.lib)
         return sse
+
+    # ---- background mosaic and moving-object masks (gme_mosaic.hip, mosaic.py)
+    def _blocking(self, what):
+        if getattr(self, "_split", False):
+            raise RuntimeError("the %s calls are blocking: the sequence is in split-phase mode" % what)
+
+    def mosaic(self, first, inv_warps, usable, ox, oy, Hc, Wc, fill=0, cull=True):
+        """The background sprite of frames first .. first+count-1 under inv_warps float64[count, 8] on the Hc x Wc canvas with
+        origin (ox, oy) (gme_seq_mosaic; ``usable`` uint8[count] or None), kept in the sequence: read_mosaic reads it."""
+        self._blocking("mosaic")
+        g = np.ascontiguousarray(np.asarray(inv_warps, dtype=np.float64).reshape(-1, 8))
+        use = None if usable is None else np.ascontiguousarray(np.asarray(usable).reshape(len(g)) != 0, dtype=np.uint8)
+        self._mosaic_shape = None
+        _check(self.lib.gme_seq_mosaic(self.handle, int(first), len(g), _p(g, _c_f64p), None if use is None else _p(use, _c_u8p),
+                                       int(ox), int(oy), int(Hc), int(Wc), int(fill), int(bool(cull))), self.lib)
+        self._mosaic_shape = (int(Hc), int(Wc))
+
+    def read_mosaic(self):
+        """(sprite uint8[Hc, Wc], count uint16[Hc, Wc]) of the last mosaic()."""
+        shape = getattr(self, "_mosaic_shape", None) or (1, 1)     # without a mosaic the library refuses before it writes
+        sprite, count = np.empty(shape, np.uint8), np.empty(shape, np.uint16)
+        _check(self.lib.gme_seq_read_mosaic(self.handle, _p(sprite, _c_u8p), _p(count, _c_u16p)), self.lib)
+        return sprite, count
+
+    def moving_masks(self, first, warps, usable, ox, oy, threshold=16, min_count=3):
+        """Masks of frames first .. first+count-1 against the sequence's mosaic under warps float64[count, 8]
+        (gme_seq_moving_masks) -> (known int64[count], moving int64[count]); read_masks_range reads the masks."""
+        self._blocking("mosaic")
+        a = np.ascontiguousarray(np.asarray(warps, dtype=np.float64).reshape(-1, 8))
+        use = None if usable is None else np.ascontiguousarray(np.asarray(usable).reshape(len(a)) != 0, dtype=np.uint8)
+        known, moving = np.zeros(len(a), np.int64), np.zeros(len(a), np.int64)
+        _check(self.lib.gme_seq_moving_masks(self.handle, int(first), len(a), _p(a, _c_f64p), None if use is None else _p(use, _c_u8p),
+                                             int(ox), int(oy), int(threshold), int(min_count), _p(known, _c_i64p),
+                                             _p(moving, _c_i64p)), self.lib)
+        return known, moving
+
+    def read_masks_range(self, first, count):
+        """Masks (0 / 1) of frames first .. first+count-1 -> uint8[count, H, W] with one wait."""
+        out = np.empty((int(count), self.H, self.W), dtype=np.uint8)
+        _check(self.lib.gme_seq_read_masks_range(self.handle, int(first), int(count), _p(out, _c_u8p)), self.lib)
+        return out
 
 
 _default = None

@@ -494,6 +494,12 @@ extern "C" void gme_seq_destroy(gme_seq* s)
     plane_free(&s->warped);
     if (s->warp_params) hipFree(s->warp_params);
     if (s->warp_counts) hipFree(s->warp_counts);
+    if (s->mosaic_sprite) hipFree(s->mosaic_sprite);
+    if (s->mosaic_count) hipFree(s->mosaic_count);
+    plane_free(&s->masks);
+    if (s->mosaic_params) hipFree(s->mosaic_params);
+    if (s->mosaic_usable) hipFree(s->mosaic_usable);
+    if (s->mosaic_counts) hipFree(s->mosaic_counts);
     if (s->summary) hipFree(s->summary);
     if (s->gathered) hipFree(s->gathered);
     if (s->ready) hipEventDestroy(s->ready);
@@ -1686,4 +1692,149 @@ extern "C" int gme_seq_frame_sse(gme_seq* s, int warped, int first, int count, i
     if (rc) return rc;
     GME_HIP_TRY(hipMemcpyAsync(sse_out, s->warp_counts, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Background mosaic and moving-object masks (gme_mosaic.hip): blocking calls on the resident frames.
+// ---------------------------------------------------------------------------
+static int mosaic_rows(gme_seq* s)
+{
+    if (s->mosaic_params) return GME_OK;
+    if (hipMalloc((void**)&s->mosaic_params, (size_t)s->N_cap * 8 * sizeof(double)) != hipSuccess ||
+        hipMalloc((void**)&s->mosaic_usable, (size_t)s->N_cap) != hipSuccess ||
+        hipMalloc((void**)&s->mosaic_counts, (size_t)s->N_cap * 2 * sizeof(unsigned long long)) != hipSuccess) {
+        if (s->mosaic_params) hipFree(s->mosaic_params);
+        if (s->mosaic_usable) hipFree(s->mosaic_usable);
+        s->mosaic_params = nullptr;
+        s->mosaic_usable = nullptr;
+        gme_set_error("out of device memory (mosaic parameters)");
+        return GME_ERR_NOMEM;
+    }
+    return GME_OK;
+}
+
+// the per-frame rows of a call: parameters and usable flags (all ones for NULL) to the device
+static int mosaic_put_rows(gme_seq* s, int count, const double* params, const uint8_t* usable)
+{
+    hipStream_t st = s->ctx->stream;
+    GME_HIP_TRY(hipMemcpyAsync(s->mosaic_params, params, (size_t)count * 8 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (usable) GME_HIP_TRY(hipMemcpyAsync(s->mosaic_usable, usable, (size_t)count, hipMemcpyHostToDevice, st));
+    else GME_HIP_TRY(hipMemsetAsync(s->mosaic_usable, 1, (size_t)count, st));
+    return GME_OK;
+}
+
+extern "C" int gme_seq_mosaic(gme_seq* s, int first, int count, const double* inv_warps, const uint8_t* usable, int ox, int oy,
+                              int Hc, int Wc, int fill, int cull)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_mosaic: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(first >= 0 && count >= 1 && first + count <= s->N, GME_ERR_ARG, "gme_seq_mosaic: frames [%d, %d) outside [0, %d)",
+                first, first + count, s->N);
+    GME_REQUIRE(count <= 65535, GME_ERR_ARG, "gme_seq_mosaic: %d frames (the sample counts are 16 bits: at most 65535)", count);
+    GME_REQUIRE(inv_warps != nullptr, GME_ERR_ARG, "gme_seq_mosaic: null parameters");
+    GME_REQUIRE(Hc >= 1 && Wc >= 1 && (long long)Hc * round_up(Wc, 64) <= 0x7FFFFFFFLL && Wc <= 0x7FFFFFFF - 64, GME_ERR_ARG,
+                "gme_seq_mosaic: canvas %d x %d (1 x 1 .. 2^31 - 1 pixels, rows padded to 64)", Hc, Wc);
+    GME_REQUIRE(fill >= 0 && fill <= 255, GME_ERR_ARG, "gme_seq_mosaic: fill %d (0 .. 255)", fill);
+    GME_REQUIRE(cull == 0 || cull == 1, GME_ERR_ARG, "gme_seq_mosaic: cull %d (0 off, 1 on)", cull);
+    int rc = mosaic_rows(s);
+    if (rc) return rc;
+    const int pitch = round_up(Wc, 64);
+    const size_t pixels = (size_t)Hc * (size_t)pitch;
+    s->mosaic_valid = false;
+    if (pixels > s->mosaic_cap) {
+        if (s->mosaic_sprite) hipFree(s->mosaic_sprite);
+        if (s->mosaic_count) hipFree(s->mosaic_count);
+        s->mosaic_sprite = nullptr;
+        s->mosaic_count = nullptr;
+        s->mosaic_cap = 0;
+        if (hipMalloc((void**)&s->mosaic_sprite, pixels) != hipSuccess ||
+            hipMalloc((void**)&s->mosaic_count, pixels * sizeof(uint16_t)) != hipSuccess) {
+            if (s->mosaic_sprite) hipFree(s->mosaic_sprite);
+            s->mosaic_sprite = nullptr;
+            gme_set_error("out of device memory (a mosaic of %d x %d)", Hc, Wc);
+            return GME_ERR_NOMEM;
+        }
+        s->mosaic_cap = pixels;
+    }
+    GME_HIP_TRY(hipMemsetAsync(s->mosaic_sprite, 0, pixels, ctx->stream));
+    GME_HIP_TRY(hipMemsetAsync(s->mosaic_count, 0, pixels * sizeof(uint16_t), ctx->stream));
+    rc = mosaic_put_rows(s, count, inv_warps, usable);
+    if (rc) return rc;
+    rc = launch_mosaic_median(ctx, s->level[2], first, count, s->mosaic_params, s->mosaic_usable, ox, oy, Hc, Wc, fill, cull,
+                              s->mosaic_sprite, s->mosaic_count, pitch);
+    if (rc) return rc;
+    rc = ctx_finish(ctx);
+    if (rc) return rc;
+    s->mosaic_Hc = Hc; s->mosaic_Wc = Wc; s->mosaic_pitch = pitch;
+    s->mosaic_valid = true;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_mosaic(gme_seq* s, uint8_t* sprite, uint16_t* count)
+{
+    GME_REQUIRE(s != nullptr && sprite != nullptr, GME_ERR_ARG, "gme_seq_read_mosaic: null pointer");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(s->mosaic_valid, GME_ERR_ARG, "gme_seq_read_mosaic: no mosaic was built (gme_seq_mosaic first)");
+    const int Hc = s->mosaic_Hc, Wc = s->mosaic_Wc, pitch = s->mosaic_pitch;
+    GME_HIP_TRY(hipMemcpy2DAsync(sprite, Wc, s->mosaic_sprite, pitch, Wc, Hc, hipMemcpyDeviceToHost, s->ctx->stream));
+    if (count)
+        GME_HIP_TRY(hipMemcpy2DAsync(count, (size_t)Wc * sizeof(uint16_t), s->mosaic_count, (size_t)pitch * sizeof(uint16_t),
+                                     (size_t)Wc * sizeof(uint16_t), Hc, hipMemcpyDeviceToHost, s->ctx->stream));
+    return ctx_finish(s->ctx);
+}
+
+extern "C" int gme_seq_moving_masks(gme_seq* s, int first, int count, const double* warps, const uint8_t* usable, int ox, int oy,
+                                    int threshold, int min_count, int64_t* known_out, int64_t* moving_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_moving_masks: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->N, GME_ERR_ARG,
+                "gme_seq_moving_masks: frames [%d, %d) outside [0, %d)", first, first + count, s->N);
+    GME_REQUIRE(warps != nullptr || count == 0, GME_ERR_ARG, "gme_seq_moving_masks: null parameters");
+    GME_REQUIRE(threshold >= 0 && threshold <= 255, GME_ERR_ARG, "gme_seq_moving_masks: threshold %d (0 .. 255)", threshold);
+    GME_REQUIRE(min_count >= 1, GME_ERR_ARG, "gme_seq_moving_masks: min_count %d (at least 1)", min_count);
+    GME_REQUIRE(s->mosaic_valid, GME_ERR_ARG, "gme_seq_moving_masks: no mosaic was built (gme_seq_mosaic first)");
+    if (count == 0) return GME_OK;
+    int rc = mosaic_rows(s);
+    if (rc) return rc;
+    if (!s->masks.ptr) {
+        rc = plane_alloc(ctx, &s->masks, s->N_cap, s->H, s->W);
+        if (rc) return rc;
+        s->masks_written.assign((size_t)s->N_cap, 0);
+    }
+    rc = mosaic_put_rows(s, count, warps, usable);
+    if (rc) return rc;
+    unsigned long long* known = s->mosaic_counts;
+    unsigned long long* moving = s->mosaic_counts + s->N_cap;
+    GME_HIP_TRY(hipMemsetAsync(s->mosaic_counts, 0, (size_t)s->N_cap * 2 * sizeof(unsigned long long), ctx->stream));
+    rc = launch_moving_masks(ctx, s->level[2], s->masks, first, count, s->mosaic_params, s->mosaic_usable, s->mosaic_sprite,
+                             s->mosaic_count, s->mosaic_pitch, s->mosaic_Hc, s->mosaic_Wc, ox, oy, threshold, min_count, known,
+                             moving);
+    if (rc) return rc;
+    if (known_out)
+        GME_HIP_TRY(hipMemcpyAsync(known_out, known, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (moving_out)
+        GME_HIP_TRY(hipMemcpyAsync(moving_out, moving, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = ctx_finish(ctx);
+    if (rc) return rc;
+    for (int k = first; k < first + count; ++k) s->masks_written[(size_t)k] = 1;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_masks_range(gme_seq* s, int first, int count, uint8_t* out)
+{
+    GME_REQUIRE(s != nullptr && out != nullptr, GME_ERR_ARG, "gme_seq_read_masks_range: null pointer");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->N, GME_ERR_ARG,
+                "gme_seq_read_masks_range: frames [%d, %d) outside [0, %d)", first, first + count, s->N);
+    bool written = s->masks.ptr != nullptr || count == 0;
+    for (int k = first; written && k < first + count; ++k) written = s->masks_written[(size_t)k] != 0;
+    GME_REQUIRE(written, GME_ERR_ARG, "gme_seq_read_masks_range: the masks of frames [%d, %d) were never computed", first,
+                first + count);
+    for (int k = 0; k < count; ++k)
+        GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * s->H * s->W, s->W, s->masks.at(first + k), s->masks.pitch, s->W, s->H,
+                                     hipMemcpyDeviceToHost, s->ctx->stream));
+    return ctx_finish(s->ctx);
 }

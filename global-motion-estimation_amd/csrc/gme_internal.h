@@ -137,6 +137,19 @@ struct gme_seq {
     std::vector<uint8_t> warped_written;
     double* warp_params = nullptr;       // [N_cap][8]
     unsigned long long* warp_counts = nullptr;   // [N_cap] valid samples, or squared errors of gme_seq_frame_sse
+    // background mosaic (gme_mosaic.hip): sprite and sample counts [Hc][pitch] of the last gme_seq_mosaic, the masks of
+    // gme_seq_moving_masks (N_cap planes, allocated by its first call) with which of them were written, and N_cap rows of
+    // parameters, usable flags and known / moving counts
+    uint8_t* mosaic_sprite = nullptr;
+    uint16_t* mosaic_count = nullptr;
+    size_t mosaic_cap = 0;               // pixels the two were allocated for
+    int mosaic_Hc = 0, mosaic_Wc = 0, mosaic_pitch = 0;
+    bool mosaic_valid = false;
+    Plane masks;
+    std::vector<uint8_t> masks_written;
+    double* mosaic_params = nullptr;     // [N_cap][8]
+    uint8_t* mosaic_usable = nullptr;    // [N_cap]
+    unsigned long long* mosaic_counts = nullptr;   // [2][N_cap] known, moving
     uint8_t* synth_canvas = nullptr;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -319,6 +332,18 @@ int launch_warp_frames(gme_ctx* ctx, const Plane& src, const Plane& dst, int fir
                        int fill, unsigned long long* valid);
 // sse[k] = sum (p[first + k + 1] - p[first + k])^2, k < count (device)
 int launch_frame_sse(gme_ctx* ctx, const Plane& p, int first, int count, unsigned long long* sse);
+
+// ---- gme_mosaic.hip: background mosaic and moving-object masks --------------------------------
+// sprite / cnt [Hc][out_pitch] = lower median / number of the in-frame samples of frames first .. first + count - 1 of src at
+// every canvas pixel (fill where there is none); G[count][8] and usable[count] on the device; cull 0 samples every frame
+// at every pixel
+int launch_mosaic_median(gme_ctx* ctx, const Plane& src, int first, int count, const double* G, const uint8_t* usable, int ox,
+                         int oy, int Hc, int Wc, int fill, int cull, uint8_t* sprite, uint16_t* cnt, int out_pitch);
+// masks of frames first .. first + count - 1 into dst, their known and moving pixels into known[count] and moving[count]
+// (device, zeroed by the caller); A[count][8] and usable[count] on the device
+int launch_moving_masks(gme_ctx* ctx, const Plane& src, const Plane& dst, int first, int count, const double* A,
+                        const uint8_t* usable, const uint8_t* sprite, const uint16_t* cnt, int sp_pitch, int Hc, int Wc, int ox,
+                        int oy, int threshold, int min_count, unsigned long long* known, unsigned long long* moving);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -9,6 +9,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py suggest -p <video|frame dir> [-fi 1] [-f 1]                 # parameter heuristics
     python gme_cli.py projective -p <video|frame dir> -fi 1 [-f 1]                # direct projective refinement of one pair
     python gme_cli.py stabilize -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--radius 15]   # video stabilization
+    python gme_cli.py mosaic -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--anchor 0] [--threshold 16] [--min-count 3] [--no-masks]   # background mosaic, moving-object masks
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -62,6 +63,16 @@ def _parser():
     st.add_argument("--max-crop", type=float, default=0.25, help="cap of the auto crop")
     st.add_argument("--border", choices=("constant", "replicate"), default="constant")
     st.add_argument("--fill", type=int, default=0, help="value of border pixels under --border constant")
+    mo = sub.add_parser("mosaic", help="background mosaic and moving-object masks from the estimated camera path (mosaic.py, DESIGN.md 7d)")
+    mo.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    mo.add_argument("-o", "--output", dest="outdir", type=str, required=True,
+                    help="directory for mosaic.png, masks/%%04d.png and mosaic.json")
+    mo.add_argument("--estimator", choices=("projective", "affine"), default="projective")
+    mo.add_argument("--anchor", type=int, default=0, help="the frame whose coordinates the canvas is laid out in")
+    mo.add_argument("--threshold", type=int, default=16, help="mean residual of the 3x3 neighbourhood above which a pixel moves, grey levels")
+    mo.add_argument("--min-count", dest="min_count", type=int, default=3, help="samples a sprite pixel needs before it predicts anything")
+    mo.add_argument("--fill", type=int, default=0, help="value of sprite pixels no frame covers")
+    mo.add_argument("--no-masks", dest="masks", action="store_false", help="build the mosaic only")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -94,6 +105,40 @@ def _stabilize(args):
     print("{} frames of shape {}, crop {:.4f}".format(len(out), out.shape[1:], res["crop"]))
     print("itf before: {:.4f} dB".format(res["itf_before"]))
     print("itf after:  {:.4f} dB".format(res["itf_after"]))
+    return res
+
+
+def _mosaic(args):
+    """The sprite into OUTDIR/mosaic.png, the masks (0 / 255) into OUTDIR/masks/%04d.png, the run's record into
+    OUTDIR/mosaic.json."""
+    import json
+    import os
+    import numpy as np
+    import mosaic
+    import utils
+    frames = np.stack([np.asarray(f, dtype=np.uint8) for f in utils.get_video_frames(args.path)])
+    sprite, masks, res = mosaic.mosaic(frames, estimator=args.estimator, anchor=args.anchor, threshold=args.threshold,
+                                       min_count=args.min_count, fill=args.fill, masks=args.masks)
+    os.makedirs(args.outdir, exist_ok=True)
+    utils.write_image(os.path.join(args.outdir, "mosaic.png"), sprite)
+    if masks is not None:
+        d = os.path.join(args.outdir, "masks")
+        os.makedirs(d, exist_ok=True)
+        for k, m in enumerate(masks):
+            utils.write_image(os.path.join(d, "%04d.png" % k), m * np.uint8(255))
+    record = {"options": {"path": args.path, "estimator": args.estimator, "anchor": args.anchor, "threshold": args.threshold,
+                          "min_count": args.min_count, "fill": args.fill, "masks": bool(args.masks)},
+              "frames": int(len(frames)), "origin": [res["ox"], res["oy"]], "size": [res["Hc"], res["Wc"]],
+              "frame_flags": res["flags"].tolist(), "pair_params": res["h"].tolist(), "pair_flags": res["pair_flags"].tolist(),
+              "known": res["known"].tolist() if masks is not None else None,
+              "moving": res["moving"].tolist() if masks is not None else None}
+    with open(os.path.join(args.outdir, "mosaic.json"), "w") as f:
+        json.dump(record, f, indent=1)
+    print("{} frames of shape {}: canvas {} x {} at origin ({}, {})".format(len(frames), frames.shape[1:], res["Hc"], res["Wc"],
+                                                                          res["ox"], res["oy"]))
+    print("covered: {:.2f} % of the canvas".format(100.0 * float(np.mean(res["count"] > 0))))
+    if masks is not None:
+        print("moving: {:.2f} % of the known pixels".format(100.0 * float(res["moving"].sum()) / max(1, int(res["known"].sum()))))
     return res
 
 
@@ -162,6 +207,8 @@ def main(argv=None):
         return _projective(args)
     if args.command == "stabilize":
         return _stabilize(args)
+    if args.command == "mosaic":
+        return _mosaic(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")

@@ -576,6 +576,24 @@ class ShardedSequence:
         lane, k = self._lane_of(pair)
         return lane.seq.read_compensated(k)
 
+    def _pair_warps(self, estimator, procedure, search_window, outlier_fraction, max_iters):
+        """This shard's pair warps (frame distance 1) as projective parameters -> (h float64[P_local, 8], flags
+        int32[P_local]), each lane estimating its own pairs: "projective" the direct refinement, "affine" the indirect
+        estimate written as a projective warp.  The first half of stabilize() and mosaic()."""
+        bs = int(motion.BBME_BLOCK_SIZE)
+
+        def estimate(lane):
+            n = lane.hi - lane.lo
+            if estimator == "affine":
+                h = roadmap.affine_to_projective(motion.estimate_sequence(lane.seq, 1, procedure, search_window), bs)
+                return h[:n], np.zeros(n, np.int32)
+            h, flags = roadmap.refine_sequence(lane.seq, 1, None, outlier_fraction, max_iters, procedure, search_window)
+            return h[:n], flags[:n]
+        parts = self._each(estimate)
+        h_loc = np.concatenate([h for h, _ in parts], axis=0) if parts else np.zeros((0, 8))
+        f_loc = np.concatenate([f for _, f in parts]) if parts else np.zeros(0, np.int32)
+        return h_loc, f_loc
+
     # ---- video stabilization (stabilize.py, gme_stab.hip, DESIGN.md section 7c)
     def stabilize(self, estimator="projective", radius=15, sigma=None, crop="auto", max_crop=0.25, border="constant", fill=0,
                   procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10):
@@ -592,18 +610,7 @@ class ShardedSequence:
         bid = stab.border_id(border)
         if not 0 <= int(fill) <= 255:
             raise ValueError("fill %d outside 0 .. 255" % fill)
-        bs = int(motion.BBME_BLOCK_SIZE)
-
-        def estimate(lane):
-            n = lane.hi - lane.lo
-            if estimator == "affine":
-                h = roadmap.affine_to_projective(motion.estimate_sequence(lane.seq, 1, procedure, search_window), bs)
-                return h[:n], np.zeros(n, np.int32)
-            h, flags = roadmap.refine_sequence(lane.seq, 1, None, outlier_fraction, max_iters, procedure, search_window)
-            return h[:n], flags[:n]
-        parts = self._each(estimate)
-        h_loc = np.concatenate([h for h, _ in parts], axis=0) if parts else np.zeros((0, 8))
-        f_loc = np.concatenate([f for _, f in parts]) if parts else np.zeros(0, np.int32)
+        h_loc, f_loc = self._pair_warps(estimator, procedure, search_window, outlier_fraction, max_iters)
         h = self.gather(h_loc)
         out = stab.plan(h, self.H, self.W, radius, sigma, crop, max_crop)
         Wt = out["W"]
@@ -645,6 +652,50 @@ class ShardedSequence:
             out[k:k + n] = lane.seq.read_warped_range(j, n)
             k += n
         return out
+
+    # ---- background mosaic and moving-object masks (mosaic.py, gme_mosaic.hip)
+    def mosaic(self, estimator="projective", anchor=0, threshold=16, min_count=3, fill=0, masks=True, max_canvas_pixels=None,
+               h=None, cull=True, procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10):
+        """The background sprite of the whole video on the canvas of its camera path and, with ``masks``, the moving-object
+        mask of every frame -> result dict (mosaic.mosaic); read_mosaic and read_masks_range read them.  The pair warps are
+        estimated as stabilize() does, or taken from ``h`` (float64[P, 8]) where the path is known.  One rank, one lane: a
+        median does not combine across shards of frames."""
+        import mosaic as mos
+        import stabilize as stab
+        if self.world > 1 or len(self.lanes) > 1:
+            raise ValueError("mosaic needs the whole video in one sequence: world %d, streams %d (a median does not combine "
+                             "across shards of frames; use world = 1 and streams = 1)" % (self.world, len(self.lanes)))
+        if self.fd != 1:
+            raise ValueError("mosaic needs frame_distance 1 (this sequence has %d)" % self.fd)
+        if estimator not in stab.ESTIMATORS:
+            raise ValueError("estimator %r (choose from %r)" % (estimator, stab.ESTIMATORS))
+        if not 0 <= int(fill) <= 255:
+            raise ValueError("fill %d outside 0 .. 255" % fill)
+        if not 0 <= int(threshold) <= 255:
+            raise ValueError("threshold %d outside 0 .. 255" % threshold)
+        if int(min_count) < 1:
+            raise ValueError("min_count %d < 1" % min_count)
+        if h is None:
+            h, pair_flags = self._pair_warps(estimator, procedure, search_window, outlier_fraction, max_iters)
+        else:
+            h = np.asarray(h, dtype=np.float64).reshape(self.n_pairs_total, 8)
+            pair_flags, estimator = np.zeros(len(h), np.int32), "given"
+        out = mos.plan(h, self.H, self.W, anchor, max_canvas_pixels)
+        usable = out["flags"] == 0
+        self.seq.mosaic(0, out["G"], usable, out["ox"], out["oy"], out["Hc"], out["Wc"], int(fill), cull)
+        out.update(h=h, pair_flags=pair_flags, estimator=estimator, threshold=int(threshold), min_count=int(min_count))
+        if masks:
+            out["known"], out["moving"] = self.seq.moving_masks(0, out["A"], usable, out["ox"], out["oy"], int(threshold),
+                                                                int(min_count))
+        return out
+
+    def read_mosaic(self):
+        """(sprite uint8[Hc, Wc], count uint16[Hc, Wc]) of the last mosaic()."""
+        return self.seq.read_mosaic()
+
+    def read_masks_range(self, first, count):
+        """Moving-object masks (0 / 1) of frames first .. first+count-1 -> uint8[count, H, W]."""
+        return self.seq.read_masks_range(first, count)
 
     def gather(self, local_rows):
         """All-gather of this shard's per-pair rows (float64[P_local, k]) -> float64[P_total, k] on every rank, over the

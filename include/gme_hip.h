@@ -312,6 +312,27 @@ GME_API int gme_seq_read_warped_range(gme_seq *seq, int first, int count, uint8_
 /* sse_out[k] = sum (f[first+k+1] - f[first+k])^2, k < count; warped 0: the resident frames, 1: the warped ones */
 GME_API int gme_seq_frame_sse(gme_seq *seq, int warped, int first, int count, int64_t *sse_out);
 
+/* Background mosaic and moving-object masks (host definition mosaic.py).  Blocking calls on the
+ * resident frames; sprite, counts and masks are kept in the sequence (allocated on first use).
+ * gme_seq_mosaic: canvas pixel (x, y) of the Hc x Wc canvas with origin (ox, oy) samples frame first+k at direct.warp(
+ *   inv_warps[k], x + ox, y + oy) where that point lies in the frame (usable[k] != 0; NULL: every frame); the sample is the
+ *   bilinear value rounded to nearest.  count[y][x] = number of samples, sprite[y][x] = their lower median (rank
+ *   (count - 1) / 2 in ascending order), `fill` where there is none.  cull 1 skips, per 64-pixel row segment, the frames
+ *   whose footprint provably misses it (the result is the same bytes); 0 samples every frame everywhere.
+ * gme_seq_moving_masks: frame pixel (u, v) of frame first+k is compared with the sprite sampled at direct.warp(warps[k], u,
+ *   v) - (ox, oy), known where that point lies in the canvas and its four taps have count >= min_count; mask = 1 where the
+ *   pixel is known and the residuals |frame - background| of the known pixels of its 3x3 neighbourhood sum to more than
+ *   threshold times their number.  One byte per pixel (0 / 1); known_out / moving_out [count] (may be NULL) count the
+ *   known and the mask pixels per frame.  A frame with usable[k] == 0 gets an all-zero mask and zero counts.
+ * A range outside [0, N), more than 65535 frames, a canvas of more than 2^31 - 1 pixels, a fill or threshold outside
+ * 0 .. 255, min_count < 1, masks before a mosaic, or a read of what was never written is GME_ERR_ARG. */
+GME_API int gme_seq_mosaic(gme_seq *seq, int first, int count, const double *inv_warps, const uint8_t *usable, int ox, int oy,
+                           int Hc, int Wc, int fill, int cull);
+GME_API int gme_seq_read_mosaic(gme_seq *seq, uint8_t *sprite, uint16_t *count);
+GME_API int gme_seq_moving_masks(gme_seq *seq, int first, int count, const double *warps, const uint8_t *usable, int ox, int oy,
+                                 int threshold, int min_count, int64_t *known_out, int64_t *moving_out);
+GME_API int gme_seq_read_masks_range(gme_seq *seq, int first, int count, uint8_t *out);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
