@@ -11,9 +11,10 @@
 // (persistent workgroups that prefetch the next tile into registers, bbme_sea_common.h: persistent_tiles).
 // Per tile (NB adjacent macroblocks, one wave each, as in k_exh_qsad16):
 //   A  stage the search window of `cur` and the anchors in LDS; quadrant sums of each anchor;
-//   A' 8x8 box sums S8 of the staged window, in LDS, two separable passes: the horizontal one is
-//      two v_qsad_pk_u16_u8 against a zero reference (four sliding 8-byte sums per lane-op), the
-//      vertical one packed u16 adds -- no per-frame table, no extra HBM traffic;
+//   A' 8x8 box sums S8 of the staged window, in LDS: per lane and window row one v_qsad_pk_u16_u8
+//      against a zero reference (four sliding 4-byte sums) whose accumulator adds up the rows; an
+//      output row is the difference of two of those cumulative sums plus the neighbour lane's
+//      (DPP wave_shl:1), i.e. the other 4-byte half -- no per-frame table, no extra HBM traffic;
 //   B  LB for all NC^2 candidates of the wave's block: four S8 reads, two v_perm_b32 and two
 //      v_sad_u16 per candidate; per lane: min LB of each of its R patches (R rows x 4 columns);
 //   C  UB := SAD of the candidate with the smallest LB and of the zero vector (64 lanes x 1 dword);

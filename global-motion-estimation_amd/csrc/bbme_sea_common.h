@@ -163,36 +163,63 @@ __device__ __forceinline__ void stage_window(const SeaDev& d, uint32_t* win, con
     }
 }
 
-// A': 8x8 box sums of the staged window.  Thread (column quad sq, row chunk ch) walks CH+7 window
-// rows: per row two QSADs against a zero reference give the four horizontal 8-byte sums
-// r8(row, 4sq .. 4sq+3) (packed u16); the vertical 8-row sum slides with a ring of 8 rows in
-// registers: S8(y) = S8(y-1) + r8(y+7) - r8(y-1).  s8[y][sq] = packed S8(y, 4sq .. 4sq+3).
+// A': 8x8 box sums of the staged window.  Lane (row chunk ch, column quad sq) walks CH+7 window rows.  Per row ONE
+// QSAD against a zero reference gives the four sliding 4-byte sums h4(4sq .. 4sq+3) of the lane's own quad (packed
+// u16), and its accumulator operand adds them up over the rows for nothing: C(r) = h4 of rows 0 .. r (at most 24 rows
+// x 1020 < 2^16).  An output row takes V = C(y+7) - C(y-1) from a ring of 8 cumulative sums in registers -- the
+// vertical 8-row sum of the lane's own 4-byte columns -- and adds the V of quad sq + 1, which the next lane has just
+// formed, with a DPP wave_shl:1: S8(y, x) = V(x) + V(x + 4).  All of that is 32-bit subtracts and adds on the packed
+// pairs (component-wise C grows and V <= 8160, so nothing borrows from or carries into the upper half); the adds take
+// the DPP operand directly.  s8[y][sq] = packed S8(y, 4sq .. 4sq+3).
+// Each lane used to compute both 4-byte halves of its 8-byte sums itself (two QSADs, 16 window bytes per row) and to
+// slide the vertical sum by a packed subtract and add per row: half of the QSADs and window reads repeated the
+// neighbour's, and the warm-up rows paid for sums nobody stored.
+//
+// Lanes: a row segment (the quads of one chunk) lies on consecutive lanes of one wave, 64 / SL segments per wave
+// (XQ = 28: two chunks on lanes 0 .. 55, four waves hold the eight chunks).  The last lane of a segment has no
+// neighbour -- what wave_shl hands it belongs to another chunk, or to nobody.  Where its quad is padding (XQ > need)
+// that value is never read and the segment is the XQ quads themselves; where the bound phase reads it (XQ == need) the
+// segment gets one more lane, a donor for quad XQ (window dwords XQ, XQ + 1 < pitch: what the second QSAD of quad
+// XQ - 1 used to read) that stores nothing: SL = XQ + (XQ == need), from shape_of's constants.  A segment longer than
+// a wave is cut into pieces 63 quads apart: lane 63 of a piece only donates, the next piece starts with its quad.
+// Every lane of the wave runs the row loop (DPP reads disabled lanes as invalid), idle ones on window dword 0; only
+// the store is predicated.  The trip count is wave-uniform.
 // CH = s8_rows / 8 is a template parameter so that the ring indices and the warm-up are resolved
 // at compile time (a run-time row count cost 5 % of the whole search in guards).
 template <int CH>
-__device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid)
+__device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid, int need)
 {
-    typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
+    static_assert((CH + 7) * 1020 < 65536, "cumulative 4-byte sums must fit 16 bits");
     const int XQ = d.xq;
-    for (int it = tid; it < 8 * XQ; it += blockDim.x) {
-        const int ch = div_small(it, d.magic_xq), sq = it - ch * XQ;
-        int pi = (ch * CH) * d.pitch_dw + sq, oi = (ch * CH) * XQ + sq;     // running offsets: adds, no r * pitch multiplies
-        u16x4 ring[8], sum = { 0, 0, 0, 0 };
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int SL = XQ == need ? XQ + 1 : XQ;                       // lanes per segment: its quads, and a donor if the last one is read
+    const bool wide = SL > 64;                                     // pieces: one per wave and pass
+    const uint32_t magic_sl = XQ == need ? div_magic(SL) : d.magic_xq;
+    const int SEG = wide ? 1 : div_small(64, magic_sl);            // whole segments per wave
+    const int units = wide ? 8 * div_small(XQ + 62, div_magic(63)) : 8;       // pieces (unit = piece * 8 + chunk) or chunks
+    const int ls = wide ? 0 : div_small(lane, magic_sl);           // the lane's segment inside its wave
+    for (int u = wave * SEG; u < units; u += d.nb * SEG) {
+        const int ch = wide ? (u & 7) : u + ls;
+        const int sq = wide ? (u >> 3) * 63 + lane : lane - ls * SL;
+        const bool active = wide ? sq < SL : (ls < SEG && ch < 8);
+        const bool stores = active && sq < XQ && (!wide || lane < 63);
+        int pi = active ? (ch * CH) * d.pitch_dw + sq : 0, oi = (ch * CH) * XQ + sq;     // running offsets: adds, no r * pitch multiplies
+        uint64_t ring[8], acc = 0;
 #pragma unroll
         for (int r = 0; r < CH + 7; ++r) {
-            const uint64_t w0 = *(const u64_a4*)(win + pi), w1 = *(const u64_a4*)(win + pi + 1);
+            acc = __builtin_amdgcn_qsad_pk_u16_u8(*(const u64_a4*)(win + pi), 0u, acc);
             pi += d.pitch_dw;
             asm volatile("" : "+v"(pi));
-            const u16x4 h = __builtin_bit_cast(u16x4, __builtin_amdgcn_qsad_pk_u16_u8(
-                                w1, 0u, __builtin_amdgcn_qsad_pk_u16_u8(w0, 0u, (uint64_t)0)));
-            if (r >= 8) sum -= ring[r & 7];
-            sum += h;
-            ring[r & 7] = h;
             if (r >= 7) {
-                s8[oi] = __builtin_bit_cast(uint64_t, sum);
+                uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
+                if (r >= 8) { lo -= (uint32_t)ring[r & 7]; hi -= (uint32_t)(ring[r & 7] >> 32); }
+                lo += SEA_DPP(lo, 0x130);                          // wave_shl:1 -- lane + 1's
+                hi += SEA_DPP(hi, 0x130);
+                if (stores) s8[oi] = ((uint64_t)hi << 32) | lo;
                 oi += XQ;
                 asm volatile("" : "+v"(oi));
             }
+            ring[r & 7] = acc;
         }
     }
 }
@@ -203,9 +230,10 @@ __device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* wi
 template <int R>
 __device__ __forceinline__ void box_sums8(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid)
 {
-    if (d.tr == 1) box_sums8_ch<2 * R + 1>(d, win, s8, tid);
-    else if (d.tr == 2) box_sums8_ch<2 * R + 3>(d, win, s8, tid);
-    else box_sums8_ch<2 * R + 7>(d, win, s8, tid);
+    const int need = 4 * R + 4 * (d.tc - 1) + 2;           // quads per row the bound phase reads (shape_of); XQ >= need
+    if (d.tr == 1) box_sums8_ch<2 * R + 1>(d, win, s8, tid, need);
+    else if (d.tr == 2) box_sums8_ch<2 * R + 3>(d, win, s8, tid, need);
+    else box_sums8_ch<2 * R + 7>(d, win, s8, tid, need);
 }
 
 // quadrant sums of the anchor held one dword per lane (lane = row * 4 + dword): the quad swap pairs
