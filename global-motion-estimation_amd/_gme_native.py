@@ -107,6 +107,10 @@ _SIGNATURES = {
     "gme_seq_read_mosaic": (_i, [_vp, _c_u8p, _c_u16p]),
     "gme_seq_moving_masks": (_i, [_vp, _i, _i, _c_f64p, _c_u8p, _i, _i, _i, _i, _c_i64p, _c_i64p]),
     "gme_seq_read_masks_range": (_i, [_vp, _i, _i, _c_u8p]),
+    "gme_subpel_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i32p, _c_i64p]),
+    "gme_seq_subpel": (_i, [_vp, _i, _i, _i, _i]),
+    "gme_seq_read_qmv": (_i, [_vp, _i, _i, _c_i32p, _c_i64p]),
+    "gme_seq_compensate_qpel": (_i, [_vp, _i, _i, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -343,6 +347,34 @@ class Context:
         _check(self.lib.gme_sse_u8(self.handle, _p(a, _c_u8p), _p(b, _c_u8p), a.shape[0], a.shape[1], a.strides[0],
                                    b.strides[0], ctypes.byref(v)), self.lib)
         return v.value
+
+
+    def subpel(self, prev, cur, mf, block_size, pnorm, levels=2):
+        """Quarter-pel refinement of the integer field mf int32[H // bs, W // bs, 2] of one pair (gme_subpel_u8, subpel.refine)
+        -> (qfield int32[h, w, 2] in quarter pixels, cost int64[h, w])."""
+        prev, cur = as_frame(prev, "previous"), as_frame(cur, "current")
+        if prev.shape != cur.shape:
+            raise AssertionError("previous and current differ in shape (bbme.py:59)")
+        levels = _subpel_levels(levels)
+        H, W = prev.shape
+        block_size = _block_size(block_size)
+        if cur.strides[0] != prev.strides[0]:
+            cur, prev = np.ascontiguousarray(cur), np.ascontiguousarray(prev)
+        h, w = int(H / block_size), int(W / block_size)
+        mf32 = np.ascontiguousarray(np.asarray(mf)[:, :, :2].astype(np.int32))
+        if mf32.shape != (h, w, 2):
+            raise ValueError("the field of a %d x %d frame at block size %d is %r, not %r" % (H, W, block_size, (h, w, 2), mf32.shape))
+        q, cost = np.zeros((h, w, 2), np.int32), np.zeros((h, w), np.int64)
+        _check(self.lib.gme_subpel_u8(self.handle, _p(prev, _c_u8p), _p(cur, _c_u8p), H, W, prev.strides[0], block_size, int(pnorm),
+                                      levels, _p(mf32, _c_i32p), _p(q, _c_i32p), _p(cost, _c_i64p)), self.lib)
+        return q, cost
+
+
+def _subpel_levels(levels):
+    levels = int(levels)
+    if levels not in (0, 1, 2):
+        raise ValueError("levels %d (0: integer, 1: half-pel, 2: quarter-pel)" % levels)
+    return levels
 
 
 class Sequence:
@@ -756,6 +788,31 @@ class Sequence:
         out = np.empty((int(count), self.H, self.W), dtype=np.uint8)
         _check(self.lib.gme_seq_read_masks_range(self.handle, int(first), int(count), _p(out, _c_u8p)), self.lib)
         return out
+
+    # ---- quarter-pel block matching (bbme_subpel.hip, subpel.py)
+    def subpel(self, frame_distance, block_size, pnorm, levels=2):
+        """Refine the field of the last bbme() (same frame distance and block size) to half (levels 1) or quarter pixels (2)
+        on the device (gme_seq_subpel); read_qmv reads the result, compensate_qpel compensates with it."""
+        self._blocking("sub-pel")
+        _check(self.lib.gme_seq_subpel(self.handle, int(frame_distance), _block_size(block_size), int(pnorm), _subpel_levels(levels)),
+               self.lib)
+
+    def read_qmv(self, first=0, count=None):
+        """(qfield int32[count, h, w, 2] in quarter pixels, cost int64[count, h, w]) of pairs first .. first+count-1 of the
+        last subpel()."""
+        shape = getattr(self, "_mv_shape", (0, 0, 0, 2))
+        count = shape[0] - first if count is None else count
+        q, cost = np.empty((max(count, 0),) + tuple(shape[1:]), np.int32), np.empty((max(count, 0),) + tuple(shape[1:3]), np.int64)
+        _check(self.lib.gme_seq_read_qmv(self.handle, int(first), int(count), _p(q, _c_i32p), _p(cost, _c_i64p)), self.lib)
+        return q, cost
+
+    def compensate_qpel(self, frame_distance, block_size):
+        """Compensated frames of the refined field (gme_seq_compensate_qpel, subpel.compensate) -> sse int64[P] against the
+        current frames; read_compensated(_range) reads the frames."""
+        self._blocking("sub-pel")
+        sse = np.zeros(max(getattr(self, "_mv_shape", (0,))[0], 1), np.int64)
+        _check(self.lib.gme_seq_compensate_qpel(self.handle, int(frame_distance), _block_size(block_size), _p(sse, _c_i64p)), self.lib)
+        return sse[:getattr(self, "_mv_shape", (0,))[0]]
 
 
 _default = None

@@ -441,6 +441,47 @@ extern "C" int gme_sse_u8(gme_ctx* ctx, const uint8_t* a, const uint8_t* b_, int
     return rc;
 }
 
+static int subpel_check(const char* who, int H, int W, int bs, int pnorm, int levels)
+{
+    GME_REQUIRE(bs >= 1 && bs <= 4096, GME_ERR_ARG, "%s: block_size %d (1 .. 4096)", who, bs);
+    GME_REQUIRE(pnorm == 0 || pnorm == 1, GME_ERR_ARG, "%s: pnorm_distance %d out of range (bbme.py:60)", who, pnorm);
+    GME_REQUIRE(levels >= 0 && levels <= 2, GME_ERR_ARG, "%s: levels %d (0 integer, 1 half-pel, 2 quarter-pel)", who, levels);
+    GME_REQUIRE(H <= 0x7FFFFFFF / 4 - 4 && W <= 0x7FFFFFFF / 4 - 4, GME_ERR_ARG, "%s: a %d x %d frame in quarter units", who, H, W);
+    return GME_OK;
+}
+
+extern "C" int gme_subpel_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int H, int W, int stride, int block_size,
+                             int pnorm, int levels, const int32_t* mf_in, int32_t* qmf_out, int64_t* cost_out)
+{
+    GME_ENTER(ctx);
+    int rc = GME_OK;
+    GME_REQUIRE(prev && cur && mf_in && qmf_out && cost_out, GME_ERR_ARG, "gme_subpel_u8: null pointer");
+    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_subpel_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
+    rc = subpel_check("gme_subpel_u8", H, W, block_size, pnorm, levels);
+    if (rc) return rc;
+    const int h = H / block_size, w = W / block_size;
+    if (h == 0 || w == 0) return GME_OK;
+    const int pitch = round_up(W, 64);
+    const size_t plane = (size_t)round_up(pitch * H, 256), n = (size_t)h * w;
+    Carver c;
+    const size_t o_prev = c.take(plane + pitch), o_cur = c.take(plane + pitch);
+    const size_t o_mf = c.take(n * 2 * sizeof(int32_t)), o_q = c.take(n * 2 * sizeof(int32_t)), o_c = c.take(n * sizeof(long long));
+    void* base = nullptr;
+    rc = ctx_scratch(ctx, c.off, &base);
+    if (rc) return rc;
+    uint8_t* b = (uint8_t*)base;
+    GME_HIP_TRY(hipMemsetAsync(b + o_prev, 0, o_mf - o_prev, ctx->stream));
+    GME_HIP_TRY(hipMemcpy2DAsync(b + o_prev, pitch, prev, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
+    GME_HIP_TRY(hipMemcpy2DAsync(b + o_cur, pitch, cur, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(b + o_mf, mf_in, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_subpel_refine(ctx, b + o_prev, b + o_cur, 0, 1, H, W, pitch, block_size, pnorm, levels, (const int32_t*)(b + o_mf),
+                              (int32_t*)(b + o_q), (long long*)(b + o_c));
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(qmf_out, b + o_q, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(cost_out, b + o_c, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -500,6 +541,8 @@ extern "C" void gme_seq_destroy(gme_seq* s)
     if (s->mosaic_params) hipFree(s->mosaic_params);
     if (s->mosaic_usable) hipFree(s->mosaic_usable);
     if (s->mosaic_counts) hipFree(s->mosaic_counts);
+    if (s->qmv) hipFree(s->qmv);
+    if (s->qcost) hipFree(s->qcost);
     if (s->summary) hipFree(s->summary);
     if (s->gathered) hipFree(s->gathered);
     if (s->ready) hipEventDestroy(s->ready);
@@ -751,6 +794,8 @@ extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, i
     rc = ensure(&s->mv, &s->mv_bytes, (size_t)pairs * h * w * 2 * sizeof(int32_t));
     if (rc) return rc;
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
+    s->mv_fd = fd; s->mv_bs = bs;
+    s->qmv_valid = false;
     const Plane& p = s->level[2];
     BbmeJob job;
     job.prev = p.at(0); job.cur = p.at(fd); job.plane_stride = p.stride; job.pairs = pairs;
@@ -802,6 +847,8 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     rc = ensure(&s->mv, &s->mv_bytes, (size_t)(s->N - fd) * per * sizeof(int32_t));
     if (rc) return rc;
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
+    s->mv_fd = fd; s->mv_bs = bs;
+    s->qmv_valid = false;
     const Plane& p = s->level[2];
     // one table kind for the whole call: every chunk's launches carry at most `pairs` pairs, so one that the matrix-core
     // kernel would take at the largest also takes it at every chunk, and a smaller chunk of a declined call keeps kind 1
@@ -1837,4 +1884,81 @@ extern "C" int gme_seq_read_masks_range(gme_seq* s, int first, int count, uint8_
         GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * s->H * s->W, s->W, s->masks.at(first + k), s->masks.pitch, s->W, s->H,
                                      hipMemcpyDeviceToHost, s->ctx->stream));
     return ctx_finish(s->ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Quarter-pel block matching (bbme_subpel.hip): blocking calls on the field of the last gme_seq_bbme.
+// ---------------------------------------------------------------------------
+static int subpel_field(gme_seq* s, const char* who, int fd, int bs)
+{
+    GME_REQUIRE(s->mv != nullptr && s->mv_pairs > 0, GME_ERR_STATE, "%s before gme_seq_bbme", who);
+    GME_REQUIRE(s->mv_fd == fd && s->mv_bs == bs, GME_ERR_STATE,
+                "%s: frame distance %d, block size %d, but the field of the last gme_seq_bbme has %d and %d", who, fd, bs, s->mv_fd,
+                s->mv_bs);
+    GME_REQUIRE(s->mv_pairs <= s->N - fd, GME_ERR_STATE, "%s: the field has %d pairs, the sequence %d", who, s->mv_pairs, s->N - fd);
+    return GME_OK;
+}
+
+extern "C" int gme_seq_subpel(gme_seq* s, int fd, int bs, int pnorm, int levels)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_subpel: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = subpel_check("gme_seq_subpel", s->H, s->W, bs, pnorm, levels);
+    if (rc) return rc;
+    rc = subpel_field(s, "gme_seq_subpel", fd, bs);
+    if (rc) return rc;
+    const size_t n = (size_t)s->mv_pairs * s->mv_h * s->mv_w;
+    s->qmv_valid = false;
+    rc = ensure(&s->qmv, &s->qmv_bytes, n * 2 * sizeof(int32_t));
+    if (rc) return rc;
+    rc = ensure(&s->qcost, &s->qcost_bytes, n * sizeof(long long));
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    rc = launch_subpel_refine(ctx, p.at(0), p.at(fd), p.stride, s->mv_pairs, s->H, s->W, p.pitch, bs, pnorm, levels, s->mv, s->qmv,
+                              s->qcost);
+    if (rc) return rc;
+    rc = ctx_finish(ctx);
+    if (rc) return rc;
+    s->qmv_valid = true;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_qmv(gme_seq* s, int first_pair, int count, int32_t* qmf_out, int64_t* cost_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_qmv: null sequence");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(s->qmv_valid, GME_ERR_STATE, "gme_seq_read_qmv before gme_seq_subpel");
+    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG,
+                "gme_seq_read_qmv: pairs [%d, %d) outside [0, %d)", first_pair, first_pair + count, s->mv_pairs);
+    const size_t per = (size_t)s->mv_h * s->mv_w;
+    if (qmf_out)
+        GME_HIP_TRY(hipMemcpyAsync(qmf_out, s->qmv + per * 2 * first_pair, per * 2 * count * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   s->ctx->stream));
+    if (cost_out)
+        GME_HIP_TRY(hipMemcpyAsync(cost_out, s->qcost + per * first_pair, per * count * sizeof(long long), hipMemcpyDeviceToHost,
+                                   s->ctx->stream));
+    return ctx_finish(s->ctx);
+}
+
+extern "C" int gme_seq_compensate_qpel(gme_seq* s, int fd, int bs, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_compensate_qpel: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "frame_distance %d needs at least %d frames", fd, fd + 1);
+    GME_REQUIRE(bs >= 1, GME_ERR_ARG, "block_size %d", bs);
+    GME_REQUIRE(s->qmv_valid, GME_ERR_STATE, "gme_seq_compensate_qpel before gme_seq_subpel");
+    int rc = subpel_field(s, "gme_seq_compensate_qpel", fd, bs);
+    if (rc) return rc;
+    const int pairs = s->mv_pairs;
+    rc = ensure_comp(s, fd, pairs);
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    rc = launch_compensate_qpel(ctx, p.at(0), p.at(fd), p.stride, pairs, s->H, s->W, p.pitch, bs, s->qmv, s->comp.ptr, s->comp.stride,
+                                s->comp.pitch, s->sse);
+    if (rc) return rc;
+    if (sse_out)
+        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
 }

@@ -98,6 +98,7 @@ struct gme_seq {
     int32_t* mv = nullptr;        // [P][h][w][2]
     size_t mv_bytes = 0;
     int mv_h = 0, mv_w = 0, mv_pairs = 0;
+    int mv_fd = 0, mv_bs = 0;     // frame distance and block size of the search that wrote `mv`
     uint32_t* sqbox[3] = { nullptr, nullptr, nullptr };   // per level: 16x16 box sums of squares per frame (MSE fast path)
     size_t sqbox_bytes[3] = { 0, 0, 0 };
     bool sqbox_valid[3] = { false, false, false };
@@ -150,6 +151,12 @@ struct gme_seq {
     double* mosaic_params = nullptr;     // [N_cap][8]
     uint8_t* mosaic_usable = nullptr;    // [N_cap]
     unsigned long long* mosaic_counts = nullptr;   // [2][N_cap] known, moving
+    // quarter-pel refinement (bbme_subpel.hip): the refined field and its costs of the last gme_seq_subpel, allocated by
+    // its first call; valid until the next block-matching call replaces `mv`
+    int32_t* qmv = nullptr;              // [P][h][w][2], quarter units
+    long long* qcost = nullptr;          // [P][h][w]
+    size_t qmv_bytes = 0, qcost_bytes = 0;
+    bool qmv_valid = false;
     uint8_t* synth_canvas = nullptr;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -344,6 +351,16 @@ int launch_mosaic_median(gme_ctx* ctx, const Plane& src, int first, int count, c
 int launch_moving_masks(gme_ctx* ctx, const Plane& src, const Plane& dst, int first, int count, const double* A,
                         const uint8_t* usable, const uint8_t* sprite, const uint16_t* cnt, int sp_pitch, int Hc, int Wc, int ox,
                         int oy, int threshold, int min_count, unsigned long long* known, unsigned long long* moving);
+
+// ---- bbme_subpel.hip: quarter-pel refinement and compensation ------------------------------------
+// qmf[pairs][H / bs][W / bs][2] (quarter units) and cost[pairs][H / bs][W / bs] = subpel.refine of the integer field mf of the
+// same shape; pair k reads the planes prev + k * plane_stride and cur + k * plane_stride (device)
+int launch_subpel_refine(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W,
+                         int pitch, int bs, int pnorm, int levels, const int32_t* mf, int32_t* qmf, long long* cost);
+// out planes = subpel.compensate of the prev planes by qmf, sse[pairs] (device) = squared error of each against its cur plane
+int launch_compensate_qpel(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W,
+                           int pitch, int bs, const int32_t* qmf, uint8_t* out, long long out_stride, int out_pitch,
+                           unsigned long long* sse);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -10,6 +10,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py projective -p <video|frame dir> -fi 1 [-f 1]                # direct projective refinement of one pair
     python gme_cli.py stabilize -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--radius 15]   # video stabilization
     python gme_cli.py mosaic -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--anchor 0] [--threshold 16] [--min-count 3] [--no-masks]   # background mosaic, moving-object masks
+    python gme_cli.py subpel -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--levels 2] [-o OUTDIR]   # quarter-pel block matching of one pair
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -73,6 +74,17 @@ def _parser():
     mo.add_argument("--min-count", dest="min_count", type=int, default=3, help="samples a sprite pixel needs before it predicts anything")
     mo.add_argument("--fill", type=int, default=0, help="value of sprite pixels no frame covers")
     mo.add_argument("--no-masks", dest="masks", action="store_false", help="build the mosaic only")
+    sp = sub.add_parser("subpel", help="quarter-pel block matching of one frame pair: refine, compensate, report (subpel.py, DESIGN.md 7e)")
+    sp.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    sp.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the current frame")
+    sp.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=1)
+    sp.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16)
+    sp.add_argument("-sw", "--search-window", dest="search_window", type=int, default=16)
+    sp.add_argument("-sp", "--searching-procedure", dest="searching_procedure", type=int, default=0,
+                    help="0: exhaustive, 1: three-step, 2: 2-D log, 3: diamond")
+    sp.add_argument("-pn", "--p-norm", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    sp.add_argument("--levels", type=int, default=2, help="0: integer, 1: half-pel, 2: quarter-pel")
+    sp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for subpel.json")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -139,6 +151,37 @@ def _mosaic(args):
     print("covered: {:.2f} % of the canvas".format(100.0 * float(np.mean(res["count"] > 0))))
     if masks is not None:
         print("moving: {:.2f} % of the known pixels".format(100.0 * float(res["moving"].sum()) / max(1, int(res["known"].sum()))))
+    return res
+
+
+def _subpel(args):
+    """Median vector, share of blocks moved off the integer vector and the PSNR of both compensations of one pair; the same
+    record into OUTDIR/subpel.json."""
+    import json
+    import os
+    import subpel
+    import utils
+    frames = utils.get_video_frames(args.path)
+    if not args.fd <= args.fi < len(frames) or args.fd < 1:
+        raise IndexError("frames %d and %d of %d" % (args.fi - args.fd, args.fi, len(frames)))
+    res = subpel.report(frames[args.fi - args.fd], frames[args.fi], args.block_size, args.search_window, args.searching_procedure,
+                        args.pnorm, args.levels)
+    record = {"options": {"path": args.path, "frame_index": args.fi, "frame_distance": args.fd, "block_size": args.block_size,
+                          "search_window": args.search_window, "searching_procedure": args.searching_procedure,
+                          "pnorm": args.pnorm, "levels": args.levels},
+              "shape": list(res["mf"].shape[:2])}
+    record.update({k: res[k] for k in ("median_vector", "moved_share", "sse_integer", "sse_qpel", "psnr_integer", "psnr_qpel",
+                                       "psnr_gain")})
+    print("frames {} -> {}: {} x {} blocks of {}".format(args.fi - args.fd, args.fi, record["shape"][0], record["shape"][1],
+                                                         args.block_size))
+    print("median vector: ({:.2f}, {:.2f}) px".format(*record["median_vector"]))
+    print("moved off the integer vector: {:.2f} % of the blocks".format(100.0 * record["moved_share"]))
+    print("psnr integer:     {:.4f} dB".format(record["psnr_integer"]))
+    print("psnr quarter-pel: {:.4f} dB  (gain {:+.4f} dB)".format(record["psnr_qpel"], record["psnr_gain"]))
+    if args.outdir:
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "subpel.json"), "w") as f:
+            json.dump(record, f, indent=1)
     return res
 
 
@@ -209,6 +252,8 @@ def main(argv=None):
         return _stabilize(args)
     if args.command == "mosaic":
         return _mosaic(args)
+    if args.command == "subpel":
+        return _subpel(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")

@@ -47,6 +47,9 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    direct.py), with dense sub-pixel compensation under it.  It is a separate estimator, not an entry of ``MODELS``.
    **Stabilization.**  ``stabilize.stabilize`` chains the pair warps of either estimator into a camera path, smooths it and
    warps every frame on the device (k_warp_frames, csrc/gme_stab.hip).
+   **Quarter-pel block matching.**  ``subpel.motion_field`` refines the integer field of any search to half and quarter
+   pixels and ``Sequence.compensate_qpel`` compensates with it (k_subpel_refine / k_compensate_qpel, csrc/bbme_subpel.hip;
+   host definition subpel.py).  The fits above still take integer vectors.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

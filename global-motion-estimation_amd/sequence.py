@@ -468,6 +468,25 @@ class ShardedSequence:
             return lane.seq.read_mv(0, lane.hi - lane.lo)
         return np.concatenate(self._each(run), axis=0)
 
+    def motion_fields_subpel(self, block_size, search_window, procedure, pnorm, levels=2, compensate=False):
+        """motion_fields refined to half (levels 1) or quarter pixels (2) on the device (subpel.py) for
+        every local pair -> (qfield int32[P_local, h, w, 2] in quarter pixels, cost int64[P_local, h, w]) and, with
+        ``compensate``, sse int64[P_local] of the quarter-pel compensation against the current frames (the frames: lane
+        sequences' read_compensated_range)."""
+        levels = _native._subpel_levels(levels)
+        h, w = int(self.H / block_size), int(self.W / block_size)
+        if not self.lanes:
+            empty = (np.zeros((0, h, w, 2), np.int32), np.zeros((0, h, w), np.int64))
+            return empty + (np.zeros(0, np.int64),) if compensate else empty
+
+        def run(lane):
+            n = lane.hi - lane.lo
+            lane.seq.bbme(self.fd, block_size, search_window, procedure, pnorm)
+            lane.seq.subpel(self.fd, block_size, pnorm, levels)
+            q, cost = lane.seq.read_qmv(0, n)
+            return (q, cost, lane.seq.compensate_qpel(self.fd, block_size)[:n]) if compensate else (q, cost)
+        return tuple(np.concatenate(part, axis=0) for part in zip(*self._each(run)))
+
     def estimate(self, procedure=3, search_window=2, model=None):
         """motion.global_motion_estimation for every local pair -> float64[P_local, 6].  ``model``: one of roadmap.MODELS
         (roadmap.stages per lane); the second-order models return float64[P_local, 12]."""

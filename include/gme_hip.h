@@ -333,6 +333,30 @@ GME_API int gme_seq_moving_masks(gme_seq *seq, int first, int count, const doubl
                                  int threshold, int min_count, int64_t *known_out, int64_t *moving_out);
 GME_API int gme_seq_read_masks_range(gme_seq *seq, int first, int count, uint8_t *out);
 
+/* Quarter-pel block matching (host definition subpel.py).  A quarter-pel field is int32[h][w][2] in
+ * units of 1/4 pixel (4 * mf is the integer field mf); everything is integer and equals the host definition bit for bit.
+ * The block of an image at origin (X, Y) in quarter units: x0 = X >> 2, fx = X & 3 (floor), the same for y; inside iff x0 >= 0,
+ * y0 >= 0, x0 + bs - 1 + (fx != 0) <= W - 1 and y0 + bs - 1 + (fy != 0) <= H - 1; pixel = ((4-fx)(4-fy) p00 + fx(4-fy) p01 +
+ * (4-fx) fy p10 + fx fy p11 + 8) >> 4.
+ * gme_subpel_u8: one pair on host buffers.  From 4 * mf_in[i][j] and its cost against the anchor block of `prev` (sum |d|
+ *   for pnorm 0, sum d^2 for 1), levels >= 1 tries the eight candidates at +-2 quarter units (column offset in the outer loop),
+ *   levels == 2 then the eight at +-1 around the half-pel winner; candidates that are not inside are skipped, only a strictly
+ *   smaller cost replaces the best.  A block whose integer match is not inside keeps 4 * mf_in and gets cost -1.
+ *   qmf_out int32[H/bs][W/bs][2], cost_out int64[H/bs][W/bs].
+ * gme_seq_subpel: the same for every pair of the field the last gme_seq_bbme left, kept in the sequence (allocated on first
+ *   use); GME_ERR_STATE if there is no such field or it was made with another frame distance or block size.
+ * gme_seq_read_qmv: pairs first_pair .. first_pair + count - 1 of it; either output may be NULL.
+ * gme_seq_compensate_qpel: with the refined field, block (i, j) of compensated frame k becomes the interpolated block of
+ *   frame k at (4 j bs - q0, 4 i bs - q1) where that block is inside, elsewhere (and beyond the last whole block) the copy of
+ *   frame k; written into the sequence's compensated frames (gme_seq_read_compensated_range reads them); sse_out[pairs] (may be
+ *   NULL) = exact squared error against frame k + frame_distance.
+ * Blocking calls.  levels outside 0 .. 2, a bad norm or block size, or a pair range outside the field is GME_ERR_ARG. */
+GME_API int gme_subpel_u8(gme_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int H, int W, int stride, int block_size,
+                          int pnorm, int levels, const int32_t *mf_in, int32_t *qmf_out, int64_t *cost_out);
+GME_API int gme_seq_subpel(gme_seq *seq, int frame_distance, int block_size, int pnorm, int levels);
+GME_API int gme_seq_read_qmv(gme_seq *seq, int first_pair, int count, int32_t *qmf_out, int64_t *cost_out);
+GME_API int gme_seq_compensate_qpel(gme_seq *seq, int frame_distance, int block_size, int64_t *sse_out);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
