@@ -124,9 +124,11 @@ def test_redo_path_small_batches_and_window_sizes(native, monkeypatch):
 
 
 def test_pyramids_odd_and_tiny_shapes(native):
-    """k_pyrdown (two output rows per thread, seven row loads), k_pyrdown_edge16 (16-byte row chunks) and the per-pixel
-    border kernel on shapes with odd heights / widths, widths that are no multiple of 4, fewer than 16 columns and
-    fewer than 4 rows: every level equals the C oracle's restatement of cv2.pyrDown (utils.py:34-51)."""
+    """Pyramids of shapes with odd heights / widths, widths that are no multiple of 4, fewer than 16 columns and fewer than
+    4 rows: every level equals the C oracle's restatement of cv2.pyrDown (utils.py:34-51).  Levels whose source width is a
+    multiple of 8 (16, 8, 24, 40, 128, 64, 1000 here, one height each) take k_pyrdown_lds; the others take k_pyrdown (two output
+    rows per thread, seven row loads) with k_pyrdown_edge16 (16-byte row chunks, widths 20 and 500) or the per-pixel
+    k_pyrdown_edge.  The walk over each kernel's path boundaries is tests/test_gpu_frame_kernels.py."""
     import utils
     co = c_oracle()
     rng = np.random.default_rng(5)
