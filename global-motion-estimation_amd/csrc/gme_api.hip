@@ -55,29 +55,21 @@ extern "C" gme_ctx* gme_create(int device_id)
     if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&ctx->prop, device_id) != hipSuccess ||
         hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
-        hipMalloc((void**)&ctx->status, GME_STATUS_WORDS * sizeof(int)) != hipSuccess ||
+        ctx->status.ensure(GME_STATUS_WORDS, "status words") != GME_OK ||
         hipMemsetAsync(ctx->status, 0, GME_STATUS_WORDS * sizeof(int), ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
         gme_set_error("gme_create: HIP initialisation failed on device %d: %s", device_id,
                       hipGetErrorString(hipGetLastError()));
-        if (ctx->status) hipFree(ctx->status);
-        if (ctx->ev0) hipEventDestroy(ctx->ev0);
-        if (ctx->ev1) hipEventDestroy(ctx->ev1);
-        if (ctx->stream) hipStreamDestroy(ctx->stream);
-        delete ctx;
-        return nullptr;
-    }
-    if (strncmp(ctx->prop.gcnArchName, "gfx950", 6) != 0) {
+    else if (strncmp(ctx->prop.gcnArchName, "gfx950", 6) != 0)
         gme_set_error("gme_create: device %d is %s; this library carries gfx950 code only", device_id,
                       ctx->prop.gcnArchName);
-        hipFree(ctx->status);
-        hipEventDestroy(ctx->ev0);
-        hipEventDestroy(ctx->ev1);
-        hipStreamDestroy(ctx->stream);
-        delete ctx;
-        return nullptr;
-    }
-    return ctx;
+    else
+        return ctx;
+    if (ctx->ev0) hipEventDestroy(ctx->ev0);
+    if (ctx->ev1) hipEventDestroy(ctx->ev1);
+    if (ctx->stream) hipStreamDestroy(ctx->stream);
+    delete ctx;
+    return nullptr;
 }
 
 extern "C" void gme_destroy(gme_ctx* ctx)
@@ -87,16 +79,12 @@ extern "C" void gme_destroy(gme_ctx* ctx)
     gme_comm_destroy(ctx);
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    if (ctx->scratch) hipFree(ctx->scratch);
-    if (ctx->redo_list) hipFree(ctx->redo_list);
-    if (ctx->stage) hipFree(ctx->stage);
-    if (ctx->status) hipFree(ctx->status);
     if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
     if (ctx->back_stream) hipStreamDestroy(ctx->back_stream);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;                                            // frees the context's device buffers
 }
 
 // Every entry point that touches a context holds its mutex for the whole call: the context owns ONE
@@ -238,62 +226,49 @@ extern "C" int gme_timer_stop(gme_ctx* ctx, float* elapsed_ms)
 
 int ctx_scratch(gme_ctx* ctx, size_t bytes, void** out)
 {
-    if (bytes > ctx->scratch_bytes) {
-        GME_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch) hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        const size_t want = (bytes + (1u << 20)) & ~((size_t)(1u << 20) - 1);
-        if (hipMalloc(&ctx->scratch, want) != hipSuccess) {
-            gme_set_error("out of device memory (%zu bytes of scratch)", want);
-            return GME_ERR_NOMEM;
-        }
-        ctx->scratch_bytes = want;
+    if (bytes > ctx->scratch.cap) {
+        GME_HIP_TRY(hipStreamSynchronize(ctx->stream));        // work in flight may still read the old block
+        const int rc = ctx->scratch.ensure((bytes + (1u << 20)) & ~((size_t)(1u << 20) - 1), "scratch");
+        if (rc) return rc;
     }
-    *out = ctx->scratch;
+    *out = ctx->scratch.get();
     return GME_OK;
 }
 
 int ctx_redo_list(gme_ctx* ctx, size_t entries, uint32_t** out)
 {
-    if (entries > ctx->redo_cap) {
+    if (entries > ctx->redo_list.cap) {
         GME_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->redo_list) hipFree(ctx->redo_list);
-        ctx->redo_list = nullptr;
-        ctx->redo_cap = 0;
-        const size_t want = (entries + 4095) & ~(size_t)4095;
-        if (hipMalloc((void**)&ctx->redo_list, want * sizeof(uint32_t)) != hipSuccess) {
-            gme_set_error("out of device memory (%zu redo entries)", want);
-            return GME_ERR_NOMEM;
+        const int rc = ctx->redo_list.ensure((entries + 4095) & ~(size_t)4095, "redo entries");
+        if (rc) return rc;
+    }
+    *out = ctx->redo_list.get();
+    return GME_OK;
+}
+
+int plane_alloc(gme_ctx* ctx, PlaneBuf* p, int count, int H, int W)
+{
+    *p = PlaneBuf();
+    Plane v;
+    v.H = H; v.W = W; v.count = count;
+    v.pitch = round_up(W, 64);
+    v.stride = (int64_t)round_up(v.pitch * H, 256);
+    if (count != 0 && H != 0 && W != 0) {
+        // one guard row behind the stack: dword loads near the last row never leave the allocation
+        const int rc = p->mem.ensure(v.bytes() + v.pitch, "frames");
+        if (rc) return rc;
+        v.ptr = p->mem.get();
+        // on the context's stream: a null-stream memset would not be ordered against the
+        // kernels this (non-blocking) stream runs next and could land on top of their output
+        const hipError_t e = hipMemsetAsync(v.ptr, 0, v.bytes() + v.pitch, ctx->stream);
+        if (e != hipSuccess) {
+            p->mem.reset();
+            gme_set_error("hipMemsetAsync of %zu bytes of frames failed: %s", v.bytes() + v.pitch, hipGetErrorString(e));
+            return GME_ERR_HIP;
         }
-        ctx->redo_cap = want;
     }
-    *out = ctx->redo_list;
+    static_cast<Plane&>(*p) = v;
     return GME_OK;
-}
-
-int plane_alloc(gme_ctx* ctx, Plane* p, int count, int H, int W)
-{
-    p->H = H; p->W = W; p->count = count;
-    p->pitch = round_up(W, 64);
-    p->stride = (int64_t)round_up(p->pitch * H, 256);
-    p->ptr = nullptr;
-    if (count == 0 || H == 0 || W == 0) return GME_OK;
-    // one guard row behind the stack: dword loads near the last row never leave the allocation
-    if (hipMalloc((void**)&p->ptr, p->bytes() + p->pitch) != hipSuccess) {
-        gme_set_error("out of device memory (%zu bytes of frames)", p->bytes());
-        return GME_ERR_NOMEM;
-    }
-    // on the context's stream: a null-stream memset would not be ordered against the
-    // kernels this (non-blocking) stream runs next and could land on top of their output
-    GME_HIP_TRY(hipMemsetAsync(p->ptr, 0, p->bytes() + p->pitch, ctx->stream));
-    return GME_OK;
-}
-
-void plane_free(Plane* p)
-{
-    if (p->ptr) hipFree(p->ptr);
-    p->ptr = nullptr;
 }
 
 // carve `n` sub-buffers out of the context scratch, 256-byte aligned
@@ -498,57 +473,16 @@ extern "C" gme_seq* gme_seq_create(gme_ctx* ctx, int n_frames, int H, int W)
     return s;
 }
 
-static void free_fit(FitLevelBuf& f)
-{
-    if (f.gt) hipFree(f.gt);
-    if (f.model) hipFree(f.model);
-    if (f.mask) hipFree(f.mask);
-    if (f.diff) hipFree(f.diff);
-    if (f.list) hipFree(f.list);
-    if (f.thr) hipFree(f.thr);
-    if (f.sums) hipFree(f.sums);
-    if (f.sums2) hipFree(f.sums2);
-    f = FitLevelBuf();
-}
-
 extern "C" void gme_seq_destroy(gme_seq* s)
 {
     if (!s) return;
     std::lock_guard<std::mutex> lock(s->ctx->mu);
     hipSetDevice(s->ctx->device);
     hipStreamSynchronize(s->ctx->stream);
-    for (int l = 0; l < 3; ++l) { plane_free(&s->level[l]); free_fit(s->fit[l]); }
-    s->fit_mv.gt = nullptr;
-    free_fit(s->fit_mv);
-    if (s->mv_params) hipFree(s->mv_params);
-    plane_free(&s->comp);
-    if (s->mv) hipFree(s->mv);
-    for (int l = 0; l < 3; ++l) if (s->sqbox[l]) hipFree(s->sqbox[l]);
-    if (s->params0) hipFree(s->params0);
-    if (s->params_in) hipFree(s->params_in);
-    if (s->solve_flags) hipFree(s->solve_flags);
-    if (s->sse) hipFree(s->sse);
-    if (s->comp_params) hipFree(s->comp_params);
-    if (s->comp_mf) hipFree(s->comp_mf);
-    if (s->synth_canvas) hipFree(s->synth_canvas);
-    if (s->direct) hipFree(s->direct);
-    plane_free(&s->warped);
-    if (s->warp_params) hipFree(s->warp_params);
-    if (s->warp_counts) hipFree(s->warp_counts);
-    if (s->mosaic_sprite) hipFree(s->mosaic_sprite);
-    if (s->mosaic_count) hipFree(s->mosaic_count);
-    plane_free(&s->masks);
-    if (s->mosaic_params) hipFree(s->mosaic_params);
-    if (s->mosaic_usable) hipFree(s->mosaic_usable);
-    if (s->mosaic_counts) hipFree(s->mosaic_counts);
-    if (s->qmv) hipFree(s->qmv);
-    if (s->qcost) hipFree(s->qcost);
-    if (s->summary) hipFree(s->summary);
-    if (s->gathered) hipFree(s->gathered);
     if (s->ready) hipEventDestroy(s->ready);
     if (s->upload_gate) hipEventDestroy(s->upload_gate);
     if (s->uploaded) hipEventDestroy(s->uploaded);
-    delete s;
+    delete s;                                              // frees the sequence's device buffers
 }
 
 // Split-phase calls: with the switch on, gme_seq_gme_begin / gme_seq_gme_fit / gme_seq_compensate queue their work
@@ -624,37 +558,38 @@ namespace {
 struct Uploader {
     std::mutex mu;
     hipStream_t stream = nullptr;
-    uint8_t* stage = nullptr;        // device staging of tight host frames, repacked into the pitched planes
+    // Device staging of tight host frames, repacked into the pitched planes.  The one device block no DevBuf owns: the
+    // array below lives as long as the process, and a destructor there would call hipFree after the HIP runtime has
+    // shut down.  So the pointer is raw, and the last block is never freed.
+    uint8_t* stage = nullptr;
     size_t stage_bytes = 0;
 };
 Uploader g_uploader[16];
 }  // namespace
 
-// the copies of one gme_seq_upload call on `stream`; `stage` / `stage_bytes` is the staging buffer that belongs to that stream
-static int upload_copies(gme_seq* s, hipStream_t stream, uint8_t** stage, size_t* stage_bytes, int first, int count,
+// Frames per linear copy when gme_seq_upload goes through a staging buffer (0: it does not).  Tight frames: linear copies
+// (what the DMA engines move at link speed; 2-D copies of 720-byte rows reach ~37 GB/s) through a device staging buffer,
+// spread into the pitched planes by k_repack.
+static size_t upload_stage_frames(const gme_seq* s, int count, int row_stride, int64_t frame_stride)
+{
+    if (!(row_stride == s->W && frame_stride == (int64_t)s->W * s->H && s->level[2].pitch != s->W && count > 0)) return 0;
+    size_t per = ((size_t)64 << 20) / ((size_t)s->H * s->W);
+    if (per < 1) per = 1;
+    return per > (size_t)count ? (size_t)count : per;
+}
+
+// the copies of one gme_seq_upload call on `stream`; `stage` holds `per` frames (upload_stage_frames) and belongs to that stream
+static int upload_copies(gme_seq* s, hipStream_t stream, uint8_t* stage, size_t per, int first, int count,
                          const uint8_t* frames, int row_stride, int64_t frame_stride)
 {
     const Plane& p = s->level[2];
     gme_ctx* ctx = s->ctx;
-    if (row_stride == s->W && frame_stride == (int64_t)s->W * s->H && p.pitch != s->W && count > 0) {
-        // tight frames: linear copies (what the DMA engines move at link speed; 2-D copies of 720-byte rows reach
-        // ~37 GB/s) through a device staging buffer, spread into the pitched planes by k_repack
+    if (per > 0) {
         const size_t frame_bytes = (size_t)s->H * s->W;
-        size_t per = ((size_t)64 << 20) / frame_bytes;
-        if (per < 1) per = 1;
-        if (per > (size_t)count) per = (size_t)count;
-        if (per * frame_bytes > *stage_bytes) {
-            GME_HIP_TRY(hipStreamSynchronize(stream));
-            if (ctx->copy_stream && stage == &ctx->stage) GME_HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
-            if (*stage) hipFree(*stage);
-            *stage = nullptr; *stage_bytes = 0;
-            if (hipMalloc((void**)stage, per * frame_bytes) != hipSuccess) { gme_set_error("out of device memory (staging)"); return GME_ERR_NOMEM; }
-            *stage_bytes = per * frame_bytes;
-        }
         for (int f0 = 0; f0 < count; f0 += (int)per) {
             const int n = count - f0 < (int)per ? count - f0 : (int)per;
-            GME_HIP_TRY(hipMemcpyAsync(*stage, frames + (int64_t)f0 * frame_stride, (size_t)n * frame_bytes, hipMemcpyHostToDevice, stream));
-            int rc2 = launch_repack(ctx, stream, *stage, n, s->H, s->W, p.at(first + f0), p.pitch, p.stride);
+            GME_HIP_TRY(hipMemcpyAsync(stage, frames + (int64_t)f0 * frame_stride, (size_t)n * frame_bytes, hipMemcpyHostToDevice, stream));
+            int rc2 = launch_repack(ctx, stream, stage, n, s->H, s->W, p.at(first + f0), p.pitch, p.stride);
             if (rc2) return rc2;
         }
     } else if (p.stride == (int64_t)p.pitch * s->H && frame_stride == (int64_t)row_stride * s->H) {
@@ -680,6 +615,7 @@ extern "C" int gme_seq_upload(gme_seq* s, int first, int count, const uint8_t* f
     s->pyramids_valid = false;
     s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
     gme_drop_run(s);
+    const size_t per = upload_stage_frames(s, count, row_stride, frame_stride), stage_bytes = per * s->H * s->W;
     if (s->split_phase && ctx->device >= 0 && ctx->device < 16) {
         // split-phase: the copies are queued and the call returns; `frames` must stay untouched until a later
         // gme_seq_wait / gme_sync on this sequence has returned.  They run on the device's shared upload stream, behind
@@ -694,14 +630,27 @@ extern "C" int gme_seq_upload(gme_seq* s, int first, int count, const uint8_t* f
         }
         GME_HIP_TRY(hipEventRecord(s->upload_gate, ctx->stream));
         GME_HIP_TRY(hipStreamWaitEvent(u.stream, s->upload_gate, 0));
-        int rc = upload_copies(s, u.stream, &u.stage, &u.stage_bytes, first, count, frames, row_stride, frame_stride);
+        if (stage_bytes > u.stage_bytes) {
+            GME_HIP_TRY(hipStreamSynchronize(u.stream));
+            if (u.stage) (void)hipFree(u.stage);               // see Uploader::stage
+            u.stage = nullptr; u.stage_bytes = 0;
+            if (hipMalloc((void**)&u.stage, stage_bytes) != hipSuccess) { gme_set_error("out of device memory (staging)"); return GME_ERR_NOMEM; }
+            u.stage_bytes = stage_bytes;
+        }
+        int rc = upload_copies(s, u.stream, u.stage, per, first, count, frames, row_stride, frame_stride);
         if (rc) return rc;
         GME_HIP_TRY(hipEventRecord(s->uploaded, u.stream));
         GME_HIP_TRY(hipStreamWaitEvent(ctx->stream, s->uploaded, 0));
         GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream));
         return GME_OK;
     }
-    int rc = upload_copies(s, ctx->stream, &ctx->stage, &ctx->stage_bytes, first, count, frames, row_stride, frame_stride);
+    if (stage_bytes > ctx->stage.cap) {
+        GME_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (ctx->copy_stream) GME_HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
+        const int rc = ctx->stage.ensure(stage_bytes, "staging");
+        if (rc) return rc;
+    }
+    int rc = upload_copies(s, ctx->stream, ctx->stage, per, first, count, frames, row_stride, frame_stride);
     if (rc) return rc;
     GME_HIP_TRY(hipStreamSynchronize(ctx->stream));      // the host buffer may be reused on return
     return GME_OK;
@@ -713,10 +662,8 @@ extern "C" int gme_seq_synth(gme_seq* s, uint64_t seed, int t0)
     GME_ENTER(s->ctx);
     int rc = GME_OK;
     if (!s->synth_canvas) {
-        if (hipMalloc((void**)&s->synth_canvas, (size_t)2048 * 4096) != hipSuccess) {
-            gme_set_error("out of device memory (synthetic canvas)");
-            return GME_ERR_NOMEM;
-        }
+        rc = s->synth_canvas.ensure((size_t)2048 * 4096, "synthetic canvas");
+        if (rc) return rc;
         s->synth_valid = false;
     }
     if (!s->synth_valid || s->synth_seed != seed) {
@@ -739,38 +686,30 @@ extern "C" int gme_seq_invalidate(gme_seq* s)
     return GME_OK;
 }
 
+// planes first .. first + count - 1 of a stack into out[count][H][W] (tight), queued on the context's stream
+static int read_planes(gme_ctx* ctx, const Plane& p, int first, int count, uint8_t* out)
+{
+    for (int k = 0; k < count; ++k)
+        GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * p.H * p.W, p.W, p.at(first + k), p.pitch, p.W, p.H, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+    return GME_OK;
+}
+
 extern "C" int gme_seq_read_frame(gme_seq* s, int level, int index, uint8_t* out)
 {
     GME_REQUIRE(s != nullptr && out != nullptr, GME_ERR_ARG, "gme_seq_read_frame: null pointer");
     GME_ENTER(s->ctx);
     GME_REQUIRE(level >= 0 && level <= 2 && index >= 0 && index < s->N_cap, GME_ERR_ARG, "gme_seq_read_frame: bad index");
     GME_REQUIRE(level == 2 || s->pyramids_valid, GME_ERR_STATE, "pyramid levels exist only after gme_seq_gme_begin");
-    const Plane& p = s->level[level];
-    GME_HIP_TRY(hipMemcpy2DAsync(out, p.W, p.at(index), p.pitch, p.W, p.H, hipMemcpyDeviceToHost, s->ctx->stream));
-    return ctx_finish(s->ctx);
-}
-
-template <typename T>
-static int ensure(T** ptr, size_t* have, size_t want_bytes)
-{
-    if (*ptr && *have >= want_bytes) return GME_OK;
-    if (*ptr) hipFree(*ptr);
-    *ptr = nullptr; *have = 0;
-    if (want_bytes == 0) return GME_OK;
-    if (hipMalloc((void**)ptr, want_bytes) != hipSuccess) {
-        gme_set_error("out of device memory (%zu bytes)", want_bytes);
-        return GME_ERR_NOMEM;
-    }
-    *have = want_bytes;
-    return GME_OK;
+    const int rc = read_planes(s->ctx, s->level[level], index, 1, out);
+    return rc ? rc : ctx_finish(s->ctx);
 }
 
 // auxiliary table (bbme_aux_kind) for every frame of one pyramid level
 static int seq_sqbox(gme_seq* s, int level, int kind)
 {
     const Plane& p = s->level[level];
-    const size_t bytes = (size_t)p.stride * p.count * sizeof(uint32_t);
-    int rc = ensure(&s->sqbox[level], &s->sqbox_bytes[level], bytes);
+    int rc = s->sqbox[level].ensure((size_t)p.stride * p.count, "box sums");
     if (rc) return rc;
     if (!s->sqbox_valid[level] || s->sqbox_kind[level] != kind) {
         rc = launch_aux_table(s->ctx, kind, p.ptr, p.stride, s->N, p.H, p.W, p.pitch, s->sqbox[level], p.stride);
@@ -791,7 +730,7 @@ extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, i
     rc = bbme_check_args(s->H, s->W, bs, sw, procedure, pnorm);
     if (rc) return rc;
     const int pairs = s->N - fd, h = s->H / bs, w = s->W / bs;
-    rc = ensure(&s->mv, &s->mv_bytes, (size_t)pairs * h * w * 2 * sizeof(int32_t));
+    rc = s->mv.ensure((size_t)pairs * h * w * 2, "motion field");
     if (rc) return rc;
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
     s->mv_fd = fd; s->mv_bs = bs;
@@ -844,7 +783,7 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     if (rc) return rc;
     const int pairs = count - fd, h = s->H / bs, w = s->W / bs;
     const size_t per = (size_t)h * w * 2;
-    rc = ensure(&s->mv, &s->mv_bytes, (size_t)(s->N - fd) * per * sizeof(int32_t));
+    rc = s->mv.ensure((size_t)(s->N - fd) * per, "motion field");
     if (rc) return rc;
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
     s->mv_fd = fd; s->mv_bs = bs;
@@ -854,7 +793,7 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     // kernel would take at the largest also takes it at every chunk, and a smaller chunk of a declined call keeps kind 1
     const int aux = bbme_aux_kind(s->H, s->W, p.pitch, pairs, bs, sw, procedure, pnorm);
     if (aux) {
-        rc = ensure(&s->sqbox[2], &s->sqbox_bytes[2], (size_t)p.stride * p.count * sizeof(uint32_t));
+        rc = s->sqbox[2].ensure((size_t)p.stride * p.count, "box sums");
         if (rc) return rc;
     }
     if (!ctx->copy_stream) {
@@ -868,12 +807,10 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     const bool tight = row_stride == s->W && frame_stride == (int64_t)s->W * s->H && p.pitch != s->W;
     if (tight) {
         const size_t want = (size_t)(chunk_frames < count ? chunk_frames : count) * s->H * s->W;
-        if (want > ctx->stage_bytes) {
+        if (want > ctx->stage.cap) {
             GME_HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
-            if (ctx->stage) hipFree(ctx->stage);
-            ctx->stage = nullptr; ctx->stage_bytes = 0;
-            if (hipMalloc((void**)&ctx->stage, want) != hipSuccess) { gme_set_error("out of device memory (%zu bytes of staging)", want); return GME_ERR_NOMEM; }
-            ctx->stage_bytes = want;
+            rc = ctx->stage.ensure(want, "staging");
+            if (rc) return rc;
         }
     }
     const int nchunks = (count + chunk_frames - 1) / chunk_frames;
@@ -989,30 +926,22 @@ extern "C" int gme_seq_read_mv(gme_seq* s, int first_pair, int count, int32_t* m
     return ctx_finish(s->ctx);
 }
 
-// gt: the level's own field, or (borrowed_gt) one the fit only reads -- then never allocated or freed here.
-// full: also the stage buffers of the fit (model field, mask, sums, ...); the dense level needs gt only.
+// Buffers of one level for `pairs` fields of h x w, all or none.  gt: the level's own field, or (borrowed_gt) one the fit
+// only reads, which is then never allocated or freed here.  full: also the stage buffers of the fit (model field, mask,
+// sums, ...); the dense level needs gt only.
 static int alloc_fit(FitLevelBuf& f, int pairs, int h, int w, bool full, int32_t* borrowed_gt = nullptr)
 {
-    free_fit(f);
+    f = FitLevelBuf();                                     // sized for this shape, not for the largest so far
+    const size_t n = (size_t)pairs * h * w, nf = full ? n : 0, pf = nf ? (size_t)pairs : 0;
+    const int rc = dev_ensure_all("GME level buffers",
+                                  { { f.gt_own, borrowed_gt ? 0 : n * 2 }, { f.model, nf * 2 }, { f.mask, nf }, { f.diff, nf },
+                                    { f.list, (size_t)h * w * 16 > FIT_LIST_LDS_BYTES ? nf : 0 }, { f.thr, pf }, { f.sums, pf * 15 },
+                                    { f.sums2, pf * 27 } });
+    if (rc) return rc;
     f.h = h; f.w = w;
-    const size_t n = (size_t)pairs * h * w;
-    if (n == 0) return GME_OK;
-    bool ok = true;
-    if (borrowed_gt) f.gt = borrowed_gt;
-    else ok = hipMalloc((void**)&f.gt, n * 2 * sizeof(int32_t)) == hipSuccess;
-    if (full) {
-        ok = ok && hipMalloc((void**)&f.model, n * 2 * sizeof(int16_t)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&f.mask, n) == hipSuccess;
-        ok = ok && hipMalloc((void**)&f.diff, n * sizeof(int32_t)) == hipSuccess;
-        if ((size_t)h * w * 16 > FIT_LIST_LDS_BYTES) ok = ok && hipMalloc(&f.list, n * 16) == hipSuccess;
-        ok = ok && hipMalloc((void**)&f.thr, (size_t)pairs * sizeof(int32_t)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&f.sums, (size_t)pairs * 15 * sizeof(double)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&f.sums2, (size_t)pairs * 27 * sizeof(double)) == hipSuccess;
-    }
-    if (!ok) { gme_set_error("out of device memory (GME level buffers)"); return GME_ERR_NOMEM; }
+    f.gt = borrowed_gt ? borrowed_gt : f.gt_own.get();
     return GME_OK;
 }
-
 
 // BBME of one pyramid level for the pairs of the current GME run (gme_seq_gme_begin's arguments):
 // level 0 = dense field (bs 2, diamond, MSE: motion.py:27-29; bbme.py:18 default norm).
@@ -1100,24 +1029,21 @@ static int gme_begin_common(gme_seq* s, int fd, int bbme_bs, int procedure, int 
     rc = seq_pyramids(s);
     if (rc) return rc;
     const int cap_pairs = s->N_cap - fd;                   // buffers hold the sequence's full count: gme_seq_set_frames never reallocates
-    if (s->gme_alloc_pairs < (size_t)cap_pairs || s->gme_bs != bbme_bs) {
+    if (s->params0.cap < (size_t)cap_pairs * 6 || s->gme_bs != bbme_bs) {
+        // one group: whatever fails, no level and no parameter block is left that a later call could take for allocated
+        s->params0.reset(); s->params_in.reset(); s->solve_flags.reset();
         rc = alloc_fit(s->fit[0], cap_pairs, s->level[0].H / 2, s->level[0].W / 2, false);
-        if (rc) return rc;
-        for (int l = 1; l <= 2; ++l) {
+        for (int l = 1; l <= 2 && rc == GME_OK; ++l)
             rc = alloc_fit(s->fit[l], cap_pairs, s->level[l].H / bbme_bs, s->level[l].W / bbme_bs, true);
-            if (rc) return rc;
+        if (rc == GME_OK)
+            rc = dev_ensure_all("parameters", { { s->params0, (size_t)cap_pairs * 6 }, { s->solve_flags, (size_t)cap_pairs },
+                                                { s->params_in, (size_t)cap_pairs * 12 } });      // 12: gme_seq_gme_fit2
+        if (rc) {
+            for (int l = 0; l <= 2; ++l) s->fit[l] = FitLevelBuf();
+            s->gme_bs = 0;
+            gme_drop_run(s);
+            return rc;
         }
-        if (s->params0) hipFree(s->params0);
-        if (s->params_in) hipFree(s->params_in);
-        if (s->solve_flags) hipFree(s->solve_flags);
-        s->params0 = nullptr; s->params_in = nullptr; s->solve_flags = nullptr;
-        if (hipMalloc((void**)&s->params0, (size_t)cap_pairs * 6 * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&s->solve_flags, (size_t)(cap_pairs > 0 ? cap_pairs : 1) * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc((void**)&s->params_in, (size_t)cap_pairs * 12 * sizeof(double)) != hipSuccess) {      // 12: gme_seq_gme_fit2
-            gme_set_error("out of device memory (parameters)");
-            return GME_ERR_NOMEM;
-        }
-        s->gme_alloc_pairs = cap_pairs;
     }
     s->gme_fd = fd; s->gme_bs = bbme_bs; s->gme_pairs = pairs;
     s->gme_procedure = procedure; s->gme_sw = sw;
@@ -1215,12 +1141,12 @@ static int ensure_fit_mv(gme_seq* s)
 {
     FitLevelBuf& f = s->fit_mv;
     if (!(f.h == s->mv_h && f.w == s->mv_w && s->fit_mv_pairs == s->mv_pairs && f.model)) {
-        f.gt = nullptr;                       // borrowed, never freed here
+        s->fit_mv_pairs = 0;
         const int rc = alloc_fit(f, s->mv_pairs, s->mv_h, s->mv_w, true, s->mv);
         if (rc) return rc;
         s->fit_mv_pairs = s->mv_pairs;
     }
-    f.gt = s->mv;
+    f.gt = s->mv;                             // gme_seq_bbme may have moved it since
     return GME_OK;
 }
 
@@ -1240,9 +1166,7 @@ static int seq_fit(gme_seq* s, int order, const char* who, int level, const doub
         rc = ensure_fit_mv(s);
         if (rc) return rc;
         pairs = s->mv_pairs;
-        size_t have = s->mv_params_bytes;
-        rc = ensure(&s->mv_params, &have, (size_t)pairs * width * sizeof(double));
-        s->mv_params_bytes = have;
+        rc = s->mv_params.ensure((size_t)pairs * width, "fit parameters");
         if (rc) return rc;
         dparams = s->mv_params;
     } else {
@@ -1298,17 +1222,11 @@ static int ensure_comp(gme_seq* s, int fd, int pairs)
     gme_ctx* ctx = s->ctx;
     if (!s->comp.ptr || s->comp.count < pairs) {
         const int cap_pairs = s->N_cap - fd > pairs ? s->N_cap - fd : pairs;
-        plane_free(&s->comp);
+        s->sse.reset(); s->comp_params.reset();
         int rc = plane_alloc(ctx, &s->comp, cap_pairs, s->H, s->W);
-        if (rc) return rc;
-        if (s->sse) hipFree(s->sse);
-        if (s->comp_params) hipFree(s->comp_params);
-        s->sse = nullptr; s->comp_params = nullptr;
-        if (hipMalloc((void**)&s->sse, (size_t)cap_pairs * sizeof(unsigned long long)) != hipSuccess ||
-            hipMalloc((void**)&s->comp_params, (size_t)cap_pairs * 12 * sizeof(double)) != hipSuccess) {     // 12: gme_seq_compensate2
-            gme_set_error("out of device memory");
-            return GME_ERR_NOMEM;
-        }
+        if (rc == GME_OK)
+            rc = dev_ensure_all("compensation", { { s->sse, (size_t)cap_pairs }, { s->comp_params, (size_t)cap_pairs * 12 } });      // 12: gme_seq_compensate2
+        if (rc) { s->comp = PlaneBuf(); return rc; }       // all or nothing: comp.ptr and comp.count say what the three hold
     }
     return GME_OK;
 }
@@ -1342,7 +1260,7 @@ static int seq_compensate(gme_seq* s, int order, const char* who, int fd, int bs
     rc = ensure_comp(s, fd, pairs);
     if (rc) return rc;
     if (order == 2) {
-        rc = ensure(&s->comp_mf, &s->comp_mf_bytes, (size_t)pairs * h * w * 2 * sizeof(int32_t));
+        rc = s->comp_mf.ensure((size_t)pairs * h * w * 2, "order-2 field");
         if (rc) return rc;
     }
     rc = copy_small(ctx, s->comp_params, params, (size_t)pairs * order_params(order) * sizeof(double), hipMemcpyHostToDevice,
@@ -1373,9 +1291,8 @@ extern "C" int gme_seq_read_compensated_range(gme_seq* s, int first, int count, 
     GME_ENTER(s->ctx);
     GME_REQUIRE(s->comp.ptr && first >= 0 && count >= 0 && first + count <= s->comp.count, GME_ERR_STATE,
                 "gme_seq_read_compensated_range: pairs %d .. %d of %d", first, first + count, s->comp.ptr ? s->comp.count : 0);
-    for (int k = 0; k < count; ++k)
-        GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * s->H * s->W, s->W, s->comp.at(first + k), s->comp.pitch, s->W, s->H,
-                                     hipMemcpyDeviceToHost, s->ctx->stream));
+    const int rc = read_planes(s->ctx, s->comp, first, count, out);
+    if (rc) return rc;
     GME_HIP_TRY(hipStreamSynchronize(s->ctx->stream));
     return GME_OK;
 }
@@ -1447,7 +1364,7 @@ static int seq_device_solve(gme_seq* s, int order, int model, const char* who, i
     rc = ensure_comp(s, fd, pairs);
     if (rc) return rc;
     if (order == 2) {
-        rc = ensure(&s->comp_mf, &s->comp_mf_bytes, (size_t)pairs * h * w * 2 * sizeof(int32_t));
+        rc = s->comp_mf.ensure((size_t)pairs * h * w * 2, "order-2 field");
         if (rc) return rc;
     }
     GME_HIP_TRY(hipMemsetAsync(s->solve_flags, 0, (size_t)(pairs > 0 ? pairs : 1) * sizeof(int32_t), ctx->stream));
@@ -1499,8 +1416,8 @@ extern "C" int gme_seq_read_compensated(gme_seq* s, int pair, uint8_t* out)
     GME_REQUIRE(s != nullptr && out != nullptr, GME_ERR_ARG, "gme_seq_read_compensated: null pointer");
     GME_ENTER(s->ctx);
     GME_REQUIRE(s->comp.ptr && pair >= 0 && pair < s->comp.count, GME_ERR_STATE, "gme_seq_read_compensated: no such pair");
-    GME_HIP_TRY(hipMemcpy2DAsync(out, s->W, s->comp.at(pair), s->comp.pitch, s->W, s->H, hipMemcpyDeviceToHost, s->ctx->stream));
-    return ctx_finish(s->ctx);
+    const int rc = read_planes(s->ctx, s->comp, pair, 1, out);
+    return rc ? rc : ctx_finish(s->ctx);
 }
 
 // ---------------------------------------------------------------------------
@@ -1663,13 +1580,9 @@ static int stab_buffers(gme_seq* s)
 {
     if (s->warped.ptr) return GME_OK;
     int rc = plane_alloc(s->ctx, &s->warped, s->N_cap, s->H, s->W);
-    if (rc) return rc;
-    if (hipMalloc((void**)&s->warp_params, (size_t)s->N_cap * 8 * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&s->warp_counts, (size_t)s->N_cap * sizeof(unsigned long long)) != hipSuccess) {
-        plane_free(&s->warped);
-        gme_set_error("out of device memory (stabilization buffers)");
-        return GME_ERR_NOMEM;
-    }
+    if (rc == GME_OK)
+        rc = dev_ensure_all("stabilization buffers", { { s->warp_params, (size_t)s->N_cap * 8 }, { s->warp_counts, (size_t)s->N_cap } });
+    if (rc) { s->warped = PlaneBuf(); s->warped_written.clear(); return rc; }
     s->warped_written.assign((size_t)s->N_cap, 0);
     return GME_OK;
 }
@@ -1716,10 +1629,8 @@ extern "C" int gme_seq_read_warped_range(gme_seq* s, int first, int count, uint8
                 "gme_seq_read_warped_range: frames [%d, %d) outside [0, %d)", first, first + count, s->N);
     GME_REQUIRE(stab_written(s, first, count), GME_ERR_ARG, "gme_seq_read_warped_range: frames [%d, %d) were never warped",
                 first, first + count);
-    for (int k = 0; k < count; ++k)
-        GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * s->H * s->W, s->W, s->warped.at(first + k), s->warped.pitch, s->W, s->H,
-                                     hipMemcpyDeviceToHost, s->ctx->stream));
-    return ctx_finish(s->ctx);
+    const int rc = read_planes(s->ctx, s->warped, first, count, out);
+    return rc ? rc : ctx_finish(s->ctx);
 }
 
 extern "C" int gme_seq_frame_sse(gme_seq* s, int warped, int first, int count, int64_t* sse_out)
@@ -1747,17 +1658,8 @@ extern "C" int gme_seq_frame_sse(gme_seq* s, int warped, int first, int count, i
 static int mosaic_rows(gme_seq* s)
 {
     if (s->mosaic_params) return GME_OK;
-    if (hipMalloc((void**)&s->mosaic_params, (size_t)s->N_cap * 8 * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&s->mosaic_usable, (size_t)s->N_cap) != hipSuccess ||
-        hipMalloc((void**)&s->mosaic_counts, (size_t)s->N_cap * 2 * sizeof(unsigned long long)) != hipSuccess) {
-        if (s->mosaic_params) hipFree(s->mosaic_params);
-        if (s->mosaic_usable) hipFree(s->mosaic_usable);
-        s->mosaic_params = nullptr;
-        s->mosaic_usable = nullptr;
-        gme_set_error("out of device memory (mosaic parameters)");
-        return GME_ERR_NOMEM;
-    }
-    return GME_OK;
+    return dev_ensure_all("mosaic parameters", { { s->mosaic_params, (size_t)s->N_cap * 8 }, { s->mosaic_usable, (size_t)s->N_cap },
+                                                 { s->mosaic_counts, (size_t)s->N_cap * 2 } });
 }
 
 // the per-frame rows of a call: parameters and usable flags (all ones for NULL) to the device
@@ -1789,20 +1691,10 @@ extern "C" int gme_seq_mosaic(gme_seq* s, int first, int count, const double* in
     const int pitch = round_up(Wc, 64);
     const size_t pixels = (size_t)Hc * (size_t)pitch;
     s->mosaic_valid = false;
-    if (pixels > s->mosaic_cap) {
-        if (s->mosaic_sprite) hipFree(s->mosaic_sprite);
-        if (s->mosaic_count) hipFree(s->mosaic_count);
-        s->mosaic_sprite = nullptr;
-        s->mosaic_count = nullptr;
-        s->mosaic_cap = 0;
-        if (hipMalloc((void**)&s->mosaic_sprite, pixels) != hipSuccess ||
-            hipMalloc((void**)&s->mosaic_count, pixels * sizeof(uint16_t)) != hipSuccess) {
-            if (s->mosaic_sprite) hipFree(s->mosaic_sprite);
-            s->mosaic_sprite = nullptr;
-            gme_set_error("out of device memory (a mosaic of %d x %d)", Hc, Wc);
-            return GME_ERR_NOMEM;
-        }
-        s->mosaic_cap = pixels;
+    if (pixels > s->mosaic_sprite.cap) {
+        s->mosaic_sprite.reset(); s->mosaic_count.reset();     // both go before either comes back: no more memory at the peak
+        rc = dev_ensure_all("mosaic", { { s->mosaic_sprite, pixels }, { s->mosaic_count, pixels } });
+        if (rc) return rc;
     }
     GME_HIP_TRY(hipMemsetAsync(s->mosaic_sprite, 0, pixels, ctx->stream));
     GME_HIP_TRY(hipMemsetAsync(s->mosaic_count, 0, pixels * sizeof(uint16_t), ctx->stream));
@@ -1848,7 +1740,7 @@ extern "C" int gme_seq_moving_masks(gme_seq* s, int first, int count, const doub
     if (rc) return rc;
     if (!s->masks.ptr) {
         rc = plane_alloc(ctx, &s->masks, s->N_cap, s->H, s->W);
-        if (rc) return rc;
+        if (rc) { s->masks_written.clear(); return rc; }
         s->masks_written.assign((size_t)s->N_cap, 0);
     }
     rc = mosaic_put_rows(s, count, warps, usable);
@@ -1880,10 +1772,8 @@ extern "C" int gme_seq_read_masks_range(gme_seq* s, int first, int count, uint8_
     for (int k = first; written && k < first + count; ++k) written = s->masks_written[(size_t)k] != 0;
     GME_REQUIRE(written, GME_ERR_ARG, "gme_seq_read_masks_range: the masks of frames [%d, %d) were never computed", first,
                 first + count);
-    for (int k = 0; k < count; ++k)
-        GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * s->H * s->W, s->W, s->masks.at(first + k), s->masks.pitch, s->W, s->H,
-                                     hipMemcpyDeviceToHost, s->ctx->stream));
-    return ctx_finish(s->ctx);
+    const int rc = read_planes(s->ctx, s->masks, first, count, out);
+    return rc ? rc : ctx_finish(s->ctx);
 }
 
 // ---------------------------------------------------------------------------
@@ -1910,9 +1800,9 @@ extern "C" int gme_seq_subpel(gme_seq* s, int fd, int bs, int pnorm, int levels)
     if (rc) return rc;
     const size_t n = (size_t)s->mv_pairs * s->mv_h * s->mv_w;
     s->qmv_valid = false;
-    rc = ensure(&s->qmv, &s->qmv_bytes, n * 2 * sizeof(int32_t));
+    rc = s->qmv.ensure(n * 2, "quarter-pel field");
     if (rc) return rc;
-    rc = ensure(&s->qcost, &s->qcost_bytes, n * sizeof(long long));
+    rc = s->qcost.ensure(n, "quarter-pel costs");
     if (rc) return rc;
     const Plane& p = s->level[2];
     rc = launch_subpel_refine(ctx, p.at(0), p.at(fd), p.stride, s->mv_pairs, s->H, s->W, p.pitch, bs, pnorm, levels, s->mv, s->qmv,

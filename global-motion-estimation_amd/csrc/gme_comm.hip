@@ -168,25 +168,14 @@ extern "C" int gme_comm_info(gme_ctx* ctx, int* rank_out, int* world_out)
 }
 
 // ---- per-pair summary rows of the last block-matching field, and their exchange ---------------------------------
-static int grow(double** ptr, size_t* have, size_t want)
-{
-    if (*ptr && *have >= want) return GME_OK;
-    if (*ptr) hipFree(*ptr);
-    *ptr = nullptr; *have = 0;
-    if (hipMalloc((void**)ptr, want) != hipSuccess) { gme_set_error("out of device memory (%zu bytes of summary rows)", want); return GME_ERR_NOMEM; }
-    *have = want;
-    return GME_OK;
-}
-
 static int summary_rows(gme_seq* s, int n_max)
 {
     gme_ctx* ctx = s->ctx;
     GME_REQUIRE(s->mv != nullptr && s->mv_pairs > 0, GME_ERR_STATE, "no motion field yet: call gme_seq_bbme first");
     GME_REQUIRE(n_max >= s->mv_pairs, GME_ERR_ARG, "%d rows do not hold the %d pairs of this sequence", n_max, s->mv_pairs);
-    const size_t bytes = (size_t)n_max * 6 * sizeof(double);
-    if (!s->summary || s->summary_bytes < bytes) {
+    if (s->summary.cap < (size_t)n_max * 6) {
         GME_HIP_TRY(hipStreamSynchronize(ctx->stream));        // an earlier gather may still read the old rows
-        int rc = grow(&s->summary, &s->summary_bytes, bytes);
+        int rc = s->summary.ensure((size_t)n_max * 6, "summary rows");
         if (rc) return rc;
     }
     if (n_max > s->mv_pairs)                                   // the padding other ranks receive
@@ -220,9 +209,9 @@ extern "C" int gme_seq_mv_summary_gather(gme_seq* s, int n_max, double* out)
     int rc = summary_rows(s, n_max);
     if (rc) return rc;
     const size_t block = (size_t)n_max * 6, bytes = block * sizeof(double) * (size_t)ctx->comm_world;
-    if (!s->gathered || s->gathered_bytes < bytes) {
+    if (s->gathered.cap < block * (size_t)ctx->comm_world) {
         GME_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        rc = grow(&s->gathered, &s->gathered_bytes, bytes);
+        rc = s->gathered.ensure(block * (size_t)ctx->comm_world, "summary rows");
         if (rc) return rc;
     }
     GME_RCCL_TRY(g_rccl.allgather(s->summary, s->gathered, block, kFloat64, ctx->comm, ctx->stream));

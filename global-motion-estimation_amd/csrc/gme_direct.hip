@@ -431,17 +431,9 @@ static int direct_ws(gme_seq* s, int pairs, DirectWs* ws)
     const size_t b_st = P * sizeof(DirectState), b_hist = P * HIST_BINS * sizeof(uint32_t), b_slab = P * tiles * SLAB * sizeof(double);
     const size_t b_io = P * (8 + 8 + 48) * sizeof(double) + P * sizeof(int32_t);
     const size_t want = b_st + b_hist + b_slab + b_io;
-    if (s->direct_bytes < want) {
-        if (s->direct) hipFree(s->direct);
-        s->direct = nullptr;
-        s->direct_bytes = 0;
-        if (hipMalloc(&s->direct, want) != hipSuccess) {
-            gme_set_error("out of device memory (direct refinement workspace)");
-            return GME_ERR_NOMEM;
-        }
-        s->direct_bytes = want;
-    }
-    char* b = (char*)s->direct;
+    const int rc = s->direct.ensure(want, "direct refinement workspace");
+    if (rc) return rc;
+    char* b = (char*)s->direct.get();
     ws->st = (DirectState*)b; b += b_st;
     ws->hist = (uint32_t*)b; b += b_hist;
     ws->slab = (double*)b; b += b_slab;

@@ -8,8 +8,7 @@
 #include <vector>
 
 #include "../../include/gme_hip.h"
-
-void gme_set_error(const char* fmt, ...);
+#include "dev_buf.h"
 
 #define GME_HIP_TRY(expr)                                                                  \
     do {                                                                                   \
@@ -29,7 +28,7 @@ void gme_set_error(const char* fmt, ...);
         }                                  \
     } while (0)
 
-// An image plane (or a stack of equally sized planes) in HBM.
+// An image plane (or a stack of equally sized planes) in HBM: a view that is copied freely and owns nothing.
 // pitch is a multiple of 64 bytes; bytes between W and pitch are zero.
 struct Plane {
     uint8_t* ptr = nullptr;
@@ -38,6 +37,11 @@ struct Plane {
     int count = 0;
     size_t bytes() const { return (size_t)stride * (size_t)count; }
     uint8_t* at(int i) const { return ptr + (int64_t)i * stride; }
+};
+
+// A plane stack with its memory (plane_alloc).  Wherever a Plane is wanted it is the view of the whole stack.
+struct PlaneBuf : Plane {
+    DevBuf<uint8_t> mem;
 };
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -49,18 +53,15 @@ struct gme_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipDeviceProp_t prop;
     // growable device scratch for the single-pair convenience calls
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
-    int* status = nullptr;        // device words (GME_STATUS_WORDS): [0] set by kernels whose safety guards trip;
+    DevBuf<uint8_t> scratch;
+    DevBuf<int> status;           // device words (GME_STATUS_WORDS): [0] set by kernels whose safety guards trip;
                                   // [GME_STATUS_TILECTR ..] per-XCD tile counters of the persistent search kernels,
                                   // [GME_STATUS_STATS ..] per-XCD statistics of the last block-matching call (16 words apart)
     void* comm = nullptr;         // RCCL communicator (gme_comm.hip), one per context = per rank
     int comm_rank = 0, comm_world = 0;
     hipStream_t copy_stream = nullptr, back_stream = nullptr;   // gme_seq_bbme_streamed: uploads / read-backs beside the kernels
-    uint8_t* stage = nullptr;        // device staging of tight host frames (gme_seq_bbme_streamed), repacked into the planes
-    size_t stage_bytes = 0;
-    uint32_t* redo_list = nullptr;   // tiles the elimination kernels hand to the brute-force redo kernel (grown on demand)
-    size_t redo_cap = 0;             // entries
+    DevBuf<uint8_t> stage;        // device staging of tight host frames (gme_seq_bbme_streamed), repacked into the planes
+    DevBuf<uint32_t> redo_list;   // tiles the elimination kernels hand to the brute-force redo kernel (grown on demand)
     char plan[192] = "";          // kernel / tile shape / schedule the last block-matching call chose (gme_last_bbme_info)
     long long plan_patches = 0;   // candidate patches that call's bound was applied to (0: a kernel without elimination)
 };
@@ -71,19 +72,19 @@ int ctx_redo_list(gme_ctx* ctx, size_t entries, uint32_t** out);
 void plan_note(gme_ctx* ctx, long long patches, const char* fmt, ...);
 
 int ctx_scratch(gme_ctx* ctx, size_t bytes, void** out);
-int plane_alloc(gme_ctx* ctx, Plane* p, int count, int H, int W);
-void plane_free(Plane* p);
+int plane_alloc(gme_ctx* ctx, PlaneBuf* p, int count, int H, int W);      // a failure leaves *p empty (no memory, a null view)
 
 struct FitLevelBuf {
     int h = 0, w = 0;             // motion-field shape at this level
-    int32_t* gt = nullptr;        // [P][h][w][2]
-    int16_t* model = nullptr;     // [P][h][w][2]
-    uint8_t* mask = nullptr;      // [P][h][w]
-    int32_t* diff = nullptr;      // [P][h][w] L1 distance gt vs model
-    void* list = nullptr;         // [P][h][w] int4 inlier list, only for fields too large for LDS
-    int32_t* thr = nullptr;       // [P]
-    double* sums = nullptr;       // [P][15]
-    double* sums2 = nullptr;      // [P][27] order-2 sums (gme_seq_gme_fit2)
+    int32_t* gt = nullptr;        // [P][h][w][2]: gt_own, or a field the fit only reads (gme_seq::fit_mv borrows gme_seq::mv)
+    DevBuf<int32_t> gt_own;
+    DevBuf<int16_t> model;        // [P][h][w][2]
+    DevBuf<uint8_t> mask;         // [P][h][w]
+    DevBuf<int32_t> diff;         // [P][h][w] L1 distance gt vs model
+    DevBuf<int4> list;            // [P][h][w] inlier list, only for fields too large for LDS
+    DevBuf<int32_t> thr;          // [P]
+    DevBuf<double> sums;          // [P][15]
+    DevBuf<double> sums2;         // [P][27] order-2 sums (gme_seq_gme_fit2)
 };
 // the fit kernels keep a level's inlier list in LDS up to this size (two workgroups per CU), in `list` above it
 constexpr size_t FIT_LIST_LDS_BYTES = 40 * 1024;
@@ -92,15 +93,13 @@ struct gme_seq {
     gme_ctx* ctx = nullptr;
     int N = 0, H = 0, W = 0;      // N: frames in use (gme_seq_set_frames), <= N_cap
     int N_cap = 0;                // frames the sequence was created for: every buffer is sized for it
-    Plane level[3];               // level[2] = full resolution, [1], [0] = pyramid
+    PlaneBuf level[3];            // level[2] = full resolution, [1], [0] = pyramid
     bool pyramids_valid = false;
     // generic BBME result
-    int32_t* mv = nullptr;        // [P][h][w][2]
-    size_t mv_bytes = 0;
+    DevBuf<int32_t> mv;           // [P][h][w][2]
     int mv_h = 0, mv_w = 0, mv_pairs = 0;
     int mv_fd = 0, mv_bs = 0;     // frame distance and block size of the search that wrote `mv`
-    uint32_t* sqbox[3] = { nullptr, nullptr, nullptr };   // per level: 16x16 box sums of squares per frame (MSE fast path)
-    size_t sqbox_bytes[3] = { 0, 0, 0 };
+    DevBuf<uint32_t> sqbox[3];    // per level: 16x16 box sums of squares per frame (MSE fast path)
     bool sqbox_valid[3] = { false, false, false };
     int sqbox_kind[3] = { 0, 0, 0 };
     // GME state
@@ -111,53 +110,46 @@ struct gme_seq {
     hipEvent_t ready = nullptr;   // recorded behind the last result copy of such a call; gme_seq_wait waits on it
     hipEvent_t upload_gate = nullptr, uploaded = nullptr;   // split-phase gme_seq_upload: ties the shared upload stream to this context's stream
     FitLevelBuf fit[3];           // fit[0].gt = dense field
-    FitLevelBuf fit_mv;           // stage buffers for fitting `mv` directly (gt not owned)
+    FitLevelBuf fit_mv;           // stage buffers for fitting `mv` directly: its gt is mv, gt_own stays empty
     int fit_mv_pairs = 0;
-    double* mv_params = nullptr;  // [P][6] parameters for fit_mv ([P][12] after gme_seq_gme_fit2)
-    size_t mv_params_bytes = 0;
-    float* params0 = nullptr;     // [P][6]
-    double* params_in = nullptr;  // [P][6], or [P][12] for gme_seq_gme_fit2 (room for 12 per pair)
-    int32_t* solve_flags = nullptr;      // [P] gme_seq_gme_device_solve: pairs whose device solve must be redone on the host
-    size_t gme_alloc_pairs = 0;
+    DevBuf<double> mv_params;     // [P][6] parameters for fit_mv ([P][12] after gme_seq_gme_fit2)
+    // sized together with fit[] by gme_begin_common: params0 holds 6 floats for each pair they were allocated for
+    DevBuf<float> params0;        // [P][6]
+    DevBuf<double> params_in;     // [P][6], or [P][12] for gme_seq_gme_fit2 (room for 12 per pair)
+    DevBuf<int32_t> solve_flags;  // [P] gme_seq_gme_device_solve: pairs whose device solve must be redone on the host
     // compensation
-    Plane comp;                   // [P] compensated frames
-    double* comp_params = nullptr;       // [P][6], or [P][12] for gme_seq_compensate2 (room for 12 per pair)
-    int32_t* comp_mf = nullptr;          // [P][h][w][2] order-2 field gme_seq_compensate2 compensates with
-    size_t comp_mf_bytes = 0;
-    unsigned long long* sse = nullptr;   // [P]
+    PlaneBuf comp;                // [P] compensated frames
+    DevBuf<double> comp_params;   // [P][6], or [P][12] for gme_seq_compensate2 (room for 12 per pair)
+    DevBuf<int32_t> comp_mf;      // [P][h][w][2] order-2 field gme_seq_compensate2 compensates with
+    DevBuf<unsigned long long> sse;      // [P]
     // per-pair summary rows of `mv` (gme_seq_mv_summary) and their all-gather over the ranks (gme_seq_mv_summary_gather)
-    double* summary = nullptr;           // [n_max][6], zero-padded behind mv_pairs rows
-    size_t summary_bytes = 0;
-    double* gathered = nullptr;          // [world][n_max][6]
-    size_t gathered_bytes = 0;
-    void* direct = nullptr;              // gme_direct.hip: per-pair refinement state, histograms, slabs and parameters
-    size_t direct_bytes = 0;
+    DevBuf<double> summary;       // [n_max][6], zero-padded behind mv_pairs rows
+    DevBuf<double> gathered;      // [world][n_max][6]
+    DevBuf<uint8_t> direct;       // gme_direct.hip: per-pair refinement state, histograms, slabs and parameters
     // stabilization (gme_stab.hip): the warped frames (N_cap, allocated by the first gme_seq_warp_frames), which of them a
     // warp has written, and N_cap rows of parameters and counts
-    Plane warped;
+    PlaneBuf warped;
     std::vector<uint8_t> warped_written;
-    double* warp_params = nullptr;       // [N_cap][8]
-    unsigned long long* warp_counts = nullptr;   // [N_cap] valid samples, or squared errors of gme_seq_frame_sse
+    DevBuf<double> warp_params;          // [N_cap][8]
+    DevBuf<unsigned long long> warp_counts;      // [N_cap] valid samples, or squared errors of gme_seq_frame_sse
     // background mosaic (gme_mosaic.hip): sprite and sample counts [Hc][pitch] of the last gme_seq_mosaic, the masks of
     // gme_seq_moving_masks (N_cap planes, allocated by its first call) with which of them were written, and N_cap rows of
     // parameters, usable flags and known / moving counts
-    uint8_t* mosaic_sprite = nullptr;
-    uint16_t* mosaic_count = nullptr;
-    size_t mosaic_cap = 0;               // pixels the two were allocated for
+    DevBuf<uint8_t> mosaic_sprite;       // both hold the same number of pixels
+    DevBuf<uint16_t> mosaic_count;
     int mosaic_Hc = 0, mosaic_Wc = 0, mosaic_pitch = 0;
     bool mosaic_valid = false;
-    Plane masks;
+    PlaneBuf masks;
     std::vector<uint8_t> masks_written;
-    double* mosaic_params = nullptr;     // [N_cap][8]
-    uint8_t* mosaic_usable = nullptr;    // [N_cap]
-    unsigned long long* mosaic_counts = nullptr;   // [2][N_cap] known, moving
+    DevBuf<double> mosaic_params;        // [N_cap][8]
+    DevBuf<uint8_t> mosaic_usable;       // [N_cap]
+    DevBuf<unsigned long long> mosaic_counts;    // [2][N_cap] known, moving
     // quarter-pel refinement (bbme_subpel.hip): the refined field and its costs of the last gme_seq_subpel, allocated by
     // its first call; valid until the next block-matching call replaces `mv`
-    int32_t* qmv = nullptr;              // [P][h][w][2], quarter units
-    long long* qcost = nullptr;          // [P][h][w]
-    size_t qmv_bytes = 0, qcost_bytes = 0;
+    DevBuf<int32_t> qmv;                 // [P][h][w][2], quarter units
+    DevBuf<long long> qcost;             // [P][h][w]
     bool qmv_valid = false;
-    uint8_t* synth_canvas = nullptr;
+    DevBuf<uint8_t> synth_canvas;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
 };

@@ -669,3 +669,25 @@ def test_cli_lists_commands(capsys):
     gme_cli.main(["info"])
     out = capsys.readouterr().out
     assert "three-step" in out and "similarity" in out and "device:" in out
+
+
+def test_device_memory_has_one_owner():
+    """Every hipMalloc / hipFree of the library is in dev_buf.h, but for the staging block of the process-wide upload lane
+    (gme_api.hip says why); the shared structs keep no free routine and no byte count beside an owned pointer."""
+    csrc = os.path.join(REPO, "global-motion-estimation_amd", "csrc")
+    sites = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            for n, line in enumerate(open(os.path.join(csrc, f)).read().splitlines(), 1):
+                if re.search(r"\bhip(Malloc|Free)\s*\(", line):
+                    sites.setdefault(f, []).append((n, line))
+    assert set(sites) == {"dev_buf.h", "gme_api.hip"}, sites
+    assert len(sites["dev_buf.h"]) == 2, sites["dev_buf.h"]                 # one that allocates, one that frees
+    assert all(re.search(r"\bu\.stage\b", line) for _, line in sites["gme_api.hip"]), sites["gme_api.hip"]
+    assert len(sites["gme_api.hip"]) == 2, sites["gme_api.hip"]
+    api = open(os.path.join(csrc, "gme_api.hip")).read()
+    uploader = api[api.index("struct Uploader"):api.index("Uploader g_uploader")]
+    assert "never freed" in uploader and "runtime" in uploader             # the exception is explained where it is declared
+    internal = open(os.path.join(csrc, "gme_internal.h")).read()
+    assert "plane_free" not in internal
+    assert re.findall(r"\b[a-z0-9_]+_bytes\b", internal) == []
