@@ -32,40 +32,71 @@ namespace {
 using namespace sea;
 
 // B: lower bounds of the 4R x R candidates of one lane (candidate rows prow*R + i, columns
-// q*4R + 4k + e).  GUARD = false is the branch-free body for blocks whose whole window is inside
-// the frame (84 % of them at 720x480, sw = 16); GUARD = true skips candidates outside [lo, hi].
-template <int R, bool GUARD>
+// q*4R + 4k + e).  GUARD_NONE is the body for blocks whose whole window is inside the frame (84 % of
+// them at 720x480, sw = 16).  The others decide validity once per lane, before the row loop, and let it ride
+// on an operand the body has anyway, so that every candidate keeps the unguarded instructions:
+//   GUARD_ROWS (all columns valid: blocks at the top and bottom edge)  the inner v_sad_u16 of a candidate row
+//       outside [lo_r, hi_r] starts from PENALTY instead of 0;
+//   GUARD_ALL  (frame corners, left and right edge, partial size classes with their padding candidates)  the start
+//       value also takes PENALTY for a column above hi_c: one v_cndmask_b32 per candidate on a lane mask formed
+//       once per column; below lo_c whole patches go (lo_c is a multiple of 4), after the loop.
+// A penalised bound lies above 65280, the largest real one (and SAD), and below 2^18, so its key fits 32 bits
+// and stays above every real key.  The table rows and quads such a candidate reads exist (the table is sized by
+// R, not by the frame); what they hold does not matter.  A patch whose smallest key is a penalised one has no
+// valid candidate: 0xFFFFFFFF, as if no key had been formed.
+constexpr int GUARD_NONE = 0, GUARD_ROWS = 1, GUARD_ALL = 2;
+constexpr uint32_t PENALTY = 1u << 17;
+constexpr uint32_t FIRST_INVALID_KEY = 65536u << 13;     // above every real key, not above any penalised one
+template <int R, int GUARD>
 __device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int prow, int q, uint32_t a01, uint32_t a23,
                                              int lo_r, int hi_r, int lo_c, int hi_c, uint32_t (&pkey)[R])
 {
+    // R >= 4 keeps the earlier form for every edge block (GUARD_ALL there; GUARD_ROWS is not used), which skips invalid
+    // rows and candidates by compares of their own: in the <5, 7, 38> instance, already at its 80 VGPRs, the column
+    // masks spilled three VGPRs and GUARD_ROWS beside the earlier form one
+    constexpr bool SKIP = GUARD == GUARD_ALL && R >= 4;
 #pragma unroll
     for (int k = 0; k < R; ++k) pkey[k] = 0xFFFFFFFFu;
+    uint32_t seed[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const int ri = prow * R + i;
+        seed[i] = (GUARD == GUARD_NONE || SKIP || (ri >= lo_r && ri <= hi_r)) ? 0u : PENALTY;
+    }
+    // the lane's valid columns j = 4k + e are nlo .. nhi (none: nhi < nlo).  nlo is a multiple of 4 (sw is, block
+    // columns are multiples of 16): on the low side whole patches go, after the loop.
+    const int nlo = lo_c - q * 4 * R, nhi = hi_c - q * 4 * R;
     const uint64_t* top = sp0;
     const uint64_t* bot = sp0 + 8 * XQ;
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         const int ri = prow * R + i;
-        if (!GUARD || (ri >= lo_r && ri <= hi_r)) {
+        if (!SKIP || (ri >= lo_r && ri <= hi_r)) {
             uint64_t t[R + 2], b[R + 2];                   // quads k and k + 2 for k < R: R + 2 distinct ones
 #pragma unroll
             for (int k = 0; k < R + 2; ++k) { t[k] = top[k]; b[k] = bot[k]; }
 #pragma unroll
             for (int k = 0; k < R; ++k) {
-                const int ci0 = q * 4 * R + 4 * k;
-                if (GUARD && (ci0 > hi_c || ci0 + 3 < lo_c)) continue;
+                if (SKIP && (4 * k > nhi || 4 * k + 3 < nlo)) continue;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    if (GUARD && (ci0 + e < lo_c || ci0 + e > hi_c)) continue;
+                    if (SKIP && (4 * k + e < nlo || 4 * k + e > nhi)) continue;
                     const uint32_t sel = (e & 1) ? 0x07060302u : 0x05040100u;
                     const uint32_t tp = __builtin_amdgcn_perm((uint32_t)(t[k + 2] >> (32 * (e >> 1))), (uint32_t)(t[k] >> (32 * (e >> 1))), sel);
                     const uint32_t bt = __builtin_amdgcn_perm((uint32_t)(b[k + 2] >> (32 * (e >> 1))), (uint32_t)(b[k] >> (32 * (e >> 1))), sel);
-                    const uint32_t lb = __builtin_amdgcn_sad_u16(tp, a01, __builtin_amdgcn_sad_u16(bt, a23, 0u));
+                    const uint32_t start = (GUARD != GUARD_ALL || SKIP || 4 * k + e <= nhi) ? seed[i] : PENALTY;
+                    const uint32_t lb = __builtin_amdgcn_sad_u16(tp, a01, __builtin_amdgcn_sad_u16(bt, a23, start));
                     pkey[k] = min(pkey[k], (lb << 13) + (uint32_t)((4 * k + e) * R + i));
                 }
             }
         }
         top += XQ;
         bot += XQ;
+    }
+    if constexpr (GUARD != GUARD_NONE && !SKIP) {
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            if (pkey[k] >= FIRST_INVALID_KEY || (GUARD == GUARD_ALL && 4 * k < nlo)) pkey[k] = 0xFFFFFFFFu;
     }
 }
 
@@ -112,6 +143,7 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaDev& d, const uint3
         hi += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, 0xB1, 0xF, 0xF, false);
         lo += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo, 0x4E, 0xF, 0xF, false);            // quad_perm [2,3,0,1]
         hi += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, 0x4E, 0xF, 0xF, false);
+        asm volatile("" : "+v"(lo), "+v"(hi));     // pinned here: sunk under `active` the adds leave their DPP moves behind
         acc[i] = ((uint64_t)hi << 32) | lo;
     }
     uint32_t key = 0xFFFFFFFFu;
@@ -143,9 +175,9 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaDev& d, const uint3
                 key = min(key, (sad << 13) | (uint32_t)(ci * NC + ri));
             }
         }
-        // quad minimum (a disabled source lane would hand back `key` itself; quads are uniform in `active`)
-        key = min(key, (uint32_t)__builtin_amdgcn_update_dpp((int)key, (int)key, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-        key = min(key, (uint32_t)__builtin_amdgcn_update_dpp((int)key, (int)key, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+        // quad minimum (a disabled source lane would hand back the minimum's identity; quads are uniform in `active`)
+        key = min(key, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)key, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+        key = min(key, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)key, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
     }
     return key;
 }
@@ -153,7 +185,7 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaDev& d, const uint3
 // Phases A' .. F of one tile.  On entry the window and the anchors are staged, *count == 0 and the
 // workgroup has passed a barrier; there is no barrier after F.
 // Returns true (workgroup-uniform) when the tile was handed to the redo kernel instead (SeaDev::redo_list).
-template <int R>
+template <int R, bool FIXED>
 __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                             uint32_t mine, uint32_t a01, uint32_t a23, int tid, int tile_id)
 {
@@ -177,7 +209,7 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
     const int prow = lane >> 2, q = lane & 3;
 
     // ---- A': 8x8 box sums of the window (bbme_sea_common.h) ------------------------------------
-    box_sums8<R>(d, win, s8, tid);
+    box_sums8<R, FIXED>(d, win, s8, tid);
     __syncthreads();
 
     // ---- B: lower bounds of the wave's own block --------------------------------------------
@@ -190,10 +222,13 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
         // consistent index will do here: the bound only has to name one good candidate)
         uint32_t pkey[R];
         const uint64_t* sp0 = s8 + (16 * wb.wr + prow * R) * XQ + wb.wc * 4 + q * R;
-        if (rows_inside && lo_c == 0 && hi_c == NC - 1)                                // wave-uniform
-            lower_bounds<R, false>(sp0, XQ, prow, q, a01, a23, lo_r, hi_r, lo_c, hi_c, pkey);
+        const bool cols_inside = NC == 16 * R && lo_c == 0 && hi_c == NC - 1;           // and no padding candidates
+        if (rows_inside && cols_inside)                                                // wave-uniform, all three
+            lower_bounds<R, GUARD_NONE>(sp0, XQ, prow, q, a01, a23, lo_r, hi_r, lo_c, hi_c, pkey);
+        else if (R <= 3 && cols_inside)                                                // R >= 4: see lower_bounds
+            lower_bounds<R, GUARD_ROWS>(sp0, XQ, prow, q, a01, a23, lo_r, hi_r, lo_c, hi_c, pkey);
         else
-            lower_bounds<R, true>(sp0, XQ, prow, q, a01, a23, lo_r, hi_r, lo_c, hi_c, pkey);
+            lower_bounds<R, GUARD_ALL>(sp0, XQ, prow, q, a01, a23, lo_r, hi_r, lo_c, hi_c, pkey);
         // pkd[k] = (smallest bound of patch k) << 13 | scan index of the patch's FIRST candidate: no candidate of the
         // patch can have a smaller key (sad << 13 | scan index).  A patch without valid candidates keeps 0xFFFFE000 | index,
         // above every real key (sad <= 65280 < 2^16).
@@ -364,6 +399,7 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
                 hi += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, 0xB1, 0xF, 0xF, false);
                 lo += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo, 0x4E, 0xF, 0xF, false);            // quad_perm [2,3,0,1]
                 hi += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, 0x4E, 0xF, 0xF, false);
+                asm volatile("" : "+v"(lo), "+v"(hi));     // pinned here: sunk under `active` the adds leave their DPP moves behind
                 acc[i] = ((uint64_t)hi << 32) | lo;
             }
             if (active) {
@@ -395,9 +431,9 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
                         key = min(key, (sad << 13) | (uint32_t)(ci * NC + ri));
                     }
                 }
-                // quad minimum (a disabled source lane would hand back `key` itself; quads are uniform in `active`)
-                key = min(key, (uint32_t)__builtin_amdgcn_update_dpp((int)key, (int)key, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-                key = min(key, (uint32_t)__builtin_amdgcn_update_dpp((int)key, (int)key, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+                // quad minimum (a disabled source lane would hand back the minimum's identity; quads are uniform in `active`)
+                key = min(key, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)key, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+                key = min(key, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)key, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
                 if (sub == 0 && key != 0xFFFFFFFFu) atomicMin(&best[2 * w2], key);
             }
             __syncthreads();
@@ -487,7 +523,8 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
 }
 
 // What the shared tile drivers (bbme_sea_common.h: one_tile, persistent_tiles) need from this kernel.
-template <int R>
+// FIXED: the geometry-fixed instances (fix_geometry), whose strides are compile-time constants
+template <int R, bool FIXED = false>
 struct MaeTile {
     struct Pre { uint32_t a01, a23; };
     static __device__ __forceinline__ Pre prep(const SeaDev&, uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
@@ -502,7 +539,7 @@ struct MaeTile {
     static __device__ __forceinline__ bool phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                   uint32_t mine, const Pre& p, int tid, int tile_id)
     {
-        return tile_phases<R>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, tid, tile_id);
+        return tile_phases<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, tid, tile_id);
     }
     static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.best + 2 * wave + 1; }
 };
@@ -521,7 +558,7 @@ __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p(SeaDev d)
     fix_geometry<R, GEO>(d);
     const Layout L = layout_of(d, R);
     if ((threadIdx.x & 63) == 0) lds[L.best + 2 * (threadIdx.x >> 6) + 1] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);   // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MaeTile<R>>(d, lds, L);
+    persistent_tiles<NV, MaeTile<R, GEO != 0>>(d, lds, L);
 }
 
 // What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.

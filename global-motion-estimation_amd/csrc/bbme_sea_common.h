@@ -169,8 +169,13 @@ __device__ __forceinline__ void stage_window(const SeaDev& d, uint32_t* win, con
 // x 1020 < 2^16).  An output row takes V = C(y+7) - C(y-1) from a ring of 8 cumulative sums in registers -- the
 // vertical 8-row sum of the lane's own 4-byte columns -- and adds the V of quad sq + 1, which the next lane has just
 // formed, with a DPP wave_shl:1: S8(y, x) = V(x) + V(x + 4).  All of that is 32-bit subtracts and adds on the packed
-// pairs (component-wise C grows and V <= 8160, so nothing borrows from or carries into the upper half); the adds take
-// the DPP operand directly.  s8[y][sq] = packed S8(y, 4sq .. 4sq+3).
+// pairs (component-wise C grows and V <= 8160, so nothing borrows from or carries into the upper half).  Each add is one
+// v_add_u32_dpp (wave_shl:1, bound_ctrl) executed by every lane: the sum is pinned in front of the store's predicate
+// (an empty asm), because an add sunk under `if (stores)` leaves a v_mov_b32 0 and a v_mov_b32_dpp behind.  A lane
+// without a source adds 0; its value is never stored or read.  s8[y][sq] = packed S8(y, 4sq .. 4sq+3).
+// In a geometry-fixed instance (FIXED) both strides are constants: the window reads are ds_read2_b32 with instruction
+// offsets from one base register per 254 / pitch + 1 rows (the second offset ends at 255 dwords), the table stores
+// ds_write_b64 with byte offsets from a single one.  Run-time geometry keeps running offsets.
 // Each lane used to compute both 4-byte halves of its 8-byte sums itself (two QSADs, 16 window bytes per row) and to
 // slide the vertical sum by a packed subtract and add per row: half of the QSADs and window reads repeated the
 // neighbour's, and the warm-up rows paid for sums nobody stored.
@@ -186,7 +191,7 @@ __device__ __forceinline__ void stage_window(const SeaDev& d, uint32_t* win, con
 // the store is predicated.  The trip count is wave-uniform.
 // CH = s8_rows / 8 is a template parameter so that the ring indices and the warm-up are resolved
 // at compile time (a run-time row count cost 5 % of the whole search in guards).
-template <int CH>
+template <int CH, bool FIXED>
 __device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid, int need)
 {
     static_assert((CH + 7) * 1020 < 65536, "cumulative 4-byte sums must fit 16 bits");
@@ -198,26 +203,46 @@ __device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* wi
     const int SEG = wide ? 1 : div_small(64, magic_sl);            // whole segments per wave
     const int units = wide ? 8 * div_small(XQ + 62, div_magic(63)) : 8;       // pieces (unit = piece * 8 + chunk) or chunks
     const int ls = wide ? 0 : div_small(lane, magic_sl);           // the lane's segment inside its wave
+    // FIXED: rows a ds_read2_b32 reaches from one base register (its second offset, in dwords, ends at 255)
+    const int RB = FIXED ? 254 / d.pitch_dw + 1 : 1;
     for (int u = wave * SEG; u < units; u += d.nb * SEG) {
         const int ch = wide ? (u & 7) : u + ls;
         const int sq = wide ? (u >> 3) * 63 + lane : lane - ls * SL;
         const bool active = wide ? sq < SL : (ls < SEG && ch < 8);
         const bool stores = active && sq < XQ && (!wide || lane < 63);
-        int pi = active ? (ch * CH) * d.pitch_dw + sq : 0, oi = (ch * CH) * XQ + sq;     // running offsets: adds, no r * pitch multiplies
+        // run-time geometry: running offsets (adds, no r * pitch multiplies), kept in registers by the empty asm.
+        // FIXED: both strides are constants, so the reads go by instruction offsets from one base per RB rows and
+        // the stores by instruction offsets from a single one.
+        int pi = active ? (ch * CH) * d.pitch_dw + sq : 0, oi = (ch * CH) * XQ + sq;
         uint64_t ring[8], acc = 0;
 #pragma unroll
         for (int r = 0; r < CH + 7; ++r) {
-            acc = __builtin_amdgcn_qsad_pk_u16_u8(*(const u64_a4*)(win + pi), 0u, acc);
-            pi += d.pitch_dw;
-            asm volatile("" : "+v"(pi));
+            if constexpr (FIXED) {
+                if (r > 0 && r % RB == 0) {
+                    pi += RB * d.pitch_dw;
+                    asm volatile("" : "+v"(pi));                   // a base register, not an offset too large for the encoding
+                }
+                acc = __builtin_amdgcn_qsad_pk_u16_u8(*(const u64_a4*)(win + pi + (r % RB) * d.pitch_dw), 0u, acc);
+            } else {
+                acc = __builtin_amdgcn_qsad_pk_u16_u8(*(const u64_a4*)(win + pi), 0u, acc);
+                pi += d.pitch_dw;
+                asm volatile("" : "+v"(pi));
+            }
             if (r >= 7) {
                 uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
                 if (r >= 8) { lo -= (uint32_t)ring[r & 7]; hi -= (uint32_t)(ring[r & 7] >> 32); }
                 lo += SEA_DPP(lo, 0x130);                          // wave_shl:1 -- lane + 1's
                 hi += SEA_DPP(hi, 0x130);
-                if (stores) s8[oi] = ((uint64_t)hi << 32) | lo;
-                oi += XQ;
-                asm volatile("" : "+v"(oi));
+                // the sums are pinned here, for every lane: left to itself the compiler sinks the adds under the store's
+                // predicate, where they no longer fuse with the DPP moves (one v_add_u32_dpp each)
+                asm volatile("" : "+v"(lo), "+v"(hi));
+                if constexpr (FIXED) {
+                    if (stores) s8[oi + (r - 7) * XQ] = ((uint64_t)hi << 32) | lo;
+                } else {
+                    if (stores) s8[oi] = ((uint64_t)hi << 32) | lo;
+                    oi += XQ;
+                    asm volatile("" : "+v"(oi));
+                }
             }
             ring[r & 7] = acc;
         }
@@ -227,13 +252,14 @@ __device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* wi
 // s8_rows = 16R + 8 + 16 (tr - 1) is a multiple of 8 for every tile height: 8 chunks of 2R + 2 tr - 1 rows
 // (four chunks of twice the rows for two-row tiles were measured too -- 7 warm-up rows per chunk are 44 % of a 9-row
 // chunk's work and 28 % of an 18-row one's, but half as many lanes share it; A/B in DESIGN.md)
-template <int R>
+// FIXED: the caller is a geometry-fixed instance (fix_geometry): d.pitch_dw and d.xq are compile-time constants there
+template <int R, bool FIXED>
 __device__ __forceinline__ void box_sums8(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid)
 {
     const int need = 4 * R + 4 * (d.tc - 1) + 2;           // quads per row the bound phase reads (shape_of); XQ >= need
-    if (d.tr == 1) box_sums8_ch<2 * R + 1>(d, win, s8, tid, need);
-    else if (d.tr == 2) box_sums8_ch<2 * R + 3>(d, win, s8, tid, need);
-    else box_sums8_ch<2 * R + 7>(d, win, s8, tid, need);
+    if (d.tr == 1) box_sums8_ch<2 * R + 1, FIXED>(d, win, s8, tid, need);
+    else if (d.tr == 2) box_sums8_ch<2 * R + 3, FIXED>(d, win, s8, tid, need);
+    else box_sums8_ch<2 * R + 7, FIXED>(d, win, s8, tid, need);
 }
 
 // quadrant sums of the anchor held one dword per lane (lane = row * 4 + dword): the quad swap pairs

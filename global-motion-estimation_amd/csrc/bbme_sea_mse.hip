@@ -142,7 +142,7 @@ __device__ __forceinline__ uint32_t bounds2_patch(const uint64_t* sp, int XQ, in
 }
 
 // Phases A' .. F of one tile (entry conditions as tile_phases() of bbme_sea.hip, plus a2s[] filled).
-template <int R>
+template <int R, bool FIXED>
 __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                 uint32_t mine, uint32_t a01, uint32_t a23, uint32_t mine2, int tid, int tile_id)
 {
@@ -165,7 +165,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
     const int prow = lane >> 2, q = lane & 3;
 
     // ---- A'
-    box_sums8<R>(d, win, s8, tid);
+    box_sums8<R, FIXED>(d, win, s8, tid);
     __syncthreads();
 
     // ---- B
@@ -409,7 +409,8 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
 }
 
 // What the shared tile drivers (bbme_sea_common.h: one_tile, persistent_tiles) need from this kernel.
-template <int R>
+// FIXED: the geometry-fixed instances (fix_geometry), whose strides are compile-time constants
+template <int R, bool FIXED = false>
 struct MseTile {
     struct Pre { uint32_t a01, a23, mine2; };
     static __device__ __forceinline__ Pre prep(const SeaDev&, uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
@@ -430,7 +431,7 @@ struct MseTile {
     static __device__ __forceinline__ bool phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                   uint32_t mine, const Pre& p, int tid, int tile_id)
     {
-        return tile_phases_mse<R>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id);
+        return tile_phases_mse<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id);
     }
     static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.prev + wave; }
 };
@@ -449,7 +450,7 @@ __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p_mse(SeaDe
     fix_geometry<R, GEO>(d);
     const Layout L = layout_of(d, R);
     if ((threadIdx.x & 63) == 0) lds[L.prev + (threadIdx.x >> 6)] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);    // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MseTile<R>>(d, lds, L);
+    persistent_tiles<NV, MseTile<R, GEO != 0>>(d, lds, L);
 }
 
 // What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.
