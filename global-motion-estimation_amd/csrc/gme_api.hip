@@ -155,6 +155,18 @@ extern "C" int gme_sync(gme_ctx* ctx)
     return ctx_finish(ctx);
 }
 
+// statistics of the last block-matching call, summed over the XCDs: surviving patches, tiles redone, patches listed
+static int read_bbme_stats(gme_ctx* ctx, int64_t (&sum)[3])
+{
+    uint32_t st[8 * 16];
+    GME_HIP_TRY(hipMemcpyAsync(st, ctx->status + GME_STATUS_STATS, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    sum[0] = sum[1] = sum[2] = 0;
+    for (int x = 0; x < 8; ++x)
+        for (int k = 0; k < 3; ++k) sum[k] += st[16 * x + k];
+    return GME_OK;
+}
+
 extern "C" int gme_last_bbme_info(gme_ctx* ctx, char* plan, int plan_len, int64_t* patches, int64_t* surviving,
                                   int64_t* redo_tiles)
 {
@@ -162,13 +174,11 @@ extern "C" int gme_last_bbme_info(gme_ctx* ctx, char* plan, int plan_len, int64_
     if (plan && plan_len > 0) snprintf(plan, plan_len, "%s", ctx->plan);
     if (patches) *patches = ctx->plan_patches;
     if (surviving || redo_tiles) {
-        uint32_t st[8 * 16];
-        GME_HIP_TRY(hipMemcpyAsync(st, ctx->status + GME_STATUS_STATS, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-        GME_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        int64_t n = 0, r = 0;
-        for (int x = 0; x < 8; ++x) { n += st[16 * x]; r += st[16 * x + 1]; }
-        if (surviving) *surviving = n;
-        if (redo_tiles) *redo_tiles = r;
+        int64_t sum[3];
+        const int rc = read_bbme_stats(ctx, sum);
+        if (rc) return rc;
+        if (surviving) *surviving = sum[0];
+        if (redo_tiles) *redo_tiles = sum[1];
     }
     return GME_OK;
 }
@@ -176,13 +186,10 @@ extern "C" int gme_last_bbme_info(gme_ctx* ctx, char* plan, int plan_len, int64_
 extern "C" int gme_last_bbme_listed(gme_ctx* ctx, int64_t* listed)
 {
     GME_ENTER(ctx);
-    uint32_t st[8 * 16];
-    GME_HIP_TRY(hipMemcpyAsync(st, ctx->status + GME_STATUS_STATS, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-    GME_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    int64_t n = 0;
-    for (int x = 0; x < 8; ++x) n += st[16 * x + 2];
-    if (listed) *listed = n;
-    return GME_OK;
+    int64_t sum[3];
+    const int rc = read_bbme_stats(ctx, sum);
+    if (rc == GME_OK && listed) *listed = sum[2];
+    return rc;
 }
 
 extern "C" void* gme_stream(gme_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
@@ -249,10 +256,7 @@ int ctx_redo_list(gme_ctx* ctx, size_t entries, uint32_t** out)
 int plane_alloc(gme_ctx* ctx, PlaneBuf* p, int count, int H, int W)
 {
     *p = PlaneBuf();
-    Plane v;
-    v.H = H; v.W = W; v.count = count;
-    v.pitch = round_up(W, 64);
-    v.stride = (int64_t)round_up(v.pitch * H, 256);
+    Plane v = plane_shape(H, W, count);
     if (count != 0 && H != 0 && W != 0) {
         // one guard row behind the stack: dword loads near the last row never leave the allocation
         const int rc = p->mem.ensure(v.bytes() + v.pitch, "frames");
@@ -271,12 +275,57 @@ int plane_alloc(gme_ctx* ctx, PlaneBuf* p, int count, int H, int W)
     return GME_OK;
 }
 
-// carve `n` sub-buffers out of the context scratch, 256-byte aligned
+// The scratch of a single-pair call: take() sub-buffers (256-byte aligned, in order), then commit() gets the block from the
+// context and sets every pointer handed to take().
 struct Carver {
-    uint8_t* base = nullptr;
-    size_t off = 0;
-    size_t take(size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; }
+    void* var[8];
+    size_t at[8], off = 0;
+    int n = 0;
+    template <class T> void take(T** v, size_t count)
+    {
+        var[n] = v; at[n++] = off;
+        off = (off + count * sizeof(T) + 255) & ~(size_t)255;
+    }
+    // a plane of plane_shape(); guard: with the guard row behind it
+    void take(Plane* v, bool guard) { take(&v->ptr, v->bytes() + (guard ? v->pitch : 0)); }
+    int commit(gme_ctx* ctx)
+    {
+        void* base = nullptr;
+        const int rc = ctx_scratch(ctx, off, &base);
+        if (rc) return rc;
+        for (int i = 0; i < n; ++i) {
+            void* ptr = (uint8_t*)base + at[i];
+            memcpy(var[i], &ptr, sizeof(ptr));                 // whatever T, *var[i] is an object pointer
+        }
+        return GME_OK;
+    }
 };
+
+// a host image with rows `stride` bytes apart into plane 0 of v, queued on the context's stream
+static hipError_t put_plane(gme_ctx* ctx, const Plane& v, const uint8_t* host, int stride)
+{
+    return hipMemcpy2DAsync(v.ptr, v.pitch, host, stride, v.W, v.H, hipMemcpyHostToDevice, ctx->stream);
+}
+
+// planes first .. first + count - 1 of a stack into out[count][H][W] (tight), queued on the context's stream
+static int read_planes(gme_ctx* ctx, const Plane& p, int first, int count, uint8_t* out)
+{
+    for (int k = 0; k < count; ++k)
+        GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * p.H * p.W, p.W, p.at(first + k), p.pitch, p.W, p.H, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+    return GME_OK;
+}
+
+// The search of the pairs (first + k, first + k + fd), k < pairs, of a plane stack into mf.
+static BbmeJob bbme_job(const Plane& p, int first, int fd, int pairs, int bs, int sw, int procedure, int pnorm, int32_t* mf)
+{
+    BbmeJob job;
+    job.prev = p.at(first); job.cur = p.at(first + fd); job.plane_stride = p.stride; job.pairs = pairs;
+    job.H = p.H; job.W = p.W; job.pitch = p.pitch;
+    job.bs = bs; job.sw = sw; job.procedure = procedure; job.pnorm = pnorm;
+    job.mf = mf;
+    return job;
+}
 
 // ---------------------------------------------------------------------------
 // single-pair calls on host buffers
@@ -285,132 +334,126 @@ extern "C" int gme_bbme_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
                            int block_size, int search_window, int procedure, int pnorm, int32_t* mf_out)
 {
     GME_ENTER(ctx);
-    int rc = GME_OK;
     GME_REQUIRE(prev && cur && mf_out, GME_ERR_ARG, "gme_bbme_u8: null pointer");
     GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_bbme_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
     GME_REQUIRE(block_size >= 1, GME_ERR_ARG, "gme_bbme_u8: block_size %d", block_size);
-    rc = bbme_check_args(H, W, block_size, search_window, procedure, pnorm);
+    int rc = bbme_check_args(H, W, block_size, search_window, procedure, pnorm);
     if (rc) return rc;
     const int h = H / block_size, w = W / block_size;
     if (h == 0 || w == 0) return GME_OK;
-    const int pitch = round_up(W, 64);
-    const size_t plane = (size_t)round_up(pitch * H, 256);
+    Plane pp = plane_shape(H, W, 1), pc = pp;
+    int32_t* mf = nullptr;
+    uint32_t* sq = nullptr;
+    const int aux = bbme_aux_kind(H, W, pp.pitch, 1, block_size, search_window, procedure, pnorm);
     Carver c;
-    const size_t o_prev = c.take(plane + pitch), o_cur = c.take(plane + pitch);
-    const size_t o_mf = c.take((size_t)h * w * 2 * sizeof(int32_t));
-    const int aux = bbme_aux_kind(H, W, pitch, 1, block_size, search_window, procedure, pnorm);
-    const bool want_sq = aux != 0;
-    const size_t o_sq = c.take(want_sq ? plane * 4 : 0);
-    void* base = nullptr;
-    rc = ctx_scratch(ctx, c.off, &base);
+    c.take(&pp, true); c.take(&pc, true);
+    c.take(&mf, (size_t)h * w * 2);
+    c.take(&sq, aux != 0 ? (size_t)pp.stride : 0);
+    rc = c.commit(ctx);
     if (rc) return rc;
-    uint8_t* b = (uint8_t*)base;
-    GME_HIP_TRY(hipMemsetAsync(b + o_prev, 0, o_mf - o_prev, ctx->stream));
-    GME_HIP_TRY(hipMemcpy2DAsync(b + o_prev, pitch, prev, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    GME_HIP_TRY(hipMemcpy2DAsync(b + o_cur, pitch, cur, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    BbmeJob job;
-    job.prev = b + o_prev; job.cur = b + o_cur; job.plane_stride = 0; job.pairs = 1;
-    job.H = H; job.W = W; job.pitch = pitch;
-    job.bs = block_size; job.sw = search_window; job.procedure = procedure; job.pnorm = pnorm;
-    job.mf = (int32_t*)(b + o_mf); job.sqbox_cur = nullptr; job.sqbox_stride = 0;
-    if (want_sq) {
-        rc = launch_aux_table(ctx, aux, b + o_cur, 0, 1, H, W, pitch, (uint32_t*)(b + o_sq), 0);
+    GME_HIP_TRY(hipMemsetAsync(pp.ptr, 0, (uint8_t*)mf - pp.ptr, ctx->stream));
+    GME_HIP_TRY(put_plane(ctx, pp, prev, stride));
+    GME_HIP_TRY(put_plane(ctx, pc, cur, stride));
+    Plane both = pp;                                           // the two carved planes as a stack
+    both.stride = pc.ptr - pp.ptr; both.count = 2;
+    auto job = bbme_job(both, 0, 1, 1, block_size, search_window, procedure, pnorm, mf);
+    if (aux != 0) {
+        rc = launch_aux_table(ctx, aux, pc.ptr, 0, 1, H, W, pc.pitch, sq, 0);
         if (rc) return rc;
-        job.sqbox_cur = (const uint32_t*)(b + o_sq);
+        job.sqbox_cur = sq;
         job.sqbox_kind = aux;
     }
     rc = launch_bbme(ctx, job);
     if (rc) return rc;
-    GME_HIP_TRY(hipMemcpyAsync(mf_out, b + o_mf, (size_t)h * w * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(mf_out, mf, (size_t)h * w * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
 }
 
 extern "C" int gme_pyrdown_u8(gme_ctx* ctx, const uint8_t* src, int H, int W, int stride, uint8_t* dst)
 {
     GME_ENTER(ctx);
-    int rc = GME_OK;
     GME_REQUIRE(src && dst && H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_pyrdown_u8: bad arguments");
-    Plane s, d;
-    s.H = H; s.W = W; s.pitch = round_up(W, 64); s.stride = round_up(s.pitch * H, 256); s.count = 1;
-    d.H = (H + 1) / 2; d.W = (W + 1) / 2; d.pitch = round_up(d.W, 64); d.stride = round_up(d.pitch * d.H, 256); d.count = 1;
+    Plane s = plane_shape(H, W, 1), d = plane_shape((H + 1) / 2, (W + 1) / 2, 1);
     Carver c;
-    const size_t o_s = c.take(s.stride), o_d = c.take(d.stride);
-    void* base = nullptr;
-    rc = ctx_scratch(ctx, c.off, &base);
+    c.take(&s, false); c.take(&d, false);
+    int rc = c.commit(ctx);
     if (rc) return rc;
-    s.ptr = (uint8_t*)base + o_s; d.ptr = (uint8_t*)base + o_d;
-    GME_HIP_TRY(hipMemcpy2DAsync(s.ptr, s.pitch, src, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
+    GME_HIP_TRY(put_plane(ctx, s, src, stride));
     rc = launch_pyrdown(ctx, s, d);
     if (rc) return rc;
-    GME_HIP_TRY(hipMemcpy2DAsync(dst, d.W, d.ptr, d.pitch, d.W, d.H, hipMemcpyDeviceToHost, ctx->stream));
+    rc = read_planes(ctx, d, 0, 1, dst);
+    return rc ? rc : ctx_finish(ctx);
+}
+
+// Model orders: 1 = affine (params [P][6], sums [P][15] = F (9) | Sx (3) | Sy (3)); 2 = the second-order models
+// (params [P][12], sums [P][27], see the section at the end of this file).
+static int order_params(int order) { return order == 1 ? 6 : 12; }
+static int order_sums(int order) { return order == 1 ? 15 : 27; }
+
+// the h x w field of one parameter vector of `order` through the scratch
+static int model_field(gme_ctx* ctx, int order, const char* who, const double* params, int h, int w, int16_t* mf_out)
+{
+    GME_ENTER(ctx);
+    GME_REQUIRE(params && mf_out && h >= 0 && w >= 0, GME_ERR_ARG, "%s: bad arguments", who);
+    if (h == 0 || w == 0) return GME_OK;
+    double* d_params = nullptr;
+    int16_t* d_field = nullptr;
+    const size_t np = (size_t)order_params(order), nf = (size_t)h * w * 2;
+    Carver c;
+    c.take(&d_params, np); c.take(&d_field, nf);
+    int rc = c.commit(ctx);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(d_params, params, np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = order == 1 ? launch_affine_field(ctx, d_params, 1, h, w, d_field) : launch_model2_field(ctx, d_params, 1, h, w, d_field, nullptr);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(mf_out, d_field, nf * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
 }
 
 extern "C" int gme_affine_field(gme_ctx* ctx, const double params[6], int h, int w, int16_t* mf_out)
 {
-    GME_ENTER(ctx);
-    int rc = GME_OK;
-    GME_REQUIRE(params && mf_out && h >= 0 && w >= 0, GME_ERR_ARG, "gme_affine_field: bad arguments");
-    if (h == 0 || w == 0) return GME_OK;
-    Carver c;
-    const size_t o_p = c.take(6 * sizeof(double)), o_f = c.take((size_t)h * w * 2 * sizeof(int16_t));
-    void* base = nullptr;
-    rc = ctx_scratch(ctx, c.off, &base);
-    if (rc) return rc;
-    uint8_t* b = (uint8_t*)base;
-    GME_HIP_TRY(hipMemcpyAsync(b + o_p, params, 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_affine_field(ctx, (const double*)(b + o_p), 1, h, w, (int16_t*)(b + o_f));
-    if (rc) return rc;
-    GME_HIP_TRY(hipMemcpyAsync(mf_out, b + o_f, (size_t)h * w * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
-    return ctx_finish(ctx);
+    return model_field(ctx, 1, "gme_affine_field", params, h, w, mf_out);
 }
 
 extern "C" int gme_compensate_u8(gme_ctx* ctx, const uint8_t* frame, int H, int W, int stride, const int32_t* mf,
                                  int h, int w, uint8_t* out)
 {
     GME_ENTER(ctx);
-    int rc = GME_OK;
     GME_REQUIRE(frame && mf && out && H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_compensate_u8: bad arguments");
     GME_REQUIRE(h > 0 && w > 0 && h <= H, GME_ERR_ARG,
                 "gme_compensate_u8: field of %d x %d blocks on a %d-row frame (motion.py:303 divides H by it)", h, w, H);
-    const int pitch = round_up(W, 64);
-    const size_t plane = (size_t)round_up(pitch * H, 256);
+    Plane pf = plane_shape(H, W, 1), po = pf;
+    int32_t* d_mf = nullptr;
     Carver c;
-    const size_t o_f = c.take(plane), o_o = c.take(plane), o_m = c.take((size_t)h * w * 2 * sizeof(int32_t));
-    void* base = nullptr;
-    rc = ctx_scratch(ctx, c.off, &base);
+    c.take(&pf, false); c.take(&po, false); c.take(&d_mf, (size_t)h * w * 2);
+    int rc = c.commit(ctx);
     if (rc) return rc;
-    uint8_t* b = (uint8_t*)base;
-    GME_HIP_TRY(hipMemcpy2DAsync(b + o_f, pitch, frame, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    GME_HIP_TRY(hipMemcpyAsync(b + o_m, mf, (size_t)h * w * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_compensate(ctx, b + o_f, 0, 1, H, W, pitch, (const int32_t*)(b + o_m), nullptr, h, w, b + o_o, 0, pitch,
-                           nullptr, 0, nullptr);
+    GME_HIP_TRY(put_plane(ctx, pf, frame, stride));
+    GME_HIP_TRY(hipMemcpyAsync(d_mf, mf, (size_t)h * w * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_compensate(ctx, pf.ptr, 0, 1, H, W, pf.pitch, d_mf, nullptr, h, w, po.ptr, 0, po.pitch, nullptr, 0, nullptr);
     if (rc) return rc;
-    GME_HIP_TRY(hipMemcpy2DAsync(out, W, b + o_o, pitch, W, H, hipMemcpyDeviceToHost, ctx->stream));
-    return ctx_finish(ctx);
+    rc = read_planes(ctx, po, 0, 1, out);
+    return rc ? rc : ctx_finish(ctx);
 }
 
 extern "C" int gme_sse_u8(gme_ctx* ctx, const uint8_t* a, const uint8_t* b_, int H, int W, int stride_a, int stride_b,
                           int64_t* sse_out)
 {
     GME_ENTER(ctx);
-    int rc = GME_OK;
     GME_REQUIRE(a && b_ && sse_out && H > 0 && W > 0 && stride_a >= W && stride_b >= W, GME_ERR_ARG,
                 "gme_sse_u8: bad arguments");
-    const int pitch = round_up(W, 64);
-    const size_t plane = (size_t)round_up(pitch * H, 256);
+    Plane pa = plane_shape(H, W, 1), pb = pa;
+    unsigned long long* d_sse = nullptr;
     Carver c;
-    const size_t o_a = c.take(plane), o_b = c.take(plane), o_s = c.take(sizeof(unsigned long long));
-    void* base = nullptr;
-    rc = ctx_scratch(ctx, c.off, &base);
+    c.take(&pa, false); c.take(&pb, false); c.take(&d_sse, 1);
+    int rc = c.commit(ctx);
     if (rc) return rc;
-    uint8_t* b = (uint8_t*)base;
-    GME_HIP_TRY(hipMemcpy2DAsync(b + o_a, pitch, a, stride_a, W, H, hipMemcpyHostToDevice, ctx->stream));
-    GME_HIP_TRY(hipMemcpy2DAsync(b + o_b, pitch, b_, stride_b, W, H, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_sse(ctx, b + o_a, 0, pitch, b + o_b, 0, pitch, 1, H, W, (unsigned long long*)(b + o_s));
+    GME_HIP_TRY(put_plane(ctx, pa, a, stride_a));
+    GME_HIP_TRY(put_plane(ctx, pb, b_, stride_b));
+    rc = launch_sse(ctx, pa.ptr, 0, pa.pitch, pb.ptr, 0, pb.pitch, 1, H, W, d_sse);
     if (rc) return rc;
     unsigned long long v = 0;
-    GME_HIP_TRY(hipMemcpyAsync(&v, b + o_s, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(&v, d_sse, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
     rc = ctx_finish(ctx);
     *sse_out = (int64_t)v;
     return rc;
@@ -429,31 +472,29 @@ extern "C" int gme_subpel_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* c
                              int pnorm, int levels, const int32_t* mf_in, int32_t* qmf_out, int64_t* cost_out)
 {
     GME_ENTER(ctx);
-    int rc = GME_OK;
     GME_REQUIRE(prev && cur && mf_in && qmf_out && cost_out, GME_ERR_ARG, "gme_subpel_u8: null pointer");
     GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_subpel_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
-    rc = subpel_check("gme_subpel_u8", H, W, block_size, pnorm, levels);
+    int rc = subpel_check("gme_subpel_u8", H, W, block_size, pnorm, levels);
     if (rc) return rc;
     const int h = H / block_size, w = W / block_size;
     if (h == 0 || w == 0) return GME_OK;
-    const int pitch = round_up(W, 64);
-    const size_t plane = (size_t)round_up(pitch * H, 256), n = (size_t)h * w;
+    const size_t n = (size_t)h * w;
+    Plane pp = plane_shape(H, W, 1), pc = pp;
+    int32_t *d_mf = nullptr, *d_q = nullptr;
+    long long* d_cost = nullptr;
     Carver c;
-    const size_t o_prev = c.take(plane + pitch), o_cur = c.take(plane + pitch);
-    const size_t o_mf = c.take(n * 2 * sizeof(int32_t)), o_q = c.take(n * 2 * sizeof(int32_t)), o_c = c.take(n * sizeof(long long));
-    void* base = nullptr;
-    rc = ctx_scratch(ctx, c.off, &base);
+    c.take(&pp, true); c.take(&pc, true);
+    c.take(&d_mf, n * 2); c.take(&d_q, n * 2); c.take(&d_cost, n);
+    rc = c.commit(ctx);
     if (rc) return rc;
-    uint8_t* b = (uint8_t*)base;
-    GME_HIP_TRY(hipMemsetAsync(b + o_prev, 0, o_mf - o_prev, ctx->stream));
-    GME_HIP_TRY(hipMemcpy2DAsync(b + o_prev, pitch, prev, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    GME_HIP_TRY(hipMemcpy2DAsync(b + o_cur, pitch, cur, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    GME_HIP_TRY(hipMemcpyAsync(b + o_mf, mf_in, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_subpel_refine(ctx, b + o_prev, b + o_cur, 0, 1, H, W, pitch, block_size, pnorm, levels, (const int32_t*)(b + o_mf),
-                              (int32_t*)(b + o_q), (long long*)(b + o_c));
+    GME_HIP_TRY(hipMemsetAsync(pp.ptr, 0, (uint8_t*)d_mf - pp.ptr, ctx->stream));
+    GME_HIP_TRY(put_plane(ctx, pp, prev, stride));
+    GME_HIP_TRY(put_plane(ctx, pc, cur, stride));
+    GME_HIP_TRY(hipMemcpyAsync(d_mf, mf_in, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_subpel_refine(ctx, pp.ptr, pc.ptr, 0, 1, H, W, pp.pitch, block_size, pnorm, levels, d_mf, d_q, d_cost);
     if (rc) return rc;
-    GME_HIP_TRY(hipMemcpyAsync(qmf_out, b + o_q, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GME_HIP_TRY(hipMemcpyAsync(cost_out, b + o_c, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(qmf_out, d_q, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
 }
 
@@ -524,12 +565,28 @@ extern "C" int gme_seq_poll(gme_seq* s)
     return GME_ERR_HIP;
 }
 
+// the ending of a call that hands results to the caller: split-phase records s->ready behind their copies, otherwise it waits
+static int seq_deliver(gme_seq* s)
+{
+    if (!s->split_phase) return ctx_finish(s->ctx);
+    GME_HIP_TRY(hipEventRecord(s->ready, s->ctx->stream));
+    return GME_OK;
+}
+
 // new frame data ends a staged GME run: searches gme_seq_gme_begin deferred must not see other frames
 // than the stages already done, so the run is dropped (gme_seq_gme_fit then asks for a new begin)
 static void gme_drop_run(gme_seq* s)
 {
     s->bbme_pending[0] = s->bbme_pending[1] = s->bbme_pending[2] = false;
     s->gme_pairs = 0;
+}
+
+// the frames changed: pyramids and auxiliary tables are stale, and a staged run ends
+static void seq_frames_changed(gme_seq* s)
+{
+    s->pyramids_valid = false;
+    s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
+    gme_drop_run(s);
 }
 
 // The sequence acts as one of `n_frames` frames (1 <= n_frames <= the count it was created with) from now on: every
@@ -543,9 +600,7 @@ extern "C" int gme_seq_set_frames(gme_seq* s, int n_frames)
     GME_REQUIRE(n_frames >= 1 && n_frames <= s->N_cap, GME_ERR_ARG, "gme_seq_set_frames: %d frames in a sequence created for %d", n_frames, s->N_cap);
     if (n_frames != s->N) {
         s->N = n_frames;
-        s->pyramids_valid = false;
-        s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
-        gme_drop_run(s);
+        seq_frames_changed(s);
     }
     return GME_OK;
 }
@@ -567,24 +622,35 @@ struct Uploader {
 Uploader g_uploader[16];
 }  // namespace
 
+// tight host frames (the usual NumPy stack) whose rows are narrower than the plane pitch: linear copy + repack
+static bool host_frames_tight(const gme_seq* s, int row_stride, int64_t frame_stride)
+{
+    return row_stride == s->W && frame_stride == (int64_t)s->W * s->H && s->level[2].pitch != s->W;
+}
+
 // Frames per linear copy when gme_seq_upload goes through a staging buffer (0: it does not).  Tight frames: linear copies
 // (what the DMA engines move at link speed; 2-D copies of 720-byte rows reach ~37 GB/s) through a device staging buffer,
 // spread into the pitched planes by k_repack.
 static size_t upload_stage_frames(const gme_seq* s, int count, int row_stride, int64_t frame_stride)
 {
-    if (!(row_stride == s->W && frame_stride == (int64_t)s->W * s->H && s->level[2].pitch != s->W && count > 0)) return 0;
+    if (!host_frames_tight(s, row_stride, frame_stride) || count <= 0) return 0;
     size_t per = ((size_t)64 << 20) / ((size_t)s->H * s->W);
     if (per < 1) per = 1;
     return per > (size_t)count ? (size_t)count : per;
 }
 
-// the copies of one gme_seq_upload call on `stream`; `stage` holds `per` frames (upload_stage_frames) and belongs to that stream
+// The copies of host frames into planes first .. first + count - 1 on `stream`, the one place that knows the three host
+// layouts; `stage` holds `per` frames (0: the frames are not tight) and belongs to that stream.
 static int upload_copies(gme_seq* s, hipStream_t stream, uint8_t* stage, size_t per, int first, int count,
                          const uint8_t* frames, int row_stride, int64_t frame_stride)
 {
     const Plane& p = s->level[2];
     gme_ctx* ctx = s->ctx;
     if (per > 0) {
+        // one linear copy (link speed), then spread into the pitched planes on the same stream: the next copy into the
+        // staging buffer is ordered behind this repack.  Measured against the two alternatives: the repack kernel
+        // reading page-locked frames across the link itself (34 against 40 GB/s) and the frames split over two copy
+        // engines (22-25 against 38-39 GB/s) were both slower.
         const size_t frame_bytes = (size_t)s->H * s->W;
         for (int f0 = 0; f0 < count; f0 += (int)per) {
             const int n = count - f0 < (int)per ? count - f0 : (int)per;
@@ -612,9 +678,7 @@ extern "C" int gme_seq_upload(gme_seq* s, int first, int count, const uint8_t* f
     GME_REQUIRE(frames && first >= 0 && count >= 0 && first + count <= s->N_cap && row_stride >= s->W, GME_ERR_ARG,
                 "gme_seq_upload: frames [%d, %d) outside the sequence of %d", first, first + count, s->N_cap);
     gme_ctx* ctx = s->ctx;
-    s->pyramids_valid = false;
-    s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
-    gme_drop_run(s);
+    seq_frames_changed(s);
     const size_t per = upload_stage_frames(s, count, row_stride, frame_stride), stage_bytes = per * s->H * s->W;
     if (s->split_phase && ctx->device >= 0 && ctx->device < 16) {
         // split-phase: the copies are queued and the call returns; `frames` must stay untouched until a later
@@ -671,27 +735,14 @@ extern "C" int gme_seq_synth(gme_seq* s, uint64_t seed, int t0)
         if (rc) return rc;
         s->synth_seed = seed; s->synth_valid = true;
     }
-    s->pyramids_valid = false;
-    s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
-    gme_drop_run(s);
+    seq_frames_changed(s);
     return launch_synth_frames(s->ctx, seed, t0, s->synth_canvas, s->level[2]);
 }
 
 extern "C" int gme_seq_invalidate(gme_seq* s)
 {
     GME_REQUIRE(s != nullptr, GME_ERR_ARG, "null sequence");
-    s->pyramids_valid = false;
-    s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
-    gme_drop_run(s);
-    return GME_OK;
-}
-
-// planes first .. first + count - 1 of a stack into out[count][H][W] (tight), queued on the context's stream
-static int read_planes(gme_ctx* ctx, const Plane& p, int first, int count, uint8_t* out)
-{
-    for (int k = 0; k < count; ++k)
-        GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * p.H * p.W, p.W, p.at(first + k), p.pitch, p.W, p.H, hipMemcpyDeviceToHost,
-                                     ctx->stream));
+    seq_frames_changed(s);
     return GME_OK;
 }
 
@@ -720,6 +771,18 @@ static int seq_sqbox(gme_seq* s, int level, int kind)
     return GME_OK;
 }
 
+// launch_bbme of a job over the resident frames of one level (pairs k, k + fd) with the auxiliary table its kernel wants
+static int seq_launch_bbme(gme_seq* s, int level, int fd, BbmeJob job)
+{
+    if (const int aux = bbme_aux_kind(job.H, job.W, job.pitch, job.pairs, job.bs, job.sw, job.procedure, job.pnorm)) {      // BASELINE config 4
+        const int rc = seq_sqbox(s, level, aux);
+        if (rc) return rc;
+        const Plane& p = s->level[level];
+        job.sqbox_cur = s->sqbox[level] + (size_t)fd * p.stride; job.sqbox_stride = p.stride; job.sqbox_kind = aux;
+    }
+    return launch_bbme(s->ctx, job);
+}
+
 extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, int pnorm)
 {
     GME_REQUIRE(s != nullptr, GME_ERR_ARG, "null sequence");
@@ -735,20 +798,7 @@ extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, i
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
     s->mv_fd = fd; s->mv_bs = bs;
     s->qmv_valid = false;
-    const Plane& p = s->level[2];
-    BbmeJob job;
-    job.prev = p.at(0); job.cur = p.at(fd); job.plane_stride = p.stride; job.pairs = pairs;
-    job.H = s->H; job.W = s->W; job.pitch = p.pitch;
-    job.bs = bs; job.sw = sw; job.procedure = procedure; job.pnorm = pnorm;
-    job.mf = s->mv; job.sqbox_cur = nullptr; job.sqbox_stride = 0;
-    if (const int aux = bbme_aux_kind(s->H, s->W, p.pitch, pairs, bs, sw, procedure, pnorm)) {
-        rc = seq_sqbox(s, 2, aux);
-        if (rc) return rc;
-        job.sqbox_cur = s->sqbox[2] + (size_t)fd * p.stride;
-        job.sqbox_stride = p.stride;
-        job.sqbox_kind = aux;
-    }
-    return launch_bbme(s->ctx, job);
+    return seq_launch_bbme(s, 2, fd, bbme_job(s->level[2], 0, fd, pairs, bs, sw, procedure, pnorm, s->mv));
 }
 
 // ---------------------------------------------------------------------------
@@ -768,6 +818,24 @@ extern "C" void gme_host_free(void* p)
 {
     if (p) hipHostFree(p);
 }
+
+// The events of one call, owned as DevBuf owns memory: add() creates them when the call asks, the destructor destroys them.
+struct EventSet {
+    std::vector<hipEvent_t> ev;
+    EventSet() = default;
+    EventSet(const EventSet&) = delete;
+    EventSet& operator=(const EventSet&) = delete;
+    ~EventSet() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    int add(size_t n)
+    {
+        for (; n > 0; --n) {
+            hipEvent_t e = nullptr;
+            GME_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            ev.push_back(e);
+        }
+        return GME_OK;
+    }
+};
 
 extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_stride, int64_t frame_stride, int count,
                                      int fd, int bs, int sw, int procedure, int pnorm, int chunk_frames, int32_t* mf_out)
@@ -800,114 +868,92 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
         GME_HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
         GME_HIP_TRY(hipStreamCreateWithFlags(&ctx->back_stream, hipStreamNonBlocking));
     }
-    s->pyramids_valid = false;
-    s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
-    gme_drop_run(s);
-    // tight frames (the usual NumPy stack) whose rows are narrower than the plane pitch: linear copy + repack
-    const bool tight = row_stride == s->W && frame_stride == (int64_t)s->W * s->H && p.pitch != s->W;
-    if (tight) {
-        const size_t want = (size_t)(chunk_frames < count ? chunk_frames : count) * s->H * s->W;
-        if (want > ctx->stage.cap) {
-            GME_HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
-            rc = ctx->stage.ensure(want, "staging");
-            if (rc) return rc;
-        }
+    seq_frames_changed(s);
+    // tight frames go through the staging buffer a chunk at a time: a chunk is one linear copy plus one repack
+    const size_t stage_frames = host_frames_tight(s, row_stride, frame_stride) ? (size_t)(chunk_frames < count ? chunk_frames : count) : 0;
+    if (stage_frames * s->H * s->W > ctx->stage.cap) {
+        GME_HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
+        rc = ctx->stage.ensure(stage_frames * s->H * s->W, "staging");
+        if (rc) return rc;
     }
     const int nchunks = (count + chunk_frames - 1) / chunk_frames;
-    std::vector<hipEvent_t> up(nchunks, nullptr), done(nchunks, nullptr);
-    auto cleanup = [&]() { for (auto e : up) if (e) hipEventDestroy(e); for (auto e : done) if (e) hipEventDestroy(e); };
-#define STREAM_TRY(expr) do { if ((expr) != hipSuccess) { gme_set_error("%s failed: %s", #expr, hipGetErrorString(hipGetLastError())); \
-                               hipStreamSynchronize(ctx->copy_stream); hipStreamSynchronize(ctx->back_stream); hipStreamSynchronize(ctx->stream); \
-                               cleanup(); return GME_ERR_HIP; } } while (0)
-    // earlier work of this context may still read or write the planes / the field buffer
-    hipEvent_t gate = nullptr;
-    STREAM_TRY(hipEventCreateWithFlags(&gate, hipEventDisableTiming));
-    up.push_back(gate);                                        // destroyed with the others
-    STREAM_TRY(hipEventRecord(gate, ctx->stream));
-    STREAM_TRY(hipStreamWaitEvent(ctx->copy_stream, gate, 0));
-    STREAM_TRY(hipStreamWaitEvent(ctx->back_stream, gate, 0));
-    int p_done = 0;                                            // pairs searched so far
+    EventSet events;                                           // per chunk: uploaded, searched; and the gate
+    rc = events.add(2 * (size_t)nchunks + 1);
+    if (rc) return rc;
+    const hipEvent_t *up = events.ev.data(), *done = up + nchunks, gate = up[2 * nchunks];
     int tab_done = 0;                                          // frames whose auxiliary table rows exist (always from frame 0:
                                                                // a later call with a smaller frame distance reads them as `cur`)
-    int back_first = 0, back_count = 0, back_chunk = -1;       // fields of the previous chunk, still to be read back
-    auto read_back = [&]() -> bool {
-        if (back_count == 0) return true;
-        if (hipStreamWaitEvent(ctx->back_stream, done[back_chunk], 0) != hipSuccess) return false;
-        const bool ok = hipMemcpyAsync(mf_out + per * back_first, s->mv + per * back_first, per * back_count * sizeof(int32_t),
-                                       hipMemcpyDeviceToHost, ctx->back_stream) == hipSuccess;
-        back_count = 0;
-        return ok;
-    };
-#define LTRY(expr) do { if ((expr) != hipSuccess) return false; } while (0)
-    // upload of chunk c on the copy stream + the event behind it
-    auto upload_chunk = [&](int c) -> bool {
-        const int f0 = c * chunk_frames, f1 = f0 + chunk_frames < count ? f0 + chunk_frames : count;
-        LTRY(hipEventCreateWithFlags(&up[c], hipEventDisableTiming));
-        LTRY(hipEventCreateWithFlags(&done[c], hipEventDisableTiming));
-        // upload of chunk c on the copy stream: it runs while the compute stream still searches chunk c - 1
-        if (tight) {
-            // one linear copy (link speed), then spread into the pitched planes on the same stream: the next chunk's
-            // copy into the staging buffer is ordered behind this repack.  Measured against the two alternatives: the
-            // repack kernel reading page-locked frames across the link itself (34 against 40 GB/s) and the chunk split
-            // over two copy engines (22-25 against 38-39 GB/s) were both slower.
-            const size_t bytes = (size_t)(f1 - f0) * s->H * s->W;
-            LTRY(hipMemcpyAsync(ctx->stage, frames + (int64_t)f0 * frame_stride, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-            if (launch_repack(ctx, ctx->copy_stream, ctx->stage, f1 - f0, s->H, s->W, p.at(f0), p.pitch, p.stride) != GME_OK) return false;
-        } else if (p.stride == (int64_t)p.pitch * s->H && frame_stride == (int64_t)row_stride * s->H) {
-            LTRY(hipMemcpy2DAsync(p.at(f0), p.pitch, frames + (int64_t)f0 * frame_stride, row_stride, s->W,
-                                        (size_t)s->H * (f1 - f0), hipMemcpyHostToDevice, ctx->copy_stream));
-        } else {
-            for (int i = f0; i < f1; ++i)
-                LTRY(hipMemcpy2DAsync(p.at(i), p.pitch, frames + (int64_t)i * frame_stride, row_stride, s->W, s->H,
-                                            hipMemcpyHostToDevice, ctx->copy_stream));
-        }
-        LTRY(hipEventRecord(up[c], ctx->copy_stream));
-        return true;
-    };
-#undef LTRY
-    if (!upload_chunk(0)) { STREAM_TRY(hipErrorUnknown); }
-    for (int c = 0; c < nchunks; ++c) {
-        const int f1 = (c + 1) * chunk_frames < count ? (c + 1) * chunk_frames : count;
-        // The NEXT chunk's upload is queued before this chunk's search is launched: a kernel launch behind a cross-stream
-        // wait on a copy holds the calling thread until that copy is done, and with the upload queued only afterwards the
-        // link idled for the host's latency between chunks (94 % of the copy-alone rate; round 3).
-        if (c + 1 < nchunks && !upload_chunk(c + 1)) { STREAM_TRY(hipErrorUnknown); }
-        // read-back of the previous chunk's fields only now, behind the next chunk's upload in program order: a copy
-        // into pageable memory may hold the calling thread until that chunk's kernel is done, and the upload
-        // queued above keeps the link busy meanwhile
-        if (!read_back()) { STREAM_TRY(hipErrorUnknown); }
-        STREAM_TRY(hipStreamWaitEvent(ctx->stream, up[c], 0));
-        const int p1 = f1 - fd;                                // pairs [p_done, p1) have both frames on the device now
-        if (p1 > p_done) {
-            BbmeJob job;
-            job.prev = p.at(p_done); job.cur = p.at(p_done + fd); job.plane_stride = p.stride; job.pairs = p1 - p_done;
-            job.H = s->H; job.W = s->W; job.pitch = p.pitch;
-            job.bs = bs; job.sw = sw; job.procedure = procedure; job.pnorm = pnorm;
-            job.mf = s->mv + per * p_done; job.sqbox_cur = nullptr; job.sqbox_stride = 0;
-            job.chained = p_done > 0;
-            if (aux) {
-                // box sums of squares of every frame uploaded since the last table launch
-                const int t0 = tab_done;
-                rc = launch_aux_table(ctx, aux, p.at(t0), p.stride, f1 - t0, p.H, p.W, p.pitch, s->sqbox[2] + (size_t)t0 * p.stride, p.stride);
-                tab_done = f1;
-                if (rc == GME_OK) { job.sqbox_cur = s->sqbox[2] + (size_t)(p_done + fd) * p.stride; job.sqbox_stride = p.stride; job.sqbox_kind = aux; }
+    // everything the call queues; a failure leaves through the one error exit below
+    auto queue_all = [&]() -> int {
+        // earlier work of this context may still read or write the planes / the field buffer
+        GME_HIP_TRY(hipEventRecord(gate, ctx->stream));
+        GME_HIP_TRY(hipStreamWaitEvent(ctx->copy_stream, gate, 0));
+        GME_HIP_TRY(hipStreamWaitEvent(ctx->back_stream, gate, 0));
+        // upload of chunk c on the copy stream + the event behind it: it runs while the compute stream still searches chunk c - 1
+        auto upload_chunk = [&](int c) -> int {
+            const int f0 = c * chunk_frames, f1 = f0 + chunk_frames < count ? f0 + chunk_frames : count;
+            const int r = upload_copies(s, ctx->copy_stream, ctx->stage, stage_frames, f0, f1 - f0, frames + (int64_t)f0 * frame_stride,
+                                        row_stride, frame_stride);
+            if (r) return r;
+            GME_HIP_TRY(hipEventRecord(up[c], ctx->copy_stream));
+            return GME_OK;
+        };
+        int p_done = 0;                                        // pairs searched so far
+        int back_first = 0, back_count = 0, back_chunk = -1;   // fields of the previous chunk, still to be read back
+        auto read_back = [&]() -> int {
+            if (back_count == 0) return GME_OK;
+            GME_HIP_TRY(hipStreamWaitEvent(ctx->back_stream, done[back_chunk], 0));
+            const int first = back_first, n = back_count;
+            back_count = 0;
+            GME_HIP_TRY(hipMemcpyAsync(mf_out + per * first, s->mv + per * first, per * n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                       ctx->back_stream));
+            return GME_OK;
+        };
+        rc = upload_chunk(0);
+        if (rc) return rc;
+        for (int c = 0; c < nchunks; ++c) {
+            const int f1 = (c + 1) * chunk_frames < count ? (c + 1) * chunk_frames : count;
+            // The NEXT chunk's upload is queued before this chunk's search is launched: a kernel launch behind a cross-stream
+            // wait on a copy holds the calling thread until that copy is done, and with the upload queued only afterwards the
+            // link idled for the host's latency between chunks (94 % of the copy-alone rate; round 3).
+            if (c + 1 < nchunks) {
+                rc = upload_chunk(c + 1);
+                if (rc) return rc;
             }
-            if (rc == GME_OK) rc = launch_bbme(ctx, job);
-            if (rc != GME_OK) {
-                hipStreamSynchronize(ctx->copy_stream); hipStreamSynchronize(ctx->back_stream); hipStreamSynchronize(ctx->stream);
-                cleanup();
-                return rc;
+            // read-back of the previous chunk's fields only now, behind the next chunk's upload in program order: a copy
+            // into pageable memory may hold the calling thread until that chunk's kernel is done, and the upload
+            // queued above keeps the link busy meanwhile
+            rc = read_back();
+            if (rc) return rc;
+            GME_HIP_TRY(hipStreamWaitEvent(ctx->stream, up[c], 0));
+            const int p1 = f1 - fd;                            // pairs [p_done, p1) have both frames on the device now
+            if (p1 > p_done) {
+                auto job = bbme_job(p, p_done, fd, p1 - p_done, bs, sw, procedure, pnorm, s->mv + per * p_done);
+                job.chained = p_done > 0;
+                if (aux) {
+                    // box sums of squares of every frame uploaded since the last table launch
+                    const int t0 = tab_done;
+                    tab_done = f1;
+                    rc = launch_aux_table(ctx, aux, p.at(t0), p.stride, f1 - t0, p.H, p.W, p.pitch, s->sqbox[2] + (size_t)t0 * p.stride, p.stride);
+                    if (rc) return rc;
+                    job.sqbox_cur = s->sqbox[2] + (size_t)(p_done + fd) * p.stride; job.sqbox_stride = p.stride; job.sqbox_kind = aux;
+                }
+                rc = launch_bbme(ctx, job);
+                if (rc) return rc;
+                GME_HIP_TRY(hipEventRecord(done[c], ctx->stream));
+                back_first = p_done; back_count = p1 - p_done; back_chunk = c;
+                p_done = p1;
             }
-            STREAM_TRY(hipEventRecord(done[c], ctx->stream));
-            back_first = p_done; back_count = p1 - p_done; back_chunk = c;
-            p_done = p1;
         }
+        return read_back();
+    };
+    rc = queue_all();
+    const hipError_t e1 = hipStreamSynchronize(ctx->copy_stream), e2 = hipStreamSynchronize(ctx->back_stream);
+    if (rc) {                                                  // the error exit: nothing of the call still runs when its events go
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
     }
-    if (!read_back()) { STREAM_TRY(hipErrorUnknown); }
-#undef STREAM_TRY
-    hipError_t e1 = hipStreamSynchronize(ctx->copy_stream), e2 = hipStreamSynchronize(ctx->back_stream);
     rc = ctx_finish(ctx);
-    cleanup();
     if (aux) { s->sqbox_valid[2] = (count == s->N && tab_done == count); s->sqbox_kind[2] = aux; }
     if (e1 != hipSuccess || e2 != hipSuccess) { gme_set_error("gme_seq_bbme_streamed: copy stream failed"); return GME_ERR_HIP; }
     return rc;
@@ -950,24 +996,10 @@ static int gme_level_bbme(gme_seq* s, int l)
     if (!s->bbme_pending[l]) return GME_OK;
     s->bbme_pending[l] = false;
     const Plane& p = s->level[l];
-    const int fd = s->gme_fd;
-    BbmeJob job;
-    job.prev = p.at(0); job.cur = p.at(fd); job.plane_stride = p.stride; job.pairs = s->gme_pairs;
-    job.H = p.H; job.W = p.W; job.pitch = p.pitch;
-    job.bs = l == 0 ? 2 : s->gme_bs;
-    job.sw = l == 0 ? 2 : s->gme_sw;
-    job.procedure = l == 0 ? GME_SEARCH_DIAMOND : s->gme_procedure;
-    job.pnorm = GME_NORM_MSE;
-    job.mf = s->fit[l].gt; job.sqbox_cur = nullptr; job.sqbox_stride = 0;
     if (s->fit[l].h == 0 || s->fit[l].w == 0) return GME_OK;
-    if (const int aux = bbme_aux_kind(p.H, p.W, p.pitch, job.pairs, job.bs, job.sw, job.procedure, job.pnorm)) {      // BASELINE config 4
-        const int rc = seq_sqbox(s, l, aux);
-        if (rc) return rc;
-        job.sqbox_cur = s->sqbox[l] + (size_t)fd * p.stride;
-        job.sqbox_stride = p.stride;
-        job.sqbox_kind = aux;
-    }
-    return launch_bbme(s->ctx, job);
+    const int fd = s->gme_fd, pairs = s->gme_pairs;
+    if (l == 0) return seq_launch_bbme(s, l, fd, bbme_job(p, 0, fd, pairs, 2, 2, GME_SEARCH_DIAMOND, GME_NORM_MSE, s->fit[l].gt));
+    return seq_launch_bbme(s, l, fd, bbme_job(p, 0, fd, pairs, s->gme_bs, s->gme_sw, s->gme_procedure, GME_NORM_MSE, s->fit[l].gt));
 }
 
 // launch whatever gme_seq_gme_begin deferred, up to and including `level`
@@ -1069,18 +1101,12 @@ extern "C" int gme_seq_gme_begin(gme_seq* s, int fd, int bbme_bs, int procedure,
     if (params0_out) {
         rc = copy_small(ctx, params0_out, s->params0, (size_t)s->gme_pairs * 6 * sizeof(float), hipMemcpyDeviceToHost, s->split_phase);
         if (rc) return rc;
-        if (s->split_phase) GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream));
-        else rc = ctx_finish(ctx);
+        rc = seq_deliver(s);
         if (rc) return rc;
         return gme_level_bbme(s, 1);                       // runs while the caller projects the parameters
     }
     return gme_flush_bbme(s, 2);
 }
-
-// Model orders: 1 = affine (params [P][6], sums [P][15] = F (9) | Sx (3) | Sy (3)); 2 = the second-order models
-// (params [P][12], sums [P][27], see the section at the end of this file).
-static int order_params(int order) { return order == 1 ? 6 : 12; }
-static int order_sums(int order) { return order == 1 ? 15 : 27; }
 
 // model field, mask and sums of level -1 (fit_mv), 1 or 2 from parameters already on the device (pstride doubles per
 // pair); result copy + event / wait.  The context is locked.
@@ -1100,10 +1126,7 @@ static int fit_launch(gme_seq* s, int order, int level, const double* dparams, i
     if (!sums_out) return GME_OK;                          // gme_seq_gme_device_solve: the sums stay on the device
     rc = copy_small(ctx, sums_out, order == 1 ? f.sums : f.sums2, (size_t)pairs * order_sums(order) * sizeof(double),
                     hipMemcpyDeviceToHost, s->split_phase);
-    if (rc) return rc;
-    if (s->split_phase) GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream));
-    else rc = ctx_finish(ctx);
-    return rc;
+    return rc ? rc : seq_deliver(s);
 }
 
 // gme_seq_gme_begin + the projection of the first parameters (motion.py:191-207 on the float32 vector: two exact doublings)
@@ -1270,9 +1293,7 @@ static int seq_compensate(gme_seq* s, int order, const char* who, int fd, int bs
     if (rc) return rc;
     if (sse_out) {
         rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase);
-        if (rc) return rc;
-        if (s->split_phase) { GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream)); return GME_OK; }
-        return ctx_finish(ctx);
+        return rc ? rc : seq_deliver(s);
     }
     return GME_OK;
 }
@@ -1392,9 +1413,7 @@ static int seq_device_solve(gme_seq* s, int order, int model, const char* who, i
     if (rc) return rc;
     if (sse_out) { rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase); if (rc) return rc; }
     rc = copy_small(ctx, flags_out, s->solve_flags, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, s->split_phase);
-    if (rc) return rc;
-    if (s->split_phase) { GME_HIP_TRY(hipEventRecord(s->ready, ctx->stream)); return GME_OK; }
-    return ctx_finish(ctx);
+    return rc ? rc : seq_deliver(s);
 }
 
 // motion.global_motion_estimation + get_motion_field_affine + compensate_frame + the squared error of results.py:50-59,109
@@ -1428,21 +1447,7 @@ extern "C" int gme_seq_read_compensated(gme_seq* s, int pair, uint8_t* out)
 // ---------------------------------------------------------------------------
 extern "C" int gme_model2_field(gme_ctx* ctx, const double params[12], int h, int w, int16_t* mf_out)
 {
-    GME_ENTER(ctx);
-    int rc = GME_OK;
-    GME_REQUIRE(params && mf_out && h >= 0 && w >= 0, GME_ERR_ARG, "gme_model2_field: bad arguments");
-    if (h == 0 || w == 0) return GME_OK;
-    Carver c;
-    const size_t o_p = c.take(12 * sizeof(double)), o_f = c.take((size_t)h * w * 2 * sizeof(int16_t));
-    void* base = nullptr;
-    rc = ctx_scratch(ctx, c.off, &base);
-    if (rc) return rc;
-    uint8_t* b = (uint8_t*)base;
-    GME_HIP_TRY(hipMemcpyAsync(b + o_p, params, 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_model2_field(ctx, (const double*)(b + o_p), 1, h, w, (int16_t*)(b + o_f), nullptr);
-    if (rc) return rc;
-    GME_HIP_TRY(hipMemcpyAsync(mf_out, b + o_f, (size_t)h * w * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
-    return ctx_finish(ctx);
+    return model_field(ctx, 2, "gme_model2_field", params, h, w, mf_out);
 }
 
 extern "C" int gme_seq_gme_begin_fit2(gme_seq* s, int fd, int bbme_bs, int procedure, int sw, double outlier_fraction,
@@ -1479,7 +1484,7 @@ extern "C" int gme_seq_gme_device_solve2(gme_seq* s, int model, int fd, int bbme
 // Direct projective refinement (gme_direct.hip): pyramids if stale, parameters up, every launch
 // queued, results down, one wait.
 // ---------------------------------------------------------------------------
-static int direct_begin(gme_seq* s, const char* who, int fd, const double* params)
+static int direct_begin(gme_seq* s, const char* who, int fd, const double* params, DirectIo* io)
 {
     GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "%s: frame_distance %d needs at least %d frames", who, fd, fd + 1);
     int rc = seq_levels(s);
@@ -1487,11 +1492,9 @@ static int direct_begin(gme_seq* s, const char* who, int fd, const double* param
     rc = seq_pyramids(s);
     if (rc) return rc;
     const int pairs = s->N - fd;
-    double *in, *out, *ev;
-    int32_t* fl;
-    rc = direct_io(s, pairs, &in, &out, &fl, &ev);
+    rc = direct_io(s, pairs, io);
     if (rc) return rc;
-    if (pairs > 0) GME_HIP_TRY(hipMemcpyAsync(in, params, (size_t)pairs * 8 * sizeof(double), hipMemcpyHostToDevice, s->ctx->stream));
+    if (pairs > 0) GME_HIP_TRY(hipMemcpyAsync(io->in, params, (size_t)pairs * 8 * sizeof(double), hipMemcpyHostToDevice, s->ctx->stream));
     return GME_OK;
 }
 
@@ -1503,18 +1506,15 @@ extern "C" int gme_seq_direct_eval(gme_seq* s, int fd, int level, const double* 
     GME_ENTER(ctx);
     GME_REQUIRE(level >= 0 && level <= 2, GME_ERR_ARG, "gme_seq_direct_eval: level %d (0 .. 2)", level);
     GME_REQUIRE(outlier_fraction >= 0.0 && outlier_fraction < 1.0, GME_ERR_ARG, "gme_seq_direct_eval: outlier_fraction %g", outlier_fraction);
-    int rc = direct_begin(s, "gme_seq_direct_eval", fd, params_in);
+    DirectIo io;
+    int rc = direct_begin(s, "gme_seq_direct_eval", fd, params_in, &io);
     if (rc) return rc;
     const int pairs = s->N - fd;
     if (pairs == 0) return GME_OK;
     rc = launch_direct_eval(s, fd, level, pairs, outlier_fraction);
     if (rc) return rc;
-    double *in, *out, *ev;
-    int32_t* fl;
-    rc = direct_io(s, pairs, &in, &out, &fl, &ev);
-    if (rc) return rc;
     std::vector<double> rows((size_t)pairs * 48);
-    GME_HIP_TRY(hipMemcpyAsync(rows.data(), ev, rows.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(rows.data(), io.eval, rows.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     rc = ctx_finish(ctx);
     if (rc) return rc;
     for (int p = 0; p < pairs; ++p) {
@@ -1537,18 +1537,15 @@ extern "C" int gme_seq_refine_projective(gme_seq* s, int fd, const double* init,
     GME_REQUIRE(outlier_fraction >= 0.0 && outlier_fraction < 1.0, GME_ERR_ARG, "gme_seq_refine_projective: outlier_fraction %g",
                 outlier_fraction);
     GME_REQUIRE(max_iters >= 1 && max_iters <= 1000, GME_ERR_ARG, "gme_seq_refine_projective: max_iters %d (1 .. 1000)", max_iters);
-    int rc = direct_begin(s, "gme_seq_refine_projective", fd, init);
+    DirectIo io;
+    int rc = direct_begin(s, "gme_seq_refine_projective", fd, init, &io);
     if (rc) return rc;
     const int pairs = s->N - fd;
     if (pairs == 0) return GME_OK;
     rc = launch_direct_refine(s, fd, pairs, outlier_fraction, max_iters);
     if (rc) return rc;
-    double *in, *out, *ev;
-    int32_t* fl;
-    rc = direct_io(s, pairs, &in, &out, &fl, &ev);
-    if (rc) return rc;
-    GME_HIP_TRY(hipMemcpyAsync(params_out, out, (size_t)pairs * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    GME_HIP_TRY(hipMemcpyAsync(flags_out, fl, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(params_out, io.out, (size_t)pairs * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(flags_out, io.flags, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
 }
 
@@ -1557,17 +1554,14 @@ extern "C" int gme_seq_compensate_projective(gme_seq* s, int fd, const double* p
     GME_REQUIRE(s != nullptr && params != nullptr, GME_ERR_ARG, "gme_seq_compensate_projective: null pointer");
     gme_ctx* ctx = s->ctx;
     GME_ENTER(ctx);
-    int rc = direct_begin(s, "gme_seq_compensate_projective", fd, params);
+    DirectIo io;
+    int rc = direct_begin(s, "gme_seq_compensate_projective", fd, params, &io);
     if (rc) return rc;
     const int pairs = s->N - fd;
     rc = ensure_comp(s, fd, pairs);
     if (rc) return rc;
     if (pairs == 0) return GME_OK;
-    double *in, *out, *ev;
-    int32_t* fl;
-    rc = direct_io(s, pairs, &in, &out, &fl, &ev);
-    if (rc) return rc;
-    rc = launch_compensate_proj(s, fd, pairs, in);
+    rc = launch_compensate_proj(s, fd, pairs, io.in);
     if (rc) return rc;
     if (sse_out) GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
@@ -1582,17 +1576,9 @@ static int stab_buffers(gme_seq* s)
     int rc = plane_alloc(s->ctx, &s->warped, s->N_cap, s->H, s->W);
     if (rc == GME_OK)
         rc = dev_ensure_all("stabilization buffers", { { s->warp_params, (size_t)s->N_cap * 8 }, { s->warp_counts, (size_t)s->N_cap } });
-    if (rc) { s->warped = PlaneBuf(); s->warped_written.clear(); return rc; }
-    s->warped_written.assign((size_t)s->N_cap, 0);
+    if (rc) { s->warped = PlaneBuf(); s->warped_written.flag.clear(); return rc; }
+    s->warped_written.flag.assign((size_t)s->N_cap, 0);
     return GME_OK;
-}
-
-static bool stab_written(const gme_seq* s, int first, int count)
-{
-    if (!s->warped.ptr) return count == 0;
-    for (int k = first; k < first + count; ++k)
-        if (!s->warped_written[(size_t)k]) return false;
-    return true;
 }
 
 extern "C" int gme_seq_warp_frames(gme_seq* s, int first, int count, const double* params, int border, int fill,
@@ -1617,7 +1603,7 @@ extern "C" int gme_seq_warp_frames(gme_seq* s, int first, int count, const doubl
                                    ctx->stream));
     rc = ctx_finish(ctx);
     if (rc) return rc;
-    for (int k = first; k < first + count; ++k) s->warped_written[(size_t)k] = 1;
+    s->warped_written.mark(first, count);
     return GME_OK;
 }
 
@@ -1627,7 +1613,7 @@ extern "C" int gme_seq_read_warped_range(gme_seq* s, int first, int count, uint8
     GME_ENTER(s->ctx);
     GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->N, GME_ERR_ARG,
                 "gme_seq_read_warped_range: frames [%d, %d) outside [0, %d)", first, first + count, s->N);
-    GME_REQUIRE(stab_written(s, first, count), GME_ERR_ARG, "gme_seq_read_warped_range: frames [%d, %d) were never warped",
+    GME_REQUIRE(s->warped_written.all(first, count), GME_ERR_ARG, "gme_seq_read_warped_range: frames [%d, %d) were never warped",
                 first, first + count);
     const int rc = read_planes(s->ctx, s->warped, first, count, out);
     return rc ? rc : ctx_finish(s->ctx);
@@ -1642,7 +1628,7 @@ extern "C" int gme_seq_frame_sse(gme_seq* s, int warped, int first, int count, i
     GME_REQUIRE(first >= 0 && count >= 0 && first + count + 1 <= s->N, GME_ERR_ARG,
                 "gme_seq_frame_sse: frames [%d, %d] outside [0, %d)", first, first + count, s->N);
     if (count == 0) return GME_OK;
-    GME_REQUIRE(!warped || stab_written(s, first, count + 1), GME_ERR_ARG, "gme_seq_frame_sse: frames [%d, %d] were never warped",
+    GME_REQUIRE(!warped || s->warped_written.all(first, count + 1), GME_ERR_ARG, "gme_seq_frame_sse: frames [%d, %d] were never warped",
                 first, first + count);
     int rc = stab_buffers(s);
     if (rc) return rc;
@@ -1740,8 +1726,8 @@ extern "C" int gme_seq_moving_masks(gme_seq* s, int first, int count, const doub
     if (rc) return rc;
     if (!s->masks.ptr) {
         rc = plane_alloc(ctx, &s->masks, s->N_cap, s->H, s->W);
-        if (rc) { s->masks_written.clear(); return rc; }
-        s->masks_written.assign((size_t)s->N_cap, 0);
+        if (rc) { s->masks_written.flag.clear(); return rc; }
+        s->masks_written.flag.assign((size_t)s->N_cap, 0);
     }
     rc = mosaic_put_rows(s, count, warps, usable);
     if (rc) return rc;
@@ -1758,7 +1744,7 @@ extern "C" int gme_seq_moving_masks(gme_seq* s, int first, int count, const doub
         GME_HIP_TRY(hipMemcpyAsync(moving_out, moving, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     rc = ctx_finish(ctx);
     if (rc) return rc;
-    for (int k = first; k < first + count; ++k) s->masks_written[(size_t)k] = 1;
+    s->masks_written.mark(first, count);
     return GME_OK;
 }
 
@@ -1768,9 +1754,7 @@ extern "C" int gme_seq_read_masks_range(gme_seq* s, int first, int count, uint8_
     GME_ENTER(s->ctx);
     GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->N, GME_ERR_ARG,
                 "gme_seq_read_masks_range: frames [%d, %d) outside [0, %d)", first, first + count, s->N);
-    bool written = s->masks.ptr != nullptr || count == 0;
-    for (int k = first; written && k < first + count; ++k) written = s->masks_written[(size_t)k] != 0;
-    GME_REQUIRE(written, GME_ERR_ARG, "gme_seq_read_masks_range: the masks of frames [%d, %d) were never computed", first,
+    GME_REQUIRE(s->masks_written.all(first, count), GME_ERR_ARG, "gme_seq_read_masks_range: the masks of frames [%d, %d) were never computed", first,
                 first + count);
     const int rc = read_planes(s->ctx, s->masks, first, count, out);
     return rc ? rc : ctx_finish(s->ctx);

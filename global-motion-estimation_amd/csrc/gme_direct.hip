@@ -415,12 +415,10 @@ __global__ void __launch_bounds__(256) k_compensate_proj(const uint8_t* prev, co
 static int direct_tiles(int H, int W) { return (int)(((long long)H * W + DIRECT_TILE - 1) / DIRECT_TILE); }
 
 // the sequence's workspace for `pairs` pairs: state | hist | slab | io (params in, params out, flags, eval rows)
-struct DirectWs {
+struct DirectWs : DirectIo {
     DirectState* st;
     uint32_t* hist;
     double* slab;
-    double *in, *out, *eval;
-    int32_t* flags;
     int tiles;
 };
 
@@ -445,12 +443,12 @@ static int direct_ws(gme_seq* s, int pairs, DirectWs* ws)
     return GME_OK;
 }
 
-int direct_io(gme_seq* s, int pairs, double** in, double** out, int32_t** flags, double** eval)
+int direct_io(gme_seq* s, int pairs, DirectIo* io)
 {
     DirectWs ws;
     const int rc = direct_ws(s, pairs, &ws);
     if (rc) return rc;
-    *in = ws.in; *out = ws.out; *flags = ws.flags; *eval = ws.eval;
+    *io = ws;
     return GME_OK;
 }
 

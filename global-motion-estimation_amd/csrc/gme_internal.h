@@ -46,6 +46,28 @@ struct PlaneBuf : Plane {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// The plane geometry of the library as a view without memory.  Whoever gives it memory adds a guard row of `pitch` bytes
+// behind the stack where dword loads near the last row must stay inside (plane_alloc; gme_bbme_u8, gme_subpel_u8).
+inline Plane plane_shape(int H, int W, int count)
+{
+    Plane v;
+    v.H = H; v.W = W; v.count = count; v.pitch = round_up(W, 64);
+    v.stride = (int64_t)round_up(v.pitch * H, 256);
+    return v;
+}
+
+// Which planes of a stack a call has written (the warped frames, the masks): empty until the stack has memory.
+struct WrittenFrames {
+    std::vector<uint8_t> flag;
+    void mark(int first, int count) { for (int k = first; k < first + count; ++k) flag[(size_t)k] = 1; }
+    bool all(int first, int count) const
+    {
+        for (int k = first; k < first + count; ++k)
+            if ((size_t)k >= flag.size() || !flag[(size_t)k]) return false;
+        return true;
+    }
+};
+
 struct gme_ctx {
     std::mutex mu;                // held by every C-ABI entry point for the whole call (gme_api.hip: GME_ENTER)
     int device = 0;
@@ -129,7 +151,7 @@ struct gme_seq {
     // stabilization (gme_stab.hip): the warped frames (N_cap, allocated by the first gme_seq_warp_frames), which of them a
     // warp has written, and N_cap rows of parameters and counts
     PlaneBuf warped;
-    std::vector<uint8_t> warped_written;
+    WrittenFrames warped_written;
     DevBuf<double> warp_params;          // [N_cap][8]
     DevBuf<unsigned long long> warp_counts;      // [N_cap] valid samples, or squared errors of gme_seq_frame_sse
     // background mosaic (gme_mosaic.hip): sprite and sample counts [Hc][pitch] of the last gme_seq_mosaic, the masks of
@@ -140,7 +162,7 @@ struct gme_seq {
     int mosaic_Hc = 0, mosaic_Wc = 0, mosaic_pitch = 0;
     bool mosaic_valid = false;
     PlaneBuf masks;
-    std::vector<uint8_t> masks_written;
+    WrittenFrames masks_written;
     DevBuf<double> mosaic_params;        // [N_cap][8]
     DevBuf<uint8_t> mosaic_usable;       // [N_cap]
     DevBuf<unsigned long long> mosaic_counts;    // [2][N_cap] known, moving
@@ -156,15 +178,15 @@ struct gme_seq {
 
 // ---- kernel launchers (bbme_kernels.hip) -----------------------------------
 struct BbmeJob {
-    const uint8_t* prev;          // first "previous" plane
-    const uint8_t* cur;           // first "current" plane
-    int64_t plane_stride;         // bytes between consecutive pairs' planes (same for prev/cur)
-    int pairs;
-    int H, W, pitch;
-    int bs, sw, procedure, pnorm;
-    int32_t* mf;                  // [pairs][H/bs][W/bs][2]
-    const uint32_t* sqbox_cur;    // optional, matches `cur` planes: [pairs][H][pitch] uint32 (SqTable)
-    int64_t sqbox_stride;         // elements between consecutive planes
+    const uint8_t* prev = nullptr;        // first "previous" plane
+    const uint8_t* cur = nullptr;         // first "current" plane
+    int64_t plane_stride = 0;     // bytes between consecutive pairs' planes (same for prev/cur)
+    int pairs = 0;
+    int H = 0, W = 0, pitch = 0;
+    int bs = 0, sw = 0, procedure = 0, pnorm = 0;
+    int32_t* mf = nullptr;        // [pairs][H/bs][W/bs][2]
+    const uint32_t* sqbox_cur = nullptr;  // optional, matches `cur` planes: [pairs][H][pitch] uint32 (SqTable)
+    int64_t sqbox_stride = 0;     // elements between consecutive planes
     int sqbox_kind = 0;           // what sqbox_cur holds (bbme_aux_kind): each kernel that reads it declines the other kind
     bool chained = false;         // a later chunk of one streamed call: keep the plan text and the statistics
     bool status_fresh = false;    // launch_bbme has just cleared the tile counters and redo words (first chunk of a call)
@@ -316,7 +338,11 @@ int launch_sse(gme_ctx* ctx, const uint8_t* a, int64_t a_stride, int a_pitch, co
 // ---- gme_direct.hip: direct projective refinement ---------------------------------------------
 // device blocks of the sequence's workspace for `pairs` pairs: in[P][8] (parameters the calls below read), out[P][8],
 // flags[P] (refinement results), eval[P][48] = threshold, n_valid, n_in, cost, sums[44] (gme_seq_direct_eval)
-int direct_io(gme_seq* s, int pairs, double** in, double** out, int32_t** flags, double** eval);
+struct DirectIo {
+    double *in = nullptr, *out = nullptr, *eval = nullptr;
+    int32_t* flags = nullptr;
+};
+int direct_io(gme_seq* s, int pairs, DirectIo* io);
 // the whole refinement of in[] (full-resolution start) into out[] / flags[], every launch queued, no wait
 int launch_direct_refine(gme_seq* s, int fd, int pairs, double outlier_fraction, int max_iters);
 // one evaluation of in[] (level-`level` coordinates) with a fresh threshold into eval[]

@@ -72,7 +72,7 @@ def _round_up(v, m):
 def pyr_lds_geometry(W):
     """(admitted, per_row, quads) of the LDS-tiled form for source width W: the predicate of launch_pyrdown
     (csrc/gme_kernels.hip, "LDS-tiled form", the `if (src.W % 8 == 0 && ...` above the k_pyrdown_lds launch), with the
-    plane pitch every entry point uses (W rounded up to 64 bytes, plane_alloc / gme_pyrdown_u8 in csrc/gme_api.hip)."""
+    plane pitch every entry point uses (W rounded up to 64 bytes, plane_shape in csrc/gme_internal.h)."""
     pitch = _round_up(W, 64)
     lpitch = (PYR_APRON + W + 2 + 7) & ~7
     lds = PYR_ROWS * lpitch
