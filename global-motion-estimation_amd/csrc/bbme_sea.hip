@@ -57,11 +57,12 @@ __device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int pr
     constexpr bool SKIP = GUARD == GUARD_ALL && R >= 4;
 #pragma unroll
     for (int k = 0; k < R; ++k) pkey[k] = 0xFFFFFFFFu;
+    constexpr uint32_t penalty = PENALTY;
     uint32_t seed[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         const int ri = prow * R + i;
-        seed[i] = (GUARD == GUARD_NONE || SKIP || (ri >= lo_r && ri <= hi_r)) ? 0u : PENALTY;
+        seed[i] = (GUARD == GUARD_NONE || SKIP || (ri >= lo_r && ri <= hi_r)) ? 0u : penalty;
     }
     // the lane's valid columns j = 4k + e are nlo .. nhi (none: nhi < nlo).  nlo is a multiple of 4 (sw is, block
     // columns are multiples of 16): on the low side whole patches go, after the loop.
@@ -84,7 +85,7 @@ __device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int pr
                     const uint32_t sel = (e & 1) ? 0x07060302u : 0x05040100u;
                     const uint32_t tp = __builtin_amdgcn_perm((uint32_t)(t[k + 2] >> (32 * (e >> 1))), (uint32_t)(t[k] >> (32 * (e >> 1))), sel);
                     const uint32_t bt = __builtin_amdgcn_perm((uint32_t)(b[k + 2] >> (32 * (e >> 1))), (uint32_t)(b[k] >> (32 * (e >> 1))), sel);
-                    const uint32_t start = (GUARD != GUARD_ALL || SKIP || 4 * k + e <= nhi) ? seed[i] : PENALTY;
+                    const uint32_t start = (GUARD != GUARD_ALL || SKIP || 4 * k + e <= nhi) ? seed[i] : penalty;
                     const uint32_t lb = __builtin_amdgcn_sad_u16(tp, a01, __builtin_amdgcn_sad_u16(bt, a23, start));
                     pkey[k] = min(pkey[k], (lb << 13) + (uint32_t)((4 * k + e) * R + i));
                 }
@@ -106,7 +107,7 @@ __device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int pr
 // the wave must call it (DPP); a quad is uniform in `ent` and `active`.
 // ent = wave << 25 | lane << 19 | k << 16 | bound: the patch of phase B's lane (prow, q), column group k, of block `wave`.
 template <int R>
-__device__ __forceinline__ uint32_t eval_patch_quad(const SeaDev& d, const uint32_t* win, const uint32_t* anchor, uint32_t ent,
+__device__ __forceinline__ uint32_t eval_patch_quad(const SeaGeo& d, int H, int W, const uint32_t* win, const uint32_t* anchor, uint32_t ent,
                                                     bool active, int sub, int trow, int bcol0, int NC)
 {
     const int w2 = ent >> 25, l2 = (ent >> 19) & 63, k2 = (ent >> 16) & 7;
@@ -151,8 +152,8 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaDev& d, const uint3
         // every lane of the quad holds the patch's R x 4 sums now; lane `sub` turns column `sub` into keys
         // (R candidates instead of 4 R on one lane)
         const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
-        const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, d.W - 16 - c02 + d.sw);
-        const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, d.H - 16 - r02 + d.sw);
+        const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
+        const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
         const bool rows_inside2 = NC == 16 * R && lo_r2 == 0 && hi_r2 == NC - 1;
         const int ci = q2 * 4 * R + 4 * k2 + sub, ri0 = prow2 * R;
         const uint32_t shift = (uint32_t)(sub & 1) * 16u;
@@ -185,8 +186,10 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaDev& d, const uint3
 // Phases A' .. F of one tile.  On entry the window and the anchors are staged, *count == 0 and the
 // workgroup has passed a barrier; there is no barrier after F.
 // Returns true (workgroup-uniform) when the tile was handed to the redo kernel instead (SeaDev::redo_list).
+// `d` is the geometry; frame size, ordered evaluation, redo list and result plane come from the argument segment
+// (bbme_sea_common.h: launch_args), once for phases A' .. D and once behind phase D's barrier for the rest.
 template <int R, bool FIXED>
-__device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
+__device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                             uint32_t mine, uint32_t a01, uint32_t a23, int tid, int tile_id)
 {
     // phase C2 and phase E with four lanes per patch (a quarter of the latency the other waves wait for) from R = 3 on:
@@ -202,7 +205,8 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
     uint32_t* work = lds + L.work;                         // [NB*64*R] entries: wave<<25 | lane<<19 | k<<16 | LB
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const WaveBlock wb = wave_block(d, trow, bcol0, wave);
+    const SeaArgs c = launch_args();
+    const WaveBlock wb = wave_block(d, c, trow, bcol0, wave);
     const int brow = wb.brow, bcol = wb.bcol;
     const bool wave_ok = wb.ok;                            // ragged last tile of a block row / column
     const int r0 = brow * 16, c0 = bcol * 16;
@@ -213,11 +217,11 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
     __syncthreads();
 
     // ---- B: lower bounds of the wave's own block --------------------------------------------
-    const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, d.H - 16 - r0 + d.sw);
+    const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, c->H - 16 - r0 + d.sw);
     const bool rows_inside = NC == 16 * R && lo_r == 0 && hi_r == NC - 1;   // and no padding candidates
     uint32_t ub_key = 0xFFFFFFFFu;
     if (wave_ok) {
-        const int lo_c = max(0, d.sw - c0), hi_c = min(NC - 1, d.W - 16 - c0 + d.sw);
+        const int lo_c = max(0, d.sw - c0), hi_c = min(NC - 1, c->W - 16 - c0 + d.sw);
         // per patch k: min over its candidates of (LB << 13) + local, local = (4k+e)*R + i (any
         // consistent index will do here: the bound only has to name one good candidate)
         uint32_t pkey[R];
@@ -286,11 +290,12 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
         int n_w = 0;                                       // patches the first upper bound leaves (statistics)
         if constexpr (E4) {
             // crowded?  Lanes with a surviving patch are counted first (one ballot); the exact count only where it matters
-            if (d.quota > 0 && __popcll(__ballot((lane_lb & 0xFFFFE000u) < ub_key)) > d.engage / 3) {
+            const int engage = c->engage;
+            if (c->quota > 0 && __popcll(__ballot((lane_lb & 0xFFFFE000u) < ub_key)) > engage / 3) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) n_w += __popcll(__ballot(pkd[k] < ub_key));
-                if (n_w > d.engage) {
-                    own_lim = first_round_limit(d, lb_key >> 13, ub_key >> 13, 13, [&](uint32_t lim) {
+                if (n_w > engage) {
+                    own_lim = first_round_limit(c, lb_key >> 13, ub_key >> 13, 13, [&](uint32_t lim) {
                         int c = 0;
 #pragma unroll
                         for (int k = 0; k < R; ++k) c += __popcll(__ballot(pkd[k] < lim));
@@ -316,7 +321,7 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
                     const int n_own = min(base_rank, 16);
                     const bool act = (lane >> 2) < n_own;
                     const uint32_t ent = act ? own[lane >> 2] : 0u;
-                    uint32_t key = eval_patch_quad<R>(d, win, anchor, ent, act, lane & 3, trow, bcol0, NC);
+                    uint32_t key = eval_patch_quad<R>(d, c->H, c->W, win, anchor, ent, act, lane & 3, trow, bcol0, NC);
                     ub_key = min(ub_key, wave_min_u32(key));
 #pragma unroll
                     for (int k = 0; k < R; ++k)
@@ -345,10 +350,12 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
         }
     }
     __syncthreads();
-    if (d.redo_list && (int)*count > d.redo_threshold) {     // workgroup-uniform: hostile tile, brute force is cheaper
-        if (tid == 0) push_redo(d, tile_id, (int)(blockIdx.x & 7));
+    const SeaArgs ce = launch_args();                      // phases E and F, and the test in front of them
+    if (ce->redo_list && (int)*count > ce->redo_threshold) {     // workgroup-uniform: hostile tile, brute force is cheaper
+        if (tid == 0) push_redo(ce, tile_id, (int)(blockIdx.x & 7));
         return true;
     }
+    const int H = ce->H, W = ce->W;
 
     if constexpr (E4) {
         // ---- E, R >= 3: four lanes per patch (the body of eval_patch_quad, kept inline here: the
@@ -406,8 +413,8 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
                 // every lane of the quad holds the patch's R x 4 sums now; lane `sub` turns column `sub` into keys
                 // (R candidates instead of 4 R on one lane), the quad's minimum goes to the block's best key
                 const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
-                const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, d.W - 16 - c02 + d.sw);
-                const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, d.H - 16 - r02 + d.sw);
+                const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
+                const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
                 const bool rows_inside2 = NC == 16 * R && lo_r2 == 0 && hi_r2 == NC - 1;
                 const int ci = q2 * 4 * R + 4 * k2 + sub, ri0 = prow2 * R;
                 const uint32_t shift = (uint32_t)(sub & 1) * 16u;
@@ -475,8 +482,8 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
                     }
                 }
                 const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
-                const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, d.W - 16 - c02 + d.sw);
-                const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, d.H - 16 - r02 + d.sw);
+                const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
+                const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
                 const bool rows_inside2 = NC == 16 * R && lo_r2 == 0 && hi_r2 == NC - 1;
                 const int ci0 = q2 * 4 * R + 4 * k2, ri0 = prow2 * R;
                 uint32_t key = 0xFFFFFFFFu;
@@ -514,7 +521,7 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
     if (wave_ok && lane == 0) {
         const int idx = (int)(best[2 * wave] & 0x1FFF);
         const int ci = idx / NC, ri = idx - ci * NC;
-        int32_t* o = d.mf + (((long long)pair * d.nbr + brow) * d.nbc + bcol) * 2;
+        int32_t* o = ce->mf + (((long long)pair * ce->nbr + brow) * ce->nbc + bcol) * 2;
         o[0] = ci - d.sw;
         o[1] = ri - d.sw;
         best[2 * wave + 1] = (uint32_t)idx;                   // next tile's third probe
@@ -527,7 +534,7 @@ __device__ __forceinline__ bool tile_phases(const SeaDev& d, uint32_t* lds, cons
 template <int R, bool FIXED = false>
 struct MaeTile {
     struct Pre { uint32_t a01, a23; };
-    static __device__ __forceinline__ Pre prep(const SeaDev&, uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
+    static __device__ __forceinline__ Pre prep(uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
     {
         Pre p = { 0, 0 };
         if (wave_ok) {
@@ -536,7 +543,7 @@ struct MaeTile {
         }
         return p;
     }
-    static __device__ __forceinline__ bool phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
+    static __device__ __forceinline__ bool phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                   uint32_t mine, const Pre& p, int tid, int tile_id)
     {
         return tile_phases<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, tid, tile_id);
@@ -548,17 +555,19 @@ template <int R>
 __global__ void __launch_bounds__(1024) k_exh_sea16(SeaDev d)
 {
     extern __shared__ uint32_t lds[];
-    one_tile<MaeTile<R>>(d, lds, layout_of(d, R));
+    const SeaGeo g = d;                                    // the by-value copy is read for its geometry only
+    one_tile<MaeTile<R>>(g, lds, layout_of(g, R));
 }
 
 template <int R, int NV, int GEO = 0>
 __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p(SeaDev d)
 {
     extern __shared__ uint32_t lds[];
-    fix_geometry<R, GEO>(d);
-    const Layout L = layout_of(d, R);
-    if ((threadIdx.x & 63) == 0) lds[L.best + 2 * (threadIdx.x >> 6) + 1] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);   // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MaeTile<R, GEO != 0>>(d, lds, L);
+    SeaGeo g = d;                                          // the by-value copy is read for its geometry only
+    fix_geometry<R, GEO>(g);
+    const Layout L = layout_of(g, R);
+    if ((threadIdx.x & 63) == 0) lds[L.best + 2 * (threadIdx.x >> 6) + 1] = (uint32_t)(g.sw * (2 * g.sw + 16) + g.sw);   // third probe of the first tile: the zero vector
+    persistent_tiles<NV, MaeTile<R, GEO != 0>>(g, lds, L);
 }
 
 // What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.

@@ -11,29 +11,42 @@ namespace sea {
 // weight of window sharing in the tile-shape score (plan()); tuned by same-box sweeps
 constexpr double SHARE_WEIGHT = 0.5;
 
-struct SeaDev {
-    const uint8_t* prev;
-    const uint8_t* cur;
-    long long plane_stride;
-    int pairs, H, W, pitch, sw;
-    int nbr, nbc;
+// The launch descriptor is the kernels' only parameter, by value.  It has two parts.
+//
+// SeaGeo: tile geometry and search range -- what the hot bodies use per candidate or per row.  A kernel copies this part
+// into registers (a geometry-fixed instance folds all of it to constants, fix_geometry).
+struct SeaGeo {
+    int sw;
     int tr, tc, nb;               // a tile is tr x tc macroblocks, one wave each: nb = tr * tc waves per workgroup
-    int wg_per_row, tile_rows, wg_per_pair;      // tiles per block row / tile rows / tiles per pair
     uint32_t magic_tc;            // wave / tc (div_small)
     int pitch_dw, win_rows;       // staged window: 16R + 15 + 16 (tr - 1) rows of pitch_dw dwords
     int s8_rows;                  // rows of the box-sum table: 16R + 8 + 16 (tr - 1)
     int rstep;                    // staging: window rows covered by one sweep of the workgroup (T / pitch_dw)
     uint32_t magic_pitch;         // n / pitch_dw == (n * magic_pitch) >> 20 for n < 4096 (div_small)
     uint32_t magic_xq;            // same for n / xq
+    int xq;                       // S8 quads (4 columns each) per window row
+};
+
+// SeaDev adds everything a tile needs a few times at most: planes, frame size, schedule, lists, statistics.  Device code
+// never reads these from the by-value copy -- held in SGPRs across the persistent kernels' tile loop they do not fit
+// the 80 SGPRs of 8 waves per SIMD and were spilled to VGPR lanes, to be read back one v_readlane_b32 each on every
+// tile.  It reads them from the kernel-argument segment where it needs them (SeaArgs, launch_args() below): scalar
+// loads, no vector instruction.  The fields are ordered so that what one block of the tile loop reads is contiguous
+// (the offsets are asserted behind the struct):
+//   [48, 112)   the prefetch: tile number -> pair, tile row, block column; planes; frame rows
+//   [100, 152)  the phases: frame size, ordered evaluation, redo list, result
+//   [152, 184)  schedule, statistics, MSE table
+struct SeaDev : SeaGeo {
     unsigned long long magic_wpp; // persistent kernel: n / wg_per_pair == (n * magic_wpp) >> 40 for n < 2^21
     unsigned long long magic_wpr; // same for n / wg_per_row
-    uint32_t* status;             // the context's status words (gme_internal.h: GME_STATUS_*):
-                                  //   + GME_STATUS_TILECTR  persistent kernel, dynamic schedule: one tile counter per XCD, 16 words apart
-                                  //   + GME_STATUS_STATS    per XCD, 16 words apart: [0] patches evaluated exactly (phase E), [1] tiles handed to
-                                  //                         the brute-force redo kernel, [2] patches phase D listed (what one
-                                  //                         round would have evaluated; == [0] without ordered evaluation)
-                                  //   + GME_STATUS_REDO     [0] length of redo_list
-    int dynamic;                  // persistent kernel: draw tiles from the per-XCD counters (else a static stride)
+    const uint8_t* cur;
+    const uint8_t* prev;
+    long long plane_stride;
+    int wg_per_pair, wg_per_row;  // tiles per pair / per block row
+    int pitch, H;
+    int nbr, nbc;
+    int W, pairs;
+    int32_t* mf;
     // Hostile content (nothing correlates: a scene cut, noise): the bound prunes little and phase E's one-patch-
     // per-lane evaluation costs more than evaluating everything in the regular layout of k_exh_qsad16 / k_exh_dot16.
     // A tile whose list is longer than redo_threshold skips phases E and F and goes to redo_list instead
@@ -47,11 +60,44 @@ struct SeaDev {
     // (almost) the block's true minimum (tools/ub_study.py).  quota <= 0: off.  `engage`: survivors from which a block
     // counts as crowded (>= quota).
     int quota, bisect, engage;
-    int32_t* mf;
-    int xq;                       // S8 quads (4 columns each) per window row
+    int dynamic;                  // persistent kernel: draw tiles from the per-XCD counters (else a static stride)
+    int tile_rows;                // tile rows per pair (host: grid_for)
+    uint32_t* status;             // the context's status words (gme_internal.h: GME_STATUS_*):
+                                  //   + GME_STATUS_TILECTR  persistent kernel, dynamic schedule: one tile counter per XCD, 16 words apart
+                                  //   + GME_STATUS_STATS    per XCD, 16 words apart: [0] patches evaluated exactly (phase E), [1] tiles handed to
+                                  //                         the brute-force redo kernel, [2] patches phase D listed (what one
+                                  //                         round would have evaluated; == [0] without ordered evaluation)
+                                  //   + GME_STATUS_REDO     [0] length of redo_list
     const uint32_t* sqbox;        // MSE only: 16x16 box sums of squares of `cur`, [pairs][H][pitch]
     long long sqbox_stride;
 };
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"     // a base and a derived class with members: not standard-layout, offsets still fixed
+static_assert(sizeof(SeaGeo) == 48 && __builtin_offsetof(SeaDev, magic_wpp) == 48 && __builtin_offsetof(SeaDev, nbc) == 108 &&
+              __builtin_offsetof(SeaDev, H) == 100 && __builtin_offsetof(SeaDev, engage) == 148 && sizeof(SeaDev) == 184,
+              "SeaDev: the groups a block of the tile loop reads with one wide scalar load");
+#pragma clang diagnostic pop
+
+// The kernel's own argument segment, seen as the SeaDev it holds (the only parameter: offset 0).  Every call returns a
+// pointer the compiler knows nothing about (the empty asm), so the loads through it stay where they are written: they
+// are neither hoisted out of the tile loop nor shared between two calls, and nothing read through it stays live
+// longer than its block.  Take one per block of work (a prefetch, a tile's phases, the loop tail), never one per kernel.
+typedef const __attribute__((address_space(4))) SeaDev* SeaArgs;
+__device__ __forceinline__ SeaArgs launch_args()
+{
+    SeaArgs p = (SeaArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+// gridDim.x from the same pointer: the hidden arguments follow the explicit ones in the segment (8-byte aligned), and
+// their first word is the grid's workgroup count in x (hidden_block_count_x, code object v5 and later; the kernels
+// read blockDim.x too, so the hidden block is always part of their segment).  One load with a constant offset: going
+// through __builtin_amdgcn_implicitarg_ptr() would put a second base register into the loop.
+static_assert(sizeof(SeaDev) % 8 == 0, "the hidden arguments start right behind SeaDev");
+__device__ __forceinline__ int launch_groups_x(SeaArgs c)
+{
+    return (int)*(const __attribute__((address_space(4))) uint32_t*)(c + 1);
+}
 
 typedef uint64_t u64_a4 __attribute__((aligned(4)));
 
@@ -68,12 +114,12 @@ __device__ __forceinline__ int div_small(int n, uint32_t magic) { return (int)(_
 // Workgroup -> (pair, tile row, first block column).  Grid = (8 * wg_per_row, tile_rows, ceil(pairs / 8)):
 // workgroups go to the 8 XCDs round robin in x-fastest order, so the low 3 bits of blockIdx.x pick
 // the pair inside a group of 8 and all tiles of one pair land on one XCD (its L2 holds the pair).
-__device__ __forceinline__ bool locate(const SeaDev& d, int* pair, int* trow, int* bcol0)
+__device__ __forceinline__ bool locate(const SeaGeo& d, SeaArgs c, int* pair, int* trow, int* bcol0)
 {
     *pair = (int)blockIdx.z * 8 + (int)(blockIdx.x & 7);
     *trow = (int)blockIdx.y;
     *bcol0 = (int)(blockIdx.x >> 3) * d.tc;
-    return *pair < d.pairs;
+    return *pair < c->pairs;
 }
 
 inline bool grid_for(const SeaDev& d, dim3* grid)
@@ -111,7 +157,7 @@ __host__ __device__ constexpr Layout make_layout(int R, int nb, int win_rows, in
     return l;
 }
 
-__device__ __forceinline__ Layout layout_of(const SeaDev& d, int R)
+__device__ __forceinline__ Layout layout_of(const SeaGeo& d, int R)
 {
     return make_layout(R, d.nb, d.win_rows, d.pitch_dw, d.xq, d.s8_rows);
 }
@@ -122,30 +168,31 @@ struct WaveBlock {
     int brow, bcol;               // block coordinates in the frame
     bool ok;                      // inside the frame's block grid (ragged last tile of a row / column)
 };
-__device__ __forceinline__ WaveBlock wave_block(const SeaDev& d, int trow, int bcol0, int wave)
+__device__ __forceinline__ WaveBlock wave_block(const SeaGeo& d, SeaArgs c, int trow, int bcol0, int wave)
 {
     WaveBlock b;
     b.wr = div_small(wave, d.magic_tc);
     b.wc = wave - b.wr * d.tc;
     b.brow = trow * d.tr + b.wr;
     b.bcol = bcol0 + b.wc;
-    b.ok = b.bcol < d.nbc && b.brow < d.nbr;
+    b.ok = b.bcol < c->nbc && b.brow < c->nbr;
     return b;
 }
 
 // A: stage the common search window of the workgroup's blocks (coalesced dword loads; rows and
 // columns outside the frame -> 0).  Thread -> one dword column and every rstep-th row, loads in
 // batches of four so that their latencies overlap.
-__device__ __forceinline__ void stage_window(const SeaDev& d, uint32_t* win, const uint8_t* cur, int bcol0, int r0)
+__device__ __forceinline__ void stage_window(const SeaGeo& d, SeaArgs c, uint32_t* win, const uint8_t* cur, int bcol0, int r0)
 {
+    const int pitch = c->pitch, H = c->H;
     const int gx0 = bcol0 * 16 - d.sw, gy0 = r0 - d.sw;
     const int rstep = d.rstep;
     const int row0 = div_small((int)threadIdx.x, d.magic_pitch), dw = (int)threadIdx.x - row0 * d.pitch_dw;
     const int gx = gx0 + 4 * dw;
-    const bool colok = gx >= 0 && gx < d.pitch;
+    const bool colok = gx >= 0 && gx < pitch;
     if (row0 < rstep) {
-        const uint8_t* src = cur + (long long)(gy0 + row0) * d.pitch + gx;
-        const long long sstep = (long long)rstep * d.pitch;
+        const uint8_t* src = cur + (long long)(gy0 + row0) * pitch + gx;
+        const long long sstep = (long long)rstep * pitch;
         uint32_t* dst = win + threadIdx.x;                     // == row0 * pitch_dw + dw
         const int dstep = rstep * d.pitch_dw;
         for (int row = row0; row < d.win_rows; row += 4 * rstep, src += 4 * sstep, dst += 4 * dstep) {
@@ -154,7 +201,7 @@ __device__ __forceinline__ void stage_window(const SeaDev& d, uint32_t* win, con
             for (int u = 0; u < 4; ++u) {
                 const int gy = gy0 + row + u * rstep;
                 v[u] = 0;
-                if (colok && row + u * rstep < d.win_rows && gy >= 0 && gy < d.H) v[u] = *(const uint32_t*)(src + u * sstep);
+                if (colok && row + u * rstep < d.win_rows && gy >= 0 && gy < H) v[u] = *(const uint32_t*)(src + u * sstep);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -192,7 +239,7 @@ __device__ __forceinline__ void stage_window(const SeaDev& d, uint32_t* win, con
 // CH = s8_rows / 8 is a template parameter so that the ring indices and the warm-up are resolved
 // at compile time (a run-time row count cost 5 % of the whole search in guards).
 template <int CH, bool FIXED>
-__device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid, int need)
+__device__ __forceinline__ void box_sums8_ch(const SeaGeo& d, const uint32_t* win, uint64_t* s8, int tid, int need)
 {
     static_assert((CH + 7) * 1020 < 65536, "cumulative 4-byte sums must fit 16 bits");
     const int XQ = d.xq;
@@ -254,7 +301,7 @@ __device__ __forceinline__ void box_sums8_ch(const SeaDev& d, const uint32_t* wi
 // chunk's work and 28 % of an 18-row one's, but half as many lanes share it; A/B in DESIGN.md)
 // FIXED: the caller is a geometry-fixed instance (fix_geometry): d.pitch_dw and d.xq are compile-time constants there
 template <int R, bool FIXED>
-__device__ __forceinline__ void box_sums8(const SeaDev& d, const uint32_t* win, uint64_t* s8, int tid)
+__device__ __forceinline__ void box_sums8(const SeaGeo& d, const uint32_t* win, uint64_t* s8, int tid)
 {
     const int need = 4 * R + 4 * (d.tc - 1) + 2;           // quads per row the bound phase reads (shape_of); XQ >= need
     if (d.tr == 1) box_sums8_ch<2 * R + 1, FIXED>(d, win, s8, tid, need);
@@ -352,11 +399,11 @@ constexpr Shape shape_of(int R, int tr, int tc)
 }
 
 // Kernels instantiated for one tile shape (GEO = tr * 16 + tc, 0 = any shape at run time) overwrite the
-// geometry fields of their by-value launch descriptor with constants: the compiler then folds every use
+// geometry part of their by-value launch descriptor (SeaGeo) with constants: the compiler then folds every use
 // (strides become immediates, the multiply-shift divisions constants, ~15 SGPRs are never loaded).
 // The host launches such an instance only when plan() chose exactly that shape (geometry_matches).
 template <int R, int GEO>
-__device__ __forceinline__ void fix_geometry(SeaDev& d)
+__device__ __forceinline__ void fix_geometry(SeaGeo& d)
 {
     if constexpr (GEO != 0) {
         constexpr int TR = GEO / 16, TC = GEO % 16;
@@ -439,11 +486,12 @@ constexpr int SEA_DEFAULT_QUOTA = 16, SEA_DEFAULT_BISECT = 5, SEA_DEFAULT_ENGAGE
 constexpr int REDO_BURST = 15;
 constexpr double REDO_DEFAULT_FRAC = 0.75;     // break-even measured on noise content
 
-__device__ __forceinline__ void push_redo(const SeaDev& d, int tile_in_xcd, int xcd)
+__device__ __forceinline__ void push_redo(SeaArgs c, int tile_in_xcd, int xcd)
 {
-    const uint32_t slot = atomicAdd(d.status + GME_STATUS_REDO, 1u);
-    d.redo_list[slot] = ((uint32_t)tile_in_xcd << 3) | (uint32_t)xcd;
-    atomicAdd(d.status + GME_STATUS_STATS + 16 * xcd + 1, 1u);
+    uint32_t* status = c->status;
+    const uint32_t slot = atomicAdd(status + GME_STATUS_REDO, 1u);
+    c->redo_list[slot] = ((uint32_t)tile_in_xcd << 3) | (uint32_t)xcd;
+    atomicAdd(status + GME_STATUS_STATS + 16 * xcd + 1, 1u);
 }
 
 // Phase C2's choice of a crowded block's first patches (wave-uniform): keys below the returned limit are scored first.
@@ -451,64 +499,75 @@ __device__ __forceinline__ void push_redo(const SeaDev& d, int tile_in_xcd, int 
 // `shift` = position of the bound inside a key).  Invariant: at most `quota` keys lie below (lo + 1) << shift, or lo is
 // the smallest bound itself (ties may exceed the quota: they all go first).
 template <class Below>
-__device__ __forceinline__ uint32_t first_round_limit(const SeaDev& d, uint32_t lo, uint32_t hi, int shift, Below below)
+__device__ __forceinline__ uint32_t first_round_limit(SeaArgs c, uint32_t lo, uint32_t hi, int shift, Below below)
 {
-    if (d.bisect < 0) return (lo + ((hi - lo) >> -d.bisect) + 1) << shift;      // no search: the lowest 1 / 2^n of the range
-    for (int s = 0; s < d.bisect && lo < hi; ++s) {
+    const int bisect = c->bisect, quota = c->quota;
+    if (bisect < 0) return (lo + ((hi - lo) >> -bisect) + 1) << shift;      // no search: the lowest 1 / 2^n of the range
+    for (int s = 0; s < bisect && lo < hi; ++s) {
         const uint32_t mid = (lo + hi) >> 1;
-        if ((int)below((mid + 1) << shift) > d.quota) hi = mid; else lo = mid;
+        if ((int)below((mid + 1) << shift) > quota) hi = mid; else lo = mid;
     }
     return (lo + 1) << shift;
 }
 
 // tile number (inside its XCD's tiles) of the one-tile kernels' workgroup: what persistent_tiles calls `t`
-__device__ __forceinline__ int tile_number(const SeaDev& d, int pair, int trow, int bcol0)
+__device__ __forceinline__ int tile_number(const SeaGeo& d, SeaArgs c, int pair, int trow, int bcol0)
 {
-    return (pair >> 3) * d.wg_per_pair + trow * d.wg_per_row + div_small(bcol0, d.magic_tc);
+    return (pair >> 3) * c->wg_per_pair + trow * c->wg_per_row + div_small(bcol0, d.magic_tc);
 }
 
 // Kern (MaeTile in bbme_sea.hip, MseTile in bbme_sea_mse.hip) supplies what the two drivers below call per tile:
-//   Pre prep(d, lds, L, wave, lane, wave_ok, mine)          the wave's anchor dword -> LDS, per-wave anchor statistics
+//   Pre prep(lds, L, wave, lane, wave_ok, mine)             the wave's anchor dword -> LDS, per-wave anchor statistics
 //   bool phases(d, lds, L, pair, trow, bcol0, mine, pre, tid, tile_id)   phases A' .. F; true: the tile went to redo_list
 //   int probe_word(L, wave)                                 LDS word of the wave's third probe: the vector its block of the
 //                                                           previous tile ended with (one_tile seeds it with the zero
 //                                                           vector; the persistent kernels seed the same word themselves)
+// `d` is the geometry part alone; what else a phase needs it reads through launch_args().
 // Count words (Layout::count) both drivers clear per tile and fold into the statistics (SeaDev::status, GME_STATUS_STATS):
 // [0] list length, [4] / [5] what phase C2 took off the list / scored, [7] MSE: length of the second list.
 
 // One-tile form of a search kernel: one workgroup per tile (grid_for, locate), the third probe seeded with the zero vector.
 template <class Kern>
-__device__ __forceinline__ void one_tile(const SeaDev& d, uint32_t* lds, const Layout L)
+__device__ __forceinline__ void one_tile(const SeaGeo& d, uint32_t* lds, const Layout L)
 {
+    const SeaArgs c = launch_args();
     int pair, trow, bcol0;
-    if (!locate(d, &pair, &trow, &bcol0)) return;          // whole workgroup
+    if (!locate(d, c, &pair, &trow, &bcol0)) return;       // whole workgroup
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     // ---- A: window, anchor
-    stage_window(d, lds + L.win, d.cur + (long long)pair * d.plane_stride, bcol0, trow * d.tr * 16);
+    const long long plane = (long long)pair * c->plane_stride;
+    stage_window(d, c, lds + L.win, c->cur + plane, bcol0, trow * d.tr * 16);
     uint32_t mine = 0;
-    const WaveBlock wb = wave_block(d, trow, bcol0, wave);
+    const WaveBlock wb = wave_block(d, c, trow, bcol0, wave);
     if (wb.ok) {
-        const uint8_t* aptr = d.prev + (long long)pair * d.plane_stride + (long long)(wb.brow * 16) * d.pitch + wb.bcol * 16;
-        mine = *(const uint32_t*)(aptr + (long long)(lane >> 2) * d.pitch + (lane & 3) * 4);
+        const int pitch = c->pitch;
+        const uint8_t* aptr = c->prev + plane + (long long)(wb.brow * 16) * pitch + wb.bcol * 16;
+        mine = *(const uint32_t*)(aptr + (long long)(lane >> 2) * pitch + (lane & 3) * 4);
     }
-    const typename Kern::Pre pre = Kern::prep(d, lds, L, wave, lane, wb.ok, mine);
+    const typename Kern::Pre pre = Kern::prep(lds, L, wave, lane, wb.ok, mine);
     if (lane == 0) lds[Kern::probe_word(L, wave)] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);      // no previous tile: the zero vector
     if (threadIdx.x == 0) { lds[L.count] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0; }
     __syncthreads();
-    Kern::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, pair, trow, bcol0));
+    Kern::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, c, pair, trow, bcol0));
     if (threadIdx.x == 0) {                                // the counts are final behind phase D's barrier
-        atomicAdd(d.status + GME_STATUS_STATS + 16 * (blockIdx.x & 7), lds[L.count] + lds[L.count + 5]);
-        atomicAdd(d.status + GME_STATUS_STATS + 16 * (blockIdx.x & 7) + 2, lds[L.count] + lds[L.count + 4]);
+        uint32_t* stats = launch_args()->status + GME_STATUS_STATS + 16 * (blockIdx.x & 7);
+        atomicAdd(stats, lds[L.count] + lds[L.count + 5]);
+        atomicAdd(stats + 2, lds[L.count] + lds[L.count + 4]);
     }
 }
+
+// tiles of the pairs with pair % 8 == xcd: what a persistent workgroup of that XCD walks
+__device__ __forceinline__ int tiles_of_xcd(SeaArgs c, int xcd) { return ((c->pairs - xcd + 7) >> 3) * c->wg_per_pair; }
+// the XCD's tile counter (dynamic schedule), or null (static)
+__device__ __forceinline__ uint32_t* tile_counter(SeaArgs c, int xcd) { return c->dynamic ? c->status + GME_STATUS_TILECTR + 16 * xcd : nullptr; }
 
 // Persistent form of a search kernel: G workgroups (as many as fit on the chip at once) walk the
 // tiles of "their" XCD's pairs.  The window and anchor of the next tile are fetched into registers
 // while the current one is searched, so the HBM/L2 latency of phase A overlaps phases A' .. F
 // instead of idling the workgroup's waves.
 //
-// Schedule: static (tile += G/8) or, with d.dynamic, dynamic: after its first tile a workgroup
+// Schedule: static (tile += G/8) or, with SeaDev::dynamic, dynamic: after its first tile a workgroup
 // draws tile numbers G/8 + n from its XCD's counter.  Thread 0 asks one tile ahead, so the
 // atomic's round trip is waited for together with the prefetched window (same vmcnt).  It is an
 // atomicInc, not atomicAdd: LLVM would aggregate an add over the wave and wait for its result at once.
@@ -516,61 +575,78 @@ __device__ __forceinline__ void one_tile(const SeaDev& d, uint32_t* lds, const L
 // Everything derived from the thread index is recomputed per tile from an opaque copy (the empty
 // asm): hoisted out of the tile loop those values cost more registers than the 64 that eight
 // waves per SIMD allow, and a spill reload (vmcnt) would wait for the prefetch it sits behind.
+// The launch constants get the same treatment on the scalar side.  The loop carries the geometry (`d`: constants in
+// a geometry-fixed instance), the LDS layout, the workgroup's number and the current tile; planes, frame size, the
+// schedule's constants, counters and lists are read from the argument segment (launch_args()) by the block that uses
+// them -- the prefetch, the tile's phases, the loop's head and tail -- and what follows from them alone (tiles of this
+// XCD, G / 8, the counter's address, the plane's extent, the staging stride) is recomputed there by scalar
+// instructions.  Carried, they were 44 to 95 spilled SGPRs per instance, read back from VGPR lanes on every tile.
 template <int NV, class Kern>
-__device__ __forceinline__ void persistent_tiles(const SeaDev& d, uint32_t* lds, const Layout L)
+__device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds, const Layout L)
 {
-    const int xcd = blockIdx.x & 7, gx = gridDim.x >> 3;
-    const int npairs_x = (d.pairs - xcd + 7) >> 3;          // pairs with pair % 8 == xcd
-    const int ntiles = npairs_x * d.wg_per_pair;
+    const int xcd = blockIdx.x & 7;
     int tile = blockIdx.x >> 3;
-    if (tile >= ntiles) return;
+    if (tile >= tiles_of_xcd(launch_args(), xcd)) return;
+    // the thread index, made opaque again at every use: ONE register carries it through the loop (a copy per tile
+    // beside threadIdx.x itself would be two), and nothing derived from it -- a lane mask such as `thread 0` is two
+    // SGPRs -- is kept across the phases
+    int tid_carried = (int)threadIdx.x;
+    auto opaque_tid = [&]() {
+        asm volatile("" : "+v"(tid_carried));
+        return tid_carried;
+    };
 
     uint32_t wv[NV], an_next = 0;
     int pair = 0, trow = 0, bcol0 = 0;
-    auto fetch = [&](int t) {
-        int tid = (int)threadIdx.x;
-        asm volatile("" : "+v"(tid));
+    auto fetch = [&](int t, int tid) {
+        const SeaArgs c = launch_args();
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
         const int row0 = div_small(tid, d.magic_pitch), dw = tid - row0 * d.pitch_dw;
-        const int lp = (int)(((unsigned long long)(unsigned)t * d.magic_wpp) >> 40);
-        const int wg = t - lp * d.wg_per_pair;
-        trow = (int)(((unsigned long long)(unsigned)wg * d.magic_wpr) >> 40);
-        bcol0 = (wg - trow * d.wg_per_row) * d.tc;
+        const int lp = (int)(((unsigned long long)(unsigned)t * c->magic_wpp) >> 40);
+        const int wg = t - lp * c->wg_per_pair;
+        const int wpr = c->wg_per_row;
+        trow = (int)(((unsigned long long)(unsigned)wg * c->magic_wpr) >> 40);
+        bcol0 = (wg - trow * wpr) * d.tc;
         pair = lp * 8 + xcd;
         // Window rows through a buffer resource over the pair's `cur` plane (H * pitch bytes): rows above or below
         // the frame give offsets outside it and the hardware range check returns 0 -- what the search wants there
         // (bbme.py:157-162 skips such candidates; they never form keys) -- so no per-row guard or branch is left.
         // Columns outside the plane and threads beyond the staging sweep get an offset that is out of range by itself.
-        const uint8_t* cur = d.cur + (long long)pair * d.plane_stride;
+        const int pitch = c->pitch;
+        const long long plane = (long long)pair * c->plane_stride;
+        const uint8_t* cur = c->cur + plane;
         const unsigned long long cur_bits = (unsigned long long)cur;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(cur_bits >> 32)) << 32) |
                     (unsigned)__builtin_amdgcn_readfirstlane((int)cur_bits)),
-            (short)0, __builtin_amdgcn_readfirstlane(d.H * d.pitch), 0x00020000);
+            (short)0, __builtin_amdgcn_readfirstlane(c->H * pitch), 0x00020000);
         const int gx0 = bcol0 * 16 - d.sw + 4 * dw, gy0 = trow * d.tr * 16 - d.sw + row0;
-        const bool colok = row0 < d.rstep && gx0 >= 0 && gx0 < d.pitch;
-        const int off0 = colok ? gy0 * d.pitch + gx0 : (int)0x80000000;
-        const int sstep = d.rstep * d.pitch;
+        const bool colok = row0 < d.rstep && gx0 >= 0 && gx0 < pitch;
+        int outside = (int)0x80000000;                      // formed here, per prefetch: hoisted, the constant holds a VGPR across the phases
+        asm volatile("" : "+v"(outside));
+        const int off0 = colok ? gy0 * pitch + gx0 : outside;
+        const int sstep = d.rstep * pitch;
 #pragma unroll
         for (int u = 0; u < NV; ++u)
             wv[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, colok ? off0 + u * sstep : off0, 0, 0);
         an_next = 0;
-        const WaveBlock wb = wave_block(d, trow, bcol0, wave);
+        const WaveBlock wb = wave_block(d, c, trow, bcol0, wave);
         if (wb.ok) {
-            const uint8_t* aptr = d.prev + (long long)pair * d.plane_stride + (long long)(wb.brow * 16) * d.pitch + wb.bcol * 16;
-            an_next = *(const uint32_t*)(aptr + (long long)(lane >> 2) * d.pitch + (lane & 3) * 4);
+            const uint8_t* aptr = c->prev + plane + (long long)(wb.brow * 16) * pitch + wb.bcol * 16;
+            an_next = *(const uint32_t*)(aptr + (long long)(lane >> 2) * pitch + (lane & 3) * 4);
         }
     };
-    fetch(tile);
-    uint32_t* ctr = d.dynamic ? d.status + GME_STATUS_TILECTR + 16 * xcd : nullptr;
+    fetch(tile, opaque_tid());
     uint32_t drawn = 0;
-    if (ctr && threadIdx.x == 0) drawn = atomicInc(ctr, 0xFFFFFFFFu);
-    if (threadIdx.x == 0) { lds[L.count] = 0; lds[L.count + 3] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0; }
+    if (opaque_tid() == 0) {
+        if (uint32_t* ctr = tile_counter(launch_args(), xcd)) drawn = atomicInc(ctr, 0xFFFFFFFFu);
+        lds[L.count] = 0; lds[L.count + 3] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0;
+    }
     uint32_t stat_scored = 0, stat_listed = 0;             // thread 0's: patches scored exactly / left by the first upper bounds
     for (;;) {
-        int tid = (int)threadIdx.x;
-        asm volatile("" : "+v"(tid));
+        const int tid = opaque_tid();
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+        const int gx = launch_groups_x(launch_args()) >> 3;             // G / 8, for thread 0 below: asked for here, ahead of the LDS stores
         {   // registers -> LDS
             const int row0 = div_small(tid, d.magic_pitch);
             if (row0 < d.rstep) {
@@ -583,21 +659,26 @@ __device__ __forceinline__ void persistent_tiles(const SeaDev& d, uint32_t* lds,
         }
         const int pair_c = pair, trow_c = trow, bcol0_c = bcol0, tile_c = tile;
         const uint32_t mine = an_next;
-        const typename Kern::Pre pre = Kern::prep(d, lds, L, wave, lane, wave_block(d, trow_c, bcol0_c, wave).ok, mine);
+        const typename Kern::Pre pre = Kern::prep(lds, L, wave, lane, wave_block(d, launch_args(), trow_c, bcol0_c, wave).ok, mine);
         if (tid == 0) {
             // the finished tile's counts (final behind its phase D barrier) -> statistics, then cleared for this tile
             const uint32_t listed = lds[L.count], c2_off = lds[L.count + 4], c2_scored = lds[L.count + 5];
             stat_scored += listed + c2_scored;
             stat_listed += listed + c2_off;
             lds[L.count] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0;
-            if (ctr) lds[L.count + 1] = (uint32_t)gx + drawn;
+            lds[L.count + 1] = (uint32_t)gx + drawn;       // dynamic schedule: the next tile (static: not read)
         }
         __syncthreads();
-        tile = ctr ? (int)lds[L.count + 1] : tile + gx;
-        const bool more = tile < ntiles;                   // workgroup-uniform
-        if (more) {
-            fetch(tile);
-            if (ctr && tid == 0) drawn = atomicInc(ctr, 0xFFFFFFFFu);
+        bool more, dynamic;
+        {   // loop tail, first half: the next tile, prefetched behind this one's phases
+            const SeaArgs c = launch_args();
+            dynamic = c->dynamic != 0;
+            tile = dynamic ? (int)lds[L.count + 1] : tile + (launch_groups_x(c) >> 3);
+            more = tile < tiles_of_xcd(c, xcd);            // workgroup-uniform
+            if (more) {
+                fetch(tile, tid);
+                if (dynamic && tid == 0) drawn = atomicInc(c->status + GME_STATUS_TILECTR + 16 * xcd, 0xFFFFFFFFu);
+            }
         }
         // A hostile tile is handed to the redo kernel.  When the tile this workgroup processed just before was
         // hostile too (a scene cut, a noisy shot: not an isolated occlusion), thread 0's wave also draws the next
@@ -606,17 +687,18 @@ __device__ __forceinline__ void persistent_tiles(const SeaDev& d, uint32_t* lds,
         // for the bound phases before brute force does the work anyway; friendly content never takes the branch.
         if (!Kern::phases(d, lds, L, pair_c, trow_c, bcol0_c, mine, pre, tid, tile_c)) {
             if (tid == 0) lds[L.count + 3] = 0;            // streak of hostile tiles (thread 0's word)
-        } else if (ctr && wave == 0) {
+        } else if (dynamic && wave == 0) {
             const int streak = (int)lds[L.count + 3];      // same address for the whole wave; only thread 0 writes it
             const int burst = streak == 0 ? 0 : streak == 1 ? 3 : streak == 2 ? 7 : REDO_BURST;
             if (burst) {
                 // lane 0 lists the tile it had drawn already, lanes 1 .. burst draw one each (one wave-aggregated
                 // atomic); the last of those becomes thread 0's new `drawn`, the others are listed
+                const SeaArgs c = launch_args();
                 uint32_t got = 0;
-                if (lane >= 1 && lane <= burst) got = atomicAdd(ctr, 1u);
-                const int t = gx + (int)(lane == 0 ? drawn : got);
-                if (lane < burst && t < ntiles) push_redo(d, t, xcd);
-                drawn = (uint32_t)__shfl((int)got, burst, 64);
+                if (lane >= 1 && lane <= burst) got = atomicAdd(c->status + GME_STATUS_TILECTR + 16 * xcd, 1u);
+                const int t = (launch_groups_x(c) >> 3) + (int)(lane == 0 ? drawn : got);
+                if (lane < burst && t < tiles_of_xcd(c, xcd)) push_redo(c, t, xcd);
+                drawn = (uint32_t)__builtin_amdgcn_readlane((int)got, __builtin_amdgcn_readfirstlane(burst));   // burst is wave-uniform
             }
             if (lane == 0) lds[L.count + 3] = (uint32_t)(streak + 1);
         }
@@ -627,9 +709,10 @@ __device__ __forceinline__ void persistent_tiles(const SeaDev& d, uint32_t* lds,
         // (the count words: a wave that has not read the list length yet can only be in a tile whose list is empty).
     }
     // thread 0 has passed the barrier behind phase D: the last tile's counts are final
-    if (threadIdx.x == 0) {
-        atomicAdd(d.status + GME_STATUS_STATS + 16 * xcd, stat_scored + lds[L.count] + lds[L.count + 5]);
-        atomicAdd(d.status + GME_STATUS_STATS + 16 * xcd + 2, stat_listed + lds[L.count] + lds[L.count + 4]);
+    if (opaque_tid() == 0) {
+        uint32_t* stats = launch_args()->status + GME_STATUS_STATS + 16 * xcd;
+        atomicAdd(stats, stat_scored + lds[L.count] + lds[L.count + 5]);
+        atomicAdd(stats + 2, stat_listed + lds[L.count] + lds[L.count + 4]);
     }
 }
 

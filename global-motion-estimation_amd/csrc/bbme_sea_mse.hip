@@ -143,7 +143,7 @@ __device__ __forceinline__ uint32_t bounds2_patch(const uint64_t* sp, int XQ, in
 
 // Phases A' .. F of one tile (entry conditions as tile_phases() of bbme_sea.hip, plus a2s[] filled).
 template <int R, bool FIXED>
-__device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
+__device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                 uint32_t mine, uint32_t a01, uint32_t a23, uint32_t mine2, int tid, int tile_id)
 {
     constexpr bool TWO = R >= TWO_LEVEL_FROM;     // two-level bound: L1 form for every candidate, squared form for the listed patches
@@ -158,7 +158,8 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
     uint32_t* work = lds + L.work;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const WaveBlock wb = wave_block(d, trow, bcol0, wave);
+    const SeaArgs c = launch_args();                       // phases A' .. D (bbme_sea.hip: tile_phases)
+    const WaveBlock wb = wave_block(d, c, trow, bcol0, wave);
     const int brow = wb.brow, bcol = wb.bcol;
     const bool wave_ok = wb.ok;
     const int r0 = brow * 16, c0 = bcol * 16;
@@ -169,10 +170,10 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
     __syncthreads();
 
     // ---- B
-    const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, d.H - 16 - r0 + d.sw);
+    const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, c->H - 16 - r0 + d.sw);
     const bool rows_inside = NC == 16 * R && lo_r == 0 && hi_r == NC - 1;   // and no padding candidates
     if (wave_ok) {
-        const int lo_c = max(0, d.sw - c0), hi_c = min(NC - 1, d.W - 16 - c0 + d.sw);
+        const int lo_c = max(0, d.sw - c0), hi_c = min(NC - 1, c->W - 16 - c0 + d.sw);
         uint32_t pkey[R];
         const uint64_t* sp0 = s8 + (16 * wb.wr + prow * R) * XQ + wb.wc * 4 + q * R;
         uint32_t patch_lb[R], lb_key = 0xFFFFFFFFu;        // patch_lb: the patch's smallest bound (TWO: L1; else floor(LBx / 32), 25 bits)
@@ -261,10 +262,12 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
         (void)ub25;
     }
     __syncthreads();
-    if (d.redo_list && (int)*count > d.redo_threshold) {     // workgroup-uniform: hostile tile, brute force is cheaper
-        if (tid == 0) push_redo(d, tile_id, (int)(blockIdx.x & 7));
+    const SeaArgs ce = launch_args();                      // phases D2 .. F, and the test in front of them
+    if (ce->redo_list && (int)*count > ce->redo_threshold) {     // workgroup-uniform: hostile tile, brute force is cheaper
+        if (tid == 0) push_redo(ce, tile_id, (int)(blockIdx.x & 7));
         return true;
     }
+    const int H = ce->H, W = ce->W, pitch = ce->pitch;
     // ---- D2 (TWO): level 2 -- the squared bound of the listed patches, one lane per patch; survivors go to a second list at the far
     // end of `work` (the lists cannot meet while the first holds at most half of the tile's patches; a longer one is scored as it is)
     const uint32_t* list = work;
@@ -294,7 +297,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
 
     // ---- E: one lane per listed patch (R + 15 window rows).  Four lanes per patch, four anchor rows each, would put four
     // times as many waves on the (long) evaluation but repeat the v_alignbyte work: measured 9 % slower.
-    const SqTable tab = sq_table(d.sqbox + (long long)pair * d.sqbox_stride, d.H, d.pitch);
+    const SqTable tab = sq_table(ce->sqbox + (long long)pair * ce->sqbox_stride, H, pitch);
     for (int base = 0; base < n; base += T) {
         const int e = base + tid;
         bool active = e < n;
@@ -359,17 +362,17 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
         }
         if (active) {
             const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
-            const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, d.W - 16 - c02 + d.sw);
-            const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, d.H - 16 - r02 + d.sw);
+            const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
+            const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
             const bool rows_inside2 = NC == 16 * R && lo_r2 == 0 && hi_r2 == NC - 1;
             const uint32_t a2 = a2s[w2];
             unsigned long long key = ~0ull;
             const int ci0 = q2 * 4 * R + 4 * k2, ri0 = prow2 * R;
-            const long long tabrow = (long long)(r02 - d.sw + ri0) * d.pitch + (c02 - d.sw + ci0);     // % 4 == 0
+            const long long tabrow = (long long)(r02 - d.sw + ri0) * pitch + (c02 - d.sw + ci0);     // % 4 == 0
             if (rows_inside2 && lo_c == 0 && hi_c == NC - 1) {
                 uint32_t b2[R][4];                             // all table reads in flight before the first use
 #pragma unroll
-                for (int i = 0; i < R; ++i) sq4(tab, tabrow + (long long)i * d.pitch, b2[i]);
+                for (int i = 0; i < R; ++i) sq4(tab, tabrow + (long long)i * pitch, b2[i]);
 #pragma unroll
                 for (int e4 = 0; e4 < 4; ++e4)
 #pragma unroll
@@ -386,7 +389,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
                     for (int i = 0; i < R; ++i) {
                         const int ri = ri0 + i;
                         if (ri < lo_r2 || ri > hi_r2) continue;
-                        const uint32_t cost = a2 + sq1(tab, tabrow + (long long)i * d.pitch + e4) - 2u * acc[i][e4];
+                        const uint32_t cost = a2 + sq1(tab, tabrow + (long long)i * pitch + e4) - 2u * acc[i][e4];
                         key = u64min_(key, ((unsigned long long)cost << 13) | (unsigned)(ci * NC + ri));
                     }
                 }
@@ -400,7 +403,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
     if (wave_ok && lane == 0) {
         const int idx = (int)(best[wave] & 0x1FFF);
         const int ci = idx / NC, ri = idx - ci * NC;
-        int32_t* o = d.mf + (((long long)pair * d.nbr + brow) * d.nbc + bcol) * 2;
+        int32_t* o = ce->mf + (((long long)pair * ce->nbr + brow) * ce->nbc + bcol) * 2;
         o[0] = ci - d.sw;
         o[1] = ri - d.sw;
         lds[L.prev + wave] = (uint32_t)idx;                // next tile's third probe
@@ -413,7 +416,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaDev& d, uint32_t* lds, 
 template <int R, bool FIXED = false>
 struct MseTile {
     struct Pre { uint32_t a01, a23, mine2; };
-    static __device__ __forceinline__ Pre prep(const SeaDev&, uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
+    static __device__ __forceinline__ Pre prep(uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
     {
         Pre p = { 0, 0, 0 };
         if (wave_ok) {
@@ -428,7 +431,7 @@ struct MseTile {
         }
         return p;
     }
-    static __device__ __forceinline__ bool phases(const SeaDev& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
+    static __device__ __forceinline__ bool phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                   uint32_t mine, const Pre& p, int tid, int tile_id)
     {
         return tile_phases_mse<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id);
@@ -440,17 +443,19 @@ template <int R>
 __global__ void __launch_bounds__(1024) k_exh_sea16_mse(SeaDev d)
 {
     extern __shared__ uint32_t lds[];
-    one_tile<MseTile<R>>(d, lds, layout_of(d, R));
+    const SeaGeo g = d;                                    // the by-value copy is read for its geometry only
+    one_tile<MseTile<R>>(g, lds, layout_of(g, R));
 }
 
 template <int R, int NV, int GEO = 0>
 __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p_mse(SeaDev d)
 {
     extern __shared__ uint32_t lds[];
-    fix_geometry<R, GEO>(d);
-    const Layout L = layout_of(d, R);
-    if ((threadIdx.x & 63) == 0) lds[L.prev + (threadIdx.x >> 6)] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);    // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MseTile<R, GEO != 0>>(d, lds, L);
+    SeaGeo g = d;                                          // the by-value copy is read for its geometry only
+    fix_geometry<R, GEO>(g);
+    const Layout L = layout_of(g, R);
+    if ((threadIdx.x & 63) == 0) lds[L.prev + (threadIdx.x >> 6)] = (uint32_t)(g.sw * (2 * g.sw + 16) + g.sw);    // third probe of the first tile: the zero vector
+    persistent_tiles<NV, MseTile<R, GEO != 0>>(g, lds, L);
 }
 
 // What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.
