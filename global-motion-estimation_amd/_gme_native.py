@@ -111,6 +111,9 @@ _SIGNATURES = {
     "gme_seq_subpel": (_i, [_vp, _i, _i, _i, _i]),
     "gme_seq_read_qmv": (_i, [_vp, _i, _i, _c_i32p, _c_i64p]),
     "gme_seq_compensate_qpel": (_i, [_vp, _i, _i, _c_i64p]),
+    "gme_hier_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p]),
+    "gme_seq_hier": (_i, [_vp, _i, _i, _i, _i, _i, _i]),
+    "gme_seq_read_hier": (_i, [_vp, _i, _i, _i, _c_i32p, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -368,6 +371,28 @@ class Context:
         _check(self.lib.gme_subpel_u8(self.handle, _p(prev, _c_u8p), _p(cur, _c_u8p), H, W, prev.strides[0], block_size, int(pnorm),
                                       levels, _p(mf32, _c_i32p), _p(q, _c_i32p), _p(cost, _c_i64p)), self.lib)
         return q, cost
+
+    def hier(self, prev, cur, block_size=16, coarse_window=8, radius=1, pnorm=0, levels=3):
+        """Hierarchical block matching of one pair (gme_hier_u8, hier.search on the device's own pyramids) -> (field
+        int32[h, w, 2] in full-resolution pixels, cost int64[h, w])."""
+        prev, cur = as_frame(prev, "previous"), as_frame(cur, "current")
+        if prev.shape != cur.shape:
+            raise AssertionError("previous and current differ in shape (bbme.py:59)")
+        block_size, coarse_window, radius, pnorm, levels = _hier_args(block_size, coarse_window, radius, pnorm, levels)
+        H, W = prev.shape
+        if cur.strides[0] != prev.strides[0]:
+            cur, prev = np.ascontiguousarray(cur), np.ascontiguousarray(prev)
+        h, w = H // block_size, W // block_size
+        mf, cost = np.zeros((h, w, 2), np.int32), np.zeros((h, w), np.int64)
+        _check(self.lib.gme_hier_u8(self.handle, _p(prev, _c_u8p), _p(cur, _c_u8p), H, W, prev.strides[0], block_size, coarse_window,
+                                    radius, pnorm, levels, _p(mf, _c_i32p), _p(cost, _c_i64p)), self.lib)
+        return mf, cost
+
+
+def _hier_args(block_size, coarse_window, radius, pnorm, levels):
+    """hier.check_args: the definition's argument rules, ValueError before the library is asked."""
+    import hier
+    return hier.check_args(block_size, coarse_window, radius, pnorm, levels)
 
 
 def _subpel_levels(levels):
@@ -813,6 +838,24 @@ class Sequence:
         sse = np.zeros(max(getattr(self, "_mv_shape", (0,))[0], 1), np.int64)
         _check(self.lib.gme_seq_compensate_qpel(self.handle, int(frame_distance), _block_size(block_size), _p(sse, _c_i64p)), self.lib)
         return sse[:getattr(self, "_mv_shape", (0,))[0]]
+
+    # ---- hierarchical block matching (bbme_hier.hip, hier.py)
+    def hier(self, frame_distance, block_size=16, coarse_window=8, radius=1, pnorm=0, levels=3):
+        """hier.search for every pair on the device (gme_seq_hier).  The level-2 field becomes the sequence's motion field:
+        read_mv, subpel, read_qmv and compensate_qpel work on it as after bbme(); read_hier reads any level with its costs."""
+        self._blocking("hierarchical search")
+        block_size, coarse_window, radius, pnorm, levels = _hier_args(block_size, coarse_window, radius, pnorm, levels)
+        _check(self.lib.gme_seq_hier(self.handle, int(frame_distance), block_size, coarse_window, radius, pnorm, levels), self.lib)
+        self._mv_shape = (self.N - int(frame_distance), self.H // block_size, self.W // block_size, 2)
+
+    def read_hier(self, level=2, first=0, count=None):
+        """(field int32[count, h, w, 2], cost int64[count, h, w]) of pairs first .. first+count-1 at pyramid level ``level`` of
+        the last hier(); a level it did not use is an IndexError."""
+        shape = getattr(self, "_mv_shape", (0, 0, 0, 2))
+        count = shape[0] - first if count is None else count
+        mf, cost = np.empty((max(count, 0),) + tuple(shape[1:]), np.int32), np.empty((max(count, 0),) + tuple(shape[1:3]), np.int64)
+        _check(self.lib.gme_seq_read_hier(self.handle, int(level), int(first), int(count), _p(mf, _c_i32p), _p(cost, _c_i64p)), self.lib)
+        return mf, cost
 
 
 _default = None

@@ -1,0 +1,251 @@
+// Hierarchical block matching (host definition: hier.py).  Block (i, j) exists at every pyramid level with
+// half the side of the level below and depends on no neighbour, so its whole coarse-to-fine search runs in one wave of one
+// kernel: +-coarse_window around (0, 0) at the coarsest level used, then +-radius around twice the parent vector at each finer
+// level.  Everything is integer: the device equals hier.search bit for bit.
+//
+// Kernel:
+//   k_hier<BS, LEVELS>  one wave per block, four blocks to a 256-thread workgroup, each wave on its own LDS slice (no workgroup
+//                       barrier).  Per level the wave stages the anchor block and the (b + 2R)^2 window of `current` around
+//                       the clamped centre in LDS, a dword per lane and step; spreads the (2R + 1)^2 candidates over its
+//                       lanes (P lanes share the rows of one candidate where there are fewer than 33); scores a row four
+//                       bytes at a time (v_alignbyte on two window dwords, then v_sad_u8, or three v_dot4 for
+//                       aa + bb - 2ab); and selects the minimum of (cost, position in the definition's order, centre = 0)
+//                       in two wave-wide minima.  BS, LEVELS: the halving chains 16-8-4, 32-16-8 and 64-32-16 as
+//                       compile-time constants; <0, 0> takes block size and level count at run time (and rows that are no
+//                       multiple of four bytes).
+#include <type_traits>
+
+#include "gme_internal.h"
+
+namespace {
+
+constexpr int HIER_THREADS = 256, HIER_WAVES = HIER_THREADS / 64;
+constexpr int HIER_MAX_BS = 64, HIER_MAX_CW = 8, HIER_MAX_R = 3, HIER_MIN_TOP = 4;
+// costs are 32-bit in the kernel (int64 at the ABI): the largest is 64 * 64 * 255^2
+static_assert((long long)HIER_MAX_BS * HIER_MAX_BS * 65025ll < (1ll << 28), "28-bit block costs");
+// the order of a candidate within a level: 0 for the centre, 1 + index in [-R, R]^2 (column offset outer) for the others
+static_assert((2 * HIER_MAX_CW + 1) * (2 * HIER_MAX_CW + 1) < (1 << 9), "9-bit candidate order");
+
+struct HierLevel {
+    const uint8_t* prev;          // first "previous" plane of the level
+    const uint8_t* cur;           // first "current" plane
+    long long stride;             // bytes between consecutive pairs' planes
+    int H, W, pitch, pad;
+    int32_t* mf;                  // [pairs][hb][wb][2]
+    long long* cost;              // [pairs][hb][wb]
+};
+struct HierArgs {
+    HierLevel lv[3];              // [2] = full resolution; levels below the first one used are not read
+    int hb, wb, bs, levels, cw, radius, pnorm;
+    int anchor_bytes;             // LDS of a wave: the anchor block (rows of round_up(b, 4) bytes), then the window
+    int slice_bytes;
+};
+
+// LDS reads of one wave behind its own LDS writes: the hardware keeps a wave's LDS operations in order, this keeps the compiler
+// from moving them across
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// t / d for 0 <= t < 1700 and 1 <= d <= 21 (checked exhaustively on the host): the candidate and staging indices of a level
+__device__ __forceinline__ int small_div(int t, int d) { return (int)(((uint32_t)t * ((1u << 20) / (uint32_t)d + 1u)) >> 20); }
+static_assert((HIER_MAX_BS + 2 * HIER_MAX_CW) * ((HIER_MAX_BS + 2 * HIER_MAX_CW + 3) / 4 + 1) < 1700, "range of small_div");
+
+// `rows` rows of `row_dwords` dwords into LDS: byte (r, c), c < cols, is plane[(y0 + r) * pitch + x0 + c] where that pixel lies
+// inside the H x W level.  Bytes at c >= cols are zero; a byte outside the level is zero or whatever the plane holds beside
+// it: it only ever enters the cost of a candidate that is not inside, which is dropped.  A dword whose four bytes lie in
+// columns [0, pitch) of a row of the level is read at once, the others byte by byte.
+__device__ __forceinline__ void stage_bytes(uint32_t* dst, int rows, int row_dwords, int cols, const uint8_t* plane, int pitch,
+                                            int H, int W, int y0, int x0, int lane)
+{
+    for (int t = lane; t < rows * row_dwords; t += 64) {
+        const int r = small_div(t, row_dwords), k = t - r * row_dwords;
+        const int y = y0 + r, x = x0 + 4 * k, left = cols - 4 * k;
+        uint32_t v = 0;
+        if (y >= 0 && y < H && left > 0) {
+            const uint8_t* src = plane + (long long)y * pitch;
+            if (x >= 0 && x + 4 <= pitch) __builtin_memcpy(&v, src + x, 4);
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (x + e >= 0 && x + e < W) v |= (uint32_t)src[x + e] << (8 * e);
+            }
+            if (left < 4) v &= (1u << (8 * left)) - 1u;
+        }
+        dst[t] = v;
+    }
+}
+
+// One level of one block: centre (cx, cy) already clamped, candidates within R of it; the level's vector into (vx, vy), its
+// cost returned.  B: the block side where it is a compile-time constant (0: b_rt).
+template <int B>
+__device__ __forceinline__ uint32_t level_search(const HierLevel& L, int pair, int b_rt, int R, int pnorm, int bi, int bj, int cx,
+                                                 int cy, uint32_t* anc, uint32_t* win, int lane, int* vx, int* vy)
+{
+    const int b = B ? B : b_rt;
+    const int nd = (b + 3) >> 2;                                  // dwords per block row
+    const int n = 2 * R + 1, ncand = n * n;
+    const int wside = b + 2 * R, wd = (wside + 3) / 4 + 1;        // window rows of wd dwords: one more than its bytes need,
+                                                                  // v_alignbyte reads the dword behind the last one it uses
+    const int x0 = bj * b, y0 = bi * b;
+    const uint8_t* pp = L.prev + (long long)pair * L.stride;
+    const uint8_t* cp = L.cur + (long long)pair * L.stride;
+    stage_bytes(anc, b, nd, b, pp, L.pitch, L.H, L.W, y0, x0, lane);
+    stage_bytes(win, wside, wd, wside, cp, L.pitch, L.H, L.W, y0 + cy - R, x0 + cx - R, lane);
+    wave_lds_fence();
+
+    // P lanes to a candidate, each a share of the rows: as many as leave every candidate a slot in one round, at most 8
+    int P = 1;
+    while (P < 8 && ncand * (P * 2) <= 64) P *= 2;
+    const int slots = 64 / P, slot = lane / P, q = lane - slot * P;
+    const uint32_t tail = (b & 3) ? (1u << (8 * (b & 3))) - 1u : 0xFFFFFFFFu;      // bytes of a row's last dword
+    uint32_t best = 0xFFFFFFFFu, best_order = 0xFFFFFFFFu;
+    for (int c0 = 0; c0 < ncand; c0 += slots) {
+        const int c = c0 + slot;
+        const bool listed = c < ncand;
+        const int cc = listed ? c : 0;
+        const int wx = small_div(cc, n), wy = cc - wx * n;        // the candidate's origin in the window (column, row)
+        const int gx = x0 + cx - R + wx, gy = y0 + cy - R + wy;   // ... and in the level
+        const bool inside = listed && gx >= 0 && gy >= 0 && gx + b <= L.W && gy + b <= L.H;
+        const uint32_t sh = (uint32_t)wx & 3u;
+        uint32_t sad = 0, aa = 0, bb = 0, ab = 0;
+        for (int y = q; y < b; y += P) {
+            const uint32_t* arow = anc + y * nd;
+            const uint32_t* wrow = win + (wy + y) * wd + (wx >> 2);
+#pragma unroll 4
+            for (int k = 0; k < nd; ++k) {
+                const uint32_t a = arow[k];
+                uint32_t v = __builtin_amdgcn_alignbyte(wrow[k + 1], wrow[k], sh);
+                if (!B || (B & 3)) { if (k == nd - 1) v &= tail; }
+                if (pnorm == 0) sad = __builtin_amdgcn_sad_u8(a, v, sad);
+                else {
+                    aa = __builtin_amdgcn_udot4(a, a, aa, false);
+                    bb = __builtin_amdgcn_udot4(v, v, bb, false);
+                    ab = __builtin_amdgcn_udot4(a, v, ab, false);
+                }
+            }
+        }
+        uint32_t part = pnorm == 0 ? sad : aa + bb - 2u * ab;     // sum (a - v)^2 of this lane's rows
+        for (int m = 1; m < P; m <<= 1) part += (uint32_t)__shfl_xor((int)part, m, 64);
+        const uint32_t order = (wx == R && wy == R) ? 0u : (uint32_t)c + 1u;
+        if (inside && (part < best || (part == best && order < best_order))) { best = part; best_order = order; }
+    }
+    const uint32_t win_cost = wave_min_u32(best);
+    const uint32_t win_order = wave_min_u32(best == win_cost ? best_order : 0xFFFFFFFFu);
+    int ox = 0, oy = 0;
+    if (win_order != 0u) {
+        const int c = (int)win_order - 1;
+        ox = small_div(c, n) - R;
+        oy = c - small_div(c, n) * n - R;
+    }
+    *vx = cx + ox;
+    *vy = cy + oy;
+    wave_lds_fence();                                            // the next level overwrites the slice
+    return win_cost;
+}
+
+// grid (ceil(wb / HIER_WAVES), hb, pairs)
+template <int BS, int LEVELS>
+__global__ void __launch_bounds__(HIER_THREADS) k_hier(const HierArgs A)
+{
+    extern __shared__ __align__(16) uint8_t lds[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int bj = blockIdx.x * HIER_WAVES + wave, bi = blockIdx.y, pair = blockIdx.z;
+    if (bj >= A.wb) return;                                      // the whole wave: nothing below synchronises across waves
+    const int bs = BS ? BS : A.bs, levels = LEVELS ? LEVELS : A.levels;
+    uint32_t* anc = (uint32_t*)(lds + (size_t)wave * A.slice_bytes);
+    uint32_t* win = (uint32_t*)(lds + (size_t)wave * A.slice_bytes + A.anchor_bytes);
+    const long long slot = ((long long)pair * A.hb + bi) * A.wb + bj;
+    int vx = 0, vy = 0;
+    auto level = [&](auto lc) {
+        constexpr int l = decltype(lc)::value;
+        if (l < 3 - levels) return;
+        const HierLevel& L = A.lv[l];
+        const int b = bs >> (2 - l);
+        const bool top = l == 3 - levels;
+        const int R = top ? A.cw : A.radius;
+        const int cx = min(max(top ? 0 : 2 * vx, -bj * b), L.W - b - bj * b);
+        const int cy = min(max(top ? 0 : 2 * vy, -bi * b), L.H - b - bi * b);
+        const uint32_t cost = level_search<(BS >> (2 - l))>(L, pair, b, R, A.pnorm, bi, bj, cx, cy, anc, win, lane, &vx, &vy);
+        if (lane == 0) {
+            L.mf[slot * 2] = vx;
+            L.mf[slot * 2 + 1] = vy;
+            L.cost[slot] = (long long)cost;
+        }
+    };
+    level(std::integral_constant<int, 0>());
+    level(std::integral_constant<int, 1>());
+    level(std::integral_constant<int, 2>());
+}
+
+template <int BS, int LEVELS>
+void hier_launch(hipStream_t stream, const HierArgs& a, int pairs)
+{
+    hipLaunchKernelGGL((k_hier<BS, LEVELS>), dim3((unsigned)((a.wb + HIER_WAVES - 1) / HIER_WAVES), (unsigned)a.hb, (unsigned)pairs),
+                       dim3(HIER_THREADS), (size_t)HIER_WAVES * a.slice_bytes, stream, a);
+}
+
+}  // namespace
+
+// the argument rules of hier.py
+int hier_check_args(const char* who, int bs, int cw, int radius, int pnorm, int levels)
+{
+    GME_REQUIRE(levels >= 1 && levels <= 3, GME_ERR_ARG, "%s: levels %d (1 .. 3)", who, levels);
+    GME_REQUIRE(pnorm == 0 || pnorm == 1, GME_ERR_ARG, "%s: pnorm_distance %d out of range (bbme.py:60)", who, pnorm);
+    GME_REQUIRE(bs >= 1 && bs <= HIER_MAX_BS && bs % (1 << (levels - 1)) == 0 && (bs >> (levels - 1)) >= HIER_MIN_TOP, GME_ERR_ARG,
+                "%s: block_size %d with %d levels (a multiple of %d, at most %d, at least %d at the coarsest level)", who, bs, levels,
+                1 << (levels - 1), HIER_MAX_BS, HIER_MIN_TOP);
+    GME_REQUIRE(cw >= 0 && cw <= HIER_MAX_CW, GME_ERR_ARG, "%s: coarse_window %d (0 .. %d)", who, cw, HIER_MAX_CW);
+    GME_REQUIRE(radius >= 0 && radius <= HIER_MAX_R, GME_ERR_ARG, "%s: radius %d (0 .. %d)", who, radius, HIER_MAX_R);
+    return GME_OK;
+}
+
+// hier.search of `pairs` pairs: level[l] holds the planes of pyramid level l (pair k = planes first_prev + k and first_cur + k
+// of the stack), mf[l] / cost[l] the level's outputs [pairs][hb][wb][2] / [pairs][hb][wb] for l >= 3 - levels; hb, wb = the
+// blocks of level 2
+int launch_hier(gme_ctx* ctx, const Plane (&level)[3], int first_prev, int first_cur, int pairs, int bs, int cw, int radius,
+                int pnorm, int levels, int32_t* const (&mf)[3], long long* const (&cost)[3])
+{
+    int rc = hier_check_args("hierarchical search", bs, cw, radius, pnorm, levels);
+    if (rc) return rc;
+    const int hb = level[2].H / bs, wb = level[2].W / bs;
+    ctx->plan[0] = 0; ctx->plan_patches = 0;
+    const bool compiled = levels == 3 && (bs == 16 || bs == 32 || bs == 64);
+    if (compiled) plan_note(ctx, 0, "k_hier<%d,3> cw %d r %d, %d x %d blocks, one wave each", bs, cw, radius, hb, wb);
+    else plan_note(ctx, 0, "k_hier<0,0> bs %d levels %d cw %d r %d, %d x %d blocks, one wave each", bs, levels, cw, radius, hb, wb);
+    if (pairs == 0 || hb == 0 || wb == 0) return GME_OK;
+    GME_REQUIRE(hb <= 65535, GME_ERR_ARG, "%d block rows", hb);
+    HierArgs a;
+    a.hb = hb; a.wb = wb; a.bs = bs; a.levels = levels; a.cw = cw; a.radius = radius; a.pnorm = pnorm;
+    a.anchor_bytes = (bs * ((bs + 3) & ~3) + 15) & ~15;
+    int window = 0;
+    for (int l = 3 - levels; l < 3; ++l) {
+        const int side = (bs >> (2 - l)) + 2 * (l == 3 - levels ? cw : radius);
+        const int bytes = side * ((side + 3) / 4 + 1) * 4;
+        if (bytes > window) window = bytes;
+    }
+    a.slice_bytes = a.anchor_bytes + ((window + 15) & ~15);
+    const long long per = (long long)hb * wb;
+    const int step = max_grid_planes();
+    for (int k = 0; k < pairs; k += step) {
+        const int n = pairs - k < step ? pairs - k : step;
+        for (int l = 0; l < 3; ++l) {
+            HierLevel& L = a.lv[l];
+            const Plane& p = level[l];
+            L = HierLevel();
+            if (l < 3 - levels) continue;
+            L.prev = p.at(first_prev + k); L.cur = p.at(first_cur + k); L.stride = p.stride;
+            L.H = p.H; L.W = p.W; L.pitch = p.pitch;
+            L.mf = mf[l] + per * k * 2; L.cost = cost[l] + per * k;
+        }
+        if (!compiled) hier_launch<0, 0>(ctx->stream, a, n);
+        else if (bs == 16) hier_launch<16, 3>(ctx->stream, a, n);
+        else if (bs == 32) hier_launch<32, 3>(ctx->stream, a, n);
+        else hier_launch<64, 3>(ctx->stream, a, n);
+    }
+    GME_HIP_TRY(hipGetLastError());
+    return GME_OK;
+}

@@ -498,6 +498,48 @@ extern "C" int gme_subpel_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* c
     return ctx_finish(ctx);
 }
 
+// Hierarchical block matching of one pair (bbme_hier.hip): both frames and their two pyramid levels in
+// the scratch, each level a stack of two planes (previous, current).
+extern "C" int gme_hier_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int H, int W, int stride, int block_size,
+                           int coarse_window, int radius, int pnorm, int levels, int32_t* mf_out, int64_t* cost_out)
+{
+    GME_ENTER(ctx);
+    GME_REQUIRE(prev && cur && mf_out, GME_ERR_ARG, "gme_hier_u8: null pointer");
+    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_hier_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
+    int rc = hier_check_args("gme_hier_u8", block_size, coarse_window, radius, pnorm, levels);
+    if (rc) return rc;
+    const int h = H / block_size, w = W / block_size;
+    if (h == 0 || w == 0) return GME_OK;
+    const size_t n = (size_t)h * w;
+    Plane lv[3];
+    lv[2] = plane_shape(H, W, 2);
+    lv[1] = plane_shape((H + 1) / 2, (W + 1) / 2, 2);
+    lv[0] = plane_shape((lv[1].H + 1) / 2, (lv[1].W + 1) / 2, 2);
+    int32_t* d_mf[3] = { nullptr, nullptr, nullptr };
+    long long* d_cost[3] = { nullptr, nullptr, nullptr };
+    Carver c;
+    for (int l = 2; l >= 0; --l) c.take(&lv[l], true);
+    c.take(&d_mf[0], n * 2 * 3);
+    c.take(&d_cost[0], n * 3);
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    for (int l = 1; l < 3; ++l) { d_mf[l] = d_mf[0] + n * 2 * l; d_cost[l] = d_cost[0] + n * l; }
+    GME_HIP_TRY(hipMemsetAsync(lv[2].ptr, 0, (uint8_t*)d_mf[0] - lv[2].ptr, ctx->stream));
+    Plane second = lv[2];
+    second.ptr = lv[2].at(1);
+    GME_HIP_TRY(put_plane(ctx, lv[2], prev, stride));
+    GME_HIP_TRY(put_plane(ctx, second, cur, stride));
+    for (int l = 1; l >= 3 - levels; --l) {
+        rc = launch_pyrdown(ctx, lv[l + 1], lv[l]);
+        if (rc) return rc;
+    }
+    rc = launch_hier(ctx, lv, 0, 1, 1, block_size, coarse_window, radius, pnorm, levels, d_mf, d_cost);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(mf_out, d_mf[2], n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost[2], n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -586,6 +628,7 @@ static void seq_frames_changed(gme_seq* s)
 {
     s->pyramids_valid = false;
     s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
+    s->hier_valid = false;
     gme_drop_run(s);
 }
 
@@ -798,6 +841,7 @@ extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, i
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
     s->mv_fd = fd; s->mv_bs = bs;
     s->qmv_valid = false;
+    s->hier_valid = false;
     return seq_launch_bbme(s, 2, fd, bbme_job(s->level[2], 0, fd, pairs, bs, sw, procedure, pnorm, s->mv));
 }
 
@@ -856,6 +900,7 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
     s->mv_fd = fd; s->mv_bs = bs;
     s->qmv_valid = false;
+    s->hier_valid = false;
     const Plane& p = s->level[2];
     // one table kind for the whole call: every chunk's launches carry at most `pairs` pairs, so one that the matrix-core
     // kernel would take at the largest also takes it at every chunk, and a smaller chunk of a declined call keeps kind 1
@@ -1835,4 +1880,68 @@ extern "C" int gme_seq_compensate_qpel(gme_seq* s, int fd, int bs, int64_t* sse_
     if (sse_out)
         GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Hierarchical block matching (bbme_hier.hip): blocking calls.  The level-2 field of gme_seq_hier is the
+// sequence's motion field (gme_seq_read_mv, gme_seq_subpel, ... take it as they take the field of gme_seq_bbme).
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_hier(gme_seq* s, int fd, int bs, int cw, int radius, int pnorm, int levels)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_hier: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "frame_distance %d needs at least %d frames", fd, fd + 1);
+    int rc = hier_check_args("gme_seq_hier", bs, cw, radius, pnorm, levels);
+    if (rc) return rc;
+    const int pairs = s->N - fd, h = s->H / bs, w = s->W / bs;
+    const size_t n = (size_t)pairs * h * w;
+    s->hier_valid = false;
+    s->qmv_valid = false;
+    rc = seq_levels(s);
+    if (rc) return rc;
+    rc = seq_pyramids(s);
+    if (rc) return rc;
+    rc = s->mv.ensure(n * 2, "motion field");
+    if (rc) return rc;
+    s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
+    s->mv_fd = fd; s->mv_bs = bs;
+    for (int l = 3 - levels; l < 3; ++l) {
+        if (l < 2) {
+            rc = s->hier_mv[l].ensure(n * 2, "hierarchical fields");
+            if (rc) return rc;
+        }
+        rc = s->hier_cost[l].ensure(n, "hierarchical costs");
+        if (rc) return rc;
+    }
+    const Plane lv[3] = { s->level[0], s->level[1], s->level[2] };
+    int32_t* const mf[3] = { s->hier_mv[0].get(), s->hier_mv[1].get(), s->mv.get() };
+    long long* const cost[3] = { s->hier_cost[0].get(), s->hier_cost[1].get(), s->hier_cost[2].get() };
+    rc = launch_hier(ctx, lv, 0, fd, pairs, bs, cw, radius, pnorm, levels, mf, cost);
+    if (rc) return rc;
+    rc = ctx_finish(ctx);
+    if (rc) return rc;
+    s->hier_levels = levels;
+    s->hier_valid = true;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_hier(gme_seq* s, int level, int first_pair, int count, int32_t* mf_out, int64_t* cost_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_hier: null sequence");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(s->hier_valid, GME_ERR_STATE, "gme_seq_read_hier before gme_seq_hier");
+    GME_REQUIRE(level >= 3 - s->hier_levels && level <= 2, GME_ERR_ARG, "gme_seq_read_hier: level %d, the last gme_seq_hier used %d .. 2",
+                level, 3 - s->hier_levels);
+    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG,
+                "gme_seq_read_hier: pairs [%d, %d) outside [0, %d)", first_pair, first_pair + count, s->mv_pairs);
+    const size_t per = (size_t)s->mv_h * s->mv_w;
+    const int32_t* mf = level == 2 ? s->mv.get() : s->hier_mv[level].get();
+    if (mf_out && per * count)
+        GME_HIP_TRY(hipMemcpyAsync(mf_out, mf + per * 2 * first_pair, per * 2 * count * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                   s->ctx->stream));
+    if (cost_out && per * count)
+        GME_HIP_TRY(hipMemcpyAsync(cost_out, s->hier_cost[level] + per * first_pair, per * count * sizeof(long long),
+                                   hipMemcpyDeviceToHost, s->ctx->stream));
+    return ctx_finish(s->ctx);
 }

@@ -171,6 +171,13 @@ struct gme_seq {
     DevBuf<int32_t> qmv;                 // [P][h][w][2], quarter units
     DevBuf<long long> qcost;             // [P][h][w]
     bool qmv_valid = false;
+    // hierarchical search (bbme_hier.hip): fields of the levels above the frame and the costs of every level of the last
+    // gme_seq_hier (its level-2 field is `mv`), allocated by its first call; valid until new frame data or the next
+    // block-matching call
+    DevBuf<int32_t> hier_mv[2];          // [P][h][w][2] of levels 0 and 1
+    DevBuf<long long> hier_cost[3];      // [P][h][w]
+    int hier_levels = 0;                 // levels the last gme_seq_hier used
+    bool hier_valid = false;
     DevBuf<uint8_t> synth_canvas;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -379,6 +386,15 @@ int launch_subpel_refine(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, 
 int launch_compensate_qpel(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W,
                            int pitch, int bs, const int32_t* qmf, uint8_t* out, long long out_stride, int out_pitch,
                            unsigned long long* sse);
+
+// ---- bbme_hier.hip: hierarchical block matching ----------------------------------------------------
+// the argument rules of hier.py (GME_ERR_ARG)
+int hier_check_args(const char* who, int bs, int cw, int radius, int pnorm, int levels);
+// hier.search of `pairs` pairs: level[l] holds the planes of pyramid level l ([2] = the frames), pair k = planes first_prev + k
+// and first_cur + k of each stack; mf[l] [pairs][hb][wb][2] and cost[l] [pairs][hb][wb] (device) for the levels
+// l >= 3 - levels, hb = H / bs and wb = W / bs of level 2.  Names the kernel instance in the context's plan.
+int launch_hier(gme_ctx* ctx, const Plane (&level)[3], int first_prev, int first_cur, int pairs, int bs, int cw, int radius,
+                int pnorm, int levels, int32_t* const (&mf)[3], long long* const (&cost)[3]);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -11,6 +11,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py stabilize -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--radius 15]   # video stabilization
     python gme_cli.py mosaic -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--anchor 0] [--threshold 16] [--min-count 3] [--no-masks]   # background mosaic, moving-object masks
     python gme_cli.py subpel -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--levels 2] [-o OUTDIR]   # quarter-pel block matching of one pair
+    python gme_cli.py hier -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-cw 8] [-r 1] [-pn 0] [--levels 3] [--subpel 0|1|2] [-o OUTDIR]   # hierarchical block matching of one pair
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -85,6 +86,17 @@ def _parser():
     sp.add_argument("-pn", "--p-norm", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
     sp.add_argument("--levels", type=int, default=2, help="0: integer, 1: half-pel, 2: quarter-pel")
     sp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for subpel.json")
+    hp = sub.add_parser("hier", help="hierarchical block matching of one frame pair: coarse-to-fine search, compensate, report (hier.py, DESIGN.md 7f)")
+    hp.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    hp.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the current frame")
+    hp.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=1)
+    hp.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="at full resolution; halved per level")
+    hp.add_argument("-cw", "--coarse-window", dest="coarse_window", type=int, default=8, help="+-pixels searched at the coarsest level (0 .. 8)")
+    hp.add_argument("-r", "--radius", dest="radius", type=int, default=1, help="+-pixels searched around twice the parent vector below it (0 .. 3)")
+    hp.add_argument("-pn", "--p-norm", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    hp.add_argument("--levels", type=int, default=3, help="pyramid levels searched (1 .. 3)")
+    hp.add_argument("--subpel", type=int, default=0, help="refine the field afterwards: 0 no, 1 half-pel, 2 quarter-pel")
+    hp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for hier.json")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -185,6 +197,46 @@ def _subpel(args):
     return res
 
 
+def _hier(args):
+    """Reach, median vector and PSNR of the compensation of one pair under the hierarchical search (with --subpel also the
+    PSNR of the quarter-pel compensation of the refined field); the same record into OUTDIR/hier.json."""
+    import json
+    import os
+    import hier
+    import utils
+    frames = utils.get_video_frames(args.path)
+    if not args.fd <= args.fi < len(frames) or args.fd < 1:
+        raise IndexError("frames %d and %d of %d" % (args.fi - args.fd, args.fi, len(frames)))
+    prev, cur = frames[args.fi - args.fd], frames[args.fi]
+    res = hier.report(prev, cur, args.block_size, args.coarse_window, args.radius, args.pnorm, args.levels)
+    record = {"options": {"path": args.path, "frame_index": args.fi, "frame_distance": args.fd, "block_size": args.block_size,
+                          "coarse_window": args.coarse_window, "radius": args.radius, "pnorm": args.pnorm, "levels": args.levels,
+                          "subpel": args.subpel},
+              "shape": list(res["field"].shape[:2])}
+    record.update({k: res[k] for k in ("reach", "median_vector", "sse", "psnr")})
+    print("frames {} -> {}: {} x {} blocks of {}".format(args.fi - args.fd, args.fi, record["shape"][0], record["shape"][1],
+                                                         args.block_size))
+    print("reach: +-{} px".format(record["reach"]))
+    print("median vector: ({:.2f}, {:.2f}) px".format(*record["median_vector"]))
+    print("psnr: {:.4f} dB".format(record["psnr"]))
+    if args.subpel:
+        import _gme_native
+        import motion
+        import subpel
+        seq = motion._pair_sequence(prev, cur)
+        seq.hier(1, args.block_size, args.coarse_window, args.radius, args.pnorm % 2, args.levels)
+        seq.subpel(1, args.block_size, args.pnorm % 2, args.subpel)
+        res["qfield"], res["qcost"] = (a[0] for a in seq.read_qmv())
+        record["sse_qpel"] = int(seq.compensate_qpel(1, args.block_size)[0]) if res["field"].size else record["sse"]
+        record["psnr_qpel"] = subpel.psnr(record["sse_qpel"], *_gme_native.as_frame(prev).shape)
+        print("psnr quarter-pel: {:.4f} dB".format(record["psnr_qpel"]))
+    if args.outdir:
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "hier.json"), "w") as f:
+            json.dump(record, f, indent=1)
+    return res
+
+
 def _projective(args):
     """h, flags and the PSNR of the block-affine and of the projective compensation of one pair."""
     import numpy as np
@@ -254,11 +306,15 @@ def main(argv=None):
         return _mosaic(args)
     if args.command == "subpel":
         return _subpel(args)
+    if args.command == "hier":
+        return _hier(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")
     print("norms: 0 MAE, 1 MSE (bbme.py:608; the bbme script always uses MSE, as upstream)")
     print("motion models (roadmap.global_motion_estimation): " + ", ".join(roadmap.MODELS))
+    print("sub-pel refinement (gme_cli.py subpel --levels): 0 integer, 1 half-pel, 2 quarter-pel   (subpel.py)")
+    print("hierarchical search (gme_cli.py hier): --levels 1 .. 3, -cw 0 .. 8, -r 0 .. 3, block size a multiple of 2^(levels-1) up to 64   (hier.py)")
     try:
         print("device: " + _gme_native.default_context().info()["name"])
     except Exception as e:      # noqa: BLE001 -- no GPU: say so, the listing above is still useful

@@ -50,6 +50,9 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    **Quarter-pel block matching.**  ``subpel.motion_field`` refines the integer field of any search to half and quarter
    pixels and ``Sequence.compensate_qpel`` compensates with it (k_subpel_refine / k_compensate_qpel, csrc/bbme_subpel.hip;
    host definition subpel.py).  The fits above still take integer vectors.
+   **Hierarchical block matching.**  ``hier.motion_field`` searches coarse to fine over the pyramid, every level of a block
+   in one wave of one kernel (k_hier, csrc/bbme_hier.hip; host definition hier.py); its field is refined to
+   quarter pixels like that of any other search.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

@@ -487,6 +487,22 @@ class ShardedSequence:
             return (q, cost, lane.seq.compensate_qpel(self.fd, block_size)[:n]) if compensate else (q, cost)
         return tuple(np.concatenate(part, axis=0) for part in zip(*self._each(run)))
 
+    def motion_fields_hier(self, block_size, coarse_window, radius, pnorm, frame_distance, levels=3):
+        """hier.search for every local pair -> (field int32[P_local, h, w, 2] in full-resolution pixels,
+        cost int64[P_local, h, w]).  ``frame_distance`` is the one the sequence was sharded for.  Each lane's level-2 field
+        stays its sequence's motion field, so the quarter-pel calls of the lane sequences refine it."""
+        block_size, coarse_window, radius, pnorm, levels = _native._hier_args(block_size, coarse_window, radius, pnorm, levels)
+        if int(frame_distance) != self.fd:
+            raise ValueError("frame_distance %d, but the sequence is sharded for %d" % (int(frame_distance), self.fd))
+        if not self.lanes:
+            h, w = self.H // block_size, self.W // block_size
+            return np.zeros((0, h, w, 2), np.int32), np.zeros((0, h, w), np.int64)
+
+        def run(lane):
+            lane.seq.hier(self.fd, block_size, coarse_window, radius, pnorm, levels)
+            return lane.seq.read_hier(2, 0, lane.hi - lane.lo)
+        return tuple(np.concatenate(part, axis=0) for part in zip(*self._each(run)))
+
     def estimate(self, procedure=3, search_window=2, model=None):
         """motion.global_motion_estimation for every local pair -> float64[P_local, 6].  ``model``: one of roadmap.MODELS
         (roadmap.stages per lane); the second-order models return float64[P_local, 12]."""

@@ -357,6 +357,30 @@ GME_API int gme_seq_subpel(gme_seq *seq, int frame_distance, int block_size, int
 GME_API int gme_seq_read_qmv(gme_seq *seq, int first_pair, int count, int32_t *qmf_out, int64_t *cost_out);
 GME_API int gme_seq_compensate_qpel(gme_seq *seq, int frame_distance, int block_size, int64_t *sse_out);
 
+/* Hierarchical block matching (host definition hier.py): a coarse-to-fine search over the pyramid, one
+ * kernel for all levels; integer throughout and equal to hier.search bit for bit.  levels in 1 .. 3: the search starts at
+ * pyramid level s = 3 - levels and ends at level 2, the frame.  The block of level l has side b_l = block_size >> (2 - l);
+ * block (i, j), i < H / block_size, j < W / block_size, has its origin at (i b_l, j b_l) of level l.  Its centre is (0, 0) at
+ * level s and twice its own vector of level l - 1 below, clamped per component so that the displaced block lies inside the
+ * level.  The centre is scored first; then the offsets in [-R, R]^2 around it (R = coarse_window at level s, radius below;
+ * column offset in the outer loop, ascending), skipping blocks that are not inside the level; only a strictly smaller cost
+ * (sum |d| for pnorm 0, sum d^2 for 1) replaces the best.  Vectors reach coarse_window * 2^(levels-1) + radius * (2^(levels-1) - 1).
+ * gme_hier_u8: one pair on host buffers, the pyramids built on the device; mf_out int32[H/bs][W/bs][2] is the level-2 field,
+ *   cost_out int64[H/bs][W/bs] its costs (may be NULL).
+ * gme_seq_hier: every pair of the resident sequence (the pyramids are built if they are stale).  The level-2 field becomes the
+ *   sequence's motion field with this block size and frame distance, as after gme_seq_bbme: gme_seq_read_mv, gme_seq_subpel,
+ *   gme_seq_read_qmv and gme_seq_compensate_qpel work on it, and an earlier quarter-pel result is no longer valid.
+ * gme_seq_read_hier: field and costs of pairs first_pair .. first_pair + count - 1 at any level the last gme_seq_hier used (either
+ *   output may be NULL); another level is GME_ERR_ARG; GME_ERR_STATE before any gme_seq_hier, after new frame data or after
+ *   another block-matching call.
+ * Blocking calls, also in split-phase mode (as gme_seq_subpel).  GME_ERR_ARG unless block_size % 2^(levels-1) == 0,
+ * block_size >> (levels - 1) >= 4, block_size <= 64, 0 <= coarse_window <= 8 and 0 <= radius <= 3.  gme_last_bbme_info names the
+ * kernel instance: k_hier<16,3>, k_hier<32,3>, k_hier<64,3>, or k_hier<0,0> (block size and levels at run time). */
+GME_API int gme_hier_u8(gme_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int H, int W, int stride, int block_size,
+                        int coarse_window, int radius, int pnorm, int levels, int32_t *mf_out, int64_t *cost_out);
+GME_API int gme_seq_hier(gme_seq *seq, int frame_distance, int block_size, int coarse_window, int radius, int pnorm, int levels);
+GME_API int gme_seq_read_hier(gme_seq *seq, int level, int first_pair, int count, int32_t *mf_out, int64_t *cost_out);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
