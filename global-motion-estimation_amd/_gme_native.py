@@ -114,6 +114,10 @@ _SIGNATURES = {
     "gme_hier_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p]),
     "gme_seq_hier": (_i, [_vp, _i, _i, _i, _i, _i, _i]),
     "gme_seq_read_hier": (_i, [_vp, _i, _i, _i, _c_i32p, _c_i64p]),
+    "gme_vbs_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i32p, _c_u8p, _c_i64p]),
+    "gme_seq_vbs": (_i, [_vp, _i, _i, _i, _i, _i, _i]),
+    "gme_seq_read_vbs": (_i, [_vp, _i, _i, _c_i32p, _c_u8p, _c_i64p]),
+    "gme_seq_compensate_vbs": (_i, [_vp, _i, _i, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -387,6 +391,32 @@ class Context:
         _check(self.lib.gme_hier_u8(self.handle, _p(prev, _c_u8p), _p(cur, _c_u8p), H, W, prev.strides[0], block_size, coarse_window,
                                     radius, pnorm, levels, _p(mf, _c_i32p), _p(cost, _c_i64p)), self.lib)
         return mf, cost
+
+    def vbs(self, prev, cur, mf, block_size, depth=2, radius=1, pnorm=0, penalty=0):
+        """The variable-block-size tree of one pair on the integer field mf int32[H // bs, W // bs, 2] (gme_vbs_u8, vbs.tree) ->
+        (leaf int32[h << depth, w << depth, 2], depth uint8[h << depth, w << depth], cost int64[h, w])."""
+        prev, cur = as_frame(prev, "previous"), as_frame(cur, "current")
+        if prev.shape != cur.shape:
+            raise AssertionError("previous and current differ in shape (bbme.py:59)")
+        block_size, depth, radius, pnorm, penalty = _vbs_args(block_size, depth, radius, pnorm, penalty)
+        H, W = prev.shape
+        if cur.strides[0] != prev.strides[0]:
+            cur, prev = np.ascontiguousarray(cur), np.ascontiguousarray(prev)
+        h, w = H // block_size, W // block_size
+        mf32 = np.ascontiguousarray(np.asarray(mf)[:, :, :2].astype(np.int32))
+        if mf32.shape != (h, w, 2):
+            raise ValueError("the field of a %d x %d frame at block size %d is %r, not %r" % (H, W, block_size, (h, w, 2), mf32.shape))
+        leaf = np.zeros((h << depth, w << depth, 2), np.int32)
+        dmap, cost = np.zeros((h << depth, w << depth), np.uint8), np.zeros((h, w), np.int64)
+        _check(self.lib.gme_vbs_u8(self.handle, _p(prev, _c_u8p), _p(cur, _c_u8p), H, W, prev.strides[0], block_size, depth, radius,
+                                   pnorm, penalty, _p(mf32, _c_i32p), _p(leaf, _c_i32p), _p(dmap, _c_u8p), _p(cost, _c_i64p)), self.lib)
+        return leaf, dmap, cost
+
+
+def _vbs_args(block_size, depth, radius, pnorm, penalty):
+    """vbs.check_args: the definition's argument rules, ValueError before the library is asked."""
+    import vbs
+    return vbs.check_args(block_size, depth, radius, pnorm, penalty)
 
 
 def _hier_args(block_size, coarse_window, radius, pnorm, levels):
@@ -856,6 +886,35 @@ class Sequence:
         mf, cost = np.empty((max(count, 0),) + tuple(shape[1:]), np.int32), np.empty((max(count, 0),) + tuple(shape[1:3]), np.int64)
         _check(self.lib.gme_seq_read_hier(self.handle, int(level), int(first), int(count), _p(mf, _c_i32p), _p(cost, _c_i64p)), self.lib)
         return mf, cost
+
+    # ---- variable-block-size motion (bbme_vbs.hip, vbs.py)
+    def vbs(self, frame_distance, block_size=16, depth=2, radius=1, pnorm=0, penalty=0):
+        """vbs.tree on the field of the last bbme() or hier() (same frame distance and block size) for every pair on the device
+        (gme_seq_vbs).  The motion field stays what it was; read_vbs reads the result, compensate_vbs compensates with it."""
+        self._blocking("variable-block-size tree")
+        block_size, depth, radius, pnorm, penalty = _vbs_args(block_size, depth, radius, pnorm, penalty)
+        _check(self.lib.gme_seq_vbs(self.handle, int(frame_distance), block_size, depth, radius, pnorm, penalty), self.lib)
+        self._vbs_depth = depth
+
+    def read_vbs(self, first=0, count=None):
+        """(leaf int32[count, h << D, w << D, 2], depth uint8[count, h << D, w << D], cost int64[count, h, w]) of pairs
+        first .. first+count-1 of the last vbs()."""
+        shape, D = getattr(self, "_mv_shape", (0, 0, 0, 2)), getattr(self, "_vbs_depth", 0)
+        count = shape[0] - first if count is None else count
+        grid = (max(count, 0), shape[1] << D, shape[2] << D)
+        leaf, dmap = np.empty(grid + (2,), np.int32), np.empty(grid, np.uint8)
+        cost = np.empty((max(count, 0),) + tuple(shape[1:3]), np.int64)
+        _check(self.lib.gme_seq_read_vbs(self.handle, int(first), int(count), _p(leaf, _c_i32p), _p(dmap, _c_u8p), _p(cost, _c_i64p)),
+               self.lib)
+        return leaf, dmap, cost
+
+    def compensate_vbs(self, frame_distance, block_size):
+        """Compensated frames of the leaf field (gme_seq_compensate_vbs, subpel.compensate_integer at the leaf size) -> sse
+        int64[P] against the current frames; read_compensated(_range) reads the frames."""
+        self._blocking("variable-block-size tree")
+        sse = np.zeros(max(getattr(self, "_mv_shape", (0,))[0], 1), np.int64)
+        _check(self.lib.gme_seq_compensate_vbs(self.handle, int(frame_distance), _block_size(block_size), _p(sse, _c_i64p)), self.lib)
+        return sse[:getattr(self, "_mv_shape", (0,))[0]]
 
 
 _default = None

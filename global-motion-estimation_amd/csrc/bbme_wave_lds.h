@@ -1,0 +1,42 @@
+// What the one-wave-per-block kernels share (bbme_hier.hip, bbme_vbs.hip): a wave's own LDS slice, filled and read by that wave
+// alone, without a workgroup barrier.
+#pragma once
+#include "gme_internal.h"
+
+// LDS reads of one wave behind its own LDS writes: the hardware keeps a wave's LDS operations in order, this keeps the compiler
+// from moving them across
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// t / d for 0 <= t < 1700 and 1 <= d <= 21 (checked exhaustively on the host): the candidate and staging indices of a block
+constexpr int SMALL_DIV_T = 1700, SMALL_DIV_D = 21;
+__device__ __forceinline__ int small_div(int t, int d) { return (int)(((uint32_t)t * ((1u << 20) / (uint32_t)d + 1u)) >> 20); }
+
+// `rows` rows of `row_dwords` dwords into LDS: byte (r, c), c < cols, is plane[(y0 + r) * pitch + x0 + c] where that pixel lies
+// inside the H x W level.  Bytes at c >= cols are zero; a byte outside the level is zero or whatever the plane holds beside
+// it: it only ever enters the cost of a candidate that is not inside, which is dropped.  A dword whose four bytes lie in
+// columns [0, pitch) of a row of the level is read at once, the others byte by byte.
+__device__ __forceinline__ void stage_bytes(uint32_t* dst, int rows, int row_dwords, int cols, const uint8_t* plane, int pitch,
+                                            int H, int W, int y0, int x0, int lane)
+{
+    for (int t = lane; t < rows * row_dwords; t += 64) {
+        const int r = small_div(t, row_dwords), k = t - r * row_dwords;
+        const int y = y0 + r, x = x0 + 4 * k, left = cols - 4 * k;
+        uint32_t v = 0;
+        if (y >= 0 && y < H && left > 0) {
+            const uint8_t* src = plane + (long long)y * pitch;
+            if (x >= 0 && x + 4 <= pitch) __builtin_memcpy(&v, src + x, 4);
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (x + e >= 0 && x + e < W) v |= (uint32_t)src[x + e] << (8 * e);
+            }
+            if (left < 4) v &= (1u << (8 * left)) - 1u;
+        }
+        dst[t] = v;
+    }
+}

@@ -540,6 +540,40 @@ extern "C" int gme_hier_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     return ctx_finish(ctx);
 }
 
+// The variable-block-size tree of one pair on a given field (bbme_vbs.hip).
+extern "C" int gme_vbs_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int H, int W, int stride, int block_size, int depth,
+                          int radius, int pnorm, int penalty, const int32_t* mf_in, int32_t* leaf_out, uint8_t* depth_out,
+                          int64_t* cost_out)
+{
+    GME_ENTER(ctx);
+    GME_REQUIRE(prev && cur && mf_in && leaf_out, GME_ERR_ARG, "gme_vbs_u8: null pointer");
+    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_vbs_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
+    int rc = vbs_check_args("gme_vbs_u8", block_size, depth, radius, pnorm, penalty);
+    if (rc) return rc;
+    const int h = H / block_size, w = W / block_size;
+    if (h == 0 || w == 0) return GME_OK;
+    const size_t n = (size_t)h * w, cells = n << (2 * depth);
+    Plane pp = plane_shape(H, W, 1), pc = pp;
+    int32_t *d_mf = nullptr, *d_leaf = nullptr;
+    long long* d_cost = nullptr;
+    uint8_t* d_dmap = nullptr;
+    Carver c;
+    c.take(&pp, true); c.take(&pc, true);
+    c.take(&d_mf, n * 2); c.take(&d_leaf, cells * 2); c.take(&d_cost, n); c.take(&d_dmap, cells);
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemsetAsync(pp.ptr, 0, (uint8_t*)d_mf - pp.ptr, ctx->stream));
+    GME_HIP_TRY(put_plane(ctx, pp, prev, stride));
+    GME_HIP_TRY(put_plane(ctx, pc, cur, stride));
+    GME_HIP_TRY(hipMemcpyAsync(d_mf, mf_in, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_vbs(ctx, pp.ptr, pc.ptr, 0, 1, H, W, pp.pitch, block_size, depth, radius, pnorm, penalty, d_mf, d_leaf, d_dmap, d_cost);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(leaf_out, d_leaf, cells * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth_out) GME_HIP_TRY(hipMemcpyAsync(depth_out, d_dmap, cells, hipMemcpyDeviceToHost, ctx->stream));
+    if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -629,6 +663,7 @@ static void seq_frames_changed(gme_seq* s)
     s->pyramids_valid = false;
     s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
     s->hier_valid = false;
+    s->vbs_valid = false;
     gme_drop_run(s);
 }
 
@@ -842,6 +877,7 @@ extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, i
     s->mv_fd = fd; s->mv_bs = bs;
     s->qmv_valid = false;
     s->hier_valid = false;
+    s->vbs_valid = false;
     return seq_launch_bbme(s, 2, fd, bbme_job(s->level[2], 0, fd, pairs, bs, sw, procedure, pnorm, s->mv));
 }
 
@@ -901,6 +937,7 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     s->mv_fd = fd; s->mv_bs = bs;
     s->qmv_valid = false;
     s->hier_valid = false;
+    s->vbs_valid = false;
     const Plane& p = s->level[2];
     // one table kind for the whole call: every chunk's launches carry at most `pairs` pairs, so one that the matrix-core
     // kernel would take at the largest also takes it at every chunk, and a smaller chunk of a declined call keeps kind 1
@@ -1897,6 +1934,7 @@ extern "C" int gme_seq_hier(gme_seq* s, int fd, int bs, int cw, int radius, int 
     const int pairs = s->N - fd, h = s->H / bs, w = s->W / bs;
     const size_t n = (size_t)pairs * h * w;
     s->hier_valid = false;
+    s->vbs_valid = false;
     s->qmv_valid = false;
     rc = seq_levels(s);
     if (rc) return rc;
@@ -1944,4 +1982,77 @@ extern "C" int gme_seq_read_hier(gme_seq* s, int level, int first_pair, int coun
         GME_HIP_TRY(hipMemcpyAsync(cost_out, s->hier_cost[level] + per * first_pair, per * count * sizeof(long long),
                                    hipMemcpyDeviceToHost, s->ctx->stream));
     return ctx_finish(s->ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Variable-block-size motion (bbme_vbs.hip): blocking calls on the field of the last gme_seq_bbme or
+// gme_seq_hier, which stays the sequence's motion field.
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_vbs(gme_seq* s, int fd, int bs, int depth, int radius, int pnorm, int penalty)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_vbs: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = vbs_check_args("gme_seq_vbs", bs, depth, radius, pnorm, penalty);
+    if (rc) return rc;
+    rc = subpel_field(s, "gme_seq_vbs", fd, bs);
+    if (rc) return rc;
+    const size_t n = (size_t)s->mv_pairs * s->mv_h * s->mv_w, cells = n << (2 * depth);
+    s->vbs_valid = false;
+    rc = s->vbs_leaf.ensure(cells * 2, "variable-block-size field");
+    if (rc) return rc;
+    rc = s->vbs_dmap.ensure(cells, "variable-block-size depths");
+    if (rc) return rc;
+    rc = s->vbs_cost.ensure(n, "variable-block-size costs");
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    rc = launch_vbs(ctx, p.at(0), p.at(fd), p.stride, s->mv_pairs, s->H, s->W, p.pitch, bs, depth, radius, pnorm, penalty, s->mv,
+                    s->vbs_leaf, s->vbs_dmap, s->vbs_cost);
+    if (rc) return rc;
+    rc = ctx_finish(ctx);
+    if (rc) return rc;
+    s->vbs_depth = depth;
+    s->vbs_valid = true;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_vbs(gme_seq* s, int first_pair, int count, int32_t* leaf_out, uint8_t* depth_out, int64_t* cost_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_vbs: null sequence");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(s->vbs_valid, GME_ERR_STATE, "gme_seq_read_vbs before gme_seq_vbs");
+    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG,
+                "gme_seq_read_vbs: pairs [%d, %d) outside [0, %d)", first_pair, first_pair + count, s->mv_pairs);
+    const size_t per = (size_t)s->mv_h * s->mv_w, cells = per << (2 * s->vbs_depth);
+    if (leaf_out && cells * count)
+        GME_HIP_TRY(hipMemcpyAsync(leaf_out, s->vbs_leaf + cells * 2 * first_pair, cells * 2 * count * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, s->ctx->stream));
+    if (depth_out && cells * count)
+        GME_HIP_TRY(hipMemcpyAsync(depth_out, s->vbs_dmap + cells * first_pair, cells * count, hipMemcpyDeviceToHost, s->ctx->stream));
+    if (cost_out && per * count)
+        GME_HIP_TRY(hipMemcpyAsync(cost_out, s->vbs_cost + per * first_pair, per * count * sizeof(long long), hipMemcpyDeviceToHost,
+                                   s->ctx->stream));
+    return ctx_finish(s->ctx);
+}
+
+extern "C" int gme_seq_compensate_vbs(gme_seq* s, int fd, int bs, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_compensate_vbs: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "frame_distance %d needs at least %d frames", fd, fd + 1);
+    GME_REQUIRE(bs >= 1, GME_ERR_ARG, "block_size %d", bs);
+    GME_REQUIRE(s->vbs_valid, GME_ERR_STATE, "gme_seq_compensate_vbs before gme_seq_vbs");
+    int rc = subpel_field(s, "gme_seq_compensate_vbs", fd, bs);
+    if (rc) return rc;
+    const int pairs = s->mv_pairs;
+    rc = ensure_comp(s, fd, pairs);
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    rc = launch_compensate_vbs(ctx, p.at(0), p.at(fd), p.stride, pairs, s->H, s->W, p.pitch, bs >> s->vbs_depth, s->mv_h << s->vbs_depth,
+                               s->mv_w << s->vbs_depth, s->vbs_leaf, s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
+    if (rc) return rc;
+    if (sse_out)
+        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
 }

@@ -178,6 +178,13 @@ struct gme_seq {
     DevBuf<long long> hier_cost[3];      // [P][h][w]
     int hier_levels = 0;                 // levels the last gme_seq_hier used
     bool hier_valid = false;
+    // variable-block-size tree (bbme_vbs.hip): leaf field, depth map and root costs of the last gme_seq_vbs on `mv`, allocated
+    // by its first call; valid until new frame data or the next block-matching call
+    DevBuf<int32_t> vbs_leaf;            // [P][h << D][w << D][2]
+    DevBuf<uint8_t> vbs_dmap;            // [P][h << D][w << D]
+    DevBuf<long long> vbs_cost;          // [P][h][w]
+    int vbs_depth = 0;                   // D of the last gme_seq_vbs
+    bool vbs_valid = false;
     DevBuf<uint8_t> synth_canvas;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -395,6 +402,21 @@ int hier_check_args(const char* who, int bs, int cw, int radius, int pnorm, int 
 // l >= 3 - levels, hb = H / bs and wb = W / bs of level 2.  Names the kernel instance in the context's plan.
 int launch_hier(gme_ctx* ctx, const Plane (&level)[3], int first_prev, int first_cur, int pairs, int bs, int cw, int radius,
                 int pnorm, int levels, int32_t* const (&mf)[3], long long* const (&cost)[3]);
+
+// ---- bbme_vbs.hip: variable-block-size motion -------------------------------------------------------
+// the argument rules of vbs.py (GME_ERR_ARG)
+int vbs_check_args(const char* who, int bs, int depth, int radius, int pnorm, int penalty);
+// vbs.tree of `pairs` pairs on the field mf[pairs][H / bs][W / bs][2]: pair k reads the planes prev + k * plane_stride and
+// cur + k * plane_stride; leaf [pairs][hb << depth][wb << depth][2], dmap of the same grid, cost [pairs][hb][wb] (device).
+// Names the kernel instance in the context's plan.
+int launch_vbs(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W, int pitch,
+               int bs, int depth, int radius, int pnorm, int penalty, const int32_t* mf, int32_t* leaf, uint8_t* dmap,
+               long long* cost);
+// out planes = subpel.compensate_integer of the prev planes by leaf[pairs][hg][wg][2] at cell size g, sse[pairs] (device) =
+// squared error of each against its cur plane
+int launch_compensate_vbs(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W,
+                          int pitch, int g, int hg, int wg, const int32_t* leaf, uint8_t* out, long long out_stride, int out_pitch,
+                          unsigned long long* sse);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

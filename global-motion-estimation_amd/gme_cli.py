@@ -12,6 +12,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py mosaic -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--anchor 0] [--threshold 16] [--min-count 3] [--no-masks]   # background mosaic, moving-object masks
     python gme_cli.py subpel -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--levels 2] [-o OUTDIR]   # quarter-pel block matching of one pair
     python gme_cli.py hier -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-cw 8] [-r 1] [-pn 0] [--levels 3] [--subpel 0|1|2] [-o OUTDIR]   # hierarchical block matching of one pair
+    python gme_cli.py vbs -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--depth 2] [-r 1] [--penalty N] [--hier] [-o OUTDIR]   # variable-block-size motion of one pair
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -97,6 +98,21 @@ def _parser():
     hp.add_argument("--levels", type=int, default=3, help="pyramid levels searched (1 .. 3)")
     hp.add_argument("--subpel", type=int, default=0, help="refine the field afterwards: 0 no, 1 half-pel, 2 quarter-pel")
     hp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for hier.json")
+    vp = sub.add_parser("vbs", help="variable-block-size motion of one frame pair: search, quadtree split and refine, both compensations (vbs.py, DESIGN.md 7g)")
+    vp.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    vp.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the current frame")
+    vp.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=1, help="the previous frame is fi - fd")
+    vp.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="side of the root blocks")
+    vp.add_argument("-sw", "--search-window", dest="search_window", type=int, default=16, help="search window (with --hier: the coarse window, 0 .. 8)")
+    vp.add_argument("-sp", "--searching-procedure", dest="searching_procedure", type=int, default=0)
+    vp.add_argument("-pn", "--pnorm-distance", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    vp.add_argument("--depth", type=int, default=2, help="levels of the quadtree below the root (0 .. 2)")
+    vp.add_argument("-r", "--radius", dest="radius", type=int, default=1, help="a child is searched within +-radius of its parent's vector (0 .. 3)")
+    vp.add_argument("--penalty", type=int, default=None,
+                    help="what a split must gain (0 .. 2^30); default: one grey level per pixel of the root, bs^2 for MAE and "
+                         "16 bs^2 for MSE, a convention of this tool and not a tuned value")
+    vp.add_argument("--hier", action="store_true", help="take the root field from the hierarchical search (three levels, radius 1)")
+    vp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for vbs.json")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -193,6 +209,39 @@ def _subpel(args):
     if args.outdir:
         os.makedirs(args.outdir, exist_ok=True)
         with open(os.path.join(args.outdir, "subpel.json"), "w") as f:
+            json.dump(record, f, indent=1)
+    return res
+
+
+def _vbs(args):
+    """Share of the roots split, leaves per depth and the PSNR of the root-field and the leaf-field compensation of one pair;
+    the same record into OUTDIR/vbs.json."""
+    import json
+    import os
+    import utils
+    import vbs
+    frames = utils.get_video_frames(args.path)
+    if not args.fd <= args.fi < len(frames) or args.fd < 1:
+        raise IndexError("frames %d and %d of %d" % (args.fi - args.fd, args.fi, len(frames)))
+    if args.hier:
+        args.search_window = min(args.search_window, 8)
+    res = vbs.report(frames[args.fi - args.fd], frames[args.fi], args.block_size, args.search_window, args.searching_procedure,
+                     args.pnorm, args.depth, args.radius, args.penalty, args.hier)
+    record = {"options": {"path": args.path, "frame_index": args.fi, "frame_distance": args.fd, "block_size": args.block_size,
+                          "search_window": args.search_window, "searching_procedure": args.searching_procedure,
+                          "pnorm": args.pnorm, "depth": args.depth, "radius": args.radius, "penalty": res["penalty"],
+                          "hier": bool(args.hier)},
+              "shape": list(res["mf"].shape[:2])}
+    record.update({k: res[k] for k in ("split_share", "leaves", "sse_root", "sse_leaf", "psnr_root", "psnr_leaf", "psnr_gain")})
+    print("frames {} -> {}: {} x {} roots of {}, depth {}, radius {}, penalty {}".format(
+        args.fi - args.fd, args.fi, record["shape"][0], record["shape"][1], args.block_size, args.depth, args.radius, res["penalty"]))
+    print("roots split: {:.2f} %".format(100.0 * record["split_share"]))
+    print("leaves per depth: " + ", ".join("{} of {}".format(n, args.block_size >> d) for d, n in enumerate(record["leaves"])))
+    print("psnr root field: {:.4f} dB".format(record["psnr_root"]))
+    print("psnr leaf field: {:.4f} dB  (gain {:+.4f} dB)".format(record["psnr_leaf"], record["psnr_gain"]))
+    if args.outdir:
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "vbs.json"), "w") as f:
             json.dump(record, f, indent=1)
     return res
 
@@ -308,6 +357,8 @@ def main(argv=None):
         return _subpel(args)
     if args.command == "hier":
         return _hier(args)
+    if args.command == "vbs":
+        return _vbs(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")
@@ -315,6 +366,7 @@ def main(argv=None):
     print("motion models (roadmap.global_motion_estimation): " + ", ".join(roadmap.MODELS))
     print("sub-pel refinement (gme_cli.py subpel --levels): 0 integer, 1 half-pel, 2 quarter-pel   (subpel.py)")
     print("hierarchical search (gme_cli.py hier): --levels 1 .. 3, -cw 0 .. 8, -r 0 .. 3, block size a multiple of 2^(levels-1) up to 64   (hier.py)")
+    print("variable block size (gme_cli.py vbs): --depth 0 .. 2, -r 0 .. 3, --penalty 0 .. 2^30, roots a multiple of 2^depth up to 64, leaves of at least 4   (vbs.py)")
     try:
         print("device: " + _gme_native.default_context().info()["name"])
     except Exception as e:      # noqa: BLE001 -- no GPU: say so, the listing above is still useful

@@ -53,6 +53,10 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    **Hierarchical block matching.**  ``hier.motion_field`` searches coarse to fine over the pyramid, every level of a block
    in one wave of one kernel (k_hier, csrc/bbme_hier.hip; host definition hier.py); its field is refined to
    quarter pixels like that of any other search.
+   **Variable block size.**  ``vbs.motion_field`` splits the blocks of any search's field in four, refines each quarter
+   around its parent's vector and keeps a split only where it lowers the cost by more than a penalty, the whole tree of a
+   block in one wave of one kernel (k_vbs, csrc/bbme_vbs.hip; host definition vbs.py; DESIGN.md §7g);
+   ``Sequence.compensate_vbs`` compensates with the leaf field.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

@@ -503,6 +503,33 @@ class ShardedSequence:
             return lane.seq.read_hier(2, 0, lane.hi - lane.lo)
         return tuple(np.concatenate(part, axis=0) for part in zip(*self._each(run)))
 
+    def motion_fields_vbs(self, block_size, search_window, procedure, pnorm, depth=2, radius=1, penalty=None, hier=False,
+                          compensate=False):
+        """The search, then vbs.tree on its field for every local pair, per lane -> (leaf
+        int32[P_local, h << depth, w << depth, 2], depth uint8[P_local, h << depth, w << depth], cost int64[P_local, h, w]) and,
+        with ``compensate``, sse int64[P_local] of the leaf-field compensation against the current frames.  The search is
+        bbme(block_size, search_window, procedure, pnorm) or, with ``hier``, the hierarchical one at three levels with
+        search_window as its coarse window and radius 1.  ``penalty`` None: vbs.default_penalty."""
+        import vbs
+        penalty = vbs.default_penalty(block_size, pnorm) if penalty is None else penalty
+        block_size, depth, radius, pnorm, penalty = _native._vbs_args(block_size, depth, radius, pnorm, penalty)
+        h, w = self.H // block_size, self.W // block_size
+        if not self.lanes:
+            empty = (np.zeros((0, h << depth, w << depth, 2), np.int32), np.zeros((0, h << depth, w << depth), np.uint8),
+                     np.zeros((0, h, w), np.int64))
+            return empty + (np.zeros(0, np.int64),) if compensate else empty
+
+        def run(lane):
+            n = lane.hi - lane.lo
+            if hier:
+                lane.seq.hier(self.fd, block_size, search_window, 1, pnorm, 3)
+            else:
+                lane.seq.bbme(self.fd, block_size, search_window, procedure, pnorm)
+            lane.seq.vbs(self.fd, block_size, depth, radius, pnorm, penalty)
+            out = lane.seq.read_vbs(0, n)
+            return out + (lane.seq.compensate_vbs(self.fd, block_size)[:n],) if compensate else out
+        return tuple(np.concatenate(part, axis=0) for part in zip(*self._each(run)))
+
     def estimate(self, procedure=3, search_window=2, model=None):
         """motion.global_motion_estimation for every local pair -> float64[P_local, 6].  ``model``: one of roadmap.MODELS
         (roadmap.stages per lane); the second-order models return float64[P_local, 12]."""

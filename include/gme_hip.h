@@ -381,6 +381,39 @@ GME_API int gme_hier_u8(gme_ctx *ctx, const uint8_t *prev, const uint8_t *cur, i
 GME_API int gme_seq_hier(gme_seq *seq, int frame_distance, int block_size, int coarse_window, int radius, int pnorm, int levels);
 GME_API int gme_seq_read_hier(gme_seq *seq, int level, int first_pair, int count, int32_t *mf_out, int64_t *cost_out);
 
+/* Variable-block-size motion (host definition vbs.py): a quadtree over the blocks of an integer motion
+ * field, one kernel for the whole tree; integer throughout and equal to vbs.tree byte for byte.  block_size B is the side of
+ * the root blocks (the block size of the input field), depth D in 0 .. 2, radius r in 0 .. 3, pnorm 0 (sum |d|) or 1 (sum d^2),
+ * penalty in 0 .. 2^30.  Root (i, j), i < H / B, j < W / B, has its origin at (j B, i B) and the vector v = mf[i][j].  If its
+ * displaced block does not lie entirely in the frame it is a leaf of depth 0 with cost -1 whose cells carry v (the rule of
+ * gme_subpel_u8); otherwise its own cost c is the cost at v.  A node of depth d < D has four children of half its side, child k
+ * at row k >> 1 and column k & 1.  A child is searched around its parent's vector: the centre is scored first; then the offsets
+ * in [-r, r]^2 without it (column offset in the outer loop, ascending), skipping blocks that are not inside the frame; only a
+ * strictly smaller cost replaces the best.  Each child is a node of depth d + 1 with its winning vector and cost, resolved
+ * first.  With S = penalty + sum of the children's F the node splits iff S < c (a tie does not split), and F = min(c, S); a
+ * node of depth D is a leaf with F = c.  Every sum of a decision stays below 2^31.
+ * Result per pair, g = B >> D: leaf int32[(H/B) 2^D][(W/B) 2^D][2], every g x g cell carries the vector of the leaf that covers
+ * it; depth uint8 of the same grid, the depth of that leaf; cost int64[H/B][W/B], F of the root (penalties included) or -1.
+ * gme_vbs_u8: one pair on host buffers, mf_in int32[H/B][W/B][2]; depth_out and cost_out may be NULL.
+ * gme_seq_vbs: every pair of the field the last gme_seq_bbme or gme_seq_hier left; GME_ERR_STATE if there is no such field or it
+ *   was made with another frame distance or block size.  The result is kept in the sequence (allocated on first use) and does
+ *   not replace the sequence's motion field; it is no longer valid after new frame data or the next block-matching call.
+ * gme_seq_read_vbs: pairs first_pair .. first_pair + count - 1 of it; any output may be NULL; a range outside the field is
+ *   GME_ERR_ARG, GME_ERR_STATE where there is no valid result.
+ * gme_seq_compensate_vbs: the per-pixel rule of the integer fields at the leaf size g: pixel (a, b) of every whole cell of
+ *   compensated frame k becomes pixel (a - d1, b - d0) of frame k where that lies in the frame, elsewhere (and beyond the last
+ *   whole cell) the pixel is kept; written into the sequence's compensated frames (gme_seq_read_compensated_range reads them);
+ *   sse_out[pairs] (may be NULL) = exact squared error against frame k + frame_distance.
+ * Blocking calls, also in split-phase mode.  GME_ERR_ARG unless B % 2^D == 0, B >> D >= 4, B <= 64 and depth, radius, pnorm and
+ * penalty lie in their ranges.  gme_last_bbme_info names the kernel instance: k_vbs<16,2>, k_vbs<32,2>, or k_vbs<0,0> (block
+ * size and depth at run time). */
+GME_API int gme_vbs_u8(gme_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int H, int W, int stride, int block_size, int depth,
+                       int radius, int pnorm, int penalty, const int32_t *mf_in, int32_t *leaf_out, uint8_t *depth_out,
+                       int64_t *cost_out);
+GME_API int gme_seq_vbs(gme_seq *seq, int frame_distance, int block_size, int depth, int radius, int pnorm, int penalty);
+GME_API int gme_seq_read_vbs(gme_seq *seq, int first_pair, int count, int32_t *leaf_out, uint8_t *depth_out, int64_t *cost_out);
+GME_API int gme_seq_compensate_vbs(gme_seq *seq, int frame_distance, int block_size, int64_t *sse_out);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
