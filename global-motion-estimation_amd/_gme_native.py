@@ -118,6 +118,11 @@ _SIGNATURES = {
     "gme_seq_vbs": (_i, [_vp, _i, _i, _i, _i, _i, _i]),
     "gme_seq_read_vbs": (_i, [_vp, _i, _i, _c_i32p, _c_u8p, _c_i64p]),
     "gme_seq_compensate_vbs": (_i, [_vp, _i, _i, _c_i64p]),
+    "gme_bipred_u8": (_i, [_vp, _c_u8p, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i32p, _c_u8p, _c_i32p, _c_i32p, _c_i64p,
+                           _c_i64p, _c_u8p, _c_i64p]),
+    "gme_seq_bipred": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "gme_seq_read_bipred": (_i, [_vp, _i, _i, _c_i32p, _c_i32p, _c_u8p, _c_i32p, _c_i32p, _c_i64p, _c_i64p]),
+    "gme_seq_predict_bipred": (_i, [_vp, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -411,6 +416,37 @@ class Context:
         _check(self.lib.gme_vbs_u8(self.handle, _p(prev, _c_u8p), _p(cur, _c_u8p), H, W, prev.strides[0], block_size, depth, radius,
                                    pnorm, penalty, _p(mf32, _c_i32p), _p(leaf, _c_i32p), _p(dmap, _c_u8p), _p(cost, _c_i64p)), self.lib)
         return leaf, dmap, cost
+
+    def bipred(self, past, mid, next, f0, f1, block_size, radius=1, rounds=1, pnorm=0, penalty=0):
+        """Bidirectional prediction of ``mid`` on the integer fields f0 (into ``past``) and f1 (into ``next``), int32[H // bs,
+        W // bs, 2] (gme_bipred_u8, bipred.decide and bipred.predict) -> (mode uint8[h, w], v0 int32[h, w, 2], v1 int32[h, w, 2],
+        cost int64[h, w], costs int64[h, w, 3], predicted uint8[H, W], sse int)."""
+        frames = [as_frame(a, name) for a, name in ((past, "past"), (mid, "mid"), (next, "next"))]
+        if any(a.shape != frames[1].shape for a in frames):
+            raise AssertionError("past, mid and next differ in shape (bbme.py:59)")
+        block_size, radius, rounds, pnorm, penalty = _bipred_args(block_size, radius, rounds, pnorm, penalty)
+        H, W = frames[1].shape
+        if any(a.strides[0] != frames[1].strides[0] for a in frames):
+            frames = [np.ascontiguousarray(a) for a in frames]
+        h, w = H // block_size, W // block_size
+        fields = [np.ascontiguousarray(np.asarray(f)[:, :, :2].astype(np.int32)) for f in (f0, f1)]
+        for f in fields:
+            if f.shape != (h, w, 2):
+                raise ValueError("the field of a %d x %d frame at block size %d is %r, not %r" % (H, W, block_size, (h, w, 2), f.shape))
+        mode, v0, v1 = np.zeros((h, w), np.uint8), np.zeros((h, w, 2), np.int32), np.zeros((h, w, 2), np.int32)
+        cost, costs, pred = np.zeros((h, w), np.int64), np.zeros((h, w, 3), np.int64), np.empty((H, W), np.uint8)
+        sse = ctypes.c_int64(0)
+        _check(self.lib.gme_bipred_u8(self.handle, _p(frames[0], _c_u8p), _p(frames[1], _c_u8p), _p(frames[2], _c_u8p), H, W,
+                                      frames[1].strides[0], block_size, radius, rounds, pnorm, penalty, _p(fields[0], _c_i32p),
+                                      _p(fields[1], _c_i32p), _p(mode, _c_u8p), _p(v0, _c_i32p), _p(v1, _c_i32p), _p(cost, _c_i64p),
+                                      _p(costs, _c_i64p), _p(pred, _c_u8p), ctypes.byref(sse)), self.lib)
+        return mode, v0, v1, cost, costs, pred, sse.value
+
+
+def _bipred_args(block_size, radius, rounds, pnorm, penalty):
+    """bipred.check_args: the definition's argument rules, ValueError before the library is asked."""
+    import bipred
+    return bipred.check_args(block_size, radius, rounds, pnorm, penalty)
 
 
 def _vbs_args(block_size, depth, radius, pnorm, penalty):
@@ -915,6 +951,39 @@ class Sequence:
         sse = np.zeros(max(getattr(self, "_mv_shape", (0,))[0], 1), np.int64)
         _check(self.lib.gme_seq_compensate_vbs(self.handle, int(frame_distance), _block_size(block_size), _p(sse, _c_i64p)), self.lib)
         return sse[:getattr(self, "_mv_shape", (0,))[0]]
+
+    # ---- bidirectional block prediction (bbme_bipred.hip, bipred.py)
+    def bipred(self, frame_distance, block_size=16, search_window=16, procedure=0, pnorm=0, radius=1, rounds=1, penalty=0):
+        """bipred.decide for the targets t = fd .. N-1-fd on the device (gme_seq_bipred): both searches from every target (into
+        frame t-fd and into frame t+fd, the arguments of bbme()) and the decision.  The motion field and what was derived from it
+        stay what they were; read_bipred reads the result, predict_bipred predicts with it."""
+        self._blocking("bidirectional prediction")
+        block_size, radius, rounds, pnorm, penalty = _bipred_args(block_size, radius, rounds, pnorm, penalty)
+        fd = int(frame_distance)
+        _check(self.lib.gme_seq_bipred(self.handle, fd, block_size, int(search_window), int(procedure), pnorm, radius, rounds, penalty),
+               self.lib)
+        self._bipred_shape = (self.N - 2 * fd, self.H // block_size, self.W // block_size)
+
+    def read_bipred(self, first=0, count=None):
+        """(f0, f1 int32[count, h, w, 2], mode uint8[count, h, w], v0, v1 int32[count, h, w, 2], cost int64[count, h, w], costs
+        int64[count, h, w, 3]) of targets first .. first+count-1 of the last bipred()."""
+        shape = getattr(self, "_bipred_shape", None) or (0, 0, 0)
+        count = shape[0] - first if count is None else count
+        grid = (max(count, 0),) + tuple(shape[1:])
+        f0, f1, v0, v1 = (np.empty(grid + (2,), np.int32) for _ in range(4))
+        mode, cost, costs = np.empty(grid, np.uint8), np.empty(grid, np.int64), np.empty(grid + (3,), np.int64)
+        _check(self.lib.gme_seq_read_bipred(self.handle, int(first), int(count), _p(f0, _c_i32p), _p(f1, _c_i32p), _p(mode, _c_u8p),
+                                            _p(v0, _c_i32p), _p(v1, _c_i32p), _p(cost, _c_i64p), _p(costs, _c_i64p)), self.lib)
+        return f0, f1, mode, v0, v1, cost, costs
+
+    def predict_bipred(self):
+        """The predicted frames of the last bipred() (gme_seq_predict_bipred, bipred.predict) -> sse int64[T] against the target
+        frames; read_compensated_range(0, T) reads the frames."""
+        self._blocking("bidirectional prediction")
+        T = (getattr(self, "_bipred_shape", None) or (0,))[0]
+        sse = np.zeros(max(T, 1), np.int64)
+        _check(self.lib.gme_seq_predict_bipred(self.handle, _p(sse, _c_i64p)), self.lib)
+        return sse[:T]
 
 
 _default = None

@@ -574,6 +574,68 @@ extern "C" int gme_vbs_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur,
     return ctx_finish(ctx);
 }
 
+// Bidirectional prediction of one triple on given fields (bbme_bipred.hip): the three frames and the
+// predicted one as one stack of four planes in the scratch.
+extern "C" int gme_bipred_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid, const uint8_t* next, int H, int W, int stride,
+                             int block_size, int radius, int rounds, int pnorm, int penalty, const int32_t* f0, const int32_t* f1,
+                             uint8_t* mode_out, int32_t* v0_out, int32_t* v1_out, int64_t* cost_out, int64_t* costs_out,
+                             uint8_t* pred_out, int64_t* sse_out)
+{
+    GME_ENTER(ctx);
+    GME_REQUIRE(past && mid && next && f0 && f1 && mode_out, GME_ERR_ARG, "gme_bipred_u8: null pointer");
+    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_bipred_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
+    int rc = bipred_check_args("gme_bipred_u8", block_size, radius, rounds, pnorm, penalty);
+    if (rc) return rc;
+    const int h = H / block_size, w = W / block_size;
+    const size_t n = (size_t)h * w;
+    Plane st = plane_shape(H, W, 4);                           // past, mid, next, predicted
+    int32_t* d_vec = nullptr;                                  // f0, f1, v0, v1
+    long long* d_cost = nullptr;                               // cost, costs, then the squared error
+    uint8_t* d_mode = nullptr;
+    Carver c;
+    c.take(&st, true); c.take(&d_vec, n * 8); c.take(&d_cost, n * 4 + 1); c.take(&d_mode, n + 1);
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    int32_t *d_f0 = d_vec, *d_f1 = d_vec + n * 2, *d_v0 = d_vec + n * 4, *d_v1 = d_vec + n * 6;
+    long long* d_costs = d_cost + n;
+    unsigned long long* d_sse = (unsigned long long*)(d_cost + n * 4);
+    GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_vec - st.ptr, ctx->stream));
+    const uint8_t* host[3] = { past, mid, next };
+    for (int k = 0; k < 3; ++k) {
+        Plane one = st;
+        one.ptr = st.at(k);
+        GME_HIP_TRY(put_plane(ctx, one, host[k], stride));
+    }
+    if (n) {
+        GME_HIP_TRY(hipMemcpyAsync(d_f0, f0, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        GME_HIP_TRY(hipMemcpyAsync(d_f1, f1, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = launch_bipred(ctx, st.at(0), st.at(1), st.at(2), 0, 1, H, W, st.pitch, block_size, radius, rounds, pnorm, penalty, d_f0, d_f1,
+                       d_mode, d_v0, d_v1, d_cost, d_costs);
+    if (rc) return rc;
+    if (n) {
+        GME_HIP_TRY(hipMemcpyAsync(mode_out, d_mode, n, hipMemcpyDeviceToHost, ctx->stream));
+        if (v0_out) GME_HIP_TRY(hipMemcpyAsync(v0_out, d_v0, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (v1_out) GME_HIP_TRY(hipMemcpyAsync(v1_out, d_v1, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        if (costs_out) GME_HIP_TRY(hipMemcpyAsync(costs_out, d_costs, n * 3 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    unsigned long long sse = 0;
+    if (pred_out || sse_out) {
+        rc = launch_predict_bipred(ctx, st.at(0), st.at(1), st.at(2), 0, 1, H, W, st.pitch, block_size, d_mode, d_v0, d_v1, st.at(3), 0,
+                                   st.pitch, d_sse);
+        if (rc) return rc;
+        if (pred_out) {
+            rc = read_planes(ctx, st, 3, 1, pred_out);
+            if (rc) return rc;
+        }
+        GME_HIP_TRY(hipMemcpyAsync(&sse, d_sse, sizeof(sse), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    rc = ctx_finish(ctx);
+    if (sse_out) *sse_out = (int64_t)sse;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -664,6 +726,7 @@ static void seq_frames_changed(gme_seq* s)
     s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
     s->hier_valid = false;
     s->vbs_valid = false;
+    s->bp_valid = false;
     gme_drop_run(s);
 }
 
@@ -849,16 +912,23 @@ static int seq_sqbox(gme_seq* s, int level, int kind)
     return GME_OK;
 }
 
-// launch_bbme of a job over the resident frames of one level (pairs k, k + fd) with the auxiliary table its kernel wants
-static int seq_launch_bbme(gme_seq* s, int level, int fd, BbmeJob job)
+// launch_bbme of a job over the resident frames of one level whose first "current" plane is frame first_cur of the level,
+// with the auxiliary table its kernel wants (one table per frame, so the job's tables start at that frame's)
+static int seq_launch_bbme_from(gme_seq* s, int level, int first_cur, BbmeJob job)
 {
     if (const int aux = bbme_aux_kind(job.H, job.W, job.pitch, job.pairs, job.bs, job.sw, job.procedure, job.pnorm)) {      // BASELINE config 4
         const int rc = seq_sqbox(s, level, aux);
         if (rc) return rc;
         const Plane& p = s->level[level];
-        job.sqbox_cur = s->sqbox[level] + (size_t)fd * p.stride; job.sqbox_stride = p.stride; job.sqbox_kind = aux;
+        job.sqbox_cur = s->sqbox[level] + (size_t)first_cur * p.stride; job.sqbox_stride = p.stride; job.sqbox_kind = aux;
     }
     return launch_bbme(s->ctx, job);
+}
+
+// ... of the pairs (k, k + fd): the first pair is pair 0
+static int seq_launch_bbme(gme_seq* s, int level, int fd, BbmeJob job)
+{
+    return seq_launch_bbme_from(s, level, fd, job);
 }
 
 extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, int pnorm)
@@ -2054,5 +2124,89 @@ extern "C" int gme_seq_compensate_vbs(gme_seq* s, int fd, int bs, int64_t* sse_o
     if (rc) return rc;
     if (sse_out)
         GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Bidirectional block prediction (bbme_bipred.hip): blocking calls.  gme_seq_bipred runs both searches
+// from every target frame itself, into fields of its own, and leaves the sequence's motion field and what was derived from it
+// (quarter-pel, hierarchical, variable-block-size results) as they were.
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_bipred(gme_seq* s, int fd, int bs, int sw, int procedure, int pnorm, int radius, int rounds, int penalty)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_bipred: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(fd >= 1 && s->N - fd >= fd + 1, GME_ERR_ARG, "gme_seq_bipred: frame_distance %d needs at least %d frames", fd, 2 * fd + 1);
+    int rc = bipred_check_args("gme_seq_bipred", bs, radius, rounds, pnorm, penalty);
+    if (rc) return rc;
+    rc = bbme_check_args(s->H, s->W, bs, sw, procedure, pnorm);
+    if (rc) return rc;
+    const int T = s->N - 2 * fd, h = s->H / bs, w = s->W / bs;
+    const size_t n = (size_t)T * h * w;
+    s->bp_valid = false;
+    rc = dev_ensure_all("bidirectional prediction", { { s->bp_f0, n * 2 }, { s->bp_f1, n * 2 }, { s->bp_v0, n * 2 }, { s->bp_v1, n * 2 } });
+    if (rc) return rc;
+    rc = s->bp_mode.ensure(n, "bidirectional modes");
+    if (rc) return rc;
+    rc = dev_ensure_all("bidirectional costs", { { s->bp_cost, n }, { s->bp_costs, n * 3 } });
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    // the anchor of both searches is the target frame t = fd + k; it is looked for in frame t - fd = k and in frame t + fd
+    BbmeJob job = bbme_job(p, fd, 0, T, bs, sw, procedure, pnorm, s->bp_f0);
+    job.cur = p.at(0);
+    rc = seq_launch_bbme_from(s, 2, 0, job);
+    if (rc) return rc;
+    rc = seq_launch_bbme_from(s, 2, 2 * fd, bbme_job(p, fd, fd, T, bs, sw, procedure, pnorm, s->bp_f1));
+    if (rc) return rc;
+    rc = launch_bipred(ctx, p.at(0), p.at(fd), p.at(2 * fd), p.stride, T, s->H, s->W, p.pitch, bs, radius, rounds, pnorm, penalty, s->bp_f0,
+                       s->bp_f1, s->bp_mode, s->bp_v0, s->bp_v1, s->bp_cost, s->bp_costs);
+    if (rc) return rc;
+    rc = ctx_finish(ctx);
+    if (rc) return rc;
+    s->bp_targets = T; s->bp_h = h; s->bp_w = w; s->bp_fd = fd; s->bp_bs = bs;
+    s->bp_valid = true;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_bipred(gme_seq* s, int first, int count, int32_t* f0_out, int32_t* f1_out, uint8_t* mode_out, int32_t* v0_out,
+                                   int32_t* v1_out, int64_t* cost_out, int64_t* costs_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_bipred: null sequence");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(s->bp_valid, GME_ERR_STATE, "gme_seq_read_bipred before gme_seq_bipred");
+    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->bp_targets, GME_ERR_ARG,
+                "gme_seq_read_bipred: targets [%d, %d) outside [0, %d)", first, first + count, s->bp_targets);
+    const size_t per = (size_t)s->bp_h * s->bp_w, m = per * count;
+    hipStream_t st = s->ctx->stream;
+    if (m) {
+        const struct { void* out; const void* src; size_t elem; } parts[] = {
+            { f0_out, s->bp_f0 + per * 2 * first, 2 * sizeof(int32_t) }, { f1_out, s->bp_f1 + per * 2 * first, 2 * sizeof(int32_t) },
+            { mode_out, s->bp_mode + per * first, 1 },
+            { v0_out, s->bp_v0 + per * 2 * first, 2 * sizeof(int32_t) }, { v1_out, s->bp_v1 + per * 2 * first, 2 * sizeof(int32_t) },
+            { cost_out, s->bp_cost + per * first, sizeof(long long) }, { costs_out, s->bp_costs + per * 3 * first, 3 * sizeof(long long) },
+        };
+        for (const auto& part : parts)
+            if (part.out) GME_HIP_TRY(hipMemcpyAsync(part.out, part.src, m * part.elem, hipMemcpyDeviceToHost, st));
+    }
+    return ctx_finish(s->ctx);
+}
+
+extern "C" int gme_seq_predict_bipred(gme_seq* s, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_predict_bipred: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(s->bp_valid, GME_ERR_STATE, "gme_seq_predict_bipred before gme_seq_bipred");
+    const int T = s->bp_targets, fd = s->bp_fd;
+    GME_REQUIRE(T <= s->N - 2 * fd, GME_ERR_STATE, "gme_seq_predict_bipred: %d targets, the sequence has %d", T, s->N - 2 * fd);
+    int rc = ensure_comp(s, fd, T);
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    rc = launch_predict_bipred(ctx, p.at(0), p.at(fd), p.at(2 * fd), p.stride, T, s->H, s->W, p.pitch, s->bp_bs, s->bp_mode, s->bp_v0,
+                               s->bp_v1, s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
+    if (rc) return rc;
+    if (sse_out && T)
+        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)T * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
 }

@@ -185,6 +185,16 @@ struct gme_seq {
     DevBuf<long long> vbs_cost;          // [P][h][w]
     int vbs_depth = 0;                   // D of the last gme_seq_vbs
     bool vbs_valid = false;
+    // bidirectional prediction (bbme_bipred.hip): both fields of gme_seq_bipred's own searches, the modes, the vector pairs and
+    // the costs of its T = N - 2 fd targets, allocated by its first call; valid until new frame data.  No other call reads or
+    // writes them, and gme_seq_bipred writes nothing else of the sequence.
+    DevBuf<int32_t> bp_f0, bp_f1;        // [T][h][w][2]
+    DevBuf<uint8_t> bp_mode;             // [T][h][w]
+    DevBuf<int32_t> bp_v0, bp_v1;        // [T][h][w][2]
+    DevBuf<long long> bp_cost;           // [T][h][w]
+    DevBuf<long long> bp_costs;          // [T][h][w][3]
+    int bp_targets = 0, bp_h = 0, bp_w = 0, bp_fd = 0, bp_bs = 0;
+    bool bp_valid = false;
     DevBuf<uint8_t> synth_canvas;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -417,6 +427,21 @@ int launch_vbs(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long 
 int launch_compensate_vbs(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W,
                           int pitch, int g, int hg, int wg, const int32_t* leaf, uint8_t* out, long long out_stride, int out_pitch,
                           unsigned long long* sse);
+
+// ---- bbme_bipred.hip: bidirectional block prediction ------------------------------------------------
+// the argument rules of bipred.py (GME_ERR_ARG)
+int bipred_check_args(const char* who, int bs, int radius, int rounds, int pnorm, int penalty);
+// bipred.decide of `targets` triples on the fields f0, f1 [targets][H / bs][W / bs][2]: target k reads the planes
+// past + k * plane_stride, mid + k * plane_stride and next + k * plane_stride; mode [targets][hb][wb], v0 and v1
+// [targets][hb][wb][2], cost [targets][hb][wb], costs [targets][hb][wb][3] (device).  Names the kernel instance in the
+// context's plan.
+int launch_bipred(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid, const uint8_t* next, long long plane_stride, int targets,
+                  int H, int W, int pitch, int bs, int radius, int rounds, int pnorm, int penalty, const int32_t* f0, const int32_t* f1,
+                  uint8_t* mode, int32_t* v0, int32_t* v1, long long* cost, long long* costs);
+// out planes = bipred.predict of the past and next planes, sse[targets] (device) = squared error of each against its mid plane
+int launch_predict_bipred(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid, const uint8_t* next, long long plane_stride,
+                          int targets, int H, int W, int pitch, int bs, const uint8_t* mode, const int32_t* v0, const int32_t* v1,
+                          uint8_t* out, long long out_stride, int out_pitch, unsigned long long* sse);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -13,6 +13,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py subpel -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--levels 2] [-o OUTDIR]   # quarter-pel block matching of one pair
     python gme_cli.py hier -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-cw 8] [-r 1] [-pn 0] [--levels 3] [--subpel 0|1|2] [-o OUTDIR]   # hierarchical block matching of one pair
     python gme_cli.py vbs -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--depth 2] [-r 1] [--penalty N] [--hier] [-o OUTDIR]   # variable-block-size motion of one pair
+    python gme_cli.py bipred -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [-r 1] [--rounds 1] [--penalty N] [-o OUTDIR]   # bidirectional prediction of one frame
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -113,6 +114,20 @@ def _parser():
                          "16 bs^2 for MSE, a convention of this tool and not a tuned value")
     vp.add_argument("--hier", action="store_true", help="take the root field from the hierarchical search (three levels, radius 1)")
     vp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for vbs.json")
+    bp = sub.add_parser("bipred", help="bidirectional prediction of one frame from the frames on both sides of it: per block the past one, the next one or their average (bipred.py, DESIGN.md 7h)")
+    bp.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    bp.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the predicted frame")
+    bp.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=1, help="the references are fi - fd and fi + fd")
+    bp.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="4 .. 64")
+    bp.add_argument("-sw", "--search-window", dest="search_window", type=int, default=16)
+    bp.add_argument("-sp", "--searching-procedure", dest="searching_procedure", type=int, default=0)
+    bp.add_argument("-pn", "--pnorm-distance", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    bp.add_argument("-r", "--radius", dest="radius", type=int, default=1, help="a pass tries one vector of the averaged pair within +-radius (0 .. 2)")
+    bp.add_argument("--rounds", type=int, default=1, help="rounds of two passes, past vector then next vector (0 .. 2)")
+    bp.add_argument("--penalty", type=int, default=None,
+                    help="what the average must gain over a single reference (0 .. 2^30); default: a quarter grey level per pixel, "
+                         "bs^2 / 4 for MAE and 4 bs^2 for MSE, a convention of this tool and not a tuned value")
+    bp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for bipred.json")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -246,6 +261,39 @@ def _vbs(args):
     return res
 
 
+def _bipred(args):
+    """Mode shares, the share of refined blocks and the PSNR of the past-only, the next-only and the chosen prediction of one
+    frame; the same record into OUTDIR/bipred.json."""
+    import json
+    import os
+    import bipred
+    import utils
+    frames = utils.get_video_frames(args.path)
+    if args.fd < 1 or not args.fd <= args.fi < len(frames) - args.fd:
+        raise IndexError("frames %d, %d and %d of %d" % (args.fi - args.fd, args.fi, args.fi + args.fd, len(frames)))
+    res = bipred.report(frames[args.fi - args.fd], frames[args.fi], frames[args.fi + args.fd], args.block_size, args.search_window,
+                        args.searching_procedure, args.pnorm, args.radius, args.rounds, args.penalty)
+    record = {"options": {"path": args.path, "frame_index": args.fi, "frame_distance": args.fd, "block_size": args.block_size,
+                          "search_window": args.search_window, "searching_procedure": args.searching_procedure,
+                          "pnorm": args.pnorm, "radius": args.radius, "rounds": args.rounds, "penalty": res["penalty"]},
+              "shape": list(res["mode"].shape)}
+    record.update({k: res[k] for k in ("mode_share", "refined_share", "sse_past", "sse_next", "sse_chosen", "psnr_past", "psnr_next",
+                                       "psnr_chosen")})
+    print("frame {} from {} and {}: {} x {} blocks of {}, radius {}, rounds {}, penalty {}".format(
+        args.fi, args.fi - args.fd, args.fi + args.fd, record["shape"][0], record["shape"][1], args.block_size, args.radius, args.rounds,
+        res["penalty"]))
+    print("modes: past {:.2f} %, next {:.2f} %, average {:.2f} %, none {:.2f} %".format(*(100.0 * v for v in record["mode_share"])))
+    print("refined blocks: {:.2f} %".format(100.0 * record["refined_share"]))
+    print("psnr past only: {:.4f} dB".format(record["psnr_past"]))
+    print("psnr next only: {:.4f} dB".format(record["psnr_next"]))
+    print("psnr chosen:    {:.4f} dB".format(record["psnr_chosen"]))
+    if args.outdir:
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "bipred.json"), "w") as f:
+            json.dump(record, f, indent=1)
+    return res
+
+
 def _hier(args):
     """Reach, median vector and PSNR of the compensation of one pair under the hierarchical search (with --subpel also the
     PSNR of the quarter-pel compensation of the refined field); the same record into OUTDIR/hier.json."""
@@ -359,6 +407,8 @@ def main(argv=None):
         return _hier(args)
     if args.command == "vbs":
         return _vbs(args)
+    if args.command == "bipred":
+        return _bipred(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")
@@ -367,6 +417,7 @@ def main(argv=None):
     print("sub-pel refinement (gme_cli.py subpel --levels): 0 integer, 1 half-pel, 2 quarter-pel   (subpel.py)")
     print("hierarchical search (gme_cli.py hier): --levels 1 .. 3, -cw 0 .. 8, -r 0 .. 3, block size a multiple of 2^(levels-1) up to 64   (hier.py)")
     print("variable block size (gme_cli.py vbs): --depth 0 .. 2, -r 0 .. 3, --penalty 0 .. 2^30, roots a multiple of 2^depth up to 64, leaves of at least 4   (vbs.py)")
+    print("bidirectional prediction (gme_cli.py bipred): -bs 4 .. 64, -r 0 .. 2, --rounds 0 .. 2, --penalty 0 .. 2^30; per block the past frame, the next one or their average   (bipred.py)")
     try:
         print("device: " + _gme_native.default_context().info()["name"])
     except Exception as e:      # noqa: BLE001 -- no GPU: say so, the listing above is still useful

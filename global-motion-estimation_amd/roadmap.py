@@ -57,6 +57,10 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    around its parent's vector and keeps a split only where it lowers the cost by more than a penalty, the whole tree of a
    block in one wave of one kernel (k_vbs, csrc/bbme_vbs.hip; host definition vbs.py; DESIGN.md §7g);
    ``Sequence.compensate_vbs`` compensates with the leaf field.
+   **Bidirectional prediction.**  ``bipred.motion_field`` predicts a frame from the frames on both sides of it: per block the
+   past reference, the next one or the rounded average of both, the averaged pair refined in alternating passes, a block's
+   whole decision in one wave of one kernel (k_bipred, csrc/bbme_bipred.hip; host definition bipred.py; DESIGN.md §7h);
+   ``Sequence.predict_bipred`` writes the predicted frames.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

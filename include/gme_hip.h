@@ -414,6 +414,47 @@ GME_API int gme_seq_vbs(gme_seq *seq, int frame_distance, int block_size, int de
 GME_API int gme_seq_read_vbs(gme_seq *seq, int first_pair, int count, int32_t *leaf_out, uint8_t *depth_out, int64_t *cost_out);
 GME_API int gme_seq_compensate_vbs(gme_seq *seq, int frame_distance, int block_size, int64_t *sse_out);
 
+/* Bidirectional block prediction (host definition bipred.py): a block of the frame `mid` is predicted from
+ * the frame before it, from the frame after it, or from the rounded average of both; integer throughout and equal to
+ * bipred.decide and bipred.predict byte for byte.  block_size B in 4 .. 64, radius r in 0 .. 2, rounds in 0 .. 2, pnorm 0
+ * (sum |d|) or 1 (sum d^2), penalty in 0 .. 2^30.  Block (i, j), i < H / B, j < W / B, has its origin at (j B, i B); f0[i][j]
+ * (column, row) says where it is found in `past`, f1[i][j] where in `next` (the fields of a search with `mid` as the previous
+ * and `past`, or `next`, as the current frame).  c0 is the cost against `past` at f0, c1 against `next` at f1, each unavailable
+ * (-1) if the displaced block does not lie entirely in the frame.  cb exists only when both do: the cost of the predictor
+ * (p + n + 1) >> 1 at (f0, f1), then refined by `rounds` rounds of two passes.  Pass 1 holds the `next` vector and tries the
+ * `past` vector at its value at the start of the pass plus the offsets in [-r, r]^2 without the centre (column offset in the
+ * outer loop, ascending), skipping blocks that are not inside the frame; only a strictly smaller cost replaces the best.  Pass
+ * 2 holds the new `past` vector and does the same for the `next` vector.  Decision: (mode 0, c0), (mode 1, c1), (mode 2,
+ * cb + penalty) in that order, unavailable ones left out, only a strictly smaller value replaces the best; with none
+ * available, mode 3 and cost -1.  Every sum of a decision stays below 2^31.
+ * Result per target: mode uint8[H/B][W/B]; v0, v1 int32[H/B][W/B][2], the refined pair where mode is 2 and the inputs
+ * elsewhere; cost int64[H/B][W/B], the chosen value (penalty included) or -1; costs int64[H/B][W/B][3] = c0, c1, cb (without
+ * the penalty), -1 where unavailable.
+ * Prediction: a block of mode 0 is the `past` block at v0, of mode 1 the `next` block at v1, of mode 2 their rounded average;
+ * a block of mode 3 and every pixel beyond the last whole block is the co-located pixel of `past`.
+ * gme_bipred_u8: one triple on host buffers with the fields f0, f1 int32[H/B][W/B][2]; every output but mode_out may be NULL;
+ *   pred_out uint8[H][W] (tight) is the predicted frame and *sse_out its exact squared error against `mid`.
+ * gme_seq_bipred: the targets t = frame_distance .. N - 1 - frame_distance of the sequence, T = N - 2 frame_distance of them
+ *   (GME_ERR_ARG unless N >= 2 frame_distance + 1), target k predicted from the frames t - frame_distance and
+ *   t + frame_distance.  It runs both searches itself (the arguments and rules of gme_seq_bbme) into fields of its own and
+ *   then the decision; the sequence's motion field and the quarter-pel, hierarchical and variable-block-size results stay as
+ *   they were.  The result is kept in the sequence (allocated on first use) until new frame data.
+ * gme_seq_read_bipred: targets first .. first + count - 1 of it; any output may be NULL; a range outside [0, T) is GME_ERR_ARG,
+ *   GME_ERR_STATE where there is no valid result.
+ * gme_seq_predict_bipred: the T predicted frames into the sequence's compensated frames (gme_seq_read_compensated_range reads
+ *   them), sse_out[T] (may be NULL) = exact squared error of each against its target frame.
+ * Blocking calls, also in split-phase mode.  gme_last_bbme_info names the kernel instance: k_bipred<16>, k_bipred<32>, or
+ * k_bipred<0> (block size at run time). */
+GME_API int gme_bipred_u8(gme_ctx *ctx, const uint8_t *past, const uint8_t *mid, const uint8_t *next, int H, int W, int stride,
+                          int block_size, int radius, int rounds, int pnorm, int penalty, const int32_t *f0, const int32_t *f1,
+                          uint8_t *mode_out, int32_t *v0_out, int32_t *v1_out, int64_t *cost_out, int64_t *costs_out,
+                          uint8_t *pred_out, int64_t *sse_out);
+GME_API int gme_seq_bipred(gme_seq *seq, int frame_distance, int block_size, int search_window, int procedure, int pnorm, int radius,
+                           int rounds, int penalty);
+GME_API int gme_seq_read_bipred(gme_seq *seq, int first, int count, int32_t *f0_out, int32_t *f1_out, uint8_t *mode_out,
+                                int32_t *v0_out, int32_t *v1_out, int64_t *cost_out, int64_t *costs_out);
+GME_API int gme_seq_predict_bipred(gme_seq *seq, int64_t *sse_out);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
