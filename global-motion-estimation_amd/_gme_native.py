@@ -123,6 +123,10 @@ _SIGNATURES = {
     "gme_seq_bipred": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i]),
     "gme_seq_read_bipred": (_i, [_vp, _i, _i, _c_i32p, _c_i32p, _c_u8p, _c_i32p, _c_i32p, _c_i64p, _c_i64p]),
     "gme_seq_predict_bipred": (_i, [_vp, _c_i64p]),
+    "gme_gmc_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _c_f64p, _c_i32p, _c_u8p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
+    "gme_seq_gmc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _c_f64p]),
+    "gme_seq_read_gmc": (_i, [_vp, _i, _i, _c_i32p, _c_u8p, _c_i64p, _c_i64p, _c_u8p]),
+    "gme_seq_predict_gmc": (_i, [_vp, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -441,6 +445,36 @@ class Context:
                                       _p(fields[1], _c_i32p), _p(mode, _c_u8p), _p(v0, _c_i32p), _p(v1, _c_i32p), _p(cost, _c_i64p),
                                       _p(costs, _c_i64p), _p(pred, _c_u8p), ctypes.byref(sse)), self.lib)
         return mode, v0, v1, cost, costs, pred, sse.value
+
+    def gmc(self, ref, cur, h, f, block_size, pnorm=0, penalty=0):
+        """Global motion compensation of ``cur`` from ``ref`` under the warp h float64[8] on the integer field f int32[H // bs,
+        W // bs, 2] (gme_gmc_u8, gmc.decide and gmc.predict) -> (mode uint8[h, w], cost int64[h, w], costs int64[h, w, 2],
+        predicted uint8[H, W], sse int)."""
+        frames = [as_frame(a, name) for a, name in ((ref, "ref"), (cur, "cur"))]
+        if frames[0].shape != frames[1].shape:
+            raise AssertionError("ref and cur differ in shape (bbme.py:59)")
+        block_size, pnorm, penalty = _gmc_args(block_size, pnorm, penalty)
+        H, W = frames[1].shape
+        if frames[0].strides[0] != frames[1].strides[0]:
+            frames = [np.ascontiguousarray(a) for a in frames]
+        hb, wb = H // block_size, W // block_size
+        warp = np.ascontiguousarray(np.asarray(h, dtype=np.float64).reshape(8))
+        field = np.ascontiguousarray(np.asarray(f)[:, :, :2].astype(np.int32))
+        if field.shape != (hb, wb, 2):
+            raise ValueError("the field of a %d x %d frame at block size %d is %r, not %r" % (H, W, block_size, (hb, wb, 2), field.shape))
+        mode, cost, costs = np.zeros((hb, wb), np.uint8), np.zeros((hb, wb), np.int64), np.zeros((hb, wb, 2), np.int64)
+        pred = np.empty((H, W), np.uint8)
+        sse = ctypes.c_int64(0)
+        _check(self.lib.gme_gmc_u8(self.handle, _p(frames[0], _c_u8p), _p(frames[1], _c_u8p), H, W, frames[1].strides[0], block_size, pnorm,
+                                   penalty, _p(warp, _c_f64p), _p(field, _c_i32p), _p(mode, _c_u8p), _p(cost, _c_i64p),
+                                   _p(costs, _c_i64p), _p(pred, _c_u8p), ctypes.byref(sse)), self.lib)
+        return mode, cost, costs, pred, sse.value
+
+
+def _gmc_args(block_size, pnorm, penalty):
+    """gmc.check_args: the definition's argument rules, ValueError before the library is asked."""
+    import gmc
+    return gmc.check_args(block_size, pnorm, penalty)
 
 
 def _bipred_args(block_size, radius, rounds, pnorm, penalty):
@@ -984,6 +1018,44 @@ class Sequence:
         sse = np.zeros(max(T, 1), np.int64)
         _check(self.lib.gme_seq_predict_bipred(self.handle, _p(sse, _c_i64p)), self.lib)
         return sse[:T]
+
+    # ---- global motion compensation (bbme_gmc.hip, gmc.py)
+    def gmc(self, frame_distance, h, block_size=16, search_window=16, procedure=0, pnorm=0, penalty=0):
+        """gmc.decide for the pairs k = 0 .. N-1-fd on the device (gme_seq_gmc): frame k+fd is predicted from frame k under the
+        warp h[k] (float64[P, 8], the pairs of refine_projective); the search (frame k+fd looked for in frame k, the arguments of
+        bbme()) and the decision.  The motion field and what was derived from it stay what they were; read_gmc reads the result,
+        predict_gmc predicts with it."""
+        self._blocking("global motion compensation")
+        block_size, pnorm, penalty = _gmc_args(block_size, pnorm, penalty)
+        fd = int(frame_distance)
+        pairs = self.N - fd
+        if pairs < 0:
+            raise IndexError("frame_distance %d needs at least %d frames" % (fd, fd + 1))
+        warps = np.ascontiguousarray(np.asarray(h, dtype=np.float64).reshape(pairs, 8))
+        _check(self.lib.gme_seq_gmc(self.handle, fd, block_size, int(search_window), int(procedure), pnorm, penalty, _p(warps, _c_f64p)),
+               self.lib)
+        self._gmc_shape = (pairs, self.H // block_size, self.W // block_size)
+
+    def read_gmc(self, first=0, count=None):
+        """(f int32[count, h, w, 2], mode uint8[count, h, w], cost int64[count, h, w], costs int64[count, h, w, 2], usable
+        uint8[count]) of pairs first .. first+count-1 of the last gmc()."""
+        shape = getattr(self, "_gmc_shape", None) or (0, 0, 0)
+        count = shape[0] - first if count is None else count
+        grid = (max(count, 0),) + tuple(shape[1:])
+        f, mode, cost, costs = np.empty(grid + (2,), np.int32), np.empty(grid, np.uint8), np.empty(grid, np.int64), np.empty(grid + (2,), np.int64)
+        usable = np.empty(max(count, 0), np.uint8)
+        _check(self.lib.gme_seq_read_gmc(self.handle, int(first), int(count), _p(f, _c_i32p), _p(mode, _c_u8p), _p(cost, _c_i64p),
+                                         _p(costs, _c_i64p), _p(usable, _c_u8p)), self.lib)
+        return f, mode, cost, costs, usable
+
+    def predict_gmc(self):
+        """The predicted frames of the last gmc() (gme_seq_predict_gmc, gmc.predict) -> sse int64[P] against the frames they
+        predict; read_compensated_range(0, P) reads the frames."""
+        self._blocking("global motion compensation")
+        P = (getattr(self, "_gmc_shape", None) or (0,))[0]
+        sse = np.zeros(max(P, 1), np.int64)
+        _check(self.lib.gme_seq_predict_gmc(self.handle, _p(sse, _c_i64p)), self.lib)
+        return sse[:P]
 
 
 _default = None

@@ -58,21 +58,6 @@ struct BipredArgs {
     int anchor_bytes, window_bytes, slice_bytes;      // LDS of a wave: the block of mid, the window of past, the window of next
 };
 
-struct Score {
-    uint32_t sad = 0, aa = 0, bb = 0, ab = 0;
-    __device__ __forceinline__ void add(uint32_t a, uint32_t v, int pnorm)
-    {
-        if (pnorm == 0) sad = __builtin_amdgcn_sad_u8(a, v, sad);
-        else {
-            aa = __builtin_amdgcn_udot4(a, a, aa, false);
-            bb = __builtin_amdgcn_udot4(v, v, bb, false);
-            ab = __builtin_amdgcn_udot4(a, v, ab, false);
-        }
-    }
-    // sum |a - v| or sum (a - v)^2 of what was added (the latter modulo 2^32 until the lanes' parts are summed)
-    __device__ __forceinline__ uint32_t value(int pnorm) const { return pnorm == 0 ? sad : aa + bb - 2u * ab; }
-};
-
 constexpr uint32_t BP_ROUND_UP = 0x01010101u;                   // v_lerp_u8's third operand: (p + n + 1) >> 1 in every byte
 
 // grid (ceil(wb / BP_WAVES), hb, targets)
@@ -123,7 +108,7 @@ __global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
     // the starting costs: the block's (row, dword) pairs over the lanes, every dword read once for all three
     uint32_t c0 = BP_NONE, c1 = BP_NONE, cb = BP_NONE;
     {
-        Score s0, s1, sb;
+        RowScore s0, s1, sb;
         for (int t = lane; t < B * nd; t += 64) {
             const int y = small_div(t, nd), k = t - y * nd;
             const uint32_t a = anc[t];                           // bytes at and past column B are zero
@@ -165,7 +150,7 @@ __global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
                 const bool ok = listed && gx >= 0 && gy >= 0 && gx + B <= A.W && gy + B <= A.H;
                 const int wx = m + dx, wy = m + dy;              // ... and in the window: 0 <= wx, wx + B <= ws
                 const uint32_t wsh = (uint32_t)wx & 3u;
-                Score s;
+                RowScore s;
                 for (int y = q; y < B; y += BP_P) {
                     const uint32_t* arow = anc + y * nd;
                     const uint32_t* mrow = mw + (wy + y) * wd + (wx >> 2);

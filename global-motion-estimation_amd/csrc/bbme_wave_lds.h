@@ -1,4 +1,4 @@
-// What the one-wave-per-block kernels share (bbme_hier.hip, bbme_vbs.hip): a wave's own LDS slice, filled and read by that wave
+// What the one-wave-per-block kernels share (bbme_hier.hip, bbme_vbs.hip, bbme_bipred.hip, bbme_gmc.hip): a wave's own LDS slice, filled and read by that wave
 // alone, without a workgroup barrier.
 #pragma once
 #include "gme_internal.h"
@@ -40,3 +40,20 @@ __device__ __forceinline__ void stage_bytes(uint32_t* dst, int rows, int row_dwo
         dst[t] = v;
     }
 }
+
+// The cost of block rows four bytes at a time (k_bipred, k_gmc): v_sad_u8 for sum |a - v|, three v_dot4 for sum (a - v)^2 as
+// aa + bb - 2 ab.
+struct RowScore {
+    uint32_t sad = 0, aa = 0, bb = 0, ab = 0;
+    __device__ __forceinline__ void add(uint32_t a, uint32_t v, int pnorm)
+    {
+        if (pnorm == 0) sad = __builtin_amdgcn_sad_u8(a, v, sad);
+        else {
+            aa = __builtin_amdgcn_udot4(a, a, aa, false);
+            bb = __builtin_amdgcn_udot4(v, v, bb, false);
+            ab = __builtin_amdgcn_udot4(a, v, ab, false);
+        }
+    }
+    // sum |a - v| or sum (a - v)^2 of what was added (the latter modulo 2^32 until the lanes' parts are summed)
+    __device__ __forceinline__ uint32_t value(int pnorm) const { return pnorm == 0 ? sad : aa + bb - 2u * ab; }
+};

@@ -636,6 +636,65 @@ extern "C" int gme_bipred_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* m
     return rc;
 }
 
+// Global motion compensation of one pair on a given warp and field (bbme_gmc.hip): the two frames and the
+// predicted one as one stack of three planes in the scratch.
+extern "C" int gme_gmc_u8(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, int H, int W, int stride, int block_size, int pnorm,
+                          int penalty, const double* h, const int32_t* f, uint8_t* mode_out, int64_t* cost_out, int64_t* costs_out,
+                          uint8_t* pred_out, int64_t* sse_out)
+{
+    GME_ENTER(ctx);
+    GME_REQUIRE(ref && cur && h && f && mode_out, GME_ERR_ARG, "gme_gmc_u8: null pointer");
+    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_gmc_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
+    int rc = gmc_check_args("gme_gmc_u8", block_size, pnorm, penalty);
+    if (rc) return rc;
+    const int hb = H / block_size, wb = W / block_size;
+    const size_t n = (size_t)hb * wb;
+    Plane st = plane_shape(H, W, 3);                           // ref, cur, predicted
+    int32_t* d_f = nullptr;
+    long long* d_cost = nullptr;                               // cost, costs, then the squared error
+    double* d_h = nullptr;
+    uint8_t* d_mode = nullptr;                                 // the modes, then the usable flag
+    Carver c;
+    c.take(&st, true); c.take(&d_f, n * 2 + 1); c.take(&d_cost, n * 3 + 1); c.take(&d_h, 8); c.take(&d_mode, n + 1);
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    long long* d_costs = d_cost + n;
+    unsigned long long* d_sse = (unsigned long long*)(d_cost + n * 3);
+    uint8_t* d_usable = d_mode + n;
+    GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_f - st.ptr, ctx->stream));
+    const uint8_t* host[2] = { ref, cur };
+    for (int k = 0; k < 2; ++k) {
+        Plane one = st;
+        one.ptr = st.at(k);
+        GME_HIP_TRY(put_plane(ctx, one, host[k], stride));
+    }
+    const uint8_t usable = gmc_usable(h, H, W) ? 1 : 0;        // read by the copy below before this call returns (ctx_finish)
+    GME_HIP_TRY(hipMemcpyAsync(d_h, h, 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(d_usable, &usable, 1, hipMemcpyHostToDevice, ctx->stream));
+    if (n) GME_HIP_TRY(hipMemcpyAsync(d_f, f, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_gmc(ctx, st.at(0), st.at(1), 0, 1, H, W, st.pitch, block_size, pnorm, penalty, d_h, d_usable, d_f, d_mode, d_cost, d_costs);
+    if (rc) return rc;
+    if (n) {
+        GME_HIP_TRY(hipMemcpyAsync(mode_out, d_mode, n, hipMemcpyDeviceToHost, ctx->stream));
+        if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        if (costs_out) GME_HIP_TRY(hipMemcpyAsync(costs_out, d_costs, n * 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    unsigned long long sse = 0;
+    if (pred_out || sse_out) {
+        rc = launch_predict_gmc(ctx, st.at(0), st.at(1), 0, 1, H, W, st.pitch, block_size, d_h, d_usable, d_mode, d_f, st.at(2), 0, st.pitch,
+                                d_sse);
+        if (rc) return rc;
+        if (pred_out) {
+            rc = read_planes(ctx, st, 2, 1, pred_out);
+            if (rc) return rc;
+        }
+        GME_HIP_TRY(hipMemcpyAsync(&sse, d_sse, sizeof(sse), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    rc = ctx_finish(ctx);
+    if (sse_out) *sse_out = (int64_t)sse;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -727,6 +786,7 @@ static void seq_frames_changed(gme_seq* s)
     s->hier_valid = false;
     s->vbs_valid = false;
     s->bp_valid = false;
+    s->gm_valid = false;
     gme_drop_run(s);
 }
 
@@ -2208,5 +2268,93 @@ extern "C" int gme_seq_predict_bipred(gme_seq* s, int64_t* sse_out)
     if (rc) return rc;
     if (sse_out && T)
         GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)T * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Global motion compensation (bbme_gmc.hip): blocking calls.  gme_seq_gmc runs the search from every
+// predicted frame itself, into a field of its own, and leaves the sequence's motion field and what was derived from it
+// (quarter-pel, hierarchical, variable-block-size and bidirectional results) as they were.
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_gmc(gme_seq* s, int fd, int bs, int sw, int procedure, int pnorm, int penalty, const double* h)
+{
+    GME_REQUIRE(s != nullptr && h != nullptr, GME_ERR_ARG, "gme_seq_gmc: null pointer");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "gme_seq_gmc: frame_distance %d needs at least %d frames", fd, fd + 1);
+    int rc = gmc_check_args("gme_seq_gmc", bs, pnorm, penalty);
+    if (rc) return rc;
+    rc = bbme_check_args(s->H, s->W, bs, sw, procedure, pnorm);
+    if (rc) return rc;
+    const int P = s->N - fd, hb = s->H / bs, wb = s->W / bs;
+    const size_t n = (size_t)P * hb * wb;
+    s->gm_valid = false;
+    rc = s->gm_f.ensure(n * 2, "global motion compensation field");
+    if (rc) return rc;
+    rc = s->gm_h.ensure((size_t)P * 8, "global motion compensation warps");
+    if (rc) return rc;
+    rc = dev_ensure_all("global motion compensation modes", { { s->gm_usable, (size_t)P }, { s->gm_mode, n } });
+    if (rc) return rc;
+    rc = dev_ensure_all("global motion compensation costs", { { s->gm_cost, n }, { s->gm_costs, n * 2 } });
+    if (rc) return rc;
+    // unusable warps are found here, before the launch: the kernels take a flag per pair
+    std::vector<uint8_t> usable((size_t)P);
+    for (int k = 0; k < P; ++k) usable[(size_t)k] = gmc_usable(h + (size_t)k * 8, s->H, s->W) ? 1 : 0;
+    GME_HIP_TRY(hipMemcpyAsync(s->gm_h, h, (size_t)P * 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(s->gm_usable, usable.data(), (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+    const Plane& p = s->level[2];
+    // the anchor of the search is the predicted frame k + fd; it is looked for in frame k
+    BbmeJob job = bbme_job(p, fd, 0, P, bs, sw, procedure, pnorm, s->gm_f);
+    job.cur = p.at(0);
+    rc = seq_launch_bbme_from(s, 2, 0, job);
+    if (rc) return rc;
+    rc = launch_gmc(ctx, p.at(0), p.at(fd), p.stride, P, s->H, s->W, p.pitch, bs, pnorm, penalty, s->gm_h, s->gm_usable, s->gm_f, s->gm_mode,
+                    s->gm_cost, s->gm_costs);
+    if (rc) return rc;
+    rc = ctx_finish(ctx);                                      // `usable` is read by its copy until here
+    if (rc) return rc;
+    s->gm_pairs = P; s->gm_h_blocks = hb; s->gm_w_blocks = wb; s->gm_fd = fd; s->gm_bs = bs;
+    s->gm_valid = true;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_gmc(gme_seq* s, int first, int count, int32_t* f_out, uint8_t* mode_out, int64_t* cost_out, int64_t* costs_out,
+                                uint8_t* usable_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_gmc: null sequence");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(s->gm_valid, GME_ERR_STATE, "gme_seq_read_gmc before gme_seq_gmc");
+    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->gm_pairs, GME_ERR_ARG,
+                "gme_seq_read_gmc: pairs [%d, %d) outside [0, %d)", first, first + count, s->gm_pairs);
+    const size_t per = (size_t)s->gm_h_blocks * s->gm_w_blocks, m = per * count;
+    hipStream_t st = s->ctx->stream;
+    if (m) {
+        const struct { void* out; const void* src; size_t elem; } parts[] = {
+            { f_out, s->gm_f + per * 2 * first, 2 * sizeof(int32_t) }, { mode_out, s->gm_mode + per * first, 1 },
+            { cost_out, s->gm_cost + per * first, sizeof(long long) }, { costs_out, s->gm_costs + per * 2 * first, 2 * sizeof(long long) },
+        };
+        for (const auto& part : parts)
+            if (part.out) GME_HIP_TRY(hipMemcpyAsync(part.out, part.src, m * part.elem, hipMemcpyDeviceToHost, st));
+    }
+    if (usable_out && count) GME_HIP_TRY(hipMemcpyAsync(usable_out, s->gm_usable + first, (size_t)count, hipMemcpyDeviceToHost, st));
+    return ctx_finish(s->ctx);
+}
+
+extern "C" int gme_seq_predict_gmc(gme_seq* s, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_predict_gmc: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(s->gm_valid, GME_ERR_STATE, "gme_seq_predict_gmc before gme_seq_gmc");
+    const int P = s->gm_pairs, fd = s->gm_fd;
+    GME_REQUIRE(P <= s->N - fd, GME_ERR_STATE, "gme_seq_predict_gmc: %d pairs, the sequence has %d", P, s->N - fd);
+    int rc = ensure_comp(s, fd, P);
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    rc = launch_predict_gmc(ctx, p.at(0), p.at(fd), p.stride, P, s->H, s->W, p.pitch, s->gm_bs, s->gm_h, s->gm_usable, s->gm_mode, s->gm_f,
+                            s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
+    if (rc) return rc;
+    if (sse_out && P)
+        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)P * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
 }

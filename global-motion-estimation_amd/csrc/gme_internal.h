@@ -195,6 +195,17 @@ struct gme_seq {
     DevBuf<long long> bp_costs;          // [T][h][w][3]
     int bp_targets = 0, bp_h = 0, bp_w = 0, bp_fd = 0, bp_bs = 0;
     bool bp_valid = false;
+    // global motion compensation (bbme_gmc.hip): the field of gme_seq_gmc's own search, the warps it was given with their usable
+    // flags, the modes and the costs of its P = N - fd pairs, allocated by its first call; valid until new frame data.  No other
+    // call reads or writes them, and gme_seq_gmc writes nothing else of the sequence.
+    DevBuf<int32_t> gm_f;                // [P][h][w][2]
+    DevBuf<double> gm_h;                 // [P][8]
+    DevBuf<uint8_t> gm_usable;           // [P]
+    DevBuf<uint8_t> gm_mode;             // [P][h][w]
+    DevBuf<long long> gm_cost;           // [P][h][w]
+    DevBuf<long long> gm_costs;          // [P][h][w][2]
+    int gm_pairs = 0, gm_h_blocks = 0, gm_w_blocks = 0, gm_fd = 0, gm_bs = 0;
+    bool gm_valid = false;
     DevBuf<uint8_t> synth_canvas;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -442,6 +453,22 @@ int launch_bipred(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid, const u
 int launch_predict_bipred(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid, const uint8_t* next, long long plane_stride,
                           int targets, int H, int W, int pitch, int bs, const uint8_t* mode, const int32_t* v0, const int32_t* v1,
                           uint8_t* out, long long out_stride, int out_pitch, unsigned long long* sse);
+
+// ---- bbme_gmc.hip: global motion compensation -------------------------------------------------------
+// the argument rules of gmc.py (GME_ERR_ARG)
+int gmc_check_args(const char* who, int bs, int pnorm, int penalty);
+// gmc.usable of one warp of an H x W frame (host): the per-pair flag the two launchers take
+bool gmc_usable(const double* h, int H, int W);
+// gmc.decide of `pairs` pairs on the fields f [pairs][H / bs][W / bs][2] under the warps h [pairs][8] with their flags usable
+// [pairs]: pair k reads the planes ref + k * plane_stride and cur + k * plane_stride; mode [pairs][hb][wb], cost [pairs][hb][wb],
+// costs [pairs][hb][wb][2] (all device).  Names the kernel instance in the context's plan.
+int launch_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, long long plane_stride, int pairs, int H, int W, int pitch, int bs,
+               int pnorm, int penalty, const double* h, const uint8_t* usable, const int32_t* f, uint8_t* mode, long long* cost,
+               long long* costs);
+// out planes = gmc.predict of the ref planes, sse[pairs] (device) = squared error of each against its cur plane
+int launch_predict_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, long long plane_stride, int pairs, int H, int W, int pitch,
+                       int bs, const double* h, const uint8_t* usable, const uint8_t* mode, const int32_t* f, uint8_t* out,
+                       long long out_stride, int out_pitch, unsigned long long* sse);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

@@ -14,6 +14,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py hier -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-cw 8] [-r 1] [-pn 0] [--levels 3] [--subpel 0|1|2] [-o OUTDIR]   # hierarchical block matching of one pair
     python gme_cli.py vbs -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--depth 2] [-r 1] [--penalty N] [--hier] [-o OUTDIR]   # variable-block-size motion of one pair
     python gme_cli.py bipred -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [-r 1] [--rounds 1] [--penalty N] [-o OUTDIR]   # bidirectional prediction of one frame
+    python gme_cli.py gmc -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--penalty N] [--estimator projective|affine] [-o OUTDIR]   # global motion compensation of one pair
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -128,6 +129,20 @@ def _parser():
                     help="what the average must gain over a single reference (0 .. 2^30); default: a quarter grey level per pixel, "
                          "bs^2 / 4 for MAE and 4 bs^2 for MSE, a convention of this tool and not a tuned value")
     bp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for bipred.json")
+    gp = sub.add_parser("gmc", help="global motion compensation of one frame pair: per block the camera warp or the block's own vector (gmc.py, DESIGN.md 7i)")
+    gp.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    gp.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the predicted frame")
+    gp.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=1, help="the reference is fi - fd")
+    gp.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="4 .. 64")
+    gp.add_argument("-sw", "--search-window", dest="search_window", type=int, default=16)
+    gp.add_argument("-sp", "--searching-procedure", dest="searching_procedure", type=int, default=0)
+    gp.add_argument("-pn", "--pnorm-distance", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    gp.add_argument("--penalty", type=int, default=None,
+                    help="what the block's own vector must gain over the camera warp (0 .. 2^30); default: a quarter grey level per "
+                         "pixel, bs^2 / 4 for MAE and 4 bs^2 for MSE, bipred's convention and not a tuned value")
+    gp.add_argument("--estimator", choices=("projective", "affine"), default="projective",
+                    help="the warp: the direct projective refinement, or the indirect affine estimate written as a warp")
+    gp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for gmc.json and modes.png")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -294,6 +309,50 @@ def _bipred(args):
     return res
 
 
+def _gmc(args):
+    """The penalty, the mode shares and the PSNR of the global-only, the local-only and the chosen prediction of one frame; the
+    same record into OUTDIR/gmc.json and the mode map (0 / 128 / 255 per block, scaled up to the frame) into OUTDIR/modes.png."""
+    import json
+    import os
+    import numpy as np
+    import gmc
+    import motion
+    import roadmap
+    import utils
+    frames = utils.get_video_frames(args.path)
+    if not args.fd <= args.fi < len(frames) or args.fd < 1:
+        raise IndexError("frames %d and %d of %d" % (args.fi - args.fd, args.fi, len(frames)))
+    ref, cur = frames[args.fi - args.fd], frames[args.fi]
+    if args.estimator == "affine":
+        h = roadmap.affine_to_projective(roadmap.global_motion_estimation(ref, cur), int(motion.BBME_BLOCK_SIZE))
+    else:
+        h = roadmap.refine_projective(ref, cur)[0]
+    res = gmc.report(ref, cur, h, args.block_size, args.search_window, args.searching_procedure, args.pnorm, args.penalty)
+    record = {"options": {"path": args.path, "frame_index": args.fi, "frame_distance": args.fd, "block_size": args.block_size,
+                          "search_window": args.search_window, "searching_procedure": args.searching_procedure,
+                          "pnorm": args.pnorm, "penalty": res["penalty"], "estimator": args.estimator},
+              "shape": list(res["mode"].shape), "h": [float(v) for v in res["h"]], "usable": res["usable"]}
+    record.update({k: res[k] for k in ("mode_share", "sse_global", "sse_local", "sse_chosen", "psnr_global", "psnr_local", "psnr_chosen")})
+    print("frame {} from {}: {} x {} blocks of {}, {} warp{}, penalty {}".format(
+        args.fi, args.fi - args.fd, record["shape"][0], record["shape"][1], args.block_size, args.estimator,
+        "" if res["usable"] else " (unusable)", res["penalty"]))
+    print("modes: global {:.2f} %, local {:.2f} %, none {:.2f} %".format(*(100.0 * v for v in record["mode_share"])))
+    print("psnr global only: {:.4f} dB".format(record["psnr_global"]))
+    print("psnr local only:  {:.4f} dB".format(record["psnr_local"]))
+    print("psnr chosen:      {:.4f} dB".format(record["psnr_chosen"]))
+    if args.outdir:
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "gmc.json"), "w") as f:
+            json.dump(record, f, indent=1)
+        grey = np.array([0, 128, 255], np.uint8)[res["mode"]]
+        H, W = cur.shape
+        big = np.zeros((H, W), np.uint8)
+        tiles = np.kron(grey, np.ones((args.block_size, args.block_size), np.uint8))
+        big[:tiles.shape[0], :tiles.shape[1]] = tiles
+        utils.write_image(os.path.join(args.outdir, "modes.png"), big)
+    return res
+
+
 def _hier(args):
     """Reach, median vector and PSNR of the compensation of one pair under the hierarchical search (with --subpel also the
     PSNR of the quarter-pel compensation of the refined field); the same record into OUTDIR/hier.json."""
@@ -409,6 +468,8 @@ def main(argv=None):
         return _vbs(args)
     if args.command == "bipred":
         return _bipred(args)
+    if args.command == "gmc":
+        return _gmc(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")
@@ -418,6 +479,7 @@ def main(argv=None):
     print("hierarchical search (gme_cli.py hier): --levels 1 .. 3, -cw 0 .. 8, -r 0 .. 3, block size a multiple of 2^(levels-1) up to 64   (hier.py)")
     print("variable block size (gme_cli.py vbs): --depth 0 .. 2, -r 0 .. 3, --penalty 0 .. 2^30, roots a multiple of 2^depth up to 64, leaves of at least 4   (vbs.py)")
     print("bidirectional prediction (gme_cli.py bipred): -bs 4 .. 64, -r 0 .. 2, --rounds 0 .. 2, --penalty 0 .. 2^30; per block the past frame, the next one or their average   (bipred.py)")
+    print("global motion compensation (gme_cli.py gmc): -bs 4 .. 64, --penalty 0 .. 2^30, --estimator projective | affine; per block the camera warp or the block's own vector   (gmc.py)")
     try:
         print("device: " + _gme_native.default_context().info()["name"])
     except Exception as e:      # noqa: BLE001 -- no GPU: say so, the listing above is still useful

@@ -61,6 +61,11 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    past reference, the next one or the rounded average of both, the averaged pair refined in alternating passes, a block's
    whole decision in one wave of one kernel (k_bipred, csrc/bbme_bipred.hip; host definition bipred.py; DESIGN.md §7h);
    ``Sequence.predict_bipred`` writes the predicted frames.
+   **Global motion compensation.**  ``gmc.motion_field`` lets every block choose between the pair's camera warp, applied pixel
+   by pixel (the direct projective estimate above, or any float64[8] warp), and its own integer vector, which must beat the warp
+   by a penalty; the mode map is a block-level foreground map of one pair.  A block's whole decision runs in one wave of one
+   kernel (k_gmc, csrc/bbme_gmc.hip; host definition gmc.py); ``Sequence.predict_gmc`` writes the predicted
+   frames.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

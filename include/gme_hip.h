@@ -455,6 +455,46 @@ GME_API int gme_seq_read_bipred(gme_seq *seq, int first, int count, int32_t *f0_
                                 int32_t *v0_out, int32_t *v1_out, int64_t *cost_out, int64_t *costs_out);
 GME_API int gme_seq_predict_bipred(gme_seq *seq, int64_t *sse_out);
 
+/* Global motion compensation (host definition gmc.py): a block of the frame `cur` is predicted from the
+ * frame `ref` either by the pair's camera warp, pixel by pixel, or by the block its own integer vector points at; equal to
+ * gmc.decide and gmc.predict byte for byte.  block_size B in 4 .. 64, pnorm 0 (sum |d|) or 1 (sum d^2), penalty in 0 .. 2^30.
+ * h[8] is a warp in the convention of gme_seq_refine_projective: pixel (u, v) of `cur` samples `ref` at
+ * u' = (h0 u + h1 v + h2) / d, v' = (h3 u + h4 v + h5) / d, d = h6 u + h7 v + 1.  It is usable when it is finite and d > 0 at
+ * the four corners of the frame; an unusable warp is no error, only no block of that pair has a global candidate.  Block
+ * (i, j), i < H / B, j < W / B, has its origin at (j B, i B); f[i][j] (column, row) says where it is found in `ref` (the field
+ * of a search with `cur` as the previous and `ref` as the current frame).
+ * The global predictor pixel is floor(bilinear(ref)(u', v') + 0.5), gme_seq_compensate_projective's pixel; it exists where
+ * 0 <= u' <= W - 1 and 0 <= v' <= H - 1.  cg is the cost of the block's global pixels against the `cur` block, unavailable (-1)
+ * unless the warp is usable and all B^2 pixels exist; cl the cost of the `ref` block at f, unavailable unless the displaced
+ * block lies entirely in the frame.  Decision: (mode 0 GLOBAL, cg), (mode 1 LOCAL, cl + penalty) in that order, unavailable
+ * ones left out, only a strictly smaller value replaces the best (GLOBAL wins ties); with none available, mode 2 and cost -1.
+ * Every sum of a decision stays below 2^31.
+ * Result per pair: mode uint8[H/B][W/B]; cost int64[H/B][W/B], the chosen value (penalty included) or -1; costs
+ * int64[H/B][W/B][2] = cg, cl (without the penalty), -1 where unavailable.
+ * Prediction: a block of mode 0 is its global pixels, of mode 1 the `ref` block at f; a block of mode 2 and every pixel beyond
+ * the last whole block is the co-located pixel of `ref`.
+ * gme_gmc_u8: one pair on host buffers with the warp h and the field f int32[H/B][W/B][2]; every output but mode_out may be
+ *   NULL; pred_out uint8[H][W] (tight) is the predicted frame and *sse_out its exact squared error against `cur`.
+ * gme_seq_gmc: the P = N - frame_distance pairs of the sequence, pair k predicting frame k + frame_distance from frame k under
+ *   h[k] (h is double[P][8], the pair convention of gme_seq_refine_projective).  It runs the search itself (frame
+ *   k + frame_distance looked for in frame k; the arguments and rules of gme_seq_bbme) into a field of its own and then the
+ *   decision; the sequence's motion field and the quarter-pel, hierarchical, variable-block-size and bidirectional results
+ *   stay as they were.  The result is kept in the sequence (allocated on first use) until new frame data.
+ * gme_seq_read_gmc: pairs first .. first + count - 1 of it; any output may be NULL; usable_out uint8[count] says which warps
+ *   were usable; a range outside [0, P) is GME_ERR_ARG, GME_ERR_STATE where there is no valid result.
+ * gme_seq_predict_gmc: the P predicted frames into the sequence's compensated frames (gme_seq_read_compensated_range reads
+ *   them), sse_out[P] (may be NULL) = exact squared error of each against the frame it predicts.
+ * Blocking calls, also in split-phase mode.  gme_last_bbme_info names the kernel instance: k_gmc<16>, k_gmc<32>, or k_gmc<0>
+ * (block size at run time). */
+GME_API int gme_gmc_u8(gme_ctx *ctx, const uint8_t *ref, const uint8_t *cur, int H, int W, int stride, int block_size, int pnorm,
+                       int penalty, const double *h, const int32_t *f, uint8_t *mode_out, int64_t *cost_out, int64_t *costs_out,
+                       uint8_t *pred_out, int64_t *sse_out);
+GME_API int gme_seq_gmc(gme_seq *seq, int frame_distance, int block_size, int search_window, int procedure, int pnorm, int penalty,
+                        const double *h /* [P][8] */);
+GME_API int gme_seq_read_gmc(gme_seq *seq, int first, int count, int32_t *f_out, uint8_t *mode_out, int64_t *cost_out,
+                             int64_t *costs_out, uint8_t *usable_out);
+GME_API int gme_seq_predict_gmc(gme_seq *seq, int64_t *sse_out);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
