@@ -127,6 +127,9 @@ _SIGNATURES = {
     "gme_seq_gmc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _c_f64p]),
     "gme_seq_read_gmc": (_i, [_vp, _i, _i, _c_i32p, _c_u8p, _c_i64p, _c_i64p, _c_u8p]),
     "gme_seq_predict_gmc": (_i, [_vp, _c_i64p]),
+    "gme_prop_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_u8p]),
+    "gme_seq_prop": (_i, [_vp, _i, _i, _i, _i, _i, _i, _c_i32p]),
+    "gme_seq_read_prop": (_i, [_vp, _i, _i, _c_i32p, _c_i64p, _c_u8p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -469,6 +472,41 @@ class Context:
                                    penalty, _p(warp, _c_f64p), _p(field, _c_i32p), _p(mode, _c_u8p), _p(cost, _c_i64p),
                                    _p(costs, _c_i64p), _p(pred, _c_u8p), ctypes.byref(sse)), self.lib)
         return mode, cost, costs, pred, sse.value
+
+    def prop(self, prev, cur, f, block_size, pnorm=0, rounds=2, steps=1, t=None, g=None):
+        """Vector propagation of one pair on the prior field f int32[H // bs, W // bs, 2], with the previous pair's field ``t`` and
+        the camera field ``g`` of the same shape where given (gme_prop_u8, propagate.search) -> (mf int32[h, w, 2], cost
+        int64[h, w], source uint8[h, w])."""
+        prev, cur = as_frame(prev, "previous"), as_frame(cur, "current")
+        if prev.shape != cur.shape:
+            raise AssertionError("previous and current differ in shape (bbme.py:59)")
+        block_size, pnorm, rounds, steps = _prop_args(block_size, pnorm, rounds, steps)
+        H, W = prev.shape
+        if cur.strides[0] != prev.strides[0]:
+            cur, prev = np.ascontiguousarray(cur), np.ascontiguousarray(prev)
+        h, w = H // block_size, W // block_size
+        fields = [None if a is None else _prop_field(a, name, (h, w)) for a, name in ((f, "f"), (t, "t"), (g, "g"))]
+        if fields[0] is None:
+            raise ValueError("f is the prior field, int32[%d, %d, 2]" % (h, w))
+        mf, cost, source = np.zeros((h, w, 2), np.int32), np.zeros((h, w), np.int64), np.zeros((h, w), np.uint8)
+        _check(self.lib.gme_prop_u8(self.handle, _p(prev, _c_u8p), _p(cur, _c_u8p), H, W, prev.strides[0], block_size, pnorm, rounds, steps,
+                                    *[None if a is None else _p(a, _c_i32p) for a in fields], _p(mf, _c_i32p), _p(cost, _c_i64p),
+                                    _p(source, _c_u8p)), self.lib)
+        return mf, cost, source
+
+
+def _prop_args(block_size, pnorm, rounds, steps):
+    """propagate.check_args: the definition's argument rules, ValueError before the library is asked."""
+    import propagate
+    return propagate.check_args(block_size, pnorm, rounds, steps)
+
+
+def _prop_field(a, name, grid):
+    """A field of vector propagation as contiguous int32[..., 2] of the block grid ``grid`` (the leading axes), or ValueError."""
+    a = np.asarray(a)
+    if a.ndim != len(grid) + 1 or a.shape[:-1] != tuple(grid) or a.shape[-1] < 2:
+        raise ValueError("%s is %r, not %r" % (name, a.shape, tuple(grid) + (2,)))
+    return np.ascontiguousarray(a[..., :2].astype(np.int32))
 
 
 def _gmc_args(block_size, pnorm, penalty):
@@ -1056,6 +1094,30 @@ class Sequence:
         sse = np.zeros(max(P, 1), np.int64)
         _check(self.lib.gme_seq_predict_gmc(self.handle, _p(sse, _c_i64p)), self.lib)
         return sse[:P]
+
+    # ---- vector propagation search (bbme_prop.hip, propagate.py)
+    def prop(self, frame_distance, block_size=16, pnorm=0, rounds=2, steps=1, temporal=True, g=None):
+        """propagate.search on the field of the last bbme(), hier() or prop() (same frame distance and block size) for every pair
+        on the device (gme_seq_prop).  With ``temporal``, pair k >= 1 also scores the prior field of pair k - 1; ``g`` is the camera
+        field int32[P, h, w, 2] or None.  The result becomes the sequence's motion field: read_mv, subpel, vbs and a further prop()
+        work on it; read_prop reads it with its costs and sources."""
+        self._blocking("vector propagation")
+        block_size, pnorm, rounds, steps = _prop_args(block_size, pnorm, rounds, steps)
+        if g is not None:
+            g = _prop_field(g, "g", tuple(getattr(self, "_mv_shape", (0, 0, 0, 2))[:3]))
+        _check(self.lib.gme_seq_prop(self.handle, int(frame_distance), block_size, pnorm, rounds, steps, int(bool(temporal)),
+                                     None if g is None else _p(g, _c_i32p)), self.lib)
+
+    def read_prop(self, first=0, count=None):
+        """(mf int32[count, h, w, 2], cost int64[count, h, w], source uint8[count, h, w]) of pairs first .. first+count-1 of the
+        last prop()."""
+        shape = getattr(self, "_mv_shape", (0, 0, 0, 2))
+        count = shape[0] - first if count is None else count
+        grid = (max(count, 0),) + tuple(shape[1:3])
+        mf, cost, source = np.empty(grid + (2,), np.int32), np.empty(grid, np.int64), np.empty(grid, np.uint8)
+        _check(self.lib.gme_seq_read_prop(self.handle, int(first), int(count), _p(mf, _c_i32p), _p(cost, _c_i64p), _p(source, _c_u8p)),
+               self.lib)
+        return mf, cost, source
 
 
 _default = None

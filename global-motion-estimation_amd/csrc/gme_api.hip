@@ -695,6 +695,50 @@ extern "C" int gme_gmc_u8(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, 
     return rc;
 }
 
+// Vector propagation of one pair on given fields (bbme_prop.hip): the two frames as one stack of two planes
+// in the scratch, behind them the prior, temporal and camera fields and the two fields the rounds alternate between.
+extern "C" int gme_prop_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int H, int W, int stride, int block_size, int pnorm,
+                           int rounds, int steps, const int32_t* f, const int32_t* t, const int32_t* g, int32_t* mf_out, int64_t* cost_out,
+                           uint8_t* source_out)
+{
+    GME_ENTER(ctx);
+    GME_REQUIRE(prev && cur && f && mf_out, GME_ERR_ARG, "gme_prop_u8: null pointer");
+    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_prop_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
+    int rc = prop_check_args("gme_prop_u8", block_size, pnorm, rounds, steps);
+    if (rc) return rc;
+    const int hb = H / block_size, wb = W / block_size;
+    const size_t n = (size_t)hb * wb;
+    if (n == 0) return GME_OK;
+    Plane st = plane_shape(H, W, 2);                           // previous, current
+    int32_t* d_vec = nullptr;                                  // f, t, g, then the two working fields
+    long long* d_cost = nullptr;
+    uint8_t* d_source = nullptr;
+    Carver c;
+    c.take(&st, true); c.take(&d_vec, n * 10); c.take(&d_cost, n); c.take(&d_source, n);
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    int32_t *d_f = d_vec, *d_t = d_vec + n * 2, *d_g = d_vec + n * 4;
+    int32_t* const work[2] = { d_vec + n * 6, d_vec + n * 8 };
+    GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_vec - st.ptr, ctx->stream));
+    const uint8_t* host[2] = { prev, cur };
+    for (int k = 0; k < 2; ++k) {
+        Plane one = st;
+        one.ptr = st.at(k);
+        GME_HIP_TRY(put_plane(ctx, one, host[k], stride));
+    }
+    GME_HIP_TRY(hipMemcpyAsync(d_f, f, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (t) GME_HIP_TRY(hipMemcpyAsync(d_t, t, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (g) GME_HIP_TRY(hipMemcpyAsync(d_g, g, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    int32_t* d_mf = nullptr;
+    rc = launch_prop(ctx, st.at(0), st.at(1), 0, 1, H, W, st.pitch, block_size, pnorm, rounds, steps, d_f, t ? d_t : nullptr, 0,
+                     g ? d_g : nullptr, work, d_cost, d_source, &d_mf);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(mf_out, d_mf, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (source_out) GME_HIP_TRY(hipMemcpyAsync(source_out, d_source, n, hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -785,6 +829,7 @@ static void seq_frames_changed(gme_seq* s)
     s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
     s->hier_valid = false;
     s->vbs_valid = false;
+    s->prop_valid = false;
     s->bp_valid = false;
     s->gm_valid = false;
     gme_drop_run(s);
@@ -1008,6 +1053,7 @@ extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, i
     s->qmv_valid = false;
     s->hier_valid = false;
     s->vbs_valid = false;
+    s->prop_valid = false;
     return seq_launch_bbme(s, 2, fd, bbme_job(s->level[2], 0, fd, pairs, bs, sw, procedure, pnorm, s->mv));
 }
 
@@ -1068,6 +1114,7 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     s->qmv_valid = false;
     s->hier_valid = false;
     s->vbs_valid = false;
+    s->prop_valid = false;
     const Plane& p = s->level[2];
     // one table kind for the whole call: every chunk's launches carry at most `pairs` pairs, so one that the matrix-core
     // kernel would take at the largest also takes it at every chunk, and a smaller chunk of a declined call keeps kind 1
@@ -2065,6 +2112,7 @@ extern "C" int gme_seq_hier(gme_seq* s, int fd, int bs, int cw, int radius, int 
     const size_t n = (size_t)pairs * h * w;
     s->hier_valid = false;
     s->vbs_valid = false;
+    s->prop_valid = false;
     s->qmv_valid = false;
     rc = seq_levels(s);
     if (rc) return rc;
@@ -2357,4 +2405,72 @@ extern "C" int gme_seq_predict_gmc(gme_seq* s, int64_t* sse_out)
     if (sse_out && P)
         GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)P * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
+}
+
+// ---------------------------------------------------------------------------
+// Vector propagation search (bbme_prop.hip): blocking calls.  gme_seq_prop takes the field of the last
+// gme_seq_bbme, gme_seq_hier or gme_seq_prop as the prior F_0 and leaves its result as the sequence's motion field; with
+// `temporal`, pair k >= 1 also scores F_0 of pair k - 1 (the prior field, not the propagated one: the pairs stay independent
+// and go into one launch per round).  The rounds write fields of their own and the last one is copied over F_0 behind them, so
+// F_0 is whole while any round reads it.  Quarter-pel, hierarchical and variable-block-size results of the old field end here;
+// the bidirectional and global-motion-compensation results stay.
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_prop(gme_seq* s, int fd, int bs, int pnorm, int rounds, int steps, int temporal, const int32_t* g)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_prop: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    int rc = prop_check_args("gme_seq_prop", bs, pnorm, rounds, steps);
+    if (rc) return rc;
+    rc = subpel_field(s, "gme_seq_prop", fd, bs);
+    if (rc) return rc;
+    const int P = s->mv_pairs;
+    const size_t n = (size_t)P * s->mv_h * s->mv_w;
+    s->prop_valid = false;
+    rc = dev_ensure_all("vector propagation fields", { { s->prop_work[0], n * 2 }, { s->prop_work[1], n * 2 } });
+    if (rc) return rc;
+    if (g) {
+        rc = s->prop_g.ensure(n * 2, "camera field");
+        if (rc) return rc;
+    }
+    rc = s->prop_cost.ensure(n, "vector propagation costs");
+    if (rc) return rc;
+    rc = s->prop_source.ensure(n, "vector propagation sources");
+    if (rc) return rc;
+    if (n == 0) {
+        s->prop_valid = true;
+        return GME_OK;
+    }
+    s->qmv_valid = false;
+    s->vbs_valid = false;
+    s->hier_valid = false;
+    if (g) GME_HIP_TRY(hipMemcpyAsync(s->prop_g, g, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    const Plane& p = s->level[2];
+    int32_t* const work[2] = { s->prop_work[0].get(), s->prop_work[1].get() };
+    int32_t* result = nullptr;
+    rc = launch_prop(ctx, p.at(0), p.at(fd), p.stride, P, s->H, s->W, p.pitch, bs, pnorm, rounds, steps, s->mv, temporal ? s->mv.get() : nullptr,
+                     -1, g ? s->prop_g.get() : nullptr, work, s->prop_cost, s->prop_source, &result);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(s->mv, result, n * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    rc = ctx_finish(ctx);                                      // `g` is read by its copy until here
+    if (rc) return rc;
+    s->prop_valid = true;
+    return GME_OK;
+}
+
+extern "C" int gme_seq_read_prop(gme_seq* s, int first_pair, int count, int32_t* mf_out, int64_t* cost_out, uint8_t* source_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_prop: null sequence");
+    GME_ENTER(s->ctx);
+    GME_REQUIRE(s->prop_valid, GME_ERR_STATE, "gme_seq_read_prop before gme_seq_prop");
+    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG,
+                "gme_seq_read_prop: pairs [%d, %d) outside [0, %d)", first_pair, first_pair + count, s->mv_pairs);
+    const size_t per = (size_t)s->mv_h * s->mv_w, m = per * count;
+    hipStream_t st = s->ctx->stream;
+    if (m) {
+        if (mf_out) GME_HIP_TRY(hipMemcpyAsync(mf_out, s->mv + per * 2 * first_pair, m * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, s->prop_cost + per * first_pair, m * sizeof(long long), hipMemcpyDeviceToHost, st));
+        if (source_out) GME_HIP_TRY(hipMemcpyAsync(source_out, s->prop_source + per * first_pair, m, hipMemcpyDeviceToHost, st));
+    }
+    return ctx_finish(s->ctx);
 }

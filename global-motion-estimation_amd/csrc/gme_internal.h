@@ -206,6 +206,14 @@ struct gme_seq {
     DevBuf<long long> gm_costs;          // [P][h][w][2]
     int gm_pairs = 0, gm_h_blocks = 0, gm_w_blocks = 0, gm_fd = 0, gm_bs = 0;
     bool gm_valid = false;
+    // vector propagation (bbme_prop.hip): the two fields the rounds of gme_seq_prop alternate between (the last one is copied
+    // into `mv`), the camera field it was given, and the costs and sources of the last round, allocated by its first call;
+    // valid until new frame data or the next block-matching call
+    DevBuf<int32_t> prop_work[2];        // [P][h][w][2]
+    DevBuf<int32_t> prop_g;              // [P][h][w][2]
+    DevBuf<long long> prop_cost;         // [P][h][w]
+    DevBuf<uint8_t> prop_source;         // [P][h][w]
+    bool prop_valid = false;
     DevBuf<uint8_t> synth_canvas;
     uint64_t synth_seed = 0;
     bool synth_valid = false;
@@ -469,6 +477,18 @@ int launch_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, long long p
 int launch_predict_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, long long plane_stride, int pairs, int H, int W, int pitch,
                        int bs, const double* h, const uint8_t* usable, const uint8_t* mode, const int32_t* f, uint8_t* out,
                        long long out_stride, int out_pitch, unsigned long long* sse);
+
+// ---- bbme_prop.hip: vector propagation search --------------------------------------------------------
+// the argument rules of propagate.py (GME_ERR_ARG)
+int prop_check_args(const char* who, int bs, int pnorm, int rounds, int steps);
+// propagate.search of `pairs` pairs on the prior fields f [pairs][H / bs][W / bs][2]: pair k reads the planes
+// prev + k * plane_stride and cur + k * plane_stride, the temporal field t[k + t_shift] (t null: none; neither where
+// k + t_shift < 0) and the camera field g[k] (null: none).  The rounds alternate between work[0] and work[1] (each
+// [pairs][hb][wb][2]) and only read f, so t may lie in it; *result is the one the last round wrote, cost [pairs][hb][wb] and
+// source [pairs][hb][wb] are that round's (all device).  Names the kernel instance in the context's plan.
+int launch_prop(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W, int pitch, int bs,
+                int pnorm, int rounds, int steps, const int32_t* f, const int32_t* t, int t_shift, const int32_t* g, int32_t* const work[2],
+                long long* cost, uint8_t* source, int32_t** result);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

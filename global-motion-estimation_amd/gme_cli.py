@@ -15,6 +15,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py vbs -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--depth 2] [-r 1] [--penalty N] [--hier] [-o OUTDIR]   # variable-block-size motion of one pair
     python gme_cli.py bipred -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [-r 1] [--rounds 1] [--penalty N] [-o OUTDIR]   # bidirectional prediction of one frame
     python gme_cli.py gmc -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--penalty N] [--estimator projective|affine] [-o OUTDIR]   # global motion compensation of one pair
+    python gme_cli.py prop -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 3] [-pn 0] [--rounds 2] [--steps 1] [--no-temporal] [--camera projective|affine|none] [--hier] [-o OUTDIR]   # vector propagation search of one pair
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -143,6 +144,21 @@ def _parser():
     gp.add_argument("--estimator", choices=("projective", "affine"), default="projective",
                     help="the warp: the direct projective refinement, or the indirect affine estimate written as a warp")
     gp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for gmc.json and modes.png")
+    pp = sub.add_parser("prop", help="vector propagation search of one frame pair: neighbour, temporal and camera candidates on a prior field, refined by one pixel (propagate.py, DESIGN.md 7j)")
+    pp.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    pp.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the current frame")
+    pp.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=1, help="the previous frame is fi - fd; frame fi - 2 fd gives the temporal prior where it exists")
+    pp.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="4 .. 64")
+    pp.add_argument("-sw", "--search-window", dest="search_window", type=int, default=16, help="search window of the prior (with --hier: the coarse window, 0 .. 8)")
+    pp.add_argument("-sp", "--searching-procedure", dest="searching_procedure", type=int, default=3, help="the search that makes the prior field")
+    pp.add_argument("-pn", "--pnorm-distance", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    pp.add_argument("--rounds", type=int, default=2, help="rounds, each on the field of the round before (1 .. 4)")
+    pp.add_argument("--steps", type=int, default=1, help="refinement passes of one pixel per round (0 .. 4)")
+    pp.add_argument("--no-temporal", dest="temporal", action="store_false", help="leave out the previous pair's vector")
+    pp.add_argument("--camera", choices=("projective", "affine", "none"), default="projective",
+                    help="the camera candidate: the direct projective refinement, the indirect affine estimate written as a warp, or none")
+    pp.add_argument("--hier", action="store_true", help="take the prior field from the hierarchical search (three levels, radius 1)")
+    pp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for prop.json")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -353,6 +369,45 @@ def _gmc(args):
     return res
 
 
+def _prop(args):
+    """The share of blocks whose vector changed, the share per source class, the mean block cost and the PSNR of the integer
+    compensation before and after the propagation of one pair; the same record into OUTDIR/prop.json."""
+    import json
+    import os
+    import propagate
+    import utils
+    frames = utils.get_video_frames(args.path)
+    if not args.fd <= args.fi < len(frames) or args.fd < 1:
+        raise IndexError("frames %d and %d of %d" % (args.fi - args.fd, args.fi, len(frames)))
+    if args.hier:
+        args.search_window = min(args.search_window, 8)
+    first = args.fi - 2 * args.fd if args.fi >= 2 * args.fd else args.fi - args.fd      # the pair before, for the temporal prior
+    res = propagate.report([frames[k] for k in range(first, args.fi + 1, args.fd)], args.block_size, args.search_window,
+                           args.searching_procedure, args.pnorm, args.rounds, args.steps, args.temporal, args.camera, args.hier, 1)
+    record = {"options": {"path": args.path, "frame_index": args.fi, "frame_distance": args.fd, "block_size": args.block_size,
+                          "search_window": args.search_window, "searching_procedure": args.searching_procedure, "pnorm": args.pnorm,
+                          "rounds": args.rounds, "steps": args.steps, "temporal": res["temporal"], "camera": args.camera,
+                          "hier": bool(args.hier)},
+              "shape": list(res["mf"].shape[:2]), "h": None if res["h"] is None else [float(v) for v in res["h"]],
+              "camera_field": res["g"] is not None}
+    record.update({k: res[k] for k in ("changed_share", "source_share", "moved_share", "mean_cost_prior", "mean_cost_prop", "sse_prior",
+                                       "sse_prop", "psnr_prior", "psnr_prop")})
+    print("frames {} -> {}: {} x {} blocks of {}, rounds {}, steps {}, temporal prior {}, camera {}{}".format(
+        args.fi - args.fd, args.fi, record["shape"][0], record["shape"][1], args.block_size, args.rounds, args.steps,
+        "yes" if res["temporal"] else "no", args.camera, "" if res["g"] is not None or args.camera == "none" else " (no field)"))
+    print("vectors changed: {:.2f} %".format(100.0 * record["changed_share"]))
+    print("sources: " + ", ".join("{} {:.2f} %".format(k, 100.0 * v) for k, v in record["source_share"].items())
+          + "; moved {:.2f} %".format(100.0 * record["moved_share"]))
+    print("mean block cost: prior {:.2f}, propagated {:.2f}".format(record["mean_cost_prior"], record["mean_cost_prop"]))
+    print("psnr prior field:      {:.4f} dB".format(record["psnr_prior"]))
+    print("psnr propagated field: {:.4f} dB".format(record["psnr_prop"]))
+    if args.outdir:
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "prop.json"), "w") as f:
+            json.dump(record, f, indent=1)
+    return res
+
+
 def _hier(args):
     """Reach, median vector and PSNR of the compensation of one pair under the hierarchical search (with --subpel also the
     PSNR of the quarter-pel compensation of the refined field); the same record into OUTDIR/hier.json."""
@@ -470,6 +525,8 @@ def main(argv=None):
         return _bipred(args)
     if args.command == "gmc":
         return _gmc(args)
+    if args.command == "prop":
+        return _prop(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")
@@ -480,6 +537,7 @@ def main(argv=None):
     print("variable block size (gme_cli.py vbs): --depth 0 .. 2, -r 0 .. 3, --penalty 0 .. 2^30, roots a multiple of 2^depth up to 64, leaves of at least 4   (vbs.py)")
     print("bidirectional prediction (gme_cli.py bipred): -bs 4 .. 64, -r 0 .. 2, --rounds 0 .. 2, --penalty 0 .. 2^30; per block the past frame, the next one or their average   (bipred.py)")
     print("global motion compensation (gme_cli.py gmc): -bs 4 .. 64, --penalty 0 .. 2^30, --estimator projective | affine; per block the camera warp or the block's own vector   (gmc.py)")
+    print("vector propagation search (gme_cli.py prop): -bs 4 .. 64, --rounds 1 .. 4, --steps 0 .. 4, --camera projective | affine | none; own, neighbour, temporal, camera and zero vectors on a prior field, refined by one pixel   (propagate.py)")
     try:
         print("device: " + _gme_native.default_context().info()["name"])
     except Exception as e:      # noqa: BLE001 -- no GPU: say so, the listing above is still useful

@@ -66,6 +66,11 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    by a penalty; the mode map is a block-level foreground map of one pair.  A block's whole decision runs in one wave of one
    kernel (k_gmc, csrc/bbme_gmc.hip; host definition gmc.py); ``Sequence.predict_gmc`` writes the predicted
    frames.
+   **Vector propagation search.**  ``propagate.motion_field`` repairs the field of a fast search with the vectors a block
+   inherits: its own, its neighbours', the previous pair's, the camera's (``propagate.camera_field`` of the projective estimate
+   above, or of any float64[8] warp) and zero, the cheapest refined by one pixel per pass, in rounds that each read only the field
+   of the round before.  A block's whole decision runs in one wave of one kernel (k_prop, csrc/bbme_prop.hip; host definition
+   propagate.py); ``Sequence.prop`` leaves the result as the sequence's motion field.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

@@ -530,6 +530,35 @@ class ShardedSequence:
             return out + (lane.seq.compensate_vbs(self.fd, block_size)[:n],) if compensate else out
         return tuple(np.concatenate(part, axis=0) for part in zip(*self._each(run)))
 
+    def motion_fields_prop(self, block_size, search_window, procedure, pnorm, rounds=2, steps=1, temporal=True, g=None, hier=False):
+        """The search, then propagate.search on its field for every local pair, per lane -> (field
+        int32[P_local, h, w, 2], cost int64[P_local, h, w], source uint8[P_local, h, w]).  The search is bbme(block_size,
+        search_window, procedure, pnorm) or, with ``hier``, the hierarchical one at three levels with search_window as its coarse
+        window and radius 1.  ``g`` is the camera field int32[P_local, h, w, 2] or None.  With ``temporal`` a pair also scores
+        the prior field of the pair before it -- where that pair lies in the same lane: the first pair of every shard and of every
+        lane has no temporal prior, so a sharded run equals the single-sequence one only with ``temporal`` off.  Each lane's
+        propagated field becomes its sequence's motion field."""
+        block_size, pnorm, rounds, steps = _native._prop_args(block_size, pnorm, rounds, steps)
+        h, w = self.H // block_size, self.W // block_size
+        if g is not None:
+            g = _native._prop_field(g, "g", (self.lanes[-1].hi if self.lanes else 0, h, w))
+        if not self.lanes:
+            return np.zeros((0, h, w, 2), np.int32), np.zeros((0, h, w), np.int64), np.zeros((0, h, w), np.uint8)
+
+        def run(lane):
+            n = lane.hi - lane.lo
+            if hier:
+                lane.seq.hier(self.fd, block_size, search_window, 1, pnorm, 3)
+            else:
+                lane.seq.bbme(self.fd, block_size, search_window, procedure, pnorm)
+            own = None
+            if g is not None:                   # the lane's sequence may hold more pairs than the lane covers
+                own = np.zeros((lane.seq.N - self.fd, h, w, 2), np.int32)
+                own[:n] = g[lane.lo:lane.hi]
+            lane.seq.prop(self.fd, block_size, pnorm, rounds, steps, temporal, own)
+            return lane.seq.read_prop(0, n)
+        return tuple(np.concatenate(part, axis=0) for part in zip(*self._each(run)))
+
     def estimate(self, procedure=3, search_window=2, model=None):
         """motion.global_motion_estimation for every local pair -> float64[P_local, 6].  ``model``: one of roadmap.MODELS
         (roadmap.stages per lane); the second-order models return float64[P_local, 12]."""

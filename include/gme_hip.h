@@ -496,6 +496,32 @@ GME_API int gme_seq_read_gmc(gme_seq *seq, int first, int count, int32_t *f_out,
 GME_API int gme_seq_predict_gmc(gme_seq *seq, int64_t *sse_out);
 
 /* ---------------------------------------------------------------------------
+ * Vector propagation search (csrc/bbme_prop.hip; host definition: propagate.py): a block scores the
+ * vectors it inherits -- its own, its eight neighbours', the previous pair's, the camera's and zero -- keeps the cheapest and
+ * refines it by one pixel per pass, for `rounds` rounds that each read only the field of the round before.  All integer,
+ * byte-equal to propagate.search.  block_size 4 .. 64, pnorm 0 (sum |d|) or 1 (sum d^2), rounds 1 .. 4, steps 0 .. 4; anything
+ * else is GME_ERR_ARG.
+ * gme_prop_u8: one pair on the prior field f int32[H / bs][W / bs][2], the previous pair's field t and the camera field g (same
+ *   shape, either may be NULL) -> mf_out of that shape, cost_out int64[H / bs][W / bs] and source_out uint8[H / bs][W / bs] (may
+ *   be NULL): class of the winning candidate (0 own, 1 spatial, 2 temporal, 3 camera, 4 zero), plus 8 where a pass moved it.
+ * gme_seq_prop: every pair of the sequence.  The prior is the field the last gme_seq_bbme, gme_seq_hier or gme_seq_prop left;
+ *   GME_ERR_STATE if there is none or it was made with another frame distance or block size.  With temporal != 0, pair k >= 1
+ *   gets the PRIOR field of pair k - 1 as t (not the propagated one: the pairs stay independent and share one launch per
+ *   round); pair 0 has none.  g int32[P][H / bs][W / bs][2] or NULL.  The result becomes the sequence's motion field
+ *   (gme_seq_read_mv, gme_seq_subpel, gme_seq_vbs and a further gme_seq_prop work on it); earlier quarter-pel, hierarchical
+ *   and variable-block-size results are no longer valid, the bidirectional and global-motion-compensation results stay.
+ * gme_seq_read_prop: pairs first_pair .. first_pair + count - 1 of it; any output may be NULL; a range outside [0, P) is
+ *   GME_ERR_ARG; GME_ERR_STATE before any gme_seq_prop, after new frame data or after another block-matching call.
+ * Blocking calls, also in split-phase mode.  gme_last_bbme_info names the kernel instance: k_prop<16>, k_prop<32>, or k_prop<0>
+ * (block size at run time). */
+GME_API int gme_prop_u8(gme_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int H, int W, int stride, int block_size, int pnorm,
+                        int rounds, int steps, const int32_t *f, const int32_t *t /* may be NULL */, const int32_t *g /* may be NULL */,
+                        int32_t *mf_out, int64_t *cost_out /* may be NULL */, uint8_t *source_out /* may be NULL */);
+GME_API int gme_seq_prop(gme_seq *seq, int frame_distance, int block_size, int pnorm, int rounds, int steps, int temporal,
+                         const int32_t *g /* [P][H/B][W/B][2] or NULL */);
+GME_API int gme_seq_read_prop(gme_seq *seq, int first_pair, int count, int32_t *mf_out, int64_t *cost_out, uint8_t *source_out);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
  * the context's stream.  The reference has no distributed code; SURVEY.md §8(e) defines this split.
