@@ -591,7 +591,8 @@ class Sequence:
 
     def set_frames(self, n_frames):
         """Use only the first `n_frames` frames from now on (1 <= n_frames <= N_cap): every stage call covers the pairs of
-        frames [0, n_frames); the device buffers stay sized for N_cap.  Ends a staged GME run."""
+        frames [0, n_frames); the device buffers stay sized for N_cap.  Ends a staged GME run; a change of the count is new
+        frame data to every result the sequence keeps (include/gme_hip.h, "Result lifetimes")."""
         _check(self.lib.gme_seq_set_frames(self.handle, int(n_frames)), self.lib)
         self.N = int(n_frames)
 
@@ -874,6 +875,7 @@ class Sequence:
         return sse
 
     def read_compensated(self, pair):
+        """Compensated frame `pair` of the last compensating or predicting call; a pair that call did not write is a GmeError."""
         out = np.empty((self.H, self.W), dtype=np.uint8)
         _check(self.lib.gme_seq_read_compensated(self.handle, pair, _p(out, _c_u8p)), self.lib)
         return out

@@ -822,11 +822,13 @@ static void gme_drop_run(gme_seq* s)
     s->gme_pairs = 0;
 }
 
-// the frames changed: pyramids and auxiliary tables are stale, and a staged run ends
+// the frames changed: pyramids and auxiliary tables are stale, a staged run ends, and so does every result that was measured
+// on the old frames (the motion field stays: it is a prior; the compensated and warped frames, mosaic and masks stay too)
 static void seq_frames_changed(gme_seq* s)
 {
     s->pyramids_valid = false;
     s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
+    s->qmv_valid = false;
     s->hier_valid = false;
     s->vbs_valid = false;
     s->prop_valid = false;
@@ -1479,8 +1481,9 @@ extern "C" int gme_seq_gme_read_stage(gme_seq* s, int level, int pair, int32_t* 
     gme_ctx* ctx = s->ctx;
     GME_ENTER(ctx);
     int rc = GME_OK;
-    GME_REQUIRE(level >= -1 && level <= 2 && pair >= 0 && pair < (level < 0 ? s->fit_mv_pairs : s->gme_pairs), GME_ERR_ARG,
-                "gme_seq_gme_read_stage: bad index");
+    GME_REQUIRE(level >= -1 && level <= 2 && pair >= 0, GME_ERR_ARG, "gme_seq_gme_read_stage: bad index");
+    GME_REQUIRE(level < 0 || s->gme_pairs > 0, GME_ERR_STATE, "gme_seq_gme_read_stage before gme_seq_gme_begin");
+    GME_REQUIRE(pair < (level < 0 ? s->fit_mv_pairs : s->gme_pairs), GME_ERR_ARG, "gme_seq_gme_read_stage: bad index");
     if (level >= 0) {
         rc = gme_flush_bbme(s, level);
         if (rc) return rc;
@@ -1499,9 +1502,13 @@ extern "C" int gme_seq_gme_read_stage(gme_seq* s, int level, int pair, int32_t* 
     return rc;
 }
 
+// The compensated planes for a writer of `pairs` planes.  Every writer comes through here before it launches, so this is
+// where the planes of the writer before it end (a reallocation included); the writer marks planes 0 .. pairs - 1 with
+// comp_wrote once its launch is queued.
 static int ensure_comp(gme_seq* s, int fd, int pairs)
 {
     gme_ctx* ctx = s->ctx;
+    s->comp_written.flag.clear();
     if (!s->comp.ptr || s->comp.count < pairs) {
         const int cap_pairs = s->N_cap - fd > pairs ? s->N_cap - fd : pairs;
         s->sse.reset(); s->comp_params.reset();
@@ -1510,8 +1517,11 @@ static int ensure_comp(gme_seq* s, int fd, int pairs)
             rc = dev_ensure_all("compensation", { { s->sse, (size_t)cap_pairs }, { s->comp_params, (size_t)cap_pairs * 12 } });      // 12: gme_seq_compensate2
         if (rc) { s->comp = PlaneBuf(); return rc; }       // all or nothing: comp.ptr and comp.count say what the three hold
     }
+    s->comp_written.flag.assign((size_t)s->comp.count, 0);
     return GME_OK;
 }
+
+static void comp_wrote(gme_seq* s, int pairs) { s->comp_written.mark(0, pairs); }
 
 // Order 1 evaluates the affine field per block inside k_compensate16 / k_compensate; order 2 first writes the int32 field
 // of every pair with k_model2_field, then takes their mf32 path.  Both sum the squared error (results.py:52-59,109).
@@ -1550,6 +1560,7 @@ static int seq_compensate(gme_seq* s, int order, const char* who, int fd, int bs
     if (rc) return rc;
     rc = compensate_launch(s, order, fd, pairs, h, w);
     if (rc) return rc;
+    comp_wrote(s, pairs);
     if (sse_out) {
         rc = copy_small(ctx, sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->split_phase);
         return rc ? rc : seq_deliver(s);
@@ -1571,6 +1582,8 @@ extern "C" int gme_seq_read_compensated_range(gme_seq* s, int first, int count, 
     GME_ENTER(s->ctx);
     GME_REQUIRE(s->comp.ptr && first >= 0 && count >= 0 && first + count <= s->comp.count, GME_ERR_STATE,
                 "gme_seq_read_compensated_range: pairs %d .. %d of %d", first, first + count, s->comp.ptr ? s->comp.count : 0);
+    GME_REQUIRE(s->comp_written.all(first, count), GME_ERR_STATE,
+                "gme_seq_read_compensated_range: the last compensating call did not write all of pairs %d .. %d", first, first + count);
     const int rc = read_planes(s->ctx, s->comp, first, count, out);
     if (rc) return rc;
     GME_HIP_TRY(hipStreamSynchronize(s->ctx->stream));
@@ -1667,6 +1680,7 @@ static int seq_device_solve(gme_seq* s, int order, int model, const char* who, i
     if (rc) return rc;
     rc = compensate_launch(s, order, fd, pairs, h, w);
     if (rc) return rc;
+    comp_wrote(s, pairs);
     rc = copy_small(ctx, params_out, s->comp_params, (size_t)pairs * order_params(order) * sizeof(double), hipMemcpyDeviceToHost,
                     s->split_phase);
     if (rc) return rc;
@@ -1694,6 +1708,7 @@ extern "C" int gme_seq_read_compensated(gme_seq* s, int pair, uint8_t* out)
     GME_REQUIRE(s != nullptr && out != nullptr, GME_ERR_ARG, "gme_seq_read_compensated: null pointer");
     GME_ENTER(s->ctx);
     GME_REQUIRE(s->comp.ptr && pair >= 0 && pair < s->comp.count, GME_ERR_STATE, "gme_seq_read_compensated: no such pair");
+    GME_REQUIRE(s->comp_written.all(pair, 1), GME_ERR_STATE, "gme_seq_read_compensated: the last compensating call did not write pair %d", pair);
     const int rc = read_planes(s->ctx, s->comp, pair, 1, out);
     return rc ? rc : ctx_finish(s->ctx);
 }
@@ -1822,6 +1837,7 @@ extern "C" int gme_seq_compensate_projective(gme_seq* s, int fd, const double* p
     if (pairs == 0) return GME_OK;
     rc = launch_compensate_proj(s, fd, pairs, io.in);
     if (rc) return rc;
+    comp_wrote(s, pairs);
     if (sse_out) GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
 }
@@ -2091,6 +2107,7 @@ extern "C" int gme_seq_compensate_qpel(gme_seq* s, int fd, int bs, int64_t* sse_
     rc = launch_compensate_qpel(ctx, p.at(0), p.at(fd), p.stride, pairs, s->H, s->W, p.pitch, bs, s->qmv, s->comp.ptr, s->comp.stride,
                                 s->comp.pitch, s->sse);
     if (rc) return rc;
+    comp_wrote(s, pairs);
     if (sse_out)
         GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
@@ -2230,6 +2247,7 @@ extern "C" int gme_seq_compensate_vbs(gme_seq* s, int fd, int bs, int64_t* sse_o
     rc = launch_compensate_vbs(ctx, p.at(0), p.at(fd), p.stride, pairs, s->H, s->W, p.pitch, bs >> s->vbs_depth, s->mv_h << s->vbs_depth,
                                s->mv_w << s->vbs_depth, s->vbs_leaf, s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
     if (rc) return rc;
+    comp_wrote(s, pairs);
     if (sse_out)
         GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
@@ -2314,6 +2332,7 @@ extern "C" int gme_seq_predict_bipred(gme_seq* s, int64_t* sse_out)
     rc = launch_predict_bipred(ctx, p.at(0), p.at(fd), p.at(2 * fd), p.stride, T, s->H, s->W, p.pitch, s->bp_bs, s->bp_mode, s->bp_v0,
                                s->bp_v1, s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
     if (rc) return rc;
+    comp_wrote(s, T);
     if (sse_out && T)
         GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)T * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);
@@ -2402,6 +2421,7 @@ extern "C" int gme_seq_predict_gmc(gme_seq* s, int64_t* sse_out)
     rc = launch_predict_gmc(ctx, p.at(0), p.at(fd), p.stride, P, s->H, s->W, p.pitch, s->gm_bs, s->gm_h, s->gm_usable, s->gm_mode, s->gm_f,
                             s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
     if (rc) return rc;
+    comp_wrote(s, P);
     if (sse_out && P)
         GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)P * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_finish(ctx);

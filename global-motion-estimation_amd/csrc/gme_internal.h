@@ -56,7 +56,8 @@ inline Plane plane_shape(int H, int W, int count)
     return v;
 }
 
-// Which planes of a stack a call has written (the warped frames, the masks): empty until the stack has memory.
+// Which planes of a stack a call has written (the compensated and the warped frames, the masks): empty until the stack has
+// memory.
 struct WrittenFrames {
     std::vector<uint8_t> flag;
     void mark(int first, int count) { for (int k = first; k < first + count; ++k) flag[(size_t)k] = 1; }
@@ -140,7 +141,8 @@ struct gme_seq {
     DevBuf<double> params_in;     // [P][6], or [P][12] for gme_seq_gme_fit2 (room for 12 per pair)
     DevBuf<int32_t> solve_flags;  // [P] gme_seq_gme_device_solve: pairs whose device solve must be redone on the host
     // compensation
-    PlaneBuf comp;                // [P] compensated frames
+    PlaneBuf comp;                // [P] compensated frames: one stack for every compensating / predicting call
+    WrittenFrames comp_written;   // the planes the last of those calls wrote (ensure_comp clears, comp_wrote marks)
     DevBuf<double> comp_params;   // [P][6], or [P][12] for gme_seq_compensate2 (room for 12 per pair)
     DevBuf<int32_t> comp_mf;      // [P][h][w][2] order-2 field gme_seq_compensate2 compensates with
     DevBuf<unsigned long long> sse;      // [P]
@@ -167,7 +169,7 @@ struct gme_seq {
     DevBuf<uint8_t> mosaic_usable;       // [N_cap]
     DevBuf<unsigned long long> mosaic_counts;    // [2][N_cap] known, moving
     // quarter-pel refinement (bbme_subpel.hip): the refined field and its costs of the last gme_seq_subpel, allocated by
-    // its first call; valid until the next block-matching call replaces `mv`
+    // its first call; valid until new frame data or the next block-matching call
     DevBuf<int32_t> qmv;                 // [P][h][w][2], quarter units
     DevBuf<long long> qcost;             // [P][h][w]
     bool qmv_valid = false;

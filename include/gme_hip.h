@@ -127,14 +127,27 @@ GME_API int gme_seq_upload(gme_seq *seq, int first, int count, const uint8_t *fr
                    int64_t frame_stride);
 /* Use only the first n_frames frames (1 <= n_frames <= the count given to gme_seq_create) from now on: every stage call covers
  * the pairs of frames [0, n_frames) -- results.py:41-48 over a shorter list -- while the buffers stay sized for the full count.
- * How one sequence serves chunks of different lengths of a longer video (sequence.StreamEstimator).  Ends a staged GME run. */
+ * How one sequence serves chunks of different lengths of a longer video (sequence.StreamEstimator).  Ends a staged GME run.
+ * A change of the count is new frame data to every result the sequence keeps (see "Result lifetimes" below). */
 GME_API int gme_seq_set_frames(gme_seq *seq, int n_frames);
 /* deterministic synthetic frames t0 .. t0+N-1 generated on the device */
 GME_API int gme_seq_synth(gme_seq *seq, uint64_t seed, int t0);
-/* mark the pyramid levels stale (upload and synth do so themselves) */
+/* mark the pyramid levels stale (upload and synth do so themselves); new frame data to every result the sequence keeps */
 GME_API int gme_seq_invalidate(gme_seq *seq);
 /* level 2 = full resolution, 1 and 0 = pyramid levels (valid after gme_seq_gme_begin) */
 GME_API int gme_seq_read_frame(gme_seq *seq, int level, int index, uint8_t *out);
+
+/* Result lifetimes.  "New frame data" below is gme_seq_upload, gme_seq_synth, gme_seq_invalidate, a gme_seq_set_frames that
+ * changes the count, and the upload inside gme_seq_bbme_streamed.  Each result family states where it ends; a call that a
+ * family's text does not name leaves that result readable and byte-identical (tests/lifetime_cases.py holds the whole table,
+ * tests/test_gpu_lifetimes.py enforces it).  Three rules the families share:
+ *   - the motion field of gme_seq_read_mv survives new frame data: it is a prior (gme_seq_prop, gme_seq_vbs), replaced only by
+ *     gme_seq_bbme, gme_seq_bbme_streamed, gme_seq_hier and gme_seq_prop;
+ *   - the quarter-pel result ends with new frame data and with the next block-matching call (gme_seq_bbme,
+ *     gme_seq_bbme_streamed, gme_seq_hier, gme_seq_prop), exactly where the hierarchical, variable-block-size and propagation
+ *     results end;
+ *   - the warped frames, the mosaic and the masks are kept in the sequence through new frame data, until their own call
+ *     writes them again. */
 
 /* bbme.get_motion_field over every pair of the sequence; results stay on the device */
 GME_API int gme_seq_bbme(gme_seq *seq, int frame_distance, int block_size, int search_window,
@@ -167,7 +180,7 @@ GME_API void gme_host_free(void *p);
  * The level searches are launched so that the caller's work between the stages overlaps them:
  * begin returns once the first parameters are on the host with the level-1 search already
  * running; fit(level 1) returns its sums with the level-2 search running.  New frame data
- * (upload / synth / invalidate) ends a staged run: fit then reports GME_ERR_STATE until begin. */
+ * (upload / synth / invalidate) ends a staged run: fit and the stage read-back then report GME_ERR_STATE until begin. */
 GME_API int gme_seq_gme_begin(gme_seq *seq, int frame_distance, int bbme_block_size, int procedure,
                       int search_window, float *params0_out);
 GME_API int gme_seq_gme_fit(gme_seq *seq, int level, const double *params_in, double outlier_fraction,
@@ -185,7 +198,12 @@ GME_API int gme_seq_gme_read_stage(gme_seq *seq, int level, int pair, int32_t *g
 
 /* motion.get_motion_field_affine((H/bs, W/bs), params) + motion.compensate_frame(prev, field)
  * + sum of squared error against `cur` for every pair (results.py:52-59,109).
- * Compensated frames stay on the device; sse_out[P] may be NULL. */
+ * Compensated frames stay on the device; sse_out[P] may be NULL.
+ * The compensated frames are one stack of planes that every compensating or predicting call of the sequence writes
+ * (gme_seq_compensate, gme_seq_compensate2, gme_seq_compensate_projective, gme_seq_compensate_qpel, gme_seq_compensate_vbs,
+ * gme_seq_predict_bipred, gme_seq_predict_gmc and the device solves): each call writes planes 0 .. its own count - 1 and ends
+ * the planes of the call before it.  They stay readable through new frame data.  gme_seq_read_compensated(_range) of a
+ * range that holds a plane the last writer did not write, or before any writer, is GME_ERR_STATE. */
 GME_API int gme_seq_compensate(gme_seq *seq, int frame_distance, int block_size, const double *params,
                        int64_t *sse_out);
 GME_API int gme_seq_read_compensated(gme_seq *seq, int pair, uint8_t *out);
@@ -345,7 +363,8 @@ GME_API int gme_seq_read_masks_range(gme_seq *seq, int first, int count, uint8_t
  *   qmf_out int32[H/bs][W/bs][2], cost_out int64[H/bs][W/bs].
  * gme_seq_subpel: the same for every pair of the field the last gme_seq_bbme left, kept in the sequence (allocated on first
  *   use); GME_ERR_STATE if there is no such field or it was made with another frame distance or block size.
- * gme_seq_read_qmv: pairs first_pair .. first_pair + count - 1 of it; either output may be NULL.
+ * gme_seq_read_qmv: pairs first_pair .. first_pair + count - 1 of it; either output may be NULL.  GME_ERR_STATE before any
+ *   gme_seq_subpel, after new frame data or after the next block-matching call; gme_seq_compensate_qpel likewise.
  * gme_seq_compensate_qpel: with the refined field, block (i, j) of compensated frame k becomes the interpolated block of
  *   frame k at (4 j bs - q0, 4 i bs - q1) where that block is inside, elsewhere (and beyond the last whole block) the copy of
  *   frame k; written into the sequence's compensated frames (gme_seq_read_compensated_range reads them); sse_out[pairs] (may be
