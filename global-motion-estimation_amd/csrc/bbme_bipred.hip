@@ -17,8 +17,8 @@
 //                       depend on each other and all run in the one wave; the vectors stay in scalar registers.  <16> and <32>
 //                       are compiled; <0> takes the block size at run time (and rows that are no multiple of four bytes).
 //   k_predict_bipred    bipred.predict per pixel, with the squared error of each predicted frame against its `mid`
+#include "bbme_predict.h"
 #include "bbme_wave_lds.h"
-#include "gme_internal.h"
 
 namespace {
 
@@ -199,55 +199,45 @@ __global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
     }
 }
 
-constexpr int PB_PX = 4;                                        // output pixels per lane: one 32-bit store
-constexpr int PB_ROWS = 4;                                      // rows per workgroup: one wave per row
-constexpr int PB_THREADS = 64 * PB_ROWS;
-constexpr int PB_COLS = 64 * PB_PX;
-
-// grid (ceil(W / PB_COLS), ceil(H / PB_ROWS), targets).  Output pixel (u, v) of block (v / bs, u / bs) inside the hb x wb grid
-// is the pixel of `past` at (u + v0x, v + v0y) in mode 0, of `next` at (u + v1x, v + v1y) in mode 1 and their rounded average in
-// mode 2; in mode 3, beyond the last whole block, and wherever a pixel it would read lies outside the frame (never with the
-// modes of k_bipred), the co-located pixel of `past`.  Lanes store four pixels at once; pixels at or past W are written as
-// zero, the plane's padding.
-__global__ void __launch_bounds__(PB_THREADS) k_predict_bipred(const uint8_t* past, const uint8_t* mid, const uint8_t* next,
-                                                               long long plane_stride, int H, int W, int pitch, int bs, int hb, int wb,
-                                                               const uint8_t* mode, const int32_t* v0, const int32_t* v1, uint8_t* out,
-                                                               long long out_stride, int out_pitch, unsigned long long* sse)
-{
-    const int f = blockIdx.z, lane = threadIdx.x & 63;
-    const int v = blockIdx.y * PB_ROWS + (threadIdx.x >> 6);
-    const int u0 = blockIdx.x * PB_COLS + lane * PB_PX;
-    uint32_t err = 0;
-    if (v < H && u0 < W) {
-        const uint8_t* p = past + (long long)f * plane_stride;
-        const uint8_t* c = mid + (long long)f * plane_stride;
-        const uint8_t* q = next + (long long)f * plane_stride;
-        const int i = v / bs;
-        uint32_t packed = 0;
-#pragma unroll
-        for (int k = 0; k < PB_PX; ++k) {
-            const int u = u0 + k;
-            if (u >= W) break;
-            const int j = u / bs;
-            int o = p[(long long)v * pitch + u];
-            if (i < hb && j < wb) {
-                const long long b = ((long long)f * hb + i) * wb + j;
-                const int md = mode[b];
-                const long long pu = (long long)u + v0[b * 2], pv = (long long)v + v0[b * 2 + 1];
-                const long long qu = (long long)u + v1[b * 2], qv = (long long)v + v1[b * 2 + 1];
-                const bool pin = pu >= 0 && pu < W && pv >= 0 && pv < H, qin = qu >= 0 && qu < W && qv >= 0 && qv < H;
-                if (md == 0 && pin) o = p[pv * pitch + pu];
-                else if (md == 1 && qin) o = q[qv * pitch + qu];
-                else if (md == 2 && pin && qin) o = ((int)p[pv * pitch + pu] + (int)q[qv * pitch + qu] + 1) >> 1;
-            }
-            const int d = o - (int)c[(long long)v * pitch + u];
-            err += (uint32_t)(d * d);
-            packed |= (uint32_t)o << (8 * k);
+// The pixel of k_predict_bipred.  Output pixel (u, v) of block (v / bs, u / bs) inside the hb x wb grid is the pixel of `past` at
+// (u + v0x, v + v0y) in mode 0, of `next` at (u + v1x, v + v1y) in mode 1 and their rounded average in mode 2; in mode 3, beyond
+// the last whole block, and wherever a pixel it would read lies outside the frame (never with the modes of k_bipred), the
+// co-located pixel of `past`.
+struct BipredPixel {
+    const uint8_t* p;             // the target's `past` and `next` planes
+    const uint8_t* q;
+    const uint8_t* mode;          // its modes [hb][wb] and vector pairs [hb][wb][2]
+    const int32_t* v0;
+    const int32_t* v1;
+    int H, W, pitch, bs, hb, wb;
+    __device__ __forceinline__ int operator()(int u, int v) const
+    {
+        const int i = v / bs, j = u / bs;
+        int o = p[(long long)v * pitch + u];
+        if (i < hb && j < wb) {
+            const long long b = (long long)i * wb + j;
+            const int md = mode[b];
+            const long long pu = (long long)u + v0[b * 2], pv = (long long)v + v0[b * 2 + 1];
+            const long long qu = (long long)u + v1[b * 2], qv = (long long)v + v1[b * 2 + 1];
+            const bool pin = pu >= 0 && pu < W && pv >= 0 && pv < H, qin = qu >= 0 && qu < W && qv >= 0 && qv < H;
+            if (md == 0 && pin) o = p[pv * pitch + pu];
+            else if (md == 1 && qin) o = q[qv * pitch + qu];
+            else if (md == 2 && pin && qin) o = ((int)p[pv * pitch + pu] + (int)q[qv * pitch + qu] + 1) >> 1;
         }
-        *(uint32_t*)(out + (long long)f * out_stride + (long long)v * out_pitch + u0) = packed;
+        return o;
     }
-    const uint32_t total = wave_sum_u32(err);
-    if (lane == 0 && total) atomicAdd(&sse[f], (unsigned long long)total);
+};
+
+// the row frame of bbme_predict.h, one plane per target
+__global__ void __launch_bounds__(PRED_THREADS) k_predict_bipred(const uint8_t* past, const uint8_t* mid, const uint8_t* next,
+                                                                 long long plane_stride, int H, int W, int pitch, int bs, int hb, int wb,
+                                                                 const uint8_t* mode, const int32_t* v0, const int32_t* v1, uint8_t* out,
+                                                                 long long out_stride, int out_pitch, unsigned long long* sse)
+{
+    const int f = blockIdx.z;
+    const long long plane = (long long)f * plane_stride, blocks = (long long)f * hb * wb;
+    const BipredPixel px = { past + plane, next + plane, mode + blocks, v0 + blocks * 2, v1 + blocks * 2, H, W, pitch, bs, hb, wb };
+    predict_rows(px, mid + plane, H, W, pitch, out + (long long)f * out_stride, out_pitch, sse + f);
 }
 
 template <int BS>
@@ -294,9 +284,7 @@ int launch_bipred(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid, const u
     a.window_bytes = (side * ((side + 3) / 4 + 1) * 4 + 15) & ~15;
     a.slice_bytes = a.anchor_bytes + 2 * a.window_bytes;
     const long long per = (long long)hb * wb;
-    const int step = max_grid_planes();
-    for (int k = 0; k < targets; k += step) {
-        const int n = targets - k < step ? targets - k : step;
+    for_plane_chunks(targets, [&](int k, int n) {
         const long long off = (long long)k * plane_stride;
         a.past = past + off; a.mid = mid + off; a.next = next + off;
         a.f0 = f0 + per * k * 2; a.f1 = f1 + per * k * 2;
@@ -305,7 +293,7 @@ int launch_bipred(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid, const u
         if (!compiled) bipred_launch<0>(ctx->stream, a, n);
         else if (bs == 16) bipred_launch<16>(ctx->stream, a, n);
         else bipred_launch<32>(ctx->stream, a, n);
-    }
+    });
     GME_HIP_TRY(hipGetLastError());
     return GME_OK;
 }
@@ -319,17 +307,11 @@ int launch_predict_bipred(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid,
     if (targets == 0) return GME_OK;
     GME_REQUIRE(bs >= 1, GME_ERR_ARG, "block_size %d", bs);
     const int hb = H / bs, wb = W / bs;
-    GME_HIP_TRY(hipMemsetAsync(sse, 0, sizeof(unsigned long long) * targets, ctx->stream));
     const long long per = (long long)hb * wb;
-    const int step = max_grid_planes();
-    for (int k = 0; k < targets; k += step) {
-        const int n = targets - k < step ? targets - k : step;
+    return predict_planes(ctx, targets, sse, [&](int k, int n) {
         const long long off = (long long)k * plane_stride;
-        const dim3 grid((W + PB_COLS - 1) / PB_COLS, (H + PB_ROWS - 1) / PB_ROWS, n);
-        hipLaunchKernelGGL(k_predict_bipred, grid, dim3(PB_THREADS), 0, ctx->stream, past + off, mid + off, next + off, plane_stride, H,
-                           W, pitch, bs, hb, wb, mode + per * k, v0 + per * k * 2, v1 + per * k * 2, out + (long long)k * out_stride,
-                           out_stride, out_pitch, sse + k);
-    }
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
+        hipLaunchKernelGGL(k_predict_bipred, predict_grid(H, W, n), dim3(PRED_THREADS), 0, ctx->stream, past + off, mid + off, next + off,
+                           plane_stride, H, W, pitch, bs, hb, wb, mode + per * k, v0 + per * k * 2, v1 + per * k * 2,
+                           out + (long long)k * out_stride, out_stride, out_pitch, sse + k);
+    });
 }

@@ -18,6 +18,7 @@
 //   k_predict_gmc    gmc.predict, one wave per block-sized cell of the frame (the cells beyond the last whole block included),
 //                    mode and vector read once per cell; the squared error against `cur` is summed per workgroup and added with
 //                    one integer atomic.
+#include "bbme_predict.h"
 #include "bbme_wave_lds.h"
 #include "gme_warp.h"
 
@@ -289,9 +290,7 @@ int launch_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, long long p
     a.hb = hb; a.wb = wb; a.bs = bs; a.pnorm = pnorm; a.penalty = (uint32_t)penalty;
     a.block_bytes = (bs * ((bs + 3) / 4) * 4 + 15) & ~15;
     const long long per = (long long)hb * wb;
-    const int step = max_grid_planes();
-    for (int k = 0; k < pairs; k += step) {
-        const int n = pairs - k < step ? pairs - k : step;
+    for_plane_chunks(pairs, [&](int k, int n) {
         const long long off = (long long)k * plane_stride;
         a.ref = ref + off; a.cur = cur + off;
         a.h = h + (size_t)k * 8; a.usable = usable + k;
@@ -300,7 +299,7 @@ int launch_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, long long p
         if (!compiled) gmc_launch<0>(ctx->stream, a, n);
         else if (bs == 16) gmc_launch<16>(ctx->stream, a, n);
         else gmc_launch<32>(ctx->stream, a, n);
-    }
+    });
     GME_HIP_TRY(hipGetLastError());
     return GME_OK;
 }
@@ -315,17 +314,12 @@ int launch_predict_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, lon
     GME_REQUIRE(bs >= GM_MIN_BS && bs <= GM_MAX_BS, GME_ERR_ARG, "block_size %d (%d .. %d)", bs, GM_MIN_BS, GM_MAX_BS);
     const int hb = H / bs, wb = W / bs, ch = (H + bs - 1) / bs, cw = (W + bs - 1) / bs;
     GME_REQUIRE(ch <= 65535, GME_ERR_ARG, "%d block rows", ch);
-    GME_HIP_TRY(hipMemsetAsync(sse, 0, sizeof(unsigned long long) * pairs, ctx->stream));
     const long long per = (long long)hb * wb;
-    const int step = max_grid_planes();
-    for (int k = 0; k < pairs; k += step) {
-        const int n = pairs - k < step ? pairs - k : step;
+    return predict_planes(ctx, pairs, sse, [&](int k, int n) {
         const long long off = (long long)k * plane_stride;
         const dim3 grid((cw + GM_WAVES - 1) / GM_WAVES, ch, n);
         hipLaunchKernelGGL(k_predict_gmc, grid, dim3(GM_THREADS), 0, ctx->stream, ref + off, cur + off, plane_stride, H, W, pitch, bs, hb,
                            wb, cw, h + (size_t)k * 8, usable + k, mode + per * k, f + per * k * 2, out + (long long)k * out_stride,
                            out_stride, out_pitch, sse + k);
-    }
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
+    });
 }

@@ -195,9 +195,7 @@ int launch_hier(gme_ctx* ctx, const Plane (&level)[3], int first_prev, int first
     }
     a.slice_bytes = a.anchor_bytes + ((window + 15) & ~15);
     const long long per = (long long)hb * wb;
-    const int step = max_grid_planes();
-    for (int k = 0; k < pairs; k += step) {
-        const int n = pairs - k < step ? pairs - k : step;
+    for_plane_chunks(pairs, [&](int k, int n) {
         for (int l = 0; l < 3; ++l) {
             HierLevel& L = a.lv[l];
             const Plane& p = level[l];
@@ -211,7 +209,7 @@ int launch_hier(gme_ctx* ctx, const Plane (&level)[3], int first_prev, int first
         else if (bs == 16) hier_launch<16, 3>(ctx->stream, a, n);
         else if (bs == 32) hier_launch<32, 3>(ctx->stream, a, n);
         else hier_launch<64, 3>(ctx->stream, a, n);
-    }
+    });
     GME_HIP_TRY(hipGetLastError());
     return GME_OK;
 }

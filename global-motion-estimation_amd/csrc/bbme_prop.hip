@@ -292,12 +292,10 @@ int launch_prop(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long
     a.hb = hb; a.wb = wb; a.bs = bs; a.pnorm = pnorm; a.steps = steps;
     a.t = t;
     const long long per = (long long)hb * wb;
-    const int step = max_grid_planes();
     for (int r = 0; r < rounds; ++r) {
         const int32_t* in = r == 0 ? f : work[(r - 1) & 1];
         int32_t* out = work[r & 1];
-        for (int k = 0; k < pairs; k += step) {
-            const int n = pairs - k < step ? pairs - k : step;
+        for_plane_chunks(pairs, [&](int k, int n) {
             a.prev = prev + (long long)k * plane_stride; a.cur = cur + (long long)k * plane_stride;
             a.fin = in + per * k * 2; a.fout = out + per * k * 2;
             a.t_shift = k + t_shift;
@@ -306,7 +304,7 @@ int launch_prop(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long
             if (!compiled) prop_launch<0>(ctx->stream, a, n);
             else if (bs == 16) prop_launch<16>(ctx->stream, a, n);
             else prop_launch<32>(ctx->stream, a, n);
-        }
+        });
     }
     GME_HIP_TRY(hipGetLastError());
     return GME_OK;

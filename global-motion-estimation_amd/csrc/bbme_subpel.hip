@@ -12,7 +12,7 @@
 //                       origin is inside the frame, the copy elsewhere; squared error against `current` per pair
 #include <type_traits>
 
-#include "gme_internal.h"
+#include "bbme_predict.h"
 
 namespace {
 
@@ -20,11 +20,6 @@ constexpr int SUB_THREADS = 256;
 constexpr int SUB_STAGED_MAX_BS = 64;                           // blocks up to this size go through LDS
 // the staged instances sum a block's cost in 32 bits: bs^2 * 255^2 must stay below 2^31 (subpel.py: int64 at the ABI)
 static_assert((long long)SUB_STAGED_MAX_BS * SUB_STAGED_MAX_BS * 65025ll < (1ll << 31), "32-bit block costs");
-
-constexpr int CQ_PX = 4;                                        // output pixels per lane: one 32-bit store
-constexpr int CQ_ROWS = 4;                                      // rows per workgroup: one wave per row
-constexpr int CQ_THREADS = 64 * CQ_ROWS;
-constexpr int CQ_COLS = 64 * CQ_PX;
 
 // sum over the lanes of a group, left in every lane of it: four DPP steps inside a 16-lane row, the wave-wide sum otherwise
 template <int G>
@@ -211,51 +206,42 @@ __global__ void __launch_bounds__(SUB_THREADS) k_subpel_refine(const uint8_t* pr
     }
 }
 
-// grid (ceil(W / CQ_COLS), ceil(H / CQ_ROWS), pairs).  Output pixel (u, v) of block (i, j) = (v / bs, u / bs), i < hb and
-// j < wb: the block's origin moves to (4 j bs - q0, 4 i bs - q1) quarter units; where that block is inside, the pixel is the
-// definition's four-tap blend at its place in it, else (and beyond the last whole block) the pixel of `previous`.  Lanes
-// store four pixels at once; pixels at or past W are written as zero, the plane's padding (pitch is a multiple of 64).
-__global__ void __launch_bounds__(CQ_THREADS) k_compensate_qpel(const uint8_t* prev, const uint8_t* cur, long long plane_stride,
-                                                                int H, int W, int pitch, int bs, int hb, int wb,
-                                                                const int32_t* qmf, uint8_t* out, long long out_stride,
-                                                                int out_pitch, unsigned long long* sse)
-{
-    const int f = blockIdx.z, lane = threadIdx.x & 63;
-    const int v = blockIdx.y * CQ_ROWS + (threadIdx.x >> 6);
-    const int u0 = blockIdx.x * CQ_COLS + lane * CQ_PX;
-    uint32_t err = 0;
-    if (v < H && u0 < W) {
-        const uint8_t* p = prev + (long long)f * plane_stride;
-        const uint8_t* c = cur + (long long)f * plane_stride;
-        const int32_t* q = qmf + (long long)f * hb * wb * 2;
-        const int i = v / bs;
-        uint32_t packed = 0;
-#pragma unroll
-        for (int k = 0; k < CQ_PX; ++k) {
-            const int u = u0 + k;
-            if (u >= W) break;
-            const int j = u / bs;
-            int o = p[(long long)v * pitch + u];
-            if (i < hb && j < wb) {
-                const long long X = 4ll * j * bs - q[((long long)i * wb + j) * 2];
-                const long long Y = 4ll * i * bs - q[((long long)i * wb + j) * 2 + 1];
-                const long long x0 = X >> 2, y0 = Y >> 2;
-                const int fx = (int)(X & 3), fy = (int)(Y & 3);
-                if (x0 >= 0 && y0 >= 0 && x0 + bs - 1 + (fx != 0) <= W - 1 && y0 + bs - 1 + (fy != 0) <= H - 1) {
-                    const uint8_t* s = p + (y0 + (v - i * bs)) * pitch + x0 + (u - j * bs);
-                    // a tap of weight zero may lie past the last row or column: it is not read
-                    const int p00 = s[0], p01 = fx ? s[1] : 0, p10 = fy ? s[pitch] : 0, p11 = (fx && fy) ? s[pitch + 1] : 0;
-                    o = ((4 - fx) * (4 - fy) * p00 + fx * (4 - fy) * p01 + (4 - fx) * fy * p10 + fx * fy * p11 + 8) >> 4;
-                }
+// The pixel of k_compensate_qpel.  Output pixel (u, v) of block (i, j) = (v / bs, u / bs), i < hb and j < wb: the block's origin
+// moves to (4 j bs - q0, 4 i bs - q1) quarter units; where that block is inside, the pixel is the definition's four-tap blend at
+// its place in it, else (and beyond the last whole block) the pixel of `previous`.
+struct QpelPixel {
+    const uint8_t* p;             // the pair's `previous` plane
+    const int32_t* q;             // its field [hb][wb][2], quarter units
+    int H, W, pitch, bs, hb, wb;
+    __device__ __forceinline__ int operator()(int u, int v) const
+    {
+        const int i = v / bs, j = u / bs;
+        int o = p[(long long)v * pitch + u];
+        if (i < hb && j < wb) {
+            const long long X = 4ll * j * bs - q[((long long)i * wb + j) * 2];
+            const long long Y = 4ll * i * bs - q[((long long)i * wb + j) * 2 + 1];
+            const long long x0 = X >> 2, y0 = Y >> 2;
+            const int fx = (int)(X & 3), fy = (int)(Y & 3);
+            if (x0 >= 0 && y0 >= 0 && x0 + bs - 1 + (fx != 0) <= W - 1 && y0 + bs - 1 + (fy != 0) <= H - 1) {
+                const uint8_t* s = p + (y0 + (v - i * bs)) * pitch + x0 + (u - j * bs);
+                // a tap of weight zero may lie past the last row or column: it is not read
+                const int p00 = s[0], p01 = fx ? s[1] : 0, p10 = fy ? s[pitch] : 0, p11 = (fx && fy) ? s[pitch + 1] : 0;
+                o = ((4 - fx) * (4 - fy) * p00 + fx * (4 - fy) * p01 + (4 - fx) * fy * p10 + fx * fy * p11 + 8) >> 4;
             }
-            const int d = o - (int)c[(long long)v * pitch + u];
-            err += (uint32_t)(d * d);
-            packed |= (uint32_t)o << (8 * k);
         }
-        *(uint32_t*)(out + (long long)f * out_stride + (long long)v * out_pitch + u0) = packed;
+        return o;
     }
-    const uint32_t total = wave_sum_u32(err);
-    if (lane == 0 && total) atomicAdd(&sse[f], (unsigned long long)total);
+};
+
+// the row frame of bbme_predict.h, one plane per pair
+__global__ void __launch_bounds__(PRED_THREADS) k_compensate_qpel(const uint8_t* prev, const uint8_t* cur, long long plane_stride,
+                                                                  int H, int W, int pitch, int bs, int hb, int wb,
+                                                                  const int32_t* qmf, uint8_t* out, long long out_stride,
+                                                                  int out_pitch, unsigned long long* sse)
+{
+    const int f = blockIdx.z;
+    const QpelPixel px = { prev + (long long)f * plane_stride, qmf + (long long)f * hb * wb * 2, H, W, pitch, bs, hb, wb };
+    predict_rows(px, cur + (long long)f * plane_stride, H, W, pitch, out + (long long)f * out_stride, out_pitch, sse + f);
 }
 
 template <int G, int BS, bool STAGED>
@@ -282,9 +268,7 @@ int launch_subpel_refine(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, 
     if (pairs == 0 || hb == 0 || wb == 0) return GME_OK;
     GME_REQUIRE((long long)hb * wb <= 0x7FFFFFFFll, GME_ERR_ARG, "%d x %d blocks", hb, wb);
     const long long per = (long long)hb * wb;
-    const int step = max_grid_planes();
-    for (int k = 0; k < pairs; k += step) {
-        const int n = pairs - k < step ? pairs - k : step;
+    for_plane_chunks(pairs, [&](int k, int n) {
         const uint8_t* p = prev + (long long)k * plane_stride;
         const uint8_t* c = cur + (long long)k * plane_stride;
         const int32_t* m = mf + per * k * 2;
@@ -299,7 +283,7 @@ int launch_subpel_refine(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, 
         else if (bs < 4) SUB_GO(16, 0, true);
         else SUB_GO(64, 0, true);
 #undef SUB_GO
-    }
+    });
     GME_HIP_TRY(hipGetLastError());
     return GME_OK;
 }
@@ -312,15 +296,9 @@ int launch_compensate_qpel(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
 {
     if (pairs == 0) return GME_OK;
     const int hb = H / bs, wb = W / bs;
-    GME_HIP_TRY(hipMemsetAsync(sse, 0, sizeof(unsigned long long) * pairs, ctx->stream));
-    const int step = max_grid_planes();
-    for (int k = 0; k < pairs; k += step) {
-        const int n = pairs - k < step ? pairs - k : step;
-        const dim3 grid((W + CQ_COLS - 1) / CQ_COLS, (H + CQ_ROWS - 1) / CQ_ROWS, n);
-        hipLaunchKernelGGL(k_compensate_qpel, grid, dim3(CQ_THREADS), 0, ctx->stream, prev + (long long)k * plane_stride,
+    return predict_planes(ctx, pairs, sse, [&](int k, int n) {
+        hipLaunchKernelGGL(k_compensate_qpel, predict_grid(H, W, n), dim3(PRED_THREADS), 0, ctx->stream, prev + (long long)k * plane_stride,
                            cur + (long long)k * plane_stride, plane_stride, H, W, pitch, bs, hb, wb,
                            qmf + (long long)hb * wb * 2 * k, out + (long long)k * out_stride, out_stride, out_pitch, sse + k);
-    }
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
+    });
 }

@@ -16,8 +16,8 @@
 //                       block size and depth at run time (and leaf rows that are no multiple of four bytes).
 //   k_compensate_vbs    subpel.compensate_integer at an explicit cell size (the integer compensation kernels derive theirs from
 //                       H / h, which is another size when H is no multiple of the root), with the squared error per pair
+#include "bbme_predict.h"
 #include "bbme_wave_lds.h"
-#include "gme_internal.h"
 
 namespace {
 
@@ -235,48 +235,34 @@ __global__ void __launch_bounds__(VBS_THREADS) k_vbs(const VbsArgs A)
     if (lane == 0) A.cost[root] = (long long)F0;
 }
 
-constexpr int CV_PX = 4;                                        // output pixels per lane: one 32-bit store
-constexpr int CV_ROWS = 4;                                      // rows per workgroup: one wave per row
-constexpr int CV_THREADS = 64 * CV_ROWS;
-constexpr int CV_COLS = 64 * CV_PX;
-
-// grid (ceil(W / CV_COLS), ceil(H / CV_ROWS), pairs).  Output pixel (u, v) of cell (v / g, u / g) inside the hg x wg field is
-// the pixel of `previous` at (u - d0, v - d1) where that lies in the frame; elsewhere, and beyond the last whole cell, the
-// pixel is kept.  Lanes store four pixels at once; pixels at or past W are written as zero, the plane's padding.
-__global__ void __launch_bounds__(CV_THREADS) k_compensate_vbs(const uint8_t* prev, const uint8_t* cur, long long plane_stride, int H,
-                                                               int W, int pitch, int g, int hg, int wg, const int32_t* leaf,
-                                                               uint8_t* out, long long out_stride, int out_pitch,
-                                                               unsigned long long* sse)
-{
-    const int f = blockIdx.z, lane = threadIdx.x & 63;
-    const int v = blockIdx.y * CV_ROWS + (threadIdx.x >> 6);
-    const int u0 = blockIdx.x * CV_COLS + lane * CV_PX;
-    uint32_t err = 0;
-    if (v < H && u0 < W) {
-        const uint8_t* p = prev + (long long)f * plane_stride;
-        const uint8_t* c = cur + (long long)f * plane_stride;
-        const int32_t* q = leaf + (long long)f * hg * wg * 2;
-        const int i = v / g;
-        uint32_t packed = 0;
-#pragma unroll
-        for (int k = 0; k < CV_PX; ++k) {
-            const int u = u0 + k;
-            if (u >= W) break;
-            const int j = u / g;
-            int o = p[(long long)v * pitch + u];
-            if (i < hg && j < wg) {
-                const long long su = (long long)u - q[((long long)i * wg + j) * 2];
-                const long long sv = (long long)v - q[((long long)i * wg + j) * 2 + 1];
-                if (su >= 0 && su < W && sv >= 0 && sv < H) o = p[sv * pitch + su];
-            }
-            const int d = o - (int)c[(long long)v * pitch + u];
-            err += (uint32_t)(d * d);
-            packed |= (uint32_t)o << (8 * k);
+// The pixel of k_compensate_vbs.  Output pixel (u, v) of cell (v / g, u / g) inside the hg x wg field is the pixel of `previous`
+// at (u - d0, v - d1) where that lies in the frame; elsewhere, and beyond the last whole cell, the pixel is kept.
+struct VbsPixel {
+    const uint8_t* p;             // the pair's `previous` plane
+    const int32_t* q;             // its leaf field [hg][wg][2]
+    int H, W, pitch, g, hg, wg;
+    __device__ __forceinline__ int operator()(int u, int v) const
+    {
+        const int i = v / g, j = u / g;
+        int o = p[(long long)v * pitch + u];
+        if (i < hg && j < wg) {
+            const long long su = (long long)u - q[((long long)i * wg + j) * 2];
+            const long long sv = (long long)v - q[((long long)i * wg + j) * 2 + 1];
+            if (su >= 0 && su < W && sv >= 0 && sv < H) o = p[sv * pitch + su];
         }
-        *(uint32_t*)(out + (long long)f * out_stride + (long long)v * out_pitch + u0) = packed;
+        return o;
     }
-    const uint32_t total = wave_sum_u32(err);
-    if (lane == 0 && total) atomicAdd(&sse[f], (unsigned long long)total);
+};
+
+// the row frame of bbme_predict.h, one plane per pair
+__global__ void __launch_bounds__(PRED_THREADS) k_compensate_vbs(const uint8_t* prev, const uint8_t* cur, long long plane_stride, int H,
+                                                                 int W, int pitch, int g, int hg, int wg, const int32_t* leaf,
+                                                                 uint8_t* out, long long out_stride, int out_pitch,
+                                                                 unsigned long long* sse)
+{
+    const int f = blockIdx.z;
+    const VbsPixel px = { prev + (long long)f * plane_stride, leaf + (long long)f * hg * wg * 2, H, W, pitch, g, hg, wg };
+    predict_rows(px, cur + (long long)f * plane_stride, H, W, pitch, out + (long long)f * out_stride, out_pitch, sse + f);
 }
 
 template <int BS, int DEPTH>
@@ -325,16 +311,14 @@ int launch_vbs(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long 
     a.window_bytes = (side * ((side + 3) / 4 + 1) * 4 + 15) & ~15;
     a.slice_bytes = a.anchor_bytes + a.window_bytes + ((3 * VBS_NODE_SLOTS * 4 + 15) & ~15);
     const long long per = (long long)hb * wb, per_cells = per << (2 * depth);
-    const int step = max_grid_planes();
-    for (int k = 0; k < pairs; k += step) {
-        const int n = pairs - k < step ? pairs - k : step;
+    for_plane_chunks(pairs, [&](int k, int n) {
         a.prev = prev + (long long)k * plane_stride; a.cur = cur + (long long)k * plane_stride;
         a.mf = mf + per * k * 2; a.cost = cost + per * k;
         a.leaf = leaf + per_cells * k * 2; a.dmap = dmap + per_cells * k;
         if (!compiled) vbs_launch<0, 0>(ctx->stream, a, n);
         else if (bs == 16) vbs_launch<16, 2>(ctx->stream, a, n);
         else vbs_launch<32, 2>(ctx->stream, a, n);
-    }
+    });
     GME_HIP_TRY(hipGetLastError());
     return GME_OK;
 }
@@ -346,15 +330,9 @@ int launch_compensate_vbs(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur,
                           unsigned long long* sse)
 {
     if (pairs == 0) return GME_OK;
-    GME_HIP_TRY(hipMemsetAsync(sse, 0, sizeof(unsigned long long) * pairs, ctx->stream));
-    const int step = max_grid_planes();
-    for (int k = 0; k < pairs; k += step) {
-        const int n = pairs - k < step ? pairs - k : step;
-        const dim3 grid((W + CV_COLS - 1) / CV_COLS, (H + CV_ROWS - 1) / CV_ROWS, n);
-        hipLaunchKernelGGL(k_compensate_vbs, grid, dim3(CV_THREADS), 0, ctx->stream, prev + (long long)k * plane_stride,
+    return predict_planes(ctx, pairs, sse, [&](int k, int n) {
+        hipLaunchKernelGGL(k_compensate_vbs, predict_grid(H, W, n), dim3(PRED_THREADS), 0, ctx->stream, prev + (long long)k * plane_stride,
                            cur + (long long)k * plane_stride, plane_stride, H, W, pitch, g, hg, wg,
                            leaf + (long long)hg * wg * 2 * k, out + (long long)k * out_stride, out_stride, out_pitch, sse + k);
-    }
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
+    });
 }

@@ -307,6 +307,18 @@ static hipError_t put_plane(gme_ctx* ctx, const Plane& v, const uint8_t* host, i
     return hipMemcpy2DAsync(v.ptr, v.pitch, host, stride, v.W, v.H, hipMemcpyHostToDevice, ctx->stream);
 }
 
+// host images with rows `stride` bytes apart into planes 0, 1, ... of a stack, queued on the context's stream
+static int put_planes(gme_ctx* ctx, const Plane& st, std::initializer_list<const uint8_t*> host, int stride)
+{
+    int k = 0;
+    for (const uint8_t* image : host) {
+        Plane one = st;
+        one.ptr = st.at(k++);
+        GME_HIP_TRY(put_plane(ctx, one, image, stride));
+    }
+    return GME_OK;
+}
+
 // planes first .. first + count - 1 of a stack into out[count][H][W] (tight), queued on the context's stream
 static int read_planes(gme_ctx* ctx, const Plane& p, int first, int count, uint8_t* out)
 {
@@ -314,6 +326,36 @@ static int read_planes(gme_ctx* ctx, const Plane& p, int first, int count, uint8
         GME_HIP_TRY(hipMemcpy2DAsync(out + (size_t)k * p.H * p.W, p.W, p.at(first + k), p.pitch, p.W, p.H, hipMemcpyDeviceToHost,
                                      ctx->stream));
     return GME_OK;
+}
+
+// the pointer and shape rules of a single-pair call `who` on host images; `pointers`: none of those it needs is null
+static int oneshot_check(const char* who, bool pointers, int H, int W, int stride)
+{
+    GME_REQUIRE(pointers, GME_ERR_ARG, "%s: null pointer", who);
+    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "%s: bad shape H=%d W=%d stride=%d", who, H, W, stride);
+    return GME_OK;
+}
+
+// The ending of a single-pair call that can predict (gme_bipred_u8, gme_gmc_u8): where the caller wants the predicted frame or
+// its squared error, predict() launches it into plane `pred` of the stack with the error in *d_sse (device); then the wait.
+template <class Predict>
+static int oneshot_predict(gme_ctx* ctx, const Plane& st, int pred, const unsigned long long* d_sse, uint8_t* pred_out, int64_t* sse_out,
+                           Predict predict)
+{
+    unsigned long long sse = 0;
+    int rc = GME_OK;
+    if (pred_out || sse_out) {
+        rc = predict();
+        if (rc) return rc;
+        if (pred_out) {
+            rc = read_planes(ctx, st, pred, 1, pred_out);
+            if (rc) return rc;
+        }
+        GME_HIP_TRY(hipMemcpyAsync(&sse, d_sse, sizeof(sse), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    rc = ctx_finish(ctx);
+    if (sse_out) *sse_out = (int64_t)sse;
+    return rc;
 }
 
 // The search of the pairs (first + k, first + k + fd), k < pairs, of a plane stack into mf.
@@ -472,9 +514,9 @@ extern "C" int gme_subpel_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* c
                              int pnorm, int levels, const int32_t* mf_in, int32_t* qmf_out, int64_t* cost_out)
 {
     GME_ENTER(ctx);
-    GME_REQUIRE(prev && cur && mf_in && qmf_out && cost_out, GME_ERR_ARG, "gme_subpel_u8: null pointer");
-    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_subpel_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
-    int rc = subpel_check("gme_subpel_u8", H, W, block_size, pnorm, levels);
+    int rc = oneshot_check("gme_subpel_u8", prev && cur && mf_in && qmf_out && cost_out, H, W, stride);
+    if (rc) return rc;
+    rc = subpel_check("gme_subpel_u8", H, W, block_size, pnorm, levels);
     if (rc) return rc;
     const int h = H / block_size, w = W / block_size;
     if (h == 0 || w == 0) return GME_OK;
@@ -504,9 +546,9 @@ extern "C" int gme_hier_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
                            int coarse_window, int radius, int pnorm, int levels, int32_t* mf_out, int64_t* cost_out)
 {
     GME_ENTER(ctx);
-    GME_REQUIRE(prev && cur && mf_out, GME_ERR_ARG, "gme_hier_u8: null pointer");
-    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_hier_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
-    int rc = hier_check_args("gme_hier_u8", block_size, coarse_window, radius, pnorm, levels);
+    int rc = oneshot_check("gme_hier_u8", prev && cur && mf_out, H, W, stride);
+    if (rc) return rc;
+    rc = hier_check_args("gme_hier_u8", block_size, coarse_window, radius, pnorm, levels);
     if (rc) return rc;
     const int h = H / block_size, w = W / block_size;
     if (h == 0 || w == 0) return GME_OK;
@@ -525,10 +567,8 @@ extern "C" int gme_hier_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     if (rc) return rc;
     for (int l = 1; l < 3; ++l) { d_mf[l] = d_mf[0] + n * 2 * l; d_cost[l] = d_cost[0] + n * l; }
     GME_HIP_TRY(hipMemsetAsync(lv[2].ptr, 0, (uint8_t*)d_mf[0] - lv[2].ptr, ctx->stream));
-    Plane second = lv[2];
-    second.ptr = lv[2].at(1);
-    GME_HIP_TRY(put_plane(ctx, lv[2], prev, stride));
-    GME_HIP_TRY(put_plane(ctx, second, cur, stride));
+    rc = put_planes(ctx, lv[2], { prev, cur }, stride);
+    if (rc) return rc;
     for (int l = 1; l >= 3 - levels; --l) {
         rc = launch_pyrdown(ctx, lv[l + 1], lv[l]);
         if (rc) return rc;
@@ -546,9 +586,9 @@ extern "C" int gme_vbs_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur,
                           int64_t* cost_out)
 {
     GME_ENTER(ctx);
-    GME_REQUIRE(prev && cur && mf_in && leaf_out, GME_ERR_ARG, "gme_vbs_u8: null pointer");
-    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_vbs_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
-    int rc = vbs_check_args("gme_vbs_u8", block_size, depth, radius, pnorm, penalty);
+    int rc = oneshot_check("gme_vbs_u8", prev && cur && mf_in && leaf_out, H, W, stride);
+    if (rc) return rc;
+    rc = vbs_check_args("gme_vbs_u8", block_size, depth, radius, pnorm, penalty);
     if (rc) return rc;
     const int h = H / block_size, w = W / block_size;
     if (h == 0 || w == 0) return GME_OK;
@@ -582,9 +622,9 @@ extern "C" int gme_bipred_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* m
                              uint8_t* pred_out, int64_t* sse_out)
 {
     GME_ENTER(ctx);
-    GME_REQUIRE(past && mid && next && f0 && f1 && mode_out, GME_ERR_ARG, "gme_bipred_u8: null pointer");
-    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_bipred_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
-    int rc = bipred_check_args("gme_bipred_u8", block_size, radius, rounds, pnorm, penalty);
+    int rc = oneshot_check("gme_bipred_u8", past && mid && next && f0 && f1 && mode_out, H, W, stride);
+    if (rc) return rc;
+    rc = bipred_check_args("gme_bipred_u8", block_size, radius, rounds, pnorm, penalty);
     if (rc) return rc;
     const int h = H / block_size, w = W / block_size;
     const size_t n = (size_t)h * w;
@@ -600,12 +640,8 @@ extern "C" int gme_bipred_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* m
     long long* d_costs = d_cost + n;
     unsigned long long* d_sse = (unsigned long long*)(d_cost + n * 4);
     GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_vec - st.ptr, ctx->stream));
-    const uint8_t* host[3] = { past, mid, next };
-    for (int k = 0; k < 3; ++k) {
-        Plane one = st;
-        one.ptr = st.at(k);
-        GME_HIP_TRY(put_plane(ctx, one, host[k], stride));
-    }
+    rc = put_planes(ctx, st, { past, mid, next }, stride);
+    if (rc) return rc;
     if (n) {
         GME_HIP_TRY(hipMemcpyAsync(d_f0, f0, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         GME_HIP_TRY(hipMemcpyAsync(d_f1, f1, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -620,20 +656,10 @@ extern "C" int gme_bipred_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* m
         if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
         if (costs_out) GME_HIP_TRY(hipMemcpyAsync(costs_out, d_costs, n * 3 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     }
-    unsigned long long sse = 0;
-    if (pred_out || sse_out) {
-        rc = launch_predict_bipred(ctx, st.at(0), st.at(1), st.at(2), 0, 1, H, W, st.pitch, block_size, d_mode, d_v0, d_v1, st.at(3), 0,
-                                   st.pitch, d_sse);
-        if (rc) return rc;
-        if (pred_out) {
-            rc = read_planes(ctx, st, 3, 1, pred_out);
-            if (rc) return rc;
-        }
-        GME_HIP_TRY(hipMemcpyAsync(&sse, d_sse, sizeof(sse), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    rc = ctx_finish(ctx);
-    if (sse_out) *sse_out = (int64_t)sse;
-    return rc;
+    return oneshot_predict(ctx, st, 3, d_sse, pred_out, sse_out, [&] {
+        return launch_predict_bipred(ctx, st.at(0), st.at(1), st.at(2), 0, 1, H, W, st.pitch, block_size, d_mode, d_v0, d_v1, st.at(3), 0,
+                                     st.pitch, d_sse);
+    });
 }
 
 // Global motion compensation of one pair on a given warp and field (bbme_gmc.hip): the two frames and the
@@ -643,9 +669,9 @@ extern "C" int gme_gmc_u8(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, 
                           uint8_t* pred_out, int64_t* sse_out)
 {
     GME_ENTER(ctx);
-    GME_REQUIRE(ref && cur && h && f && mode_out, GME_ERR_ARG, "gme_gmc_u8: null pointer");
-    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_gmc_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
-    int rc = gmc_check_args("gme_gmc_u8", block_size, pnorm, penalty);
+    int rc = oneshot_check("gme_gmc_u8", ref && cur && h && f && mode_out, H, W, stride);
+    if (rc) return rc;
+    rc = gmc_check_args("gme_gmc_u8", block_size, pnorm, penalty);
     if (rc) return rc;
     const int hb = H / block_size, wb = W / block_size;
     const size_t n = (size_t)hb * wb;
@@ -662,12 +688,8 @@ extern "C" int gme_gmc_u8(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, 
     unsigned long long* d_sse = (unsigned long long*)(d_cost + n * 3);
     uint8_t* d_usable = d_mode + n;
     GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_f - st.ptr, ctx->stream));
-    const uint8_t* host[2] = { ref, cur };
-    for (int k = 0; k < 2; ++k) {
-        Plane one = st;
-        one.ptr = st.at(k);
-        GME_HIP_TRY(put_plane(ctx, one, host[k], stride));
-    }
+    rc = put_planes(ctx, st, { ref, cur }, stride);
+    if (rc) return rc;
     const uint8_t usable = gmc_usable(h, H, W) ? 1 : 0;        // read by the copy below before this call returns (ctx_finish)
     GME_HIP_TRY(hipMemcpyAsync(d_h, h, 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     GME_HIP_TRY(hipMemcpyAsync(d_usable, &usable, 1, hipMemcpyHostToDevice, ctx->stream));
@@ -679,20 +701,10 @@ extern "C" int gme_gmc_u8(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, 
         if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
         if (costs_out) GME_HIP_TRY(hipMemcpyAsync(costs_out, d_costs, n * 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     }
-    unsigned long long sse = 0;
-    if (pred_out || sse_out) {
-        rc = launch_predict_gmc(ctx, st.at(0), st.at(1), 0, 1, H, W, st.pitch, block_size, d_h, d_usable, d_mode, d_f, st.at(2), 0, st.pitch,
-                                d_sse);
-        if (rc) return rc;
-        if (pred_out) {
-            rc = read_planes(ctx, st, 2, 1, pred_out);
-            if (rc) return rc;
-        }
-        GME_HIP_TRY(hipMemcpyAsync(&sse, d_sse, sizeof(sse), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    rc = ctx_finish(ctx);
-    if (sse_out) *sse_out = (int64_t)sse;
-    return rc;
+    return oneshot_predict(ctx, st, 2, d_sse, pred_out, sse_out, [&] {
+        return launch_predict_gmc(ctx, st.at(0), st.at(1), 0, 1, H, W, st.pitch, block_size, d_h, d_usable, d_mode, d_f, st.at(2), 0, st.pitch,
+                                  d_sse);
+    });
 }
 
 // Vector propagation of one pair on given fields (bbme_prop.hip): the two frames as one stack of two planes
@@ -702,9 +714,9 @@ extern "C" int gme_prop_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
                            uint8_t* source_out)
 {
     GME_ENTER(ctx);
-    GME_REQUIRE(prev && cur && f && mf_out, GME_ERR_ARG, "gme_prop_u8: null pointer");
-    GME_REQUIRE(H > 0 && W > 0 && stride >= W, GME_ERR_ARG, "gme_prop_u8: bad shape H=%d W=%d stride=%d", H, W, stride);
-    int rc = prop_check_args("gme_prop_u8", block_size, pnorm, rounds, steps);
+    int rc = oneshot_check("gme_prop_u8", prev && cur && f && mf_out, H, W, stride);
+    if (rc) return rc;
+    rc = prop_check_args("gme_prop_u8", block_size, pnorm, rounds, steps);
     if (rc) return rc;
     const int hb = H / block_size, wb = W / block_size;
     const size_t n = (size_t)hb * wb;
@@ -720,12 +732,8 @@ extern "C" int gme_prop_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     int32_t *d_f = d_vec, *d_t = d_vec + n * 2, *d_g = d_vec + n * 4;
     int32_t* const work[2] = { d_vec + n * 6, d_vec + n * 8 };
     GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_vec - st.ptr, ctx->stream));
-    const uint8_t* host[2] = { prev, cur };
-    for (int k = 0; k < 2; ++k) {
-        Plane one = st;
-        one.ptr = st.at(k);
-        GME_HIP_TRY(put_plane(ctx, one, host[k], stride));
-    }
+    rc = put_planes(ctx, st, { prev, cur }, stride);
+    if (rc) return rc;
     GME_HIP_TRY(hipMemcpyAsync(d_f, f, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     if (t) GME_HIP_TRY(hipMemcpyAsync(d_t, t, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     if (g) GME_HIP_TRY(hipMemcpyAsync(d_g, g, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -822,16 +830,23 @@ static void gme_drop_run(gme_seq* s)
     s->gme_pairs = 0;
 }
 
+// Replacing the motion field ends what was derived from it: the quarter-pel, hierarchical, variable-block-size and propagation
+// results.  Every writer of s->mv comes through here, and so do new frames; a result type that reads the field joins this list.
+static void seq_field_replaced(gme_seq* s)
+{
+    s->qmv_valid = false;
+    s->hier_valid = false;
+    s->vbs_valid = false;
+    s->prop_valid = false;
+}
+
 // the frames changed: pyramids and auxiliary tables are stale, a staged run ends, and so does every result that was measured
 // on the old frames (the motion field stays: it is a prior; the compensated and warped frames, mosaic and masks stay too)
 static void seq_frames_changed(gme_seq* s)
 {
     s->pyramids_valid = false;
     s->sqbox_valid[0] = s->sqbox_valid[1] = s->sqbox_valid[2] = false;
-    s->qmv_valid = false;
-    s->hier_valid = false;
-    s->vbs_valid = false;
-    s->prop_valid = false;
+    seq_field_replaced(s);
     s->bp_valid = false;
     s->gm_valid = false;
     gme_drop_run(s);
@@ -1052,10 +1067,7 @@ extern "C" int gme_seq_bbme(gme_seq* s, int fd, int bs, int sw, int procedure, i
     if (rc) return rc;
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
     s->mv_fd = fd; s->mv_bs = bs;
-    s->qmv_valid = false;
-    s->hier_valid = false;
-    s->vbs_valid = false;
-    s->prop_valid = false;
+    seq_field_replaced(s);
     return seq_launch_bbme(s, 2, fd, bbme_job(s->level[2], 0, fd, pairs, bs, sw, procedure, pnorm, s->mv));
 }
 
@@ -1113,10 +1125,7 @@ extern "C" int gme_seq_bbme_streamed(gme_seq* s, const uint8_t* frames, int row_
     if (rc) return rc;
     s->mv_h = h; s->mv_w = w; s->mv_pairs = pairs;
     s->mv_fd = fd; s->mv_bs = bs;
-    s->qmv_valid = false;
-    s->hier_valid = false;
-    s->vbs_valid = false;
-    s->prop_valid = false;
+    seq_field_replaced(s);
     const Plane& p = s->level[2];
     // one table kind for the whole call: every chunk's launches carry at most `pairs` pairs, so one that the matrix-core
     // kernel would take at the largest also takes it at every chunk, and a smaller chunk of a declined call keeps kind 1
@@ -1522,6 +1531,46 @@ static int ensure_comp(gme_seq* s, int fd, int pairs)
 }
 
 static void comp_wrote(gme_seq* s, int pairs) { s->comp_written.mark(0, pairs); }
+
+// What the predicting entries of the block-field passes share behind their own state checks: the compensated planes for
+// `planes` pairs or targets, predict() (the pass's launch into s->comp and s->sse), the squared errors into sse_out where the
+// caller wants them, and the wait.
+template <class Predict>
+static int seq_predict(gme_seq* s, int fd, int planes, int64_t* sse_out, Predict predict)
+{
+    gme_ctx* ctx = s->ctx;
+    int rc = ensure_comp(s, fd, planes);
+    if (rc) return rc;
+    rc = predict();
+    if (rc) return rc;
+    comp_wrote(s, planes);
+    if (sse_out && planes)
+        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)planes * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return ctx_finish(ctx);
+}
+
+// One optional output of a reader: `bytes` per item (pair or target) from the device array `src`, whose first item is item 0.
+struct ReadPart {
+    void* out;
+    const void* src;
+    size_t bytes;
+};
+
+// The reader `who` of a result that `made_by` makes: refused unless the result stands (`valid`) and the items
+// [first, first + count) lie within its `limit` items (`noun`: what an item is); then every part the caller gave a buffer for,
+// and the wait.  Nothing is copied where there is nothing to copy.
+static int seq_read(gme_seq* s, const char* who, bool valid, const char* made_by, const char* noun, int first, int count, int limit,
+                    std::initializer_list<ReadPart> parts)
+{
+    GME_REQUIRE(valid, GME_ERR_STATE, "%s before %s", who, made_by);
+    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= limit, GME_ERR_ARG, "%s: %s [%d, %d) outside [0, %d)", who, noun, first,
+                first + count, limit);
+    for (const ReadPart& part : parts)
+        if (part.out && part.bytes * count)
+            GME_HIP_TRY(hipMemcpyAsync(part.out, (const uint8_t*)part.src + part.bytes * first, part.bytes * count, hipMemcpyDeviceToHost,
+                                       s->ctx->stream));
+    return ctx_finish(s->ctx);
+}
 
 // Order 1 evaluates the affine field per block inside k_compensate16 / k_compensate; order 2 first writes the int32 field
 // of every pair with k_model2_field, then takes their mf32 path.  Both sum the squared error (results.py:52-59,109).
@@ -2077,17 +2126,9 @@ extern "C" int gme_seq_read_qmv(gme_seq* s, int first_pair, int count, int32_t* 
 {
     GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_qmv: null sequence");
     GME_ENTER(s->ctx);
-    GME_REQUIRE(s->qmv_valid, GME_ERR_STATE, "gme_seq_read_qmv before gme_seq_subpel");
-    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG,
-                "gme_seq_read_qmv: pairs [%d, %d) outside [0, %d)", first_pair, first_pair + count, s->mv_pairs);
     const size_t per = (size_t)s->mv_h * s->mv_w;
-    if (qmf_out)
-        GME_HIP_TRY(hipMemcpyAsync(qmf_out, s->qmv + per * 2 * first_pair, per * 2 * count * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                   s->ctx->stream));
-    if (cost_out)
-        GME_HIP_TRY(hipMemcpyAsync(cost_out, s->qcost + per * first_pair, per * count * sizeof(long long), hipMemcpyDeviceToHost,
-                                   s->ctx->stream));
-    return ctx_finish(s->ctx);
+    return seq_read(s, "gme_seq_read_qmv", s->qmv_valid, "gme_seq_subpel", "pairs", first_pair, count, s->mv_pairs,
+                    { { qmf_out, s->qmv.get(), per * 2 * sizeof(int32_t) }, { cost_out, s->qcost.get(), per * sizeof(long long) } });
 }
 
 extern "C" int gme_seq_compensate_qpel(gme_seq* s, int fd, int bs, int64_t* sse_out)
@@ -2101,16 +2142,11 @@ extern "C" int gme_seq_compensate_qpel(gme_seq* s, int fd, int bs, int64_t* sse_
     int rc = subpel_field(s, "gme_seq_compensate_qpel", fd, bs);
     if (rc) return rc;
     const int pairs = s->mv_pairs;
-    rc = ensure_comp(s, fd, pairs);
-    if (rc) return rc;
     const Plane& p = s->level[2];
-    rc = launch_compensate_qpel(ctx, p.at(0), p.at(fd), p.stride, pairs, s->H, s->W, p.pitch, bs, s->qmv, s->comp.ptr, s->comp.stride,
-                                s->comp.pitch, s->sse);
-    if (rc) return rc;
-    comp_wrote(s, pairs);
-    if (sse_out)
-        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    return ctx_finish(ctx);
+    return seq_predict(s, fd, pairs, sse_out, [&] {
+        return launch_compensate_qpel(ctx, p.at(0), p.at(fd), p.stride, pairs, s->H, s->W, p.pitch, bs, s->qmv, s->comp.ptr, s->comp.stride,
+                                      s->comp.pitch, s->sse);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2127,10 +2163,7 @@ extern "C" int gme_seq_hier(gme_seq* s, int fd, int bs, int cw, int radius, int 
     if (rc) return rc;
     const int pairs = s->N - fd, h = s->H / bs, w = s->W / bs;
     const size_t n = (size_t)pairs * h * w;
-    s->hier_valid = false;
-    s->vbs_valid = false;
-    s->prop_valid = false;
-    s->qmv_valid = false;
+    seq_field_replaced(s);
     rc = seq_levels(s);
     if (rc) return rc;
     rc = seq_pyramids(s);
@@ -2163,20 +2196,14 @@ extern "C" int gme_seq_read_hier(gme_seq* s, int level, int first_pair, int coun
 {
     GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_hier: null sequence");
     GME_ENTER(s->ctx);
+    // the level indexes the table below, and which levels there are is part of the result: both checks come before it
     GME_REQUIRE(s->hier_valid, GME_ERR_STATE, "gme_seq_read_hier before gme_seq_hier");
     GME_REQUIRE(level >= 3 - s->hier_levels && level <= 2, GME_ERR_ARG, "gme_seq_read_hier: level %d, the last gme_seq_hier used %d .. 2",
                 level, 3 - s->hier_levels);
-    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG,
-                "gme_seq_read_hier: pairs [%d, %d) outside [0, %d)", first_pair, first_pair + count, s->mv_pairs);
     const size_t per = (size_t)s->mv_h * s->mv_w;
-    const int32_t* mf = level == 2 ? s->mv.get() : s->hier_mv[level].get();
-    if (mf_out && per * count)
-        GME_HIP_TRY(hipMemcpyAsync(mf_out, mf + per * 2 * first_pair, per * 2 * count * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                   s->ctx->stream));
-    if (cost_out && per * count)
-        GME_HIP_TRY(hipMemcpyAsync(cost_out, s->hier_cost[level] + per * first_pair, per * count * sizeof(long long),
-                                   hipMemcpyDeviceToHost, s->ctx->stream));
-    return ctx_finish(s->ctx);
+    return seq_read(s, "gme_seq_read_hier", s->hier_valid, "gme_seq_hier", "pairs", first_pair, count, s->mv_pairs,
+                    { { mf_out, level == 2 ? s->mv.get() : s->hier_mv[level].get(), per * 2 * sizeof(int32_t) },
+                      { cost_out, s->hier_cost[level].get(), per * sizeof(long long) } });
 }
 
 // ---------------------------------------------------------------------------
@@ -2215,19 +2242,10 @@ extern "C" int gme_seq_read_vbs(gme_seq* s, int first_pair, int count, int32_t* 
 {
     GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_vbs: null sequence");
     GME_ENTER(s->ctx);
-    GME_REQUIRE(s->vbs_valid, GME_ERR_STATE, "gme_seq_read_vbs before gme_seq_vbs");
-    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG,
-                "gme_seq_read_vbs: pairs [%d, %d) outside [0, %d)", first_pair, first_pair + count, s->mv_pairs);
     const size_t per = (size_t)s->mv_h * s->mv_w, cells = per << (2 * s->vbs_depth);
-    if (leaf_out && cells * count)
-        GME_HIP_TRY(hipMemcpyAsync(leaf_out, s->vbs_leaf + cells * 2 * first_pair, cells * 2 * count * sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, s->ctx->stream));
-    if (depth_out && cells * count)
-        GME_HIP_TRY(hipMemcpyAsync(depth_out, s->vbs_dmap + cells * first_pair, cells * count, hipMemcpyDeviceToHost, s->ctx->stream));
-    if (cost_out && per * count)
-        GME_HIP_TRY(hipMemcpyAsync(cost_out, s->vbs_cost + per * first_pair, per * count * sizeof(long long), hipMemcpyDeviceToHost,
-                                   s->ctx->stream));
-    return ctx_finish(s->ctx);
+    return seq_read(s, "gme_seq_read_vbs", s->vbs_valid, "gme_seq_vbs", "pairs", first_pair, count, s->mv_pairs,
+                    { { leaf_out, s->vbs_leaf.get(), cells * 2 * sizeof(int32_t) }, { depth_out, s->vbs_dmap.get(), cells },
+                      { cost_out, s->vbs_cost.get(), per * sizeof(long long) } });
 }
 
 extern "C" int gme_seq_compensate_vbs(gme_seq* s, int fd, int bs, int64_t* sse_out)
@@ -2241,16 +2259,11 @@ extern "C" int gme_seq_compensate_vbs(gme_seq* s, int fd, int bs, int64_t* sse_o
     int rc = subpel_field(s, "gme_seq_compensate_vbs", fd, bs);
     if (rc) return rc;
     const int pairs = s->mv_pairs;
-    rc = ensure_comp(s, fd, pairs);
-    if (rc) return rc;
     const Plane& p = s->level[2];
-    rc = launch_compensate_vbs(ctx, p.at(0), p.at(fd), p.stride, pairs, s->H, s->W, p.pitch, bs >> s->vbs_depth, s->mv_h << s->vbs_depth,
-                               s->mv_w << s->vbs_depth, s->vbs_leaf, s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
-    if (rc) return rc;
-    comp_wrote(s, pairs);
-    if (sse_out)
-        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    return ctx_finish(ctx);
+    return seq_predict(s, fd, pairs, sse_out, [&] {
+        return launch_compensate_vbs(ctx, p.at(0), p.at(fd), p.stride, pairs, s->H, s->W, p.pitch, bs >> s->vbs_depth, s->mv_h << s->vbs_depth,
+                                     s->mv_w << s->vbs_depth, s->vbs_leaf, s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2300,22 +2313,11 @@ extern "C" int gme_seq_read_bipred(gme_seq* s, int first, int count, int32_t* f0
 {
     GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_bipred: null sequence");
     GME_ENTER(s->ctx);
-    GME_REQUIRE(s->bp_valid, GME_ERR_STATE, "gme_seq_read_bipred before gme_seq_bipred");
-    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->bp_targets, GME_ERR_ARG,
-                "gme_seq_read_bipred: targets [%d, %d) outside [0, %d)", first, first + count, s->bp_targets);
-    const size_t per = (size_t)s->bp_h * s->bp_w, m = per * count;
-    hipStream_t st = s->ctx->stream;
-    if (m) {
-        const struct { void* out; const void* src; size_t elem; } parts[] = {
-            { f0_out, s->bp_f0 + per * 2 * first, 2 * sizeof(int32_t) }, { f1_out, s->bp_f1 + per * 2 * first, 2 * sizeof(int32_t) },
-            { mode_out, s->bp_mode + per * first, 1 },
-            { v0_out, s->bp_v0 + per * 2 * first, 2 * sizeof(int32_t) }, { v1_out, s->bp_v1 + per * 2 * first, 2 * sizeof(int32_t) },
-            { cost_out, s->bp_cost + per * first, sizeof(long long) }, { costs_out, s->bp_costs + per * 3 * first, 3 * sizeof(long long) },
-        };
-        for (const auto& part : parts)
-            if (part.out) GME_HIP_TRY(hipMemcpyAsync(part.out, part.src, m * part.elem, hipMemcpyDeviceToHost, st));
-    }
-    return ctx_finish(s->ctx);
+    const size_t per = (size_t)s->bp_h * s->bp_w, vec = per * 2 * sizeof(int32_t);
+    return seq_read(s, "gme_seq_read_bipred", s->bp_valid, "gme_seq_bipred", "targets", first, count, s->bp_targets,
+                    { { f0_out, s->bp_f0.get(), vec }, { f1_out, s->bp_f1.get(), vec }, { mode_out, s->bp_mode.get(), per },
+                      { v0_out, s->bp_v0.get(), vec }, { v1_out, s->bp_v1.get(), vec },
+                      { cost_out, s->bp_cost.get(), per * sizeof(long long) }, { costs_out, s->bp_costs.get(), per * 3 * sizeof(long long) } });
 }
 
 extern "C" int gme_seq_predict_bipred(gme_seq* s, int64_t* sse_out)
@@ -2326,16 +2328,11 @@ extern "C" int gme_seq_predict_bipred(gme_seq* s, int64_t* sse_out)
     GME_REQUIRE(s->bp_valid, GME_ERR_STATE, "gme_seq_predict_bipred before gme_seq_bipred");
     const int T = s->bp_targets, fd = s->bp_fd;
     GME_REQUIRE(T <= s->N - 2 * fd, GME_ERR_STATE, "gme_seq_predict_bipred: %d targets, the sequence has %d", T, s->N - 2 * fd);
-    int rc = ensure_comp(s, fd, T);
-    if (rc) return rc;
     const Plane& p = s->level[2];
-    rc = launch_predict_bipred(ctx, p.at(0), p.at(fd), p.at(2 * fd), p.stride, T, s->H, s->W, p.pitch, s->bp_bs, s->bp_mode, s->bp_v0,
-                               s->bp_v1, s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
-    if (rc) return rc;
-    comp_wrote(s, T);
-    if (sse_out && T)
-        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)T * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    return ctx_finish(ctx);
+    return seq_predict(s, fd, T, sse_out, [&] {
+        return launch_predict_bipred(ctx, p.at(0), p.at(fd), p.at(2 * fd), p.stride, T, s->H, s->W, p.pitch, s->bp_bs, s->bp_mode, s->bp_v0,
+                                     s->bp_v1, s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2390,21 +2387,11 @@ extern "C" int gme_seq_read_gmc(gme_seq* s, int first, int count, int32_t* f_out
 {
     GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_gmc: null sequence");
     GME_ENTER(s->ctx);
-    GME_REQUIRE(s->gm_valid, GME_ERR_STATE, "gme_seq_read_gmc before gme_seq_gmc");
-    GME_REQUIRE(first >= 0 && count >= 0 && first + count <= s->gm_pairs, GME_ERR_ARG,
-                "gme_seq_read_gmc: pairs [%d, %d) outside [0, %d)", first, first + count, s->gm_pairs);
-    const size_t per = (size_t)s->gm_h_blocks * s->gm_w_blocks, m = per * count;
-    hipStream_t st = s->ctx->stream;
-    if (m) {
-        const struct { void* out; const void* src; size_t elem; } parts[] = {
-            { f_out, s->gm_f + per * 2 * first, 2 * sizeof(int32_t) }, { mode_out, s->gm_mode + per * first, 1 },
-            { cost_out, s->gm_cost + per * first, sizeof(long long) }, { costs_out, s->gm_costs + per * 2 * first, 2 * sizeof(long long) },
-        };
-        for (const auto& part : parts)
-            if (part.out) GME_HIP_TRY(hipMemcpyAsync(part.out, part.src, m * part.elem, hipMemcpyDeviceToHost, st));
-    }
-    if (usable_out && count) GME_HIP_TRY(hipMemcpyAsync(usable_out, s->gm_usable + first, (size_t)count, hipMemcpyDeviceToHost, st));
-    return ctx_finish(s->ctx);
+    const size_t per = (size_t)s->gm_h_blocks * s->gm_w_blocks;
+    return seq_read(s, "gme_seq_read_gmc", s->gm_valid, "gme_seq_gmc", "pairs", first, count, s->gm_pairs,
+                    { { f_out, s->gm_f.get(), per * 2 * sizeof(int32_t) }, { mode_out, s->gm_mode.get(), per },
+                      { cost_out, s->gm_cost.get(), per * sizeof(long long) }, { costs_out, s->gm_costs.get(), per * 2 * sizeof(long long) },
+                      { usable_out, s->gm_usable.get(), 1 } });                  // one flag per pair, whatever the block grid
 }
 
 extern "C" int gme_seq_predict_gmc(gme_seq* s, int64_t* sse_out)
@@ -2415,16 +2402,11 @@ extern "C" int gme_seq_predict_gmc(gme_seq* s, int64_t* sse_out)
     GME_REQUIRE(s->gm_valid, GME_ERR_STATE, "gme_seq_predict_gmc before gme_seq_gmc");
     const int P = s->gm_pairs, fd = s->gm_fd;
     GME_REQUIRE(P <= s->N - fd, GME_ERR_STATE, "gme_seq_predict_gmc: %d pairs, the sequence has %d", P, s->N - fd);
-    int rc = ensure_comp(s, fd, P);
-    if (rc) return rc;
     const Plane& p = s->level[2];
-    rc = launch_predict_gmc(ctx, p.at(0), p.at(fd), p.stride, P, s->H, s->W, p.pitch, s->gm_bs, s->gm_h, s->gm_usable, s->gm_mode, s->gm_f,
-                            s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
-    if (rc) return rc;
-    comp_wrote(s, P);
-    if (sse_out && P)
-        GME_HIP_TRY(hipMemcpyAsync(sse_out, s->sse, (size_t)P * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    return ctx_finish(ctx);
+    return seq_predict(s, fd, P, sse_out, [&] {
+        return launch_predict_gmc(ctx, p.at(0), p.at(fd), p.stride, P, s->H, s->W, p.pitch, s->gm_bs, s->gm_h, s->gm_usable, s->gm_mode, s->gm_f,
+                                  s->comp.ptr, s->comp.stride, s->comp.pitch, s->sse);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2461,9 +2443,7 @@ extern "C" int gme_seq_prop(gme_seq* s, int fd, int bs, int pnorm, int rounds, i
         s->prop_valid = true;
         return GME_OK;
     }
-    s->qmv_valid = false;
-    s->vbs_valid = false;
-    s->hier_valid = false;
+    seq_field_replaced(s);
     if (g) GME_HIP_TRY(hipMemcpyAsync(s->prop_g, g, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     const Plane& p = s->level[2];
     int32_t* const work[2] = { s->prop_work[0].get(), s->prop_work[1].get() };
@@ -2482,15 +2462,8 @@ extern "C" int gme_seq_read_prop(gme_seq* s, int first_pair, int count, int32_t*
 {
     GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_read_prop: null sequence");
     GME_ENTER(s->ctx);
-    GME_REQUIRE(s->prop_valid, GME_ERR_STATE, "gme_seq_read_prop before gme_seq_prop");
-    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG,
-                "gme_seq_read_prop: pairs [%d, %d) outside [0, %d)", first_pair, first_pair + count, s->mv_pairs);
-    const size_t per = (size_t)s->mv_h * s->mv_w, m = per * count;
-    hipStream_t st = s->ctx->stream;
-    if (m) {
-        if (mf_out) GME_HIP_TRY(hipMemcpyAsync(mf_out, s->mv + per * 2 * first_pair, m * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, s->prop_cost + per * first_pair, m * sizeof(long long), hipMemcpyDeviceToHost, st));
-        if (source_out) GME_HIP_TRY(hipMemcpyAsync(source_out, s->prop_source + per * first_pair, m, hipMemcpyDeviceToHost, st));
-    }
-    return ctx_finish(s->ctx);
+    const size_t per = (size_t)s->mv_h * s->mv_w;
+    return seq_read(s, "gme_seq_read_prop", s->prop_valid, "gme_seq_prop", "pairs", first_pair, count, s->mv_pairs,
+                    { { mf_out, s->mv.get(), per * 2 * sizeof(int32_t) }, { cost_out, s->prop_cost.get(), per * sizeof(long long) },
+                      { source_out, s->prop_source.get(), per } });
 }

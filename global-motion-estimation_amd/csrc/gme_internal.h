@@ -168,27 +168,29 @@ struct gme_seq {
     DevBuf<double> mosaic_params;        // [N_cap][8]
     DevBuf<uint8_t> mosaic_usable;       // [N_cap]
     DevBuf<unsigned long long> mosaic_counts;    // [2][N_cap] known, moving
+    // Result lifetimes of the block-field passes below, in one place (gme_api.hip): seq_field_replaced ends what was derived from
+    // `mv`, and every writer of `mv` calls it; seq_frames_changed (new frame data, another frame count) calls it too and then ends
+    // the results that keep fields of their own.
     // quarter-pel refinement (bbme_subpel.hip): the refined field and its costs of the last gme_seq_subpel, allocated by
-    // its first call; valid until new frame data or the next block-matching call
+    // its first call; valid until seq_field_replaced
     DevBuf<int32_t> qmv;                 // [P][h][w][2], quarter units
     DevBuf<long long> qcost;             // [P][h][w]
     bool qmv_valid = false;
     // hierarchical search (bbme_hier.hip): fields of the levels above the frame and the costs of every level of the last
-    // gme_seq_hier (its level-2 field is `mv`), allocated by its first call; valid until new frame data or the next
-    // block-matching call
+    // gme_seq_hier (its level-2 field is `mv`), allocated by its first call; valid until seq_field_replaced
     DevBuf<int32_t> hier_mv[2];          // [P][h][w][2] of levels 0 and 1
     DevBuf<long long> hier_cost[3];      // [P][h][w]
     int hier_levels = 0;                 // levels the last gme_seq_hier used
     bool hier_valid = false;
     // variable-block-size tree (bbme_vbs.hip): leaf field, depth map and root costs of the last gme_seq_vbs on `mv`, allocated
-    // by its first call; valid until new frame data or the next block-matching call
+    // by its first call; valid until seq_field_replaced
     DevBuf<int32_t> vbs_leaf;            // [P][h << D][w << D][2]
     DevBuf<uint8_t> vbs_dmap;            // [P][h << D][w << D]
     DevBuf<long long> vbs_cost;          // [P][h][w]
     int vbs_depth = 0;                   // D of the last gme_seq_vbs
     bool vbs_valid = false;
     // bidirectional prediction (bbme_bipred.hip): both fields of gme_seq_bipred's own searches, the modes, the vector pairs and
-    // the costs of its T = N - 2 fd targets, allocated by its first call; valid until new frame data.  No other call reads or
+    // the costs of its T = N - 2 fd targets, allocated by its first call; valid until seq_frames_changed.  No other call reads or
     // writes them, and gme_seq_bipred writes nothing else of the sequence.
     DevBuf<int32_t> bp_f0, bp_f1;        // [T][h][w][2]
     DevBuf<uint8_t> bp_mode;             // [T][h][w]
@@ -198,7 +200,7 @@ struct gme_seq {
     int bp_targets = 0, bp_h = 0, bp_w = 0, bp_fd = 0, bp_bs = 0;
     bool bp_valid = false;
     // global motion compensation (bbme_gmc.hip): the field of gme_seq_gmc's own search, the warps it was given with their usable
-    // flags, the modes and the costs of its P = N - fd pairs, allocated by its first call; valid until new frame data.  No other
+    // flags, the modes and the costs of its P = N - fd pairs, allocated by its first call; valid until seq_frames_changed.  No other
     // call reads or writes them, and gme_seq_gmc writes nothing else of the sequence.
     DevBuf<int32_t> gm_f;                // [P][h][w][2]
     DevBuf<double> gm_h;                 // [P][8]
@@ -210,7 +212,7 @@ struct gme_seq {
     bool gm_valid = false;
     // vector propagation (bbme_prop.hip): the two fields the rounds of gme_seq_prop alternate between (the last one is copied
     // into `mv`), the camera field it was given, and the costs and sources of the last round, allocated by its first call;
-    // valid until new frame data or the next block-matching call
+    // valid until seq_field_replaced
     DevBuf<int32_t> prop_work[2];        // [P][h][w][2]
     DevBuf<int32_t> prop_g;              // [P][h][w][2]
     DevBuf<long long> prop_cost;         // [P][h][w]
@@ -355,6 +357,13 @@ int bbme_check_args(int H, int W, int bs, int sw, int procedure, int pnorm);
 
 // ---- gme_kernels.hip --------------------------------------------------------
 int max_grid_planes();
+// fn(first, n) for every chunk of `count` planes that one launch carries in its grid
+template <class Fn>
+void for_plane_chunks(int count, Fn fn)
+{
+    const int step = max_grid_planes();
+    for (int k = 0; k < count; k += step) fn(k, count - k < step ? count - k : step);
+}
 int launch_repack(gme_ctx* ctx, hipStream_t stream, const uint8_t* src, int count, int H, int W, uint8_t* dst, int pitch,
                   long long dst_stride);
 int launch_pyrdown(gme_ctx* ctx, const Plane& src, const Plane& dst);
