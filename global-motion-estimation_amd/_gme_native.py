@@ -130,6 +130,8 @@ _SIGNATURES = {
     "gme_prop_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_i64p, _c_u8p]),
     "gme_seq_prop": (_i, [_vp, _i, _i, _i, _i, _i, _i, _c_i32p]),
     "gme_seq_read_prop": (_i, [_vp, _i, _i, _c_i32p, _c_i64p, _c_u8p]),
+    "gme_interp_u8": (_i, [_vp, _c_u8p, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
+    "gme_seq_interp": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -493,6 +495,35 @@ class Context:
                                     *[None if a is None else _p(a, _c_i32p) for a in fields], _p(mf, _c_i32p), _p(cost, _c_i64p),
                                     _p(source, _c_u8p)), self.lib)
         return mf, cost, source
+
+    def interp(self, past, next, block_size, search_window=8, pnorm=0, bias=0, truth=None):
+        """The frame halfway between ``past`` and ``next`` (gme_interp_u8, interp.search and interp.interpolate) -> (mv int32[h, w,
+        2], cost int64[h, w], dist int64[h, w], frame uint8[H, W], sse int): ``sse`` is the squared error against ``truth``, the true
+        middle frame, or -1 without one."""
+        frames = [as_frame(a, name) for a, name in ((past, "past"), (next, "next")) + (() if truth is None else ((truth, "truth"),))]
+        if any(a.shape != frames[0].shape for a in frames):
+            raise AssertionError("the frames differ in shape (bbme.py:59)")
+        H, W = frames[0].shape
+        block_size, search_window, pnorm, bias = _interp_args(block_size, search_window, pnorm, bias, H, W)
+        if any(a.strides[0] != frames[0].strides[0] for a in frames):
+            frames = [np.ascontiguousarray(a) for a in frames]
+        h, w = H // block_size, W // block_size
+        mv, cost, dist = np.zeros((h, w, 2), np.int32), np.zeros((h, w), np.int64), np.zeros((h, w), np.int64)
+        made = np.empty((H, W), np.uint8)
+        sse = ctypes.c_int64(0)
+        _check(self.lib.gme_interp_u8(self.handle, _p(frames[0], _c_u8p), _p(frames[1], _c_u8p),
+                                      None if truth is None else _p(frames[2], _c_u8p), H, W, frames[0].strides[0], block_size,
+                                      search_window, pnorm, bias, _p(mv, _c_i32p), _p(cost, _c_i64p), _p(dist, _c_i64p), _p(made, _c_u8p),
+                                      ctypes.byref(sse)), self.lib)
+        return mv, cost, dist, made, sse.value
+
+
+def _interp_args(block_size, search_window, pnorm, bias, H, W):
+    """interp.check_args and interp.check_shape: the definition's argument rules, ValueError before the library is asked."""
+    import interp
+    args = interp.check_args(block_size, search_window, pnorm, bias)
+    interp.check_shape(H, W, args[0])
+    return args
 
 
 def _prop_args(block_size, pnorm, rounds, steps):
@@ -1120,6 +1151,25 @@ class Sequence:
         _check(self.lib.gme_seq_read_prop(self.handle, int(first), int(count), _p(mf, _c_i32p), _p(cost, _c_i64p), _p(source, _c_u8p)),
                self.lib)
         return mf, cost, source
+
+    # ---- motion-compensated frame interpolation (bbme_interp.hip, interp.py)
+    def interp(self, frame_distance, block_size=16, search_window=8, pnorm=0, bias=0, first=0, count=None):
+        """The frames halfway between frame k and frame k + fd for the pairs k = first .. first+count-1 (gme_seq_interp,
+        interp.search and interp.interpolate) -> (mv int32[count, h, w, 2], cost int64[count, h, w], dist int64[count, h, w], frames
+        uint8[count, H, W], sse int64[count]): ``sse`` is the squared error against frame k + fd / 2 for an even fd, -1 for an odd
+        one.  One blocking call, also in split-phase mode, that keeps nothing and leaves everything the sequence holds as it was.
+        Too few frames for the distance or a range outside the pairs is an IndexError."""
+        fd = int(frame_distance)
+        block_size, search_window, pnorm, bias = _interp_args(block_size, search_window, pnorm, bias, self.H, self.W)
+        first = int(first)
+        count = self.N - fd - first if count is None else int(count)
+        n = max(count, 0)                      # a refused range writes nothing
+        grid = (n, self.H // block_size, self.W // block_size)
+        mv, cost, dist = np.zeros(grid + (2,), np.int32), np.zeros(grid, np.int64), np.zeros(grid, np.int64)
+        frames, sse = np.empty((n, self.H, self.W), np.uint8), np.zeros(max(n, 1), np.int64)
+        _check(self.lib.gme_seq_interp(self.handle, fd, block_size, search_window, pnorm, bias, first, count, _p(mv, _c_i32p),
+                                       _p(cost, _c_i64p), _p(dist, _c_i64p), _p(frames, _c_u8p), _p(sse, _c_i64p)), self.lib)
+        return mv, cost, dist, frames, sse[:n]
 
 
 _default = None

@@ -1,4 +1,4 @@
-// What the one-wave-per-block kernels share (bbme_hier.hip, bbme_vbs.hip, bbme_bipred.hip, bbme_gmc.hip): a wave's own LDS slice, filled and read by that wave
+// What the one-wave-per-block kernels share (bbme_hier.hip, bbme_vbs.hip, bbme_bipred.hip, bbme_gmc.hip, bbme_interp.hip): a wave's own LDS slice, filled and read by that wave
 // alone, without a workgroup barrier.
 #pragma once
 #include "gme_internal.h"
@@ -34,6 +34,30 @@ __device__ __forceinline__ void stage_bytes(uint32_t* dst, int rows, int row_dwo
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (x + e >= 0 && x + e < W) v |= (uint32_t)src[x + e] << (8 * e);
+            }
+            if (left < 4) v &= (1u << (8 * left)) - 1u;
+        }
+        dst[t] = v;
+    }
+}
+
+// The clamping sibling of stage_bytes (k_interp): byte (r, c), c < cols, is plane[clamp(y0 + r, 0, H - 1) * pitch +
+// clamp(x0 + c, 0, W - 1)], the border replicated, so every byte of the window is a pixel of the level and nothing read from it
+// has to be dropped.  Bytes at c >= cols are zero.  A dword whose four bytes lie in columns [0, W) is read at once, the others
+// byte by byte.
+__device__ __forceinline__ void stage_bytes_clamped(uint32_t* dst, int rows, int row_dwords, int cols, const uint8_t* plane, int pitch,
+                                                    int H, int W, int y0, int x0, int lane)
+{
+    for (int t = lane; t < rows * row_dwords; t += 64) {
+        const int r = small_div(t, row_dwords), k = t - r * row_dwords;
+        const int x = x0 + 4 * k, left = cols - 4 * k;
+        uint32_t v = 0;
+        if (left > 0) {
+            const uint8_t* src = plane + (long long)min(max(y0 + r, 0), H - 1) * pitch;
+            if (x >= 0 && x + 4 <= W) __builtin_memcpy(&v, src + x, 4);
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v |= (uint32_t)src[min(max(x + e, 0), W - 1)] << (8 * e);
             }
             if (left < 4) v &= (1u << (8 * left)) - 1u;
         }

@@ -747,6 +747,43 @@ extern "C" int gme_prop_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     return ctx_finish(ctx);
 }
 
+// Frame interpolation of one pair (bbme_interp.hip): the two frames, the true middle frame where the caller
+// has one and the interpolated frame as one stack of four planes in the scratch.
+extern "C" int gme_interp_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* next, const uint8_t* truth, int H, int W, int stride,
+                             int block_size, int search_window, int pnorm, int bias, int32_t* mv_out, int64_t* cost_out, int64_t* dist_out,
+                             uint8_t* frame_out, int64_t* sse_out)
+{
+    GME_ENTER(ctx);
+    int rc = oneshot_check("gme_interp_u8", past && next, H, W, stride);
+    if (rc) return rc;
+    rc = interp_check_args("gme_interp_u8", H, W, block_size, search_window, pnorm, bias);
+    if (rc) return rc;
+    const size_t n = (size_t)(H / block_size) * (W / block_size);
+    Plane st = plane_shape(H, W, 4);                           // past, next, truth, interpolated
+    int32_t* d_mv = nullptr;
+    long long* d_cost = nullptr;                               // J, D, then the squared error
+    Carver c;
+    c.take(&st, true); c.take(&d_mv, n * 2); c.take(&d_cost, n * 2 + 1);
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    long long* d_dist = d_cost + n;
+    unsigned long long* d_sse = (unsigned long long*)(d_cost + n * 2);
+    GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_mv - st.ptr, ctx->stream));
+    rc = put_planes(ctx, st, { past, next, truth ? truth : past }, stride);
+    if (rc) return rc;
+    rc = launch_interp(ctx, st.at(0), st.at(1), 0, 1, H, W, st.pitch, block_size, search_window, pnorm, bias, d_mv, d_cost, d_dist);
+    if (rc) return rc;
+    if (mv_out) GME_HIP_TRY(hipMemcpyAsync(mv_out, d_mv, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (dist_out) GME_HIP_TRY(hipMemcpyAsync(dist_out, d_dist, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    int64_t sse = -1;                                          // without a true middle frame there is no error to report
+    rc = oneshot_predict(ctx, st, 3, d_sse, frame_out, truth && sse_out ? &sse : nullptr, [&] {
+        return launch_interp_frame(ctx, st.at(0), st.at(1), st.at(2), 0, 1, H, W, st.pitch, block_size, d_mv, st.at(3), 0, st.pitch, d_sse);
+    });
+    if (sse_out) *sse_out = sse;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -2466,4 +2503,66 @@ extern "C" int gme_seq_read_prop(gme_seq* s, int first_pair, int count, int32_t*
     return seq_read(s, "gme_seq_read_prop", s->prop_valid, "gme_seq_prop", "pairs", first_pair, count, s->mv_pairs,
                     { { mf_out, s->mv.get(), per * 2 * sizeof(int32_t) }, { cost_out, s->prop_cost.get(), per * sizeof(long long) },
                       { source_out, s->prop_source.get(), per } });
+}
+
+// ---------------------------------------------------------------------------
+// Motion-compensated frame interpolation (bbme_interp.hip): one blocking call that computes and returns.
+// It works in buffers of its own that live as long as the call, keeps no result and touches nothing the sequence holds (not the
+// motion field, not the compensated planes): there is nothing of it that a later call could read stale.
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_interp(gme_seq* s, int fd, int bs, int sw, int pnorm, int bias, int first_pair, int count, int32_t* mv_out,
+                              int64_t* cost_out, int64_t* dist_out, uint8_t* frames_out, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_interp: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "gme_seq_interp: frame_distance %d needs at least %d frames", fd, fd + 1);
+    int rc = interp_check_args("gme_seq_interp", s->H, s->W, bs, sw, pnorm, bias);
+    if (rc) return rc;
+    const int P = s->N - fd;
+    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= P, GME_ERR_ARG, "gme_seq_interp: pairs [%d, %d) outside [0, %d)",
+                first_pair, first_pair + count, P);
+    const size_t per = (size_t)(s->H / bs) * (s->W / bs), image = (size_t)s->H * s->W;
+    const bool truth = fd % 2 == 0, frames = frames_out || (sse_out && truth);
+    if (sse_out && !truth)
+        for (int k = 0; k < count; ++k) sse_out[k] = -1;
+    const int step = max_grid_planes(), most = count < step ? count : step;
+    DevBuf<int32_t> mv;
+    DevBuf<long long> cost;                                    // per chunk: J of every block, then D of every block
+    DevBuf<unsigned long long> sse;
+    PlaneBuf made;
+    rc = mv.ensure(per * 2 * most, "interpolation vectors");
+    if (rc) return rc;
+    rc = cost.ensure(per * 2 * most, "interpolation costs");
+    if (rc) return rc;
+    if (frames) {
+        rc = sse.ensure((size_t)most, "interpolation errors");
+        if (rc) return rc;
+        rc = plane_alloc(ctx, &made, most, s->H, s->W);
+        if (rc) return rc;
+    }
+    const Plane& p = s->level[2];
+    for (int k = 0; k < count; k += step) {
+        const int n = count - k < step ? count - k : step, at = first_pair + k;
+        long long* dist = cost.get() + per * n;
+        rc = launch_interp(ctx, p.at(at), p.at(at + fd), p.stride, n, s->H, s->W, p.pitch, bs, sw, pnorm, bias, mv, cost, dist);
+        if (rc) return rc;
+        if (mv_out) GME_HIP_TRY(hipMemcpyAsync(mv_out + per * 2 * k, mv.get(), per * 2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out + per * k, cost.get(), per * n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        if (dist_out) GME_HIP_TRY(hipMemcpyAsync(dist_out + per * k, dist, per * n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        if (frames) {
+            rc = launch_interp_frame(ctx, p.at(at), p.at(at + fd), p.at(truth ? at + fd / 2 : at), p.stride, n, s->H, s->W, p.pitch, bs, mv,
+                                     made.ptr, made.stride, made.pitch, sse);
+            if (rc) return rc;
+            if (frames_out) {
+                rc = read_planes(ctx, made, 0, n, frames_out + image * k);
+                if (rc) return rc;
+            }
+            if (sse_out && truth)
+                GME_HIP_TRY(hipMemcpyAsync(sse_out + k, sse.get(), (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        rc = ctx_finish(ctx);                                  // the next chunk writes the same buffers
+        if (rc) return rc;
+    }
+    return GME_OK;
 }

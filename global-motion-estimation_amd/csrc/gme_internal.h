@@ -501,6 +501,20 @@ int launch_prop(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long
                 int pnorm, int rounds, int steps, const int32_t* f, const int32_t* t, int t_shift, const int32_t* g, int32_t* const work[2],
                 long long* cost, uint8_t* source, int32_t** result);
 
+// ---- bbme_interp.hip: motion-compensated frame interpolation -----------------------------------------
+// the argument rules of interp.py for H x W frames (GME_ERR_ARG)
+int interp_check_args(const char* who, int H, int W, int bs, int sw, int pnorm, int bias);
+// interp.search of `pairs` pairs: pair k reads the planes past + k * plane_stride and next + k * plane_stride; mv
+// [pairs][H / bs][W / bs][2], cost (J) and dist (D) [pairs][H / bs][W / bs] (device).  Names the kernel instance in the context's
+// plan.
+int launch_interp(gme_ctx* ctx, const uint8_t* past, const uint8_t* next, long long plane_stride, int pairs, int H, int W, int pitch,
+                  int bs, int sw, int pnorm, int bias, int32_t* mv, long long* cost, long long* dist);
+// out planes = interp.interpolate of the past and next planes by mv, sse[pairs] (device) = squared error of each against its cur
+// plane (the true middle frame; any plane of the stack where there is none)
+int launch_interp_frame(gme_ctx* ctx, const uint8_t* past, const uint8_t* next, const uint8_t* cur, long long plane_stride, int pairs,
+                        int H, int W, int pitch, int bs, const int32_t* mv, uint8_t* out, long long out_stride, int out_pitch,
+                        unsigned long long* sse);
+
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);
 int launch_synth_frames(gme_ctx* ctx, uint64_t seed, int t0, const uint8_t* canvas, const Plane& dst);

@@ -16,6 +16,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py bipred -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [-r 1] [--rounds 1] [--penalty N] [-o OUTDIR]   # bidirectional prediction of one frame
     python gme_cli.py gmc -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--penalty N] [--estimator projective|affine] [-o OUTDIR]   # global motion compensation of one pair
     python gme_cli.py prop -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 3] [-pn 0] [--rounds 2] [--steps 1] [--no-temporal] [--camera projective|affine|none] [--hier] [-o OUTDIR]   # vector propagation search of one pair
+    python gme_cli.py interp -p <video|frame dir> -fi 2 [-fd 2] [-bs 16] [-sw 8] [-pn 0] [--bias N] [-o OUTDIR] [--upconvert]   # the frame between two frames; frame-rate doubling
     python gme_cli.py info                                                          # searches, norms, models, device
 """
 import argparse
@@ -159,6 +160,19 @@ def _parser():
                     help="the camera candidate: the direct projective refinement, the indirect affine estimate written as a warp, or none")
     pp.add_argument("--hier", action="store_true", help="take the prior field from the hierarchical search (three levels, radius 1)")
     pp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for prop.json")
+    ip = sub.add_parser("interp", help="motion-compensated frame interpolation: the frame halfway between two frames by a bilateral block search; frame-rate doubling of a clip (interp.py, DESIGN.md 7m)")
+    ip.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    ip.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the later frame of the pair")
+    ip.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=2,
+                    help="the earlier frame is fi - fd; for an even distance frame fi - fd / 2 is the truth the result is compared with")
+    ip.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="4 .. 64")
+    ip.add_argument("-sw", "--search-window", dest="search_window", type=int, default=8, help="0 .. 8, per half step: content may move by twice as much between the two frames")
+    ip.add_argument("-pn", "--pnorm-distance", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    ip.add_argument("--bias", type=int, default=None,
+                    help="cost of one unit of |vx| + |vy| (0 .. 2^16); default: bs^2 / 16 for MAE and bs^2 for MSE, a convention of this "
+                         "tool and not a tuned value")
+    ip.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for interp.json, interp.png and upconverted/%%04d.png")
+    ip.add_argument("--upconvert", action="store_true", help="also double the frame rate of the whole clip into OUTDIR/upconverted/%%04d.png")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -322,6 +336,47 @@ def _bipred(args):
         os.makedirs(args.outdir, exist_ok=True)
         with open(os.path.join(args.outdir, "bipred.json"), "w") as f:
             json.dump(record, f, indent=1)
+    return res
+
+
+def _interp(args):
+    """The bias, the median vector and the share of non-zero vectors of one pair and, for an even frame distance, the PSNR of the
+    interpolated frame and of the plain average against the true middle frame; the same record into OUTDIR/interp.json, the
+    frame into OUTDIR/interp.png and, with --upconvert, the clip at twice the frame rate into OUTDIR/upconverted/%04d.png."""
+    import json
+    import os
+    import numpy as np
+    import interp
+    import utils
+    frames = utils.get_video_frames(args.path)
+    if args.fd < 1 or not args.fd <= args.fi < len(frames):
+        raise IndexError("frames %d and %d of %d" % (args.fi - args.fd, args.fi, len(frames)))
+    truth = frames[args.fi - args.fd // 2] if args.fd % 2 == 0 else None
+    res = interp.report(frames[args.fi - args.fd], frames[args.fi], truth, args.block_size, args.search_window, args.pnorm, args.bias)
+    record = {"options": {"path": args.path, "frame_index": args.fi, "frame_distance": args.fd, "block_size": args.block_size,
+                          "search_window": args.search_window, "pnorm": args.pnorm % 2, "bias": res["bias"]},
+              "shape": list(res["mv"].shape[:2])}
+    record.update({k: res[k] for k in ("median_vector", "nonzero_share", "sse_interp", "sse_average", "psnr_interp", "psnr_average") if k in res})
+    print("the frame between {} and {}: {} x {} blocks of {}, window {}, bias {}".format(
+        args.fi - args.fd, args.fi, record["shape"][0], record["shape"][1], args.block_size, args.search_window, res["bias"]))
+    print("median vector: ({:g}, {:g})".format(*record["median_vector"]))
+    print("non-zero vectors: {:.2f} %".format(100.0 * record["nonzero_share"]))
+    if truth is not None:
+        print("psnr interpolation: {:.4f} dB".format(record["psnr_interp"]))
+        print("psnr plain average: {:.4f} dB".format(record["psnr_average"]))
+    if args.outdir:
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "interp.json"), "w") as f:
+            json.dump(record, f, indent=1)
+        utils.write_image(os.path.join(args.outdir, "interp.png"), res["frame"])
+        if args.upconvert:
+            d = os.path.join(args.outdir, "upconverted")
+            os.makedirs(d, exist_ok=True)
+            clip = interp.upconvert(np.stack([np.asarray(f) for f in frames]), args.block_size, args.search_window, args.pnorm, args.bias)
+            for k, f in enumerate(clip):
+                utils.write_image(os.path.join(d, "%04d.png" % k), f)
+            res["upconverted"] = clip
+            print("up-converted: {} frames into {}".format(len(clip), d))
     return res
 
 
@@ -527,6 +582,8 @@ def main(argv=None):
         return _gmc(args)
     if args.command == "prop":
         return _prop(args)
+    if args.command == "interp":
+        return _interp(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")
@@ -538,6 +595,7 @@ def main(argv=None):
     print("bidirectional prediction (gme_cli.py bipred): -bs 4 .. 64, -r 0 .. 2, --rounds 0 .. 2, --penalty 0 .. 2^30; per block the past frame, the next one or their average   (bipred.py)")
     print("global motion compensation (gme_cli.py gmc): -bs 4 .. 64, --penalty 0 .. 2^30, --estimator projective | affine; per block the camera warp or the block's own vector   (gmc.py)")
     print("vector propagation search (gme_cli.py prop): -bs 4 .. 64, --rounds 1 .. 4, --steps 0 .. 4, --camera projective | affine | none; own, neighbour, temporal, camera and zero vectors on a prior field, refined by one pixel   (propagate.py)")
+    print("frame interpolation (gme_cli.py interp): -bs 4 .. 64, -sw 0 .. 8, --bias 0 .. 2^16, --upconvert; the frame halfway between two frames by a bilateral search, borders replicated   (interp.py)")
     try:
         print("device: " + _gme_native.default_context().info()["name"])
     except Exception as e:      # noqa: BLE001 -- no GPU: say so, the listing above is still useful

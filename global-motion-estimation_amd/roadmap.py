@@ -71,6 +71,12 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    above, or of any float64[8] warp) and zero, the cheapest refined by one pixel per pass, in rounds that each read only the field
    of the round before.  A block's whole decision runs in one wave of one kernel (k_prop, csrc/bbme_prop.hip; host definition
    propagate.py); ``Sequence.prop`` leaves the result as the sequence's motion field.
+   **Frame interpolation.**  ``interp.frame`` makes the frame halfway between two frames, where there is no target block to match
+   against: a block takes the vector v for which the past frame at origin - v and the next frame at origin + v differ least
+   (a bilateral search within +-8 with a bias on |v|, the border replicated) and is their rounded average;
+   ``interp.upconvert`` doubles the frame rate of a clip.  A block's whole search runs in one wave of one kernel (k_interp,
+   csrc/bbme_interp.hip; host definition interp.py); ``Sequence.interp`` computes and returns in one call and
+   keeps nothing.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

@@ -541,6 +541,34 @@ GME_API int gme_seq_prop(gme_seq *seq, int frame_distance, int block_size, int p
 GME_API int gme_seq_read_prop(gme_seq *seq, int first_pair, int count, int32_t *mf_out, int64_t *cost_out, uint8_t *source_out);
 
 /* ---------------------------------------------------------------------------
+ * Motion-compensated frame interpolation (csrc/bbme_interp.hip; host definition: interp.py): the frame
+ * halfway between `past` and `next`.  Block (i, j) of the new frame takes the vector v = (vx, vy) within +-search_window that
+ * minimises J(v) = D(v) + bias (|vx| + |vy|), D the sum of |d| (pnorm 0) or d^2 (pnorm 1) between `past` at origin - v and
+ * `next` at origin + v, coordinates clamped to the frame (border replication); the centre first, then column offset outer, both
+ * ascending, only a strictly smaller J replaces the incumbent.  A pixel of the new frame is the rounded average of the two
+ * displaced pixels; beyond the last whole block v = 0.  All integer, byte-equal to interp.search and interp.interpolate.
+ * block_size 4 .. 64 (H >= block_size and W >= block_size), search_window 0 .. 8, pnorm 0 or 1, bias 0 .. 2^16; anything else is
+ * GME_ERR_ARG.
+ * gme_interp_u8: one pair on host buffers -> mv_out int32[H/B][W/B][2], cost_out (J) and dist_out (D of the winner)
+ *   int64[H/B][W/B], frame_out uint8[H][W] (tight), *sse_out = exact squared error of the interpolated frame against `truth`,
+ *   the true middle frame, or -1 where truth is NULL.  Any output may be NULL.
+ * gme_seq_interp: the pairs (k, k + frame_distance), k = first_pair .. first_pair + count - 1, of the P = N - frame_distance
+ *   pairs of the sequence (GME_ERR_ARG unless 1 <= frame_distance < N and the range lies in [0, P)) -> mv_out
+ *   int32[count][H/B][W/B][2], cost_out and dist_out int64[count][H/B][W/B], frames_out uint8[count][H][W] (tight), sse_out[count]
+ *   = exact squared error of each interpolated frame against frame k + frame_distance / 2 for an even frame_distance, -1 for an
+ *   odd one.  Any output may be NULL.  It computes and returns in one call, in buffers of its own that live as long as the
+ *   call: it keeps no result and leaves everything the sequence holds as it was (the motion field and what was derived from it,
+ *   the bidirectional and global-motion-compensation results, the compensated planes), so it is no part of the result lifetimes
+ *   above.
+ * Blocking calls, also in split-phase mode.  gme_last_bbme_info names the kernel instance: k_interp<16>, k_interp<32>, or
+ * k_interp<0> (block size at run time). */
+GME_API int gme_interp_u8(gme_ctx *ctx, const uint8_t *past, const uint8_t *next, const uint8_t *truth /* may be NULL */, int H, int W,
+                          int stride, int block_size, int search_window, int pnorm, int bias, int32_t *mv_out, int64_t *cost_out,
+                          int64_t *dist_out, uint8_t *frame_out, int64_t *sse_out);
+GME_API int gme_seq_interp(gme_seq *seq, int frame_distance, int block_size, int search_window, int pnorm, int bias, int first_pair,
+                           int count, int32_t *mv_out, int64_t *cost_out, int64_t *dist_out, uint8_t *frames_out, int64_t *sse_out);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
  * the context's stream.  The reference has no distributed code; SURVEY.md §8(e) defines this split.
