@@ -22,23 +22,19 @@
 
 namespace {
 
-constexpr int BP_THREADS = 256, BP_WAVES = BP_THREADS / 64;
 constexpr int BP_MIN_BS = 4, BP_MAX_BS = 64, BP_MAX_R = 2, BP_MAX_ROUNDS = 2, BP_MAX_PENALTY = 1 << 30;
-constexpr int BP_P = 8, BP_SLOTS = 64 / BP_P;                   // lanes to a candidate, candidates scored at once
+constexpr int BP_P = 8;                                         // lanes to a candidate, whatever the radius: 64 / BP_P scored at once
 constexpr int BP_MAX_CAND = (2 * BP_MAX_R + 1) * (2 * BP_MAX_R + 1);
 constexpr long long BP_MAX_COST = (long long)BP_MAX_BS * BP_MAX_BS * 65025ll;
-constexpr uint32_t BP_NONE = 0xFFFFFFFFu;                       // no cost: above every cost there is
-static_assert(BP_MAX_COST < (long long)BP_NONE, "a cost in 32 bits, below the sentinel");
+static_assert(BP_MAX_COST < (long long)NO_COST, "a cost in 32 bits, below the sentinel");
 // the order of a candidate needs 5 bits beside a cost of 29: no 32-bit key, hence the two reductions of a pass
 static_assert(BP_MAX_CAND + 1 <= (1 << 5) && (BP_MAX_COST << 5) >= (1ll << 32), "cost and order in one 32-bit key");
 // every sum of a decision in 32 bits
 static_assert((long long)BP_MAX_PENALTY + BP_MAX_COST < (1ll << 31), "31-bit decisions");
 constexpr int BP_MAX_WINDOW = BP_MAX_BS + 2 * BP_MAX_ROUNDS * BP_MAX_R;
-constexpr int BP_MAX_WINDOW_DWORDS = (BP_MAX_WINDOW + 3) / 4 + 1;
-static_assert(BP_MAX_WINDOW * BP_MAX_WINDOW_DWORDS < SMALL_DIV_T && BP_MAX_WINDOW_DWORDS <= SMALL_DIV_D && 2 * BP_MAX_R + 1 <= SMALL_DIV_D,
-              "range of small_div");
+static_assert(small_div_covers(BP_MAX_WINDOW, window_row_dwords(BP_MAX_WINDOW), 2 * BP_MAX_R + 1), "range of small_div");
 // a workgroup's LDS without an opt-in: the block and both windows of four waves
-static_assert(BP_WAVES * (BP_MAX_BS * (BP_MAX_BS / 4) * 4 + 2 * BP_MAX_WINDOW * BP_MAX_WINDOW_DWORDS * 4 + 48) <= 64 * 1024, "LDS of a workgroup");
+static_assert(BLK_WAVES * (block_bytes(BP_MAX_BS) + 2 * window_bytes(BP_MAX_WINDOW)) <= 64 * 1024, "LDS of a workgroup");
 
 struct BipredArgs {
     const uint8_t* past;          // first plane of each role; target k reads the planes k * stride bytes on
@@ -60,16 +56,16 @@ struct BipredArgs {
 
 constexpr uint32_t BP_ROUND_UP = 0x01010101u;                   // v_lerp_u8's third operand: (p + n + 1) >> 1 in every byte
 
-// grid (ceil(wb / BP_WAVES), hb, targets)
 template <int BS>
-__global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
+__global__ void __launch_bounds__(BLK_THREADS) k_bipred(const BipredArgs A)
 {
     extern __shared__ __align__(16) uint8_t lds[];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int bj = blockIdx.x * BP_WAVES + wave, bi = blockIdx.y, target = blockIdx.z;
-    if (bj >= A.wb) return;                                      // the whole wave: nothing below synchronises across waves
+    const WaveBlock w = wave_block(A.wb);
+    if (w.none) return;
+    const int wave = w.wave, lane = w.lane, bj = w.bj, bi = w.bi, target = w.z;
     const int B = BS ? BS : A.bs;
-    const int r = A.radius, n = 2 * r + 1, ncand = n * n, pnorm = A.pnorm;
+    const int r = A.radius, pnorm = A.pnorm;
+    const Square sq(r);
     const int m = A.rounds * r;                                  // how far a refined vector can lie from its input
     const long long blk = ((long long)target * A.hb + bi) * A.wb + bj;
     const int ax = __builtin_amdgcn_readfirstlane(A.f0[blk * 2]), ay = __builtin_amdgcn_readfirstlane(A.f0[blk * 2 + 1]);
@@ -95,9 +91,8 @@ __global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
     uint32_t* anc = (uint32_t*)(lds + (size_t)wave * A.slice_bytes);
     uint32_t* pw = (uint32_t*)(lds + (size_t)wave * A.slice_bytes + A.anchor_bytes);
     uint32_t* nw = (uint32_t*)(lds + (size_t)wave * A.slice_bytes + A.anchor_bytes + A.window_bytes);
-    // window rows of one dword more than their bytes need: v_alignbyte reads the dword behind the last one it uses
-    const int nd = (B + 3) >> 2, ws = B + 2 * m, wd = ((ws + 3) >> 2) + 1;
-    const uint32_t tail = (B & 3) ? (1u << (8 * (B & 3))) - 1u : 0xFFFFFFFFu;
+    const int nd = row_dwords(B), ws = B + 2 * m, wd = window_row_dwords(ws);
+    const uint32_t tail = tail_mask(B);
     constexpr bool TAIL = !BS || (BS & 3);                       // the last dword of a row may hold bytes beyond the block
     const long long plane = (long long)target * A.stride;
     stage_bytes(anc, B, nd, B, A.mid + plane, A.pitch, A.H, A.W, y0, x0, lane);
@@ -106,7 +101,7 @@ __global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
     wave_lds_fence();
 
     // the starting costs: the block's (row, dword) pairs over the lanes, every dword read once for all three
-    uint32_t c0 = BP_NONE, c1 = BP_NONE, cb = BP_NONE;
+    uint32_t c0 = NO_COST, c1 = NO_COST, cb = NO_COST;
     {
         RowScore s0, s1, sb;
         for (int t = lane; t < B * nd; t += 64) {
@@ -114,8 +109,8 @@ __global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
             const uint32_t a = anc[t];                           // bytes at and past column B are zero
             const int at = (m + y) * wd + (m >> 2) + k;
             uint32_t p = 0, q = 0;
-            if (in0) p = __builtin_amdgcn_alignbyte(pw[at + 1], pw[at], (uint32_t)m & 3u);
-            if (in1) q = __builtin_amdgcn_alignbyte(nw[at + 1], nw[at], (uint32_t)m & 3u);
+            if (in0) p = window_dword(pw, at, (uint32_t)m & 3u);
+            if (in1) q = window_dword(nw, at, (uint32_t)m & 3u);
             if (TAIL) { if (k == nd - 1) { p &= tail; q &= tail; } }
             if (in0) s0.add(a, p, pnorm);
             if (in1) s1.add(a, q, pnorm);
@@ -129,7 +124,7 @@ __global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
     // the refined vectors minus their inputs, wave-uniform: |.| <= (passes of that side so far) * r <= m
     int r0x = 0, r0y = 0, r1x = 0, r1y = 0;
     if (both && r > 0) {
-        const int slot = lane >> 3, q = lane & (BP_P - 1);
+        const LaneSplit ls(BP_P, lane);
 #pragma unroll 1
         for (int pass = 0; pass < 2 * A.rounds; ++pass) {
             const bool side = pass & 1;                          // 0: the past vector moves, 1: the next vector
@@ -140,50 +135,48 @@ __global__ void __launch_bounds__(BP_THREADS) k_bipred(const BipredArgs A)
             const int ox0 = side ? nx : px, oy0 = side ? ny : py;                // the moving side's input block in the frame
             const uint32_t hsh = (uint32_t)hx & 3u;
             uint32_t bestc = cb, besto = 0;                      // the incumbent: order 0
-            for (int i0 = 0; i0 < ncand; i0 += BP_SLOTS) {
-                const int c = i0 + slot;
-                const int ci = c < ncand ? c : 0;                // lanes beyond the list score candidate 0 and drop it
-                const int ox = small_div(ci, n), oy = ci - ox * n;               // the candidate's offset + r (column, row)
-                const bool listed = c < ncand && !(ox == r && oy == r);
+            for (int i0 = 0; i0 < sq.ncand; i0 += ls.slots) {
+                const int c = i0 + ls.slot;
+                int ox, oy;                                      // the candidate's offset + r (column, row); lanes beyond
+                sq.at(c < sq.ncand ? c : 0, &ox, &oy);           // the list score candidate 0 and drop it
+                const bool listed = c < sq.ncand && !sq.centre(ox, oy);          // the centre is the incumbent
                 const int dx = cx + ox - r, dy = cy + oy - r;    // within [-m, m] of the input vector
                 const int gx = ox0 + dx, gy = oy0 + dy;          // the candidate's block in the frame
                 const bool ok = listed && gx >= 0 && gy >= 0 && gx + B <= A.W && gy + B <= A.H;
                 const int wx = m + dx, wy = m + dy;              // ... and in the window: 0 <= wx, wx + B <= ws
                 const uint32_t wsh = (uint32_t)wx & 3u;
                 RowScore s;
-                for (int y = q; y < B; y += BP_P) {
+                for (int y = ls.q; y < B; y += BP_P) {
                     const uint32_t* arow = anc + y * nd;
                     const uint32_t* mrow = mw + (wy + y) * wd + (wx >> 2);
                     const uint32_t* hrow = hw + (hy + y) * wd + (hx >> 2);
 #pragma unroll 4
                     for (int k = 0; k < nd; ++k) {
-                        const uint32_t u = __builtin_amdgcn_alignbyte(mrow[k + 1], mrow[k], wsh);
-                        const uint32_t h = __builtin_amdgcn_alignbyte(hrow[k + 1], hrow[k], hsh);
+                        const uint32_t u = window_dword(mrow, k, wsh);
+                        const uint32_t h = window_dword(hrow, k, hsh);
                         uint32_t v = __builtin_amdgcn_lerp(u, h, BP_ROUND_UP);
                         if (TAIL) { if (k == nd - 1) v &= tail; }
                         s.add(arow[k], v, pnorm);
                     }
                 }
-                uint32_t part = s.value(pnorm);
-                for (int w = 1; w < BP_P; w <<= 1) part += (uint32_t)__shfl_xor((int)part, w, 64);
+                const uint32_t cost = ls.sum(s.value(pnorm));
                 // a lane meets its candidates in ascending order, so "strictly smaller" keeps the first of equal costs
-                if (ok && part < bestc) { bestc = part; besto = (uint32_t)c + 1u; }
+                if (ok && cost < bestc) { bestc = cost; besto = sq.order_beside_centre(c); }
             }
-            const uint32_t least = wave_min_u32(bestc);
-            const uint32_t order = wave_min_u32(bestc == least ? besto : BP_NONE);
-            if (order != 0u) {
-                const int c = (int)order - 1;
-                const int ox = small_div(c, n), oy = c - ox * n;
-                if (side) { r1x += ox - r; r1y += oy - r; }
-                else { r0x += ox - r; r0y += oy - r; }
-                cb = least;
+            const Least win = wave_least(bestc, besto);
+            if (win.order != 0u) {
+                int ox, oy;
+                sq.offset(win.order, &ox, &oy);
+                if (side) { r1x += ox; r1y += oy; }
+                else { r0x += ox; r0y += oy; }
+                cb = win.cost;
             }
         }
     }
 
     if (lane == 0) {
         // (mode 0, c0), (mode 1, c1), (mode 2, cb + penalty) in that order, only a strictly smaller value replaces the best
-        uint32_t best = BP_NONE;
+        uint32_t best = NO_COST;
         int mode = 3;
         if (in0) { mode = 0; best = c0; }
         if (in1 && (mode == 3 || c1 < best)) { mode = 1; best = c1; }
@@ -240,13 +233,6 @@ __global__ void __launch_bounds__(PRED_THREADS) k_predict_bipred(const uint8_t* 
     predict_rows(px, mid + plane, H, W, pitch, out + (long long)f * out_stride, out_pitch, sse + f);
 }
 
-template <int BS>
-void bipred_launch(hipStream_t stream, const BipredArgs& a, int targets)
-{
-    hipLaunchKernelGGL((k_bipred<BS>), dim3((unsigned)((a.wb + BP_WAVES - 1) / BP_WAVES), (unsigned)a.hb, (unsigned)targets),
-                       dim3(BP_THREADS), (size_t)BP_WAVES * a.slice_bytes, stream, a);
-}
-
 }  // namespace
 
 // the argument rules of bipred.py
@@ -255,7 +241,7 @@ int bipred_check_args(const char* who, int bs, int radius, int rounds, int pnorm
     GME_REQUIRE(bs >= BP_MIN_BS && bs <= BP_MAX_BS, GME_ERR_ARG, "%s: block_size %d (%d .. %d)", who, bs, BP_MIN_BS, BP_MAX_BS);
     GME_REQUIRE(radius >= 0 && radius <= BP_MAX_R, GME_ERR_ARG, "%s: radius %d (0 .. %d)", who, radius, BP_MAX_R);
     GME_REQUIRE(rounds >= 0 && rounds <= BP_MAX_ROUNDS, GME_ERR_ARG, "%s: rounds %d (0 .. %d)", who, rounds, BP_MAX_ROUNDS);
-    GME_REQUIRE(pnorm == 0 || pnorm == 1, GME_ERR_ARG, "%s: pnorm_distance %d out of range (bbme.py:60)", who, pnorm);
+    if (int rc = require_pnorm(who, pnorm)) return rc;
     GME_REQUIRE(penalty >= 0 && penalty <= BP_MAX_PENALTY, GME_ERR_ARG, "%s: penalty %d (0 .. 2^30)", who, penalty);
     return GME_OK;
 }
@@ -270,32 +256,26 @@ int launch_bipred(gme_ctx* ctx, const uint8_t* past, const uint8_t* mid, const u
     int rc = bipred_check_args("bidirectional prediction", bs, radius, rounds, pnorm, penalty);
     if (rc) return rc;
     const int hb = H / bs, wb = W / bs;
-    ctx->plan[0] = 0; ctx->plan_patches = 0;
     const bool compiled = bs == 16 || bs == 32;
-    if (compiled) plan_note(ctx, 0, "k_bipred<%d> r %d rounds %d penalty %d, %d x %d blocks, one wave each", bs, radius, rounds, penalty, hb, wb);
-    else plan_note(ctx, 0, "k_bipred<0> bs %d r %d rounds %d penalty %d, %d x %d blocks, one wave each", bs, radius, rounds, penalty, hb, wb);
-    if (targets == 0 || hb == 0 || wb == 0) return GME_OK;
-    GME_REQUIRE(hb <= 65535, GME_ERR_ARG, "%d block rows", hb);
     BipredArgs a;
     a.stride = plane_stride; a.H = H; a.W = W; a.pitch = pitch;
     a.hb = hb; a.wb = wb; a.bs = bs; a.radius = radius; a.rounds = rounds; a.pnorm = pnorm; a.penalty = (uint32_t)penalty;
-    const int side = bs + 2 * rounds * radius;
-    a.anchor_bytes = (bs * ((bs + 3) / 4) * 4 + 15) & ~15;
-    a.window_bytes = (side * ((side + 3) / 4 + 1) * 4 + 15) & ~15;
+    a.anchor_bytes = block_bytes(bs);
+    a.window_bytes = window_bytes(bs + 2 * rounds * radius);
     a.slice_bytes = a.anchor_bytes + 2 * a.window_bytes;
     const long long per = (long long)hb * wb;
-    for_plane_chunks(targets, [&](int k, int n) {
+    auto note = [&] {
+        if (compiled) plan_note(ctx, 0, "k_bipred<%d> r %d rounds %d penalty %d, %d x %d blocks, one wave each", bs, radius, rounds, penalty, hb, wb);
+        else plan_note(ctx, 0, "k_bipred<0> bs %d r %d rounds %d penalty %d, %d x %d blocks, one wave each", bs, radius, rounds, penalty, hb, wb);
+    };
+    return launch_wave_blocks(ctx, targets, hb, wb, a.slice_bytes, a, note, [&](int k) {
         const long long off = (long long)k * plane_stride;
         a.past = past + off; a.mid = mid + off; a.next = next + off;
         a.f0 = f0 + per * k * 2; a.f1 = f1 + per * k * 2;
         a.mode = mode + per * k; a.v0 = v0 + per * k * 2; a.v1 = v1 + per * k * 2;
         a.cost = cost + per * k; a.costs = costs + per * k * 3;
-        if (!compiled) bipred_launch<0>(ctx->stream, a, n);
-        else if (bs == 16) bipred_launch<16>(ctx->stream, a, n);
-        else bipred_launch<32>(ctx->stream, a, n);
+        return !compiled ? k_bipred<0> : bs == 16 ? k_bipred<16> : k_bipred<32>;
     });
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
 }
 
 // out planes = bipred.predict of the past and next planes by mode, v0 and v1 of [targets][H / bs][W / bs], sse[targets] (device,

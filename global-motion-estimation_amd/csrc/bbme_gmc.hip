@@ -24,17 +24,14 @@
 
 namespace {
 
-constexpr int GM_THREADS = 256, GM_WAVES = GM_THREADS / 64;
 constexpr int GM_MIN_BS = 4, GM_MAX_BS = 64, GM_MAX_PENALTY = 1 << 30;
 constexpr long long GM_MAX_COST = (long long)GM_MAX_BS * GM_MAX_BS * 65025ll;
-constexpr uint32_t GM_NONE = 0xFFFFFFFFu;                       // no cost: above every cost there is
-static_assert(GM_MAX_COST < (long long)GM_NONE, "a cost in 32 bits, below the sentinel");
+static_assert(GM_MAX_COST < (long long)NO_COST, "a cost in 32 bits, below the sentinel");
 static_assert((long long)GM_MAX_PENALTY + GM_MAX_COST < (1ll << 31), "31-bit decisions");
-constexpr int GM_MAX_DWORDS = (GM_MAX_BS + 3) / 4;
-static_assert(GM_MAX_BS * GM_MAX_DWORDS < SMALL_DIV_T && GM_MAX_DWORDS <= SMALL_DIV_D, "range of small_div");
-static_assert(GM_WAVES * 2 * GM_MAX_BS * GM_MAX_DWORDS * 4 <= 64 * 1024, "LDS of a workgroup");
+static_assert(small_div_covers(GM_MAX_BS, row_dwords(GM_MAX_BS)), "range of small_div");
+static_assert(BLK_WAVES * 2 * block_bytes(GM_MAX_BS) <= 64 * 1024, "LDS of a workgroup");
 // the squared error of a workgroup of k_predict_gmc in 32 bits
-static_assert((long long)GM_WAVES * GM_MAX_COST < (1ll << 32), "a workgroup's squared error");
+static_assert((long long)BLK_WAVES * GM_MAX_COST < (1ll << 32), "a workgroup's squared error");
 
 struct GmcArgs {
     const uint8_t* ref;           // first plane of each role; pair k reads the planes k * stride bytes on
@@ -69,14 +66,13 @@ __device__ __forceinline__ uint32_t global_px(const uint8_t* p, int pitch, const
     return (uint32_t)(int)floor(__dadd_rn(sample(p, pitch, taps_at(s, H, W)), 0.5));
 }
 
-// grid (ceil(wb / GM_WAVES), hb, pairs)
 template <int BS>
-__global__ void __launch_bounds__(GM_THREADS) k_gmc(const GmcArgs A)
+__global__ void __launch_bounds__(BLK_THREADS) k_gmc(const GmcArgs A)
 {
     extern __shared__ __align__(16) uint8_t lds[];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int bj = blockIdx.x * GM_WAVES + wave, bi = blockIdx.y, pair = blockIdx.z;
-    if (bj >= A.wb) return;                                      // the whole wave: nothing below synchronises across waves
+    const WaveBlock w = wave_block(A.wb);
+    if (w.none) return;
+    const int wave = w.wave, lane = w.lane, bj = w.bj, bi = w.bi, pair = w.z;
     const int B = BS ? BS : A.bs;
     const int pnorm = A.pnorm;
     const long long blk = ((long long)pair * A.hb + bi) * A.wb + bj;
@@ -95,7 +91,7 @@ __global__ void __launch_bounds__(GM_THREADS) k_gmc(const GmcArgs A)
     }
     uint32_t* anc = (uint32_t*)(lds + (size_t)wave * 2 * A.block_bytes);
     uint32_t* loc = (uint32_t*)(lds + (size_t)wave * 2 * A.block_bytes + A.block_bytes);
-    const int nd = (B + 3) >> 2;
+    const int nd = row_dwords(B);
     const uint8_t* ref = A.ref + (long long)pair * A.stride;
     // both blocks start at their first byte and bytes at and past column B are zero: dword t of one lies over dword t of the other
     stage_bytes(anc, B, nd, B, A.cur + (long long)pair * A.stride, A.pitch, A.H, A.W, y0, x0, lane);
@@ -127,12 +123,12 @@ __global__ void __launch_bounds__(GM_THREADS) k_gmc(const GmcArgs A)
         }
     }
     const bool global = usable && __builtin_amdgcn_ballot_w64(!ok) == 0;
-    uint32_t cg = GM_NONE, cl = GM_NONE;
+    uint32_t cg = NO_COST, cl = NO_COST;
     if (global) cg = wave_sum_u32(sg.value(pnorm));
     if (local) cl = wave_sum_u32(sl.value(pnorm));
     if (lane == 0) {
         // (mode 0, cg), (mode 1, cl + penalty) in that order, only a strictly smaller value replaces the best
-        uint32_t best = GM_NONE;
+        uint32_t best = NO_COST;
         int mode = 2;
         if (global) { mode = 0; best = cg; }
         if (local && (mode == 2 || cl + A.penalty < best)) { mode = 1; best = cl + A.penalty; }
@@ -158,23 +154,23 @@ __device__ __forceinline__ uint32_t load_px(const uint8_t* row, int x, int n, in
     return v;
 }
 
-// grid (ceil(cw / GM_WAVES), ch, pairs) with ch = ceil(H / bs), cw = ceil(W / bs) cells of bs x bs pixels, clipped to the frame.
+// grid (ceil(cw / BLK_WAVES), ch, pairs) with ch = ceil(H / bs), cw = ceil(W / bs) cells of bs x bs pixels, clipped to the frame.
 // A cell that is a whole block (row < hb, column < wb) is, in mode 0, its global predictor pixels where the pair's warp is usable
 // and the sample point lies in the frame and, in mode 1, the block of `ref` at the vector where that lies in the frame; every
 // other pixel (mode 2, the cells beyond the last whole block, and what a mode cannot supply, which the modes of k_gmc never ask
 // for) is the co-located pixel of `ref`.  Pixels at or past W are not written: they are the plane's padding.
-__global__ void __launch_bounds__(GM_THREADS) k_predict_gmc(const uint8_t* ref, const uint8_t* cur, long long plane_stride, int H, int W,
+__global__ void __launch_bounds__(BLK_THREADS) k_predict_gmc(const uint8_t* ref, const uint8_t* cur, long long plane_stride, int H, int W,
                                                             int pitch, int bs, int hb, int wb, int cw, const double* hs,
                                                             const uint8_t* usable, const uint8_t* mode, const int32_t* f, uint8_t* out,
                                                             long long out_stride, int out_pitch, unsigned long long* sse)
 {
-    __shared__ uint32_t part[GM_WAVES];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int cj = blockIdx.x * GM_WAVES + wave, ci = blockIdx.y, pair = blockIdx.z;
+    __shared__ uint32_t part[BLK_WAVES];
+    const WaveBlock w = wave_block(cw);                          // of cells: a wave without one stays for the barrier below
+    const int wave = w.wave, lane = w.lane, cj = w.bj, ci = w.bi, pair = w.z;
     uint32_t err = 0;
-    if (cj < cw) {                                               // wave-uniform
+    if (!w.none) {                                               // wave-uniform
         const int x0 = cj * bs, y0 = ci * bs;
-        const int cols = min(bs, W - x0), rows = min(bs, H - y0), nd = (cols + 3) >> 2;
+        const int cols = min(bs, W - x0), rows = min(bs, H - y0), nd = row_dwords(cols);
         const uint8_t* p = ref + (long long)pair * plane_stride;
         const uint8_t* c = cur + (long long)pair * plane_stride;
         uint8_t* o = out + (long long)pair * out_stride;
@@ -230,16 +226,9 @@ __global__ void __launch_bounds__(GM_THREADS) k_predict_gmc(const uint8_t* ref, 
     if (threadIdx.x == 0) {                                      // one error word per workgroup
         uint32_t s = 0;
 #pragma unroll
-        for (int w = 0; w < GM_WAVES; ++w) s += part[w];
+        for (int k = 0; k < BLK_WAVES; ++k) s += part[k];
         if (s) atomicAdd(&sse[pair], (unsigned long long)s);
     }
-}
-
-template <int BS>
-void gmc_launch(hipStream_t stream, const GmcArgs& a, int pairs)
-{
-    hipLaunchKernelGGL((k_gmc<BS>), dim3((unsigned)((a.wb + GM_WAVES - 1) / GM_WAVES), (unsigned)a.hb, (unsigned)pairs), dim3(GM_THREADS),
-                       (size_t)GM_WAVES * 2 * a.block_bytes, stream, a);
 }
 
 }  // namespace
@@ -248,7 +237,7 @@ void gmc_launch(hipStream_t stream, const GmcArgs& a, int pairs)
 int gmc_check_args(const char* who, int bs, int pnorm, int penalty)
 {
     GME_REQUIRE(bs >= GM_MIN_BS && bs <= GM_MAX_BS, GME_ERR_ARG, "%s: block_size %d (%d .. %d)", who, bs, GM_MIN_BS, GM_MAX_BS);
-    GME_REQUIRE(pnorm == 0 || pnorm == 1, GME_ERR_ARG, "%s: pnorm_distance %d out of range (bbme.py:60)", who, pnorm);
+    if (int rc = require_pnorm(who, pnorm)) return rc;
     GME_REQUIRE(penalty >= 0 && penalty <= GM_MAX_PENALTY, GME_ERR_ARG, "%s: penalty %d (0 .. 2^30)", who, penalty);
     return GME_OK;
 }
@@ -279,29 +268,24 @@ int launch_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, long long p
     int rc = gmc_check_args("global motion compensation", bs, pnorm, penalty);
     if (rc) return rc;
     const int hb = H / bs, wb = W / bs;
-    ctx->plan[0] = 0; ctx->plan_patches = 0;
     const bool compiled = bs == 16 || bs == 32;
-    if (compiled) plan_note(ctx, 0, "k_gmc<%d> penalty %d, %d x %d blocks, one wave each", bs, penalty, hb, wb);
-    else plan_note(ctx, 0, "k_gmc<0> bs %d penalty %d, %d x %d blocks, one wave each", bs, penalty, hb, wb);
-    if (pairs == 0 || hb == 0 || wb == 0) return GME_OK;
-    GME_REQUIRE(hb <= 65535, GME_ERR_ARG, "%d block rows", hb);
     GmcArgs a;
     a.stride = plane_stride; a.H = H; a.W = W; a.pitch = pitch;
     a.hb = hb; a.wb = wb; a.bs = bs; a.pnorm = pnorm; a.penalty = (uint32_t)penalty;
-    a.block_bytes = (bs * ((bs + 3) / 4) * 4 + 15) & ~15;
+    a.block_bytes = block_bytes(bs);
     const long long per = (long long)hb * wb;
-    for_plane_chunks(pairs, [&](int k, int n) {
+    auto note = [&] {
+        if (compiled) plan_note(ctx, 0, "k_gmc<%d> penalty %d, %d x %d blocks, one wave each", bs, penalty, hb, wb);
+        else plan_note(ctx, 0, "k_gmc<0> bs %d penalty %d, %d x %d blocks, one wave each", bs, penalty, hb, wb);
+    };
+    return launch_wave_blocks(ctx, pairs, hb, wb, 2 * a.block_bytes, a, note, [&](int k) {
         const long long off = (long long)k * plane_stride;
         a.ref = ref + off; a.cur = cur + off;
         a.h = h + (size_t)k * 8; a.usable = usable + k;
         a.f = f + per * k * 2;
         a.mode = mode + per * k; a.cost = cost + per * k; a.costs = costs + per * k * 2;
-        if (!compiled) gmc_launch<0>(ctx->stream, a, n);
-        else if (bs == 16) gmc_launch<16>(ctx->stream, a, n);
-        else gmc_launch<32>(ctx->stream, a, n);
+        return !compiled ? k_gmc<0> : bs == 16 ? k_gmc<16> : k_gmc<32>;
     });
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
 }
 
 // out planes = gmc.predict of the ref planes by h, usable, mode and f of [pairs][H / bs][W / bs], sse[pairs] (device, zeroed here)
@@ -317,8 +301,8 @@ int launch_predict_gmc(gme_ctx* ctx, const uint8_t* ref, const uint8_t* cur, lon
     const long long per = (long long)hb * wb;
     return predict_planes(ctx, pairs, sse, [&](int k, int n) {
         const long long off = (long long)k * plane_stride;
-        const dim3 grid((cw + GM_WAVES - 1) / GM_WAVES, ch, n);
-        hipLaunchKernelGGL(k_predict_gmc, grid, dim3(GM_THREADS), 0, ctx->stream, ref + off, cur + off, plane_stride, H, W, pitch, bs, hb,
+        const dim3 grid((cw + BLK_WAVES - 1) / BLK_WAVES, ch, n);
+        hipLaunchKernelGGL(k_predict_gmc, grid, dim3(BLK_THREADS), 0, ctx->stream, ref + off, cur + off, plane_stride, H, W, pitch, bs, hb,
                            wb, cw, h + (size_t)k * 8, usable + k, mode + per * k, f + per * k * 2, out + (long long)k * out_stride,
                            out_stride, out_pitch, sse + k);
     });

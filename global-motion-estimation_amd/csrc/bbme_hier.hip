@@ -20,7 +20,6 @@
 
 namespace {
 
-constexpr int HIER_THREADS = 256, HIER_WAVES = HIER_THREADS / 64;
 constexpr int HIER_MAX_BS = 64, HIER_MAX_CW = 8, HIER_MAX_R = 3, HIER_MIN_TOP = 4;
 // costs are 32-bit in the kernel (int64 at the ABI): the largest is 64 * 64 * 255^2
 static_assert((long long)HIER_MAX_BS * HIER_MAX_BS * 65025ll < (1ll << 28), "28-bit block costs");
@@ -42,8 +41,8 @@ struct HierArgs {
     int slice_bytes;
 };
 
-static_assert((HIER_MAX_BS + 2 * HIER_MAX_CW) * ((HIER_MAX_BS + 2 * HIER_MAX_CW + 3) / 4 + 1) < SMALL_DIV_T &&
-                  (HIER_MAX_BS + 2 * HIER_MAX_CW + 3) / 4 + 1 <= SMALL_DIV_D && 2 * HIER_MAX_CW + 1 <= SMALL_DIV_D, "range of small_div");
+constexpr int HIER_MAX_WINDOW = HIER_MAX_BS + 2 * HIER_MAX_CW;
+static_assert(small_div_covers(HIER_MAX_WINDOW, window_row_dwords(HIER_MAX_WINDOW), 2 * HIER_MAX_CW + 1), "range of small_div");
 
 // One level of one block: centre (cx, cy) already clamped, candidates within R of it; the level's vector into (vx, vy), its
 // cost returned.  B: the block side where it is a compile-time constant (0: b_rt).
@@ -52,10 +51,8 @@ __device__ __forceinline__ uint32_t level_search(const HierLevel& L, int pair, i
                                                  int cy, uint32_t* anc, uint32_t* win, int lane, int* vx, int* vy)
 {
     const int b = B ? B : b_rt;
-    const int nd = (b + 3) >> 2;                                  // dwords per block row
-    const int n = 2 * R + 1, ncand = n * n;
-    const int wside = b + 2 * R, wd = (wside + 3) / 4 + 1;        // window rows of wd dwords: one more than its bytes need,
-                                                                  // v_alignbyte reads the dword behind the last one it uses
+    const Square sq(R);
+    const int nd = row_dwords(b), wside = b + 2 * R, wd = window_row_dwords(wside);
     const int x0 = bj * b, y0 = bi * b;
     const uint8_t* pp = L.prev + (long long)pair * L.stride;
     const uint8_t* cp = L.cur + (long long)pair * L.stride;
@@ -63,64 +60,47 @@ __device__ __forceinline__ uint32_t level_search(const HierLevel& L, int pair, i
     stage_bytes(win, wside, wd, wside, cp, L.pitch, L.H, L.W, y0 + cy - R, x0 + cx - R, lane);
     wave_lds_fence();
 
-    // P lanes to a candidate, each a share of the rows: as many as leave every candidate a slot in one round, at most 8
-    int P = 1;
-    while (P < 8 && ncand * (P * 2) <= 64) P *= 2;
-    const int slots = 64 / P, slot = lane / P, q = lane - slot * P;
-    const uint32_t tail = (b & 3) ? (1u << (8 * (b & 3))) - 1u : 0xFFFFFFFFu;      // bytes of a row's last dword
-    uint32_t best = 0xFFFFFFFFu, best_order = 0xFFFFFFFFu;
-    for (int c0 = 0; c0 < ncand; c0 += slots) {
-        const int c = c0 + slot;
-        const bool listed = c < ncand;
-        const int cc = listed ? c : 0;
-        const int wx = small_div(cc, n), wy = cc - wx * n;        // the candidate's origin in the window (column, row)
+    const LaneSplit ls(lanes_for_one_round(sq.ncand), lane);
+    const uint32_t tail = tail_mask(b);
+    Least best;
+    for (int c0 = 0; c0 < sq.ncand; c0 += ls.slots) {
+        const int c = c0 + ls.slot;
+        const bool listed = c < sq.ncand;
+        int wx, wy;                                               // the candidate's origin in the window (column, row)
+        sq.at(listed ? c : 0, &wx, &wy);
         const int gx = x0 + cx - R + wx, gy = y0 + cy - R + wy;   // ... and in the level
         const bool inside = listed && gx >= 0 && gy >= 0 && gx + b <= L.W && gy + b <= L.H;
         const uint32_t sh = (uint32_t)wx & 3u;
-        uint32_t sad = 0, aa = 0, bb = 0, ab = 0;
-        for (int y = q; y < b; y += P) {
+        RowScore s;
+        for (int y = ls.q; y < b; y += ls.P) {
             const uint32_t* arow = anc + y * nd;
             const uint32_t* wrow = win + (wy + y) * wd + (wx >> 2);
 #pragma unroll 4
             for (int k = 0; k < nd; ++k) {
-                const uint32_t a = arow[k];
-                uint32_t v = __builtin_amdgcn_alignbyte(wrow[k + 1], wrow[k], sh);
+                uint32_t v = window_dword(wrow, k, sh);
                 if (!B || (B & 3)) { if (k == nd - 1) v &= tail; }
-                if (pnorm == 0) sad = __builtin_amdgcn_sad_u8(a, v, sad);
-                else {
-                    aa = __builtin_amdgcn_udot4(a, a, aa, false);
-                    bb = __builtin_amdgcn_udot4(v, v, bb, false);
-                    ab = __builtin_amdgcn_udot4(a, v, ab, false);
-                }
+                s.add(arow[k], v, pnorm);
             }
         }
-        uint32_t part = pnorm == 0 ? sad : aa + bb - 2u * ab;     // sum (a - v)^2 of this lane's rows
-        for (int m = 1; m < P; m <<= 1) part += (uint32_t)__shfl_xor((int)part, m, 64);
-        const uint32_t order = (wx == R && wy == R) ? 0u : (uint32_t)c + 1u;
-        if (inside && (part < best || (part == best && order < best_order))) { best = part; best_order = order; }
+        const uint32_t cost = ls.sum(s.value(pnorm));             // of this lane's rows, then of the candidate
+        if (inside) best.take(cost, sq.order(c, wx, wy));
     }
-    const uint32_t win_cost = wave_min_u32(best);
-    const uint32_t win_order = wave_min_u32(best == win_cost ? best_order : 0xFFFFFFFFu);
-    int ox = 0, oy = 0;
-    if (win_order != 0u) {
-        const int c = (int)win_order - 1;
-        ox = small_div(c, n) - R;
-        oy = c - small_div(c, n) * n - R;
-    }
+    const Least won = wave_least(best.cost, best.order);
+    int ox, oy;
+    sq.offset(won.order, &ox, &oy);
     *vx = cx + ox;
     *vy = cy + oy;
     wave_lds_fence();                                            // the next level overwrites the slice
-    return win_cost;
+    return won.cost;
 }
 
-// grid (ceil(wb / HIER_WAVES), hb, pairs)
 template <int BS, int LEVELS>
-__global__ void __launch_bounds__(HIER_THREADS) k_hier(const HierArgs A)
+__global__ void __launch_bounds__(BLK_THREADS) k_hier(const HierArgs A)
 {
     extern __shared__ __align__(16) uint8_t lds[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int bj = blockIdx.x * HIER_WAVES + wave, bi = blockIdx.y, pair = blockIdx.z;
-    if (bj >= A.wb) return;                                      // the whole wave: nothing below synchronises across waves
+    const WaveBlock w = wave_block<false>(A.wb);                 // in vector registers: faster here, see wave_block
+    if (w.none) return;
+    const int wave = w.wave, lane = w.lane, bj = w.bj, bi = w.bi, pair = w.z;
     const int bs = BS ? BS : A.bs, levels = LEVELS ? LEVELS : A.levels;
     uint32_t* anc = (uint32_t*)(lds + (size_t)wave * A.slice_bytes);
     uint32_t* win = (uint32_t*)(lds + (size_t)wave * A.slice_bytes + A.anchor_bytes);
@@ -147,20 +127,13 @@ __global__ void __launch_bounds__(HIER_THREADS) k_hier(const HierArgs A)
     level(std::integral_constant<int, 2>());
 }
 
-template <int BS, int LEVELS>
-void hier_launch(hipStream_t stream, const HierArgs& a, int pairs)
-{
-    hipLaunchKernelGGL((k_hier<BS, LEVELS>), dim3((unsigned)((a.wb + HIER_WAVES - 1) / HIER_WAVES), (unsigned)a.hb, (unsigned)pairs),
-                       dim3(HIER_THREADS), (size_t)HIER_WAVES * a.slice_bytes, stream, a);
-}
-
 }  // namespace
 
 // the argument rules of hier.py
 int hier_check_args(const char* who, int bs, int cw, int radius, int pnorm, int levels)
 {
     GME_REQUIRE(levels >= 1 && levels <= 3, GME_ERR_ARG, "%s: levels %d (1 .. 3)", who, levels);
-    GME_REQUIRE(pnorm == 0 || pnorm == 1, GME_ERR_ARG, "%s: pnorm_distance %d out of range (bbme.py:60)", who, pnorm);
+    if (int rc = require_pnorm(who, pnorm)) return rc;
     GME_REQUIRE(bs >= 1 && bs <= HIER_MAX_BS && bs % (1 << (levels - 1)) == 0 && (bs >> (levels - 1)) >= HIER_MIN_TOP, GME_ERR_ARG,
                 "%s: block_size %d with %d levels (a multiple of %d, at most %d, at least %d at the coarsest level)", who, bs, levels,
                 1 << (levels - 1), HIER_MAX_BS, HIER_MIN_TOP);
@@ -178,24 +151,21 @@ int launch_hier(gme_ctx* ctx, const Plane (&level)[3], int first_prev, int first
     int rc = hier_check_args("hierarchical search", bs, cw, radius, pnorm, levels);
     if (rc) return rc;
     const int hb = level[2].H / bs, wb = level[2].W / bs;
-    ctx->plan[0] = 0; ctx->plan_patches = 0;
     const bool compiled = levels == 3 && (bs == 16 || bs == 32 || bs == 64);
-    if (compiled) plan_note(ctx, 0, "k_hier<%d,3> cw %d r %d, %d x %d blocks, one wave each", bs, cw, radius, hb, wb);
-    else plan_note(ctx, 0, "k_hier<0,0> bs %d levels %d cw %d r %d, %d x %d blocks, one wave each", bs, levels, cw, radius, hb, wb);
-    if (pairs == 0 || hb == 0 || wb == 0) return GME_OK;
-    GME_REQUIRE(hb <= 65535, GME_ERR_ARG, "%d block rows", hb);
     HierArgs a;
     a.hb = hb; a.wb = wb; a.bs = bs; a.levels = levels; a.cw = cw; a.radius = radius; a.pnorm = pnorm;
-    a.anchor_bytes = (bs * ((bs + 3) & ~3) + 15) & ~15;
-    int window = 0;
+    a.anchor_bytes = block_bytes(bs);
+    a.slice_bytes = 0;                                            // the anchor and the largest window of a level
     for (int l = 3 - levels; l < 3; ++l) {
-        const int side = (bs >> (2 - l)) + 2 * (l == 3 - levels ? cw : radius);
-        const int bytes = side * ((side + 3) / 4 + 1) * 4;
-        if (bytes > window) window = bytes;
+        const int bytes = a.anchor_bytes + window_bytes((bs >> (2 - l)) + 2 * (l == 3 - levels ? cw : radius));
+        if (bytes > a.slice_bytes) a.slice_bytes = bytes;
     }
-    a.slice_bytes = a.anchor_bytes + ((window + 15) & ~15);
     const long long per = (long long)hb * wb;
-    for_plane_chunks(pairs, [&](int k, int n) {
+    auto note = [&] {
+        if (compiled) plan_note(ctx, 0, "k_hier<%d,3> cw %d r %d, %d x %d blocks, one wave each", bs, cw, radius, hb, wb);
+        else plan_note(ctx, 0, "k_hier<0,0> bs %d levels %d cw %d r %d, %d x %d blocks, one wave each", bs, levels, cw, radius, hb, wb);
+    };
+    return launch_wave_blocks(ctx, pairs, hb, wb, a.slice_bytes, a, note, [&](int k) {
         for (int l = 0; l < 3; ++l) {
             HierLevel& L = a.lv[l];
             const Plane& p = level[l];
@@ -205,11 +175,6 @@ int launch_hier(gme_ctx* ctx, const Plane (&level)[3], int first_prev, int first
             L.H = p.H; L.W = p.W; L.pitch = p.pitch;
             L.mf = mf[l] + per * k * 2; L.cost = cost[l] + per * k;
         }
-        if (!compiled) hier_launch<0, 0>(ctx->stream, a, n);
-        else if (bs == 16) hier_launch<16, 3>(ctx->stream, a, n);
-        else if (bs == 32) hier_launch<32, 3>(ctx->stream, a, n);
-        else hier_launch<64, 3>(ctx->stream, a, n);
+        return !compiled ? k_hier<0, 0> : bs == 16 ? k_hier<16, 3> : bs == 32 ? k_hier<32, 3> : k_hier<64, 3>;
     });
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
 }

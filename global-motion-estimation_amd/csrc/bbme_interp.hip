@@ -21,10 +21,8 @@
 
 namespace {
 
-constexpr int IP_THREADS = 256, IP_WAVES = IP_THREADS / 64;
 constexpr int IP_MIN_BS = 4, IP_MAX_BS = 64, IP_MAX_SW = 8, IP_MAX_BIAS = 1 << 16;
 constexpr long long IP_MAX_DIST = (long long)IP_MAX_BS * IP_MAX_BS * 65025ll;
-constexpr uint32_t IP_NONE = 0xFFFFFFFFu;                       // no cost: above every J there is
 // J is 32-bit in the kernel (int64 at the ABI): the largest is 64 * 64 * 255^2 + 2^16 * (8 + 8)
 static_assert(IP_MAX_DIST + (long long)IP_MAX_BIAS * 2 * IP_MAX_SW < (1ll << 31), "31-bit J");
 // a lane's share of sum a^2 + sum b^2 (RowScore, modulo 2^32 until its difference with 2 ab is taken) does not wrap either
@@ -34,11 +32,9 @@ static_assert(2 * IP_MAX_DIST < (1ll << 32), "sum a^2 + sum b^2 of a block in 32
 constexpr int IP_MAX_CAND = (2 * IP_MAX_SW + 1) * (2 * IP_MAX_SW + 1);
 static_assert(IP_MAX_CAND + 1 <= (1 << 9) && (IP_MAX_DIST << 9) >= (1ll << 32), "J and order in one 32-bit key");
 constexpr int IP_MAX_WINDOW = IP_MAX_BS + 2 * IP_MAX_SW;
-constexpr int IP_MAX_WINDOW_DWORDS = (IP_MAX_WINDOW + 3) / 4 + 1;
-static_assert(IP_MAX_WINDOW * IP_MAX_WINDOW_DWORDS < SMALL_DIV_T && IP_MAX_WINDOW_DWORDS <= SMALL_DIV_D && 2 * IP_MAX_SW + 1 <= SMALL_DIV_D &&
-                  IP_MAX_CAND < SMALL_DIV_T, "range of small_div");
+static_assert(small_div_covers(IP_MAX_WINDOW, window_row_dwords(IP_MAX_WINDOW), 2 * IP_MAX_SW + 1), "range of small_div");
 // a workgroup's LDS without an opt-in: both windows of four waves (52.5 KiB at B 64, sw 8: three workgroups to a CU)
-static_assert(IP_WAVES * (2 * IP_MAX_WINDOW * IP_MAX_WINDOW_DWORDS * 4 + 32) <= 64 * 1024, "LDS of a workgroup");
+static_assert(BLK_WAVES * 2 * window_bytes(IP_MAX_WINDOW) <= 64 * 1024, "LDS of a workgroup");
 
 struct InterpArgs {
     const uint8_t* past;          // first plane of each role; pair k reads the planes k * stride bytes on
@@ -53,38 +49,38 @@ struct InterpArgs {
     int window_bytes;             // LDS of a wave: the window of past, then the window of next
 };
 
-// grid (ceil(wb / IP_WAVES), hb, pairs)
 template <int BS>
-__global__ void __launch_bounds__(IP_THREADS) k_interp(const InterpArgs A)
+__global__ void __launch_bounds__(BLK_THREADS) k_interp(const InterpArgs A)
 {
     extern __shared__ __align__(16) uint8_t lds[];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int bj = blockIdx.x * IP_WAVES + wave, bi = blockIdx.y, pair = blockIdx.z;
-    if (bj >= A.wb) return;                                      // the whole wave: nothing below synchronises across waves
+    const WaveBlock w = wave_block(A.wb);
+    if (w.none) return;
+    const int wave = w.wave, lane = w.lane, bj = w.bj, bi = w.bi, pair = w.z;
     const int B = BS ? BS : A.bs;
-    const int sw = A.sw, n = 2 * sw + 1, ncand = n * n, pnorm = A.pnorm;
+    const int sw = A.sw, pnorm = A.pnorm;
     const int x0 = bj * B, y0 = bi * B;
     uint32_t* pw = (uint32_t*)(lds + (size_t)wave * 2 * A.window_bytes);
     uint32_t* nw = (uint32_t*)(lds + (size_t)wave * 2 * A.window_bytes + A.window_bytes);
-    // window rows of one dword more than their bytes need: v_alignbyte reads the dword behind the last one it uses
-    const int nd = (B + 3) >> 2, ws = B + 2 * sw, wd = ((ws + 3) >> 2) + 1;
-    const uint32_t tail = (B & 3) ? (1u << (8 * (B & 3))) - 1u : 0xFFFFFFFFu;
+    const int nd = row_dwords(B), ws = B + 2 * sw, wd = window_row_dwords(ws);
+    const uint32_t tail = tail_mask(B);
     constexpr bool TAIL = !BS || (BS & 3);                       // the last dword of a row may hold bytes beyond the block
     const long long plane = (long long)pair * A.stride;
     stage_bytes_clamped(pw, ws, wd, ws, A.past + plane, A.pitch, A.H, A.W, y0 - sw, x0 - sw, lane);
     stage_bytes_clamped(nw, ws, wd, ws, A.next + plane, A.pitch, A.H, A.W, y0 - sw, x0 - sw, lane);
     wave_lds_fence();
 
-    // P lanes to a candidate, each a share of the rows: as many as leave every candidate a slot in one round, at most 8
+    const Square sq(sw);
+    // lanes_for_one_round and LaneSplit written out, slot and share by division: with the shared forms this kernel carries two
+    // window values in vector registers across the staging loops and takes about 1 % longer at 1920 x 1080
     int P = 1;
-    while (P < 8 && ncand * (P * 2) <= 64) P *= 2;
+    while (P < 8 && sq.ncand * (P * 2) <= 64) P *= 2;
     const int slots = 64 / P, slot = lane / P, q = lane - slot * P;
-    uint32_t best = IP_NONE, best_order = IP_NONE;
-    for (int c0 = 0; c0 < ncand; c0 += slots) {
+    Least best;
+    for (int c0 = 0; c0 < sq.ncand; c0 += slots) {
         const int c = c0 + slot;
-        const bool listed = c < ncand;
-        const int cc = listed ? c : 0;                           // lanes beyond the list score candidate 0 and drop it
-        const int nx = small_div(cc, n), ny = cc - nx * n;       // the candidate's block in the next window (column, row): sw + o
+        const bool listed = c < sq.ncand;                        // lanes beyond the list score candidate 0 and drop it
+        int nx, ny;                                              // the candidate's block in the next window (column, row): sw + o
+        sq.at(listed ? c : 0, &nx, &ny);
         const int px = 2 * sw - nx, py = 2 * sw - ny;            // ... and in the past window: sw - o
         const uint32_t psh = (uint32_t)px & 3u, nsh = (uint32_t)nx & 3u;
         RowScore s;
@@ -93,33 +89,24 @@ __global__ void __launch_bounds__(IP_THREADS) k_interp(const InterpArgs A)
             const uint32_t* nrow = nw + (ny + y) * wd + (nx >> 2);
 #pragma unroll 4
             for (int k = 0; k < nd; ++k) {
-                uint32_t a = __builtin_amdgcn_alignbyte(prow[k + 1], prow[k], psh);
-                uint32_t v = __builtin_amdgcn_alignbyte(nrow[k + 1], nrow[k], nsh);
+                uint32_t a = window_dword(prow, k, psh);
+                uint32_t v = window_dword(nrow, k, nsh);
                 if (TAIL) { if (k == nd - 1) { a &= tail; v &= tail; } }
                 s.add(a, v, pnorm);
             }
         }
-        uint32_t part = s.value(pnorm);
-        for (int m = 1; m < P; m <<= 1) part += (uint32_t)__shfl_xor((int)part, m, 64);
-        const int ox = nx - sw, oy = ny - sw;
-        const uint32_t j = part + A.bias * (uint32_t)(abs(ox) + abs(oy));
-        const uint32_t order = (ox == 0 && oy == 0) ? 0u : (uint32_t)c + 1u;
-        if (listed && (j < best || (j == best && order < best_order))) { best = j; best_order = order; }
+        const uint32_t j = lanes_sum(s.value(pnorm), P) + A.bias * (uint32_t)(abs(nx - sw) + abs(ny - sw));
+        if (listed) best.take(j, sq.order(c, nx, ny));
     }
-    const uint32_t win_cost = wave_min_u32(best);
-    const uint32_t win_order = wave_min_u32(best == win_cost ? best_order : IP_NONE);
+    const Least win = wave_least(best.cost, best.order);
     if (lane == 0) {
-        int vx = 0, vy = 0;
-        if (win_order != 0u) {
-            const int c = (int)win_order - 1;
-            vx = small_div(c, n) - sw;
-            vy = c - small_div(c, n) * n - sw;
-        }
+        int vx, vy;
+        sq.offset(win.order, &vx, &vy);
         const long long blk = ((long long)pair * A.hb + bi) * A.wb + bj;
         A.mv[blk * 2] = vx;
         A.mv[blk * 2 + 1] = vy;
-        A.cost[blk] = (long long)win_cost;
-        A.dist[blk] = (long long)(win_cost - A.bias * (uint32_t)(abs(vx) + abs(vy)));
+        A.cost[blk] = (long long)win.cost;
+        A.dist[blk] = (long long)(win.cost - A.bias * (uint32_t)(abs(vx) + abs(vy)));
     }
 }
 
@@ -159,13 +146,6 @@ __global__ void __launch_bounds__(PRED_THREADS) k_interp_frame(const uint8_t* pa
     predict_rows(px, cur + plane, H, W, pitch, out + (long long)f * out_stride, out_pitch, sse + f);
 }
 
-template <int BS>
-void interp_launch(hipStream_t stream, const InterpArgs& a, int pairs)
-{
-    hipLaunchKernelGGL((k_interp<BS>), dim3((unsigned)((a.wb + IP_WAVES - 1) / IP_WAVES), (unsigned)a.hb, (unsigned)pairs),
-                       dim3(IP_THREADS), (size_t)IP_WAVES * 2 * a.window_bytes, stream, a);
-}
-
 }  // namespace
 
 // the argument rules of interp.py
@@ -173,7 +153,7 @@ int interp_check_args(const char* who, int H, int W, int bs, int sw, int pnorm, 
 {
     GME_REQUIRE(bs >= IP_MIN_BS && bs <= IP_MAX_BS, GME_ERR_ARG, "%s: block_size %d (%d .. %d)", who, bs, IP_MIN_BS, IP_MAX_BS);
     GME_REQUIRE(sw >= 0 && sw <= IP_MAX_SW, GME_ERR_ARG, "%s: search_window %d (0 .. %d)", who, sw, IP_MAX_SW);
-    GME_REQUIRE(pnorm == 0 || pnorm == 1, GME_ERR_ARG, "%s: pnorm_distance %d out of range (bbme.py:60)", who, pnorm);
+    if (int rc = require_pnorm(who, pnorm)) return rc;
     GME_REQUIRE(bias >= 0 && bias <= IP_MAX_BIAS, GME_ERR_ARG, "%s: bias %d (0 .. 2^16)", who, bias);
     GME_REQUIRE(H >= bs && W >= bs, GME_ERR_ARG, "%s: a %d x %d frame holds no block of %d", who, H, W, bs);
     return GME_OK;
@@ -187,28 +167,22 @@ int launch_interp(gme_ctx* ctx, const uint8_t* past, const uint8_t* next, long l
     int rc = interp_check_args("frame interpolation", H, W, bs, sw, pnorm, bias);
     if (rc) return rc;
     const int hb = H / bs, wb = W / bs;
-    ctx->plan[0] = 0; ctx->plan_patches = 0;
     const bool compiled = bs == 16 || bs == 32;
-    if (compiled) plan_note(ctx, 0, "k_interp<%d> sw %d bias %d, %d x %d blocks, one wave each", bs, sw, bias, hb, wb);
-    else plan_note(ctx, 0, "k_interp<0> bs %d sw %d bias %d, %d x %d blocks, one wave each", bs, sw, bias, hb, wb);
-    if (pairs == 0) return GME_OK;
-    GME_REQUIRE(hb <= 65535, GME_ERR_ARG, "%d block rows", hb);
     InterpArgs a;
     a.stride = plane_stride; a.H = H; a.W = W; a.pitch = pitch;
     a.hb = hb; a.wb = wb; a.bs = bs; a.sw = sw; a.pnorm = pnorm; a.bias = (uint32_t)bias;
-    const int side = bs + 2 * sw;
-    a.window_bytes = (side * ((side + 3) / 4 + 1) * 4 + 15) & ~15;
+    a.window_bytes = window_bytes(bs + 2 * sw);
     const long long per = (long long)hb * wb;
-    for_plane_chunks(pairs, [&](int k, int n) {
+    auto note = [&] {
+        if (compiled) plan_note(ctx, 0, "k_interp<%d> sw %d bias %d, %d x %d blocks, one wave each", bs, sw, bias, hb, wb);
+        else plan_note(ctx, 0, "k_interp<0> bs %d sw %d bias %d, %d x %d blocks, one wave each", bs, sw, bias, hb, wb);
+    };
+    return launch_wave_blocks(ctx, pairs, hb, wb, 2 * a.window_bytes, a, note, [&](int k) {   // H, W >= bs: there are blocks
         const long long off = (long long)k * plane_stride;
         a.past = past + off; a.next = next + off;
         a.mv = mv + per * k * 2; a.cost = cost + per * k; a.dist = dist + per * k;
-        if (!compiled) interp_launch<0>(ctx->stream, a, n);
-        else if (bs == 16) interp_launch<16>(ctx->stream, a, n);
-        else interp_launch<32>(ctx->stream, a, n);
+        return !compiled ? k_interp<0> : bs == 16 ? k_interp<16> : k_interp<32>;
     });
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
 }
 
 // out planes = interp.interpolate of the past and next planes by mv [pairs][H / bs][W / bs][2], sse[pairs] (device, zeroed here) =

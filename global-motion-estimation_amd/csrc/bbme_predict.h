@@ -1,5 +1,6 @@
-// What the predict-a-plane passes share (bbme_subpel.hip, bbme_vbs.hip, bbme_bipred.hip, bbme_gmc.hip): the row frame of the three
-// kernels that differ only in how one pixel is predicted, and the launch over the planes that all four launchers make.
+// What the predict-a-plane passes share (bbme_subpel.hip, bbme_vbs.hip, bbme_bipred.hip, bbme_gmc.hip, bbme_interp.hip): the row
+// frame of the four kernels that differ only in how one pixel is predicted, and the launch over the planes that all five
+// launchers make.
 #pragma once
 #include "gme_internal.h"
 

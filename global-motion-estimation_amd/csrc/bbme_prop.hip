@@ -19,13 +19,12 @@
 
 namespace {
 
-constexpr int PR_THREADS = 256, PR_WAVES = PR_THREADS / 64;
 constexpr int PR_MIN_BS = 4, PR_MAX_BS = 64, PR_MAX_ROUNDS = 4, PR_MAX_STEPS = 4, PR_MAX_COMPONENT = 1 << 14;
-constexpr int PR_MAX_DWORDS = (PR_MAX_BS + 3) / 4;
+constexpr int PR_MAX_DWORDS = row_dwords(PR_MAX_BS);
 constexpr int PR_CANDS = 12;                                    // own, eight neighbours, temporal, camera, zero
 constexpr int PR_MOVED = 8;
 static_assert((long long)PR_MAX_BS * PR_MAX_BS * 65025ll < (1ll << 31), "31-bit costs");
-static_assert(PR_MAX_BS * PR_MAX_DWORDS < SMALL_DIV_T && PR_MAX_DWORDS <= SMALL_DIV_D, "range of small_div");
+static_assert(small_div_covers(PR_MAX_BS, PR_MAX_DWORDS, 3), "range of small_div");
 
 struct PropArgs {
     const uint8_t* prev;          // first "previous" plane; pair k reads the planes k * stride bytes on
@@ -44,7 +43,7 @@ struct PropArgs {
 
 // the dwords of a block a lane holds: BS * (BS / 4) over 64 lanes, or the most a block of 64 needs
 template <int BS>
-constexpr int lane_dwords() { return BS ? (BS * ((BS + 3) / 4) + 63) / 64 : PR_MAX_BS * PR_MAX_DWORDS / 64; }
+constexpr int lane_dwords() { return BS ? (BS * row_dwords(BS) + 63) / 64 : PR_MAX_BS * PR_MAX_DWORDS / 64; }
 
 // What a lane knows of its share of the block: the anchor's dwords, where each lies in a block (byte offset from the block's
 // first pixel) and which of its bytes belong to the block.  A dword is always read whole: its bytes past the block's last
@@ -61,7 +60,7 @@ struct Anchor {
     // the B x B block at `base`, which lies inside the frame
     __device__ __forceinline__ void load(const uint8_t* base, int pitch, int B, int lane)
     {
-        const int nd = (B + 3) >> 2;
+        const int nd = row_dwords(B);
         total = B * nd;
 #pragma unroll
         for (int i = 0; i < N; ++i) {
@@ -118,13 +117,12 @@ __device__ __forceinline__ bool available(int H, int W, int y0, int x0, int B, i
     return x0 + vx >= 0 && y0 + vy >= 0 && x0 + vx + B <= W && y0 + vy + B <= H;
 }
 
-// grid (ceil(wb / PR_WAVES), hb, pairs)
 template <int BS>
-__global__ void __launch_bounds__(PR_THREADS) k_prop(const PropArgs A)
+__global__ void __launch_bounds__(BLK_THREADS) k_prop(const PropArgs A)
 {
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int bj = blockIdx.x * PR_WAVES + wave, bi = blockIdx.y, pair = blockIdx.z;
-    if (bj >= A.wb) return;                                      // the whole wave: nothing below synchronises across waves
+    const WaveBlock w = wave_block(A.wb);
+    if (w.none) return;
+    const int lane = w.lane, bj = w.bj, bi = w.bi, pair = w.z;
     const int B = BS ? BS : A.bs, pnorm = A.pnorm;
     const int x0 = bj * B, y0 = bi * B;
     const long long per = (long long)A.hb * A.wb, blk = (long long)pair * per + (long long)bi * A.wb + bj;
@@ -169,7 +167,7 @@ __global__ void __launch_bounds__(PR_THREADS) k_prop(const PropArgs A)
 
     // the zero vector is available to every block, so there is a first one
     int bx = 0, by = 0, src = 4;
-    uint32_t best = 0xFFFFFFFFu;                                 // costs lie below it: the first one is taken
+    uint32_t best = NO_COST;                                     // costs lie below it: the first one is taken
     const uint8_t* at = cur + (long long)y0 * A.pitch + x0;      // the co-located block: a vector (x, y) adds y * pitch + x
     if constexpr (BS != 0) {
         uint32_t px[PR_CANDS][Anchor<BS>::N];
@@ -249,20 +247,13 @@ __global__ void __launch_bounds__(PR_THREADS) k_prop(const PropArgs A)
     }
 }
 
-template <int BS>
-void prop_launch(hipStream_t stream, const PropArgs& a, int pairs)
-{
-    hipLaunchKernelGGL((k_prop<BS>), dim3((unsigned)((a.wb + PR_WAVES - 1) / PR_WAVES), (unsigned)a.hb, (unsigned)pairs), dim3(PR_THREADS), 0,
-                       stream, a);
-}
-
 }  // namespace
 
 // the argument rules of propagate.py
 int prop_check_args(const char* who, int bs, int pnorm, int rounds, int steps)
 {
     GME_REQUIRE(bs >= PR_MIN_BS && bs <= PR_MAX_BS, GME_ERR_ARG, "%s: block_size %d (%d .. %d)", who, bs, PR_MIN_BS, PR_MAX_BS);
-    GME_REQUIRE(pnorm == 0 || pnorm == 1, GME_ERR_ARG, "%s: pnorm_distance %d out of range (bbme.py:60)", who, pnorm);
+    if (int rc = require_pnorm(who, pnorm)) return rc;
     GME_REQUIRE(rounds >= 1 && rounds <= PR_MAX_ROUNDS, GME_ERR_ARG, "%s: rounds %d (1 .. %d)", who, rounds, PR_MAX_ROUNDS);
     GME_REQUIRE(steps >= 0 && steps <= PR_MAX_STEPS, GME_ERR_ARG, "%s: steps %d (0 .. %d)", who, steps, PR_MAX_STEPS);
     return GME_OK;
@@ -280,32 +271,29 @@ int launch_prop(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long
     int rc = prop_check_args("vector propagation", bs, pnorm, rounds, steps);
     if (rc) return rc;
     const int hb = H / bs, wb = W / bs;
-    ctx->plan[0] = 0; ctx->plan_patches = 0;
     const bool compiled = bs == 16 || bs == 32;
-    if (compiled) plan_note(ctx, 0, "k_prop<%d> rounds %d steps %d, %d x %d blocks, one wave each", bs, rounds, steps, hb, wb);
-    else plan_note(ctx, 0, "k_prop<0> bs %d rounds %d steps %d, %d x %d blocks, one wave each", bs, rounds, steps, hb, wb);
     *result = work[(rounds - 1) & 1];
-    if (pairs == 0 || hb == 0 || wb == 0) return GME_OK;
-    GME_REQUIRE(hb <= 65535, GME_ERR_ARG, "%d block rows", hb);
     PropArgs a;
     a.stride = plane_stride; a.H = H; a.W = W; a.pitch = pitch;
     a.hb = hb; a.wb = wb; a.bs = bs; a.pnorm = pnorm; a.steps = steps;
     a.t = t;
     const long long per = (long long)hb * wb;
-    for (int r = 0; r < rounds; ++r) {
+    auto note = [&] {
+        if (compiled) plan_note(ctx, 0, "k_prop<%d> rounds %d steps %d, %d x %d blocks, one wave each", bs, rounds, steps, hb, wb);
+        else plan_note(ctx, 0, "k_prop<0> bs %d rounds %d steps %d, %d x %d blocks, one wave each", bs, rounds, steps, hb, wb);
+    };
+    for (int r = 0; r < rounds; ++r) {                           // a launch frame per round, each with the same plan
         const int32_t* in = r == 0 ? f : work[(r - 1) & 1];
         int32_t* out = work[r & 1];
-        for_plane_chunks(pairs, [&](int k, int n) {
+        rc = launch_wave_blocks(ctx, pairs, hb, wb, 0, a, note, [&](int k) {
             a.prev = prev + (long long)k * plane_stride; a.cur = cur + (long long)k * plane_stride;
             a.fin = in + per * k * 2; a.fout = out + per * k * 2;
             a.t_shift = k + t_shift;
             a.g = g ? g + per * k * 2 : nullptr;
             a.cost = cost + per * k; a.source = source + per * k;
-            if (!compiled) prop_launch<0>(ctx->stream, a, n);
-            else if (bs == 16) prop_launch<16>(ctx->stream, a, n);
-            else prop_launch<32>(ctx->stream, a, n);
+            return !compiled ? k_prop<0> : bs == 16 ? k_prop<16> : k_prop<32>;
         });
+        if (rc) return rc;
     }
-    GME_HIP_TRY(hipGetLastError());
     return GME_OK;
 }

@@ -21,7 +21,6 @@
 
 namespace {
 
-constexpr int VBS_THREADS = 256, VBS_WAVES = VBS_THREADS / 64;
 constexpr int VBS_MAX_BS = 64, VBS_MAX_DEPTH = 2, VBS_MAX_R = 3, VBS_MIN_LEAF = 4, VBS_MAX_PENALTY = 1 << 30;
 constexpr int VBS_NODE_SLOTS = 24;                              // 1 + 4 + 16 nodes, rounded up: key, then the vector's two parts
 constexpr int VBS_ROUND_STEPS = 8;                              // what a round of items costs beside its rows, in dword steps (an estimate)
@@ -32,8 +31,7 @@ static_assert((long long)(VBS_MAX_BS / 2) * (VBS_MAX_BS / 2) * 65025ll < (1ll <<
 static_assert((long long)VBS_MAX_PENALTY + 4ll * (VBS_MAX_BS / 2) * (VBS_MAX_BS / 2) * 65025ll < (1ll << 31), "31-bit decisions");
 static_assert((long long)VBS_MAX_BS * VBS_MAX_BS * 65025ll < (1ll << 31), "31-bit root costs");
 constexpr int VBS_MAX_WINDOW = VBS_MAX_BS + 2 * VBS_MAX_DEPTH * VBS_MAX_R;
-static_assert(VBS_MAX_WINDOW * ((VBS_MAX_WINDOW + 3) / 4 + 1) < SMALL_DIV_T && (VBS_MAX_WINDOW + 3) / 4 + 1 <= SMALL_DIV_D &&
-                  2 * VBS_MAX_R + 1 <= SMALL_DIV_D, "range of small_div");
+static_assert(small_div_covers(VBS_MAX_WINDOW, window_row_dwords(VBS_MAX_WINDOW), 2 * VBS_MAX_R + 1), "range of small_div");
 
 // item / ncand for the items of one depth: 0 <= t < 16 * 49, d = (2r + 1)^2
 __host__ __device__ constexpr int item_div(int t, int d) { return (int)(((uint32_t)t * ((1u << 16) / (uint32_t)d + 1u)) >> 16); }
@@ -60,31 +58,16 @@ struct VbsArgs {
     int anchor_bytes, window_bytes, slice_bytes;      // LDS of a wave: anchor, window, then 3 * VBS_NODE_SLOTS words of nodes
 };
 
-struct Score {
-    uint32_t sad = 0, aa = 0, bb = 0, ab = 0;
-    __device__ __forceinline__ void add(uint32_t a, uint32_t v, int pnorm)
-    {
-        if (pnorm == 0) sad = __builtin_amdgcn_sad_u8(a, v, sad);
-        else {
-            aa = __builtin_amdgcn_udot4(a, a, aa, false);
-            bb = __builtin_amdgcn_udot4(v, v, bb, false);
-            ab = __builtin_amdgcn_udot4(a, v, ab, false);
-        }
-    }
-    // sum |a - v| or sum (a - v)^2 of what was added (the latter modulo 2^32 until the lanes' parts are summed)
-    __device__ __forceinline__ uint32_t value(int pnorm) const { return pnorm == 0 ? sad : aa + bb - 2u * ab; }
-};
-
-// grid (ceil(wb / VBS_WAVES), hb, pairs)
 template <int BS, int DEPTH>
-__global__ void __launch_bounds__(VBS_THREADS) k_vbs(const VbsArgs A)
+__global__ void __launch_bounds__(BLK_THREADS) k_vbs(const VbsArgs A)
 {
     extern __shared__ __align__(16) uint8_t lds[];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int bj = blockIdx.x * VBS_WAVES + wave, bi = blockIdx.y, pair = blockIdx.z;
-    if (bj >= A.wb) return;                                      // the whole wave: nothing below synchronises across waves
+    const WaveBlock w = wave_block(A.wb);
+    if (w.none) return;
+    const int wave = w.wave, lane = w.lane, bj = w.bj, bi = w.bi, pair = w.z;
     const int B = BS ? BS : A.bs, D = BS ? DEPTH : A.depth;
-    const int r = A.radius, n = 2 * r + 1, ncand = n * n, pnorm = A.pnorm;
+    const int r = A.radius, pnorm = A.pnorm;
+    const Square sq(r);
     const int m = D * r;                                         // how far a descendant's vector can lie from the root's
     const int cells = 1 << D;                                    // cells of the leaf grid along a root's side
     const long long root = ((long long)pair * A.hb + bi) * A.wb + bj;
@@ -110,23 +93,22 @@ __global__ void __launch_bounds__(VBS_THREADS) k_vbs(const VbsArgs A)
     uint32_t* key = (uint32_t*)(lds + (size_t)wave * A.slice_bytes + A.anchor_bytes + A.window_bytes);
     int* relx = (int*)key + VBS_NODE_SLOTS;                      // a node's vector minus the root's
     int* rely = relx + VBS_NODE_SLOTS;
-    // rows of one dword more than their bytes need: v_alignbyte reads the dword behind the last one it uses
-    const int na = ((B + 3) >> 2) + 1, ws = B + 2 * m, wd = ((ws + 3) >> 2) + 1;
+    // the anchor has window rows too: a child's rows are read from it at the child's byte offset
+    const int na = window_row_dwords(B), ws = B + 2 * m, wd = window_row_dwords(ws);
     stage_bytes(anc, B, na, B, A.prev + (long long)pair * A.stride, A.pitch, A.H, A.W, y0, x0, lane);
     stage_bytes(win, ws, wd, ws, A.cur + (long long)pair * A.stride, A.pitch, A.H, A.W, sy - m, sx - m, lane);
-    if (lane < VBS_NODE_SLOTS) { key[lane] = 0xFFFFFFFFu; relx[lane] = 0; rely[lane] = 0; }
+    if (lane < VBS_NODE_SLOTS) { key[lane] = NO_COST; relx[lane] = 0; rely[lane] = 0; }
     wave_lds_fence();
 
     // the root's own cost: its (row, dword) pairs over the lanes
     uint32_t c0;
     {
-        const int nd = (B + 3) >> 2;
-        const uint32_t tail = (B & 3) ? (1u << (8 * (B & 3))) - 1u : 0xFFFFFFFFu;
-        Score s;
+        const int nd = row_dwords(B);
+        const uint32_t tail = tail_mask(B);
+        RowScore s;
         for (int t = lane; t < B * nd; t += 64) {
             const int y = small_div(t, nd), k = t - y * nd;
-            const uint32_t* wrow = win + (m + y) * wd + (m >> 2) + k;
-            uint32_t v = __builtin_amdgcn_alignbyte(wrow[1], wrow[0], (uint32_t)m & 3u);
+            uint32_t v = window_dword(win + (m + y) * wd + (m >> 2), k, (uint32_t)m & 3u);
             if (!BS || (BS & 3)) { if (k == nd - 1) v &= tail; }
             s.add(anc[y * na + k], v, pnorm);                    // anchor bytes at and past column B are zero
         }
@@ -137,9 +119,9 @@ __global__ void __launch_bounds__(VBS_THREADS) k_vbs(const VbsArgs A)
     // 5 + 4 k1 + k2), each with (2r + 1)^2 candidates around its parent's vector
 #pragma unroll 1
     for (int d = 1; d <= D; ++d) {
-        const int b = B >> d, items = ncand << (2 * d), base = d == 1 ? 1 : 5;
-        const int nd = (b + 3) >> 2;
-        const uint32_t tail = (b & 3) ? (1u << (8 * (b & 3))) - 1u : 0xFFFFFFFFu;
+        const int b = B >> d, items = sq.ncand << (2 * d), base = d == 1 ? 1 : 5;
+        const int nd = row_dwords(b);
+        const uint32_t tail = tail_mask(b);
         // P lanes to an item, each a share of its rows: the P with the least work per lane over all rounds, a round counted as
         // its dword steps plus VBS_ROUND_STEPS for the indices, the reduction and the minimum
         int P = 1, steps = ((items + 63) >> 6) * (b * nd + VBS_ROUND_STEPS);
@@ -147,13 +129,14 @@ __global__ void __launch_bounds__(VBS_THREADS) k_vbs(const VbsArgs A)
             const int s = ((items * p + 63) >> 6) * (((b + p - 1) / p) * nd + VBS_ROUND_STEPS);
             if (s < steps) { steps = s; P = p; }
         }
-        const int slots = 64 / P, slot = lane >> (P == 1 ? 0 : P == 2 ? 1 : P == 4 ? 2 : 3), q = lane & (P - 1);
-        for (int i0 = 0; i0 < items; i0 += slots) {
-            const int it = i0 + slot;
+        const LaneSplit ls(P, lane);
+        for (int i0 = 0; i0 < items; i0 += ls.slots) {
+            const int it = i0 + ls.slot;
             const bool listed = it < items;
             const int ii = listed ? it : 0;
-            const int child = item_div(ii, ncand), c = ii - child * ncand;
-            const int ox = small_div(c, n), oy = c - ox * n;     // the candidate's offset + r (column, row)
+            const int child = item_div(ii, sq.ncand), c = ii - child * sq.ncand;
+            int ox, oy;                                          // the candidate's offset + r (column, row)
+            sq.at(c, &ox, &oy);
             int cx, cy, parent = 0;                              // the child's origin in the root
             if (d == 1) { cx = (child & 1) * b; cy = (child >> 1) * b; }
             else {
@@ -167,36 +150,29 @@ __global__ void __launch_bounds__(VBS_THREADS) k_vbs(const VbsArgs A)
             const bool ok = listed && gx >= 0 && gy >= 0 && gx + b <= A.W && gy + b <= A.H;
             const int wx = m + cx + dx, wy = m + cy + dy;        // ... and in the window: 0 <= wx, wx + b <= ws
             const uint32_t wsh = (uint32_t)wx & 3u, ash = (uint32_t)cx & 3u;
-            Score s;
-            for (int y = q; y < b; y += P) {
+            RowScore s;
+            for (int y = ls.q; y < b; y += ls.P) {
                 const uint32_t* arow = anc + (cy + y) * na + (cx >> 2);
                 const uint32_t* wrow = win + (wy + y) * wd + (wx >> 2);
 #pragma unroll 4
                 for (int k = 0; k < nd; ++k) {
                     uint32_t a = arow[k];
-                    uint32_t v = __builtin_amdgcn_alignbyte(wrow[k + 1], wrow[k], wsh);
+                    uint32_t v = window_dword(wrow, k, wsh);
                     if (!BS) {                                   // a child may start and end inside a dword
-                        a = __builtin_amdgcn_alignbyte(arow[k + 1], a, ash);
+                        a = window_dword(arow, k, ash);
                         if (k == nd - 1) { a &= tail; v &= tail; }
                     }
                     s.add(a, v, pnorm);
                 }
             }
-            uint32_t part = s.value(pnorm);
-            for (int w = 1; w < P; w <<= 1) part += (uint32_t)__shfl_xor((int)part, w, 64);
-            const uint32_t order = (ox == r && oy == r) ? 0u : (uint32_t)c + 1u;
-            if (ok && q == 0) atomicMin(&key[base + child], (part << 6) | order);
+            const uint32_t cost = ls.sum(s.value(pnorm));
+            if (ok && ls.q == 0) atomicMin(&key[base + child], (cost << 6) | sq.order(c, ox, oy));
         }
         wave_lds_fence();
         if (lane < (1 << (2 * d))) {                             // the winners' vectors, for the next depth and the cells
-            const uint32_t order = key[base + lane] & 63u;
             const int parent = d == 1 ? 0 : 1 + (lane >> 2);
-            int ox = 0, oy = 0;
-            if (order != 0u) {
-                const int c = (int)order - 1;
-                ox = small_div(c, n) - r;
-                oy = c - small_div(c, n) * n - r;
-            }
+            int ox, oy;
+            sq.offset(key[base + lane] & 63u, &ox, &oy);
             relx[base + lane] = relx[parent] + ox;
             rely[base + lane] = rely[parent] + oy;
         }
@@ -265,20 +241,13 @@ __global__ void __launch_bounds__(PRED_THREADS) k_compensate_vbs(const uint8_t* 
     predict_rows(px, cur + (long long)f * plane_stride, H, W, pitch, out + (long long)f * out_stride, out_pitch, sse + f);
 }
 
-template <int BS, int DEPTH>
-void vbs_launch(hipStream_t stream, const VbsArgs& a, int pairs)
-{
-    hipLaunchKernelGGL((k_vbs<BS, DEPTH>), dim3((unsigned)((a.wb + VBS_WAVES - 1) / VBS_WAVES), (unsigned)a.hb, (unsigned)pairs),
-                       dim3(VBS_THREADS), (size_t)VBS_WAVES * a.slice_bytes, stream, a);
-}
-
 }  // namespace
 
 // the argument rules of vbs.py
 int vbs_check_args(const char* who, int bs, int depth, int radius, int pnorm, int penalty)
 {
     GME_REQUIRE(depth >= 0 && depth <= VBS_MAX_DEPTH, GME_ERR_ARG, "%s: depth %d (0 .. %d)", who, depth, VBS_MAX_DEPTH);
-    GME_REQUIRE(pnorm == 0 || pnorm == 1, GME_ERR_ARG, "%s: pnorm_distance %d out of range (bbme.py:60)", who, pnorm);
+    if (int rc = require_pnorm(who, pnorm)) return rc;
     GME_REQUIRE(bs >= 1 && bs <= VBS_MAX_BS && bs % (1 << depth) == 0 && (bs >> depth) >= VBS_MIN_LEAF, GME_ERR_ARG,
                 "%s: block_size %d with depth %d (a multiple of %d, at most %d, leaves of at least %d)", who, bs, depth, 1 << depth,
                 VBS_MAX_BS, VBS_MIN_LEAF);
@@ -297,30 +266,24 @@ int launch_vbs(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long 
     int rc = vbs_check_args("variable-block-size tree", bs, depth, radius, pnorm, penalty);
     if (rc) return rc;
     const int hb = H / bs, wb = W / bs;
-    ctx->plan[0] = 0; ctx->plan_patches = 0;
     const bool compiled = depth == 2 && (bs == 16 || bs == 32);
-    if (compiled) plan_note(ctx, 0, "k_vbs<%d,2> r %d penalty %d, %d x %d roots, one wave each", bs, radius, penalty, hb, wb);
-    else plan_note(ctx, 0, "k_vbs<0,0> bs %d depth %d r %d penalty %d, %d x %d roots, one wave each", bs, depth, radius, penalty, hb, wb);
-    if (pairs == 0 || hb == 0 || wb == 0) return GME_OK;
-    GME_REQUIRE(hb <= 65535, GME_ERR_ARG, "%d block rows", hb);
     VbsArgs a;
     a.stride = plane_stride; a.H = H; a.W = W; a.pitch = pitch;
     a.hb = hb; a.wb = wb; a.bs = bs; a.depth = depth; a.radius = radius; a.pnorm = pnorm; a.penalty = (uint32_t)penalty;
-    const int side = bs + 2 * depth * radius;
-    a.anchor_bytes = (bs * ((bs + 3) / 4 + 1) * 4 + 15) & ~15;
-    a.window_bytes = (side * ((side + 3) / 4 + 1) * 4 + 15) & ~15;
+    a.anchor_bytes = window_bytes(bs);
+    a.window_bytes = window_bytes(bs + 2 * depth * radius);
     a.slice_bytes = a.anchor_bytes + a.window_bytes + ((3 * VBS_NODE_SLOTS * 4 + 15) & ~15);
     const long long per = (long long)hb * wb, per_cells = per << (2 * depth);
-    for_plane_chunks(pairs, [&](int k, int n) {
+    auto note = [&] {
+        if (compiled) plan_note(ctx, 0, "k_vbs<%d,2> r %d penalty %d, %d x %d roots, one wave each", bs, radius, penalty, hb, wb);
+        else plan_note(ctx, 0, "k_vbs<0,0> bs %d depth %d r %d penalty %d, %d x %d roots, one wave each", bs, depth, radius, penalty, hb, wb);
+    };
+    return launch_wave_blocks(ctx, pairs, hb, wb, a.slice_bytes, a, note, [&](int k) {
         a.prev = prev + (long long)k * plane_stride; a.cur = cur + (long long)k * plane_stride;
         a.mf = mf + per * k * 2; a.cost = cost + per * k;
         a.leaf = leaf + per_cells * k * 2; a.dmap = dmap + per_cells * k;
-        if (!compiled) vbs_launch<0, 0>(ctx->stream, a, n);
-        else if (bs == 16) vbs_launch<16, 2>(ctx->stream, a, n);
-        else vbs_launch<32, 2>(ctx->stream, a, n);
+        return !compiled ? k_vbs<0, 0> : bs == 16 ? k_vbs<16, 2> : k_vbs<32, 2>;
     });
-    GME_HIP_TRY(hipGetLastError());
-    return GME_OK;
 }
 
 // out planes = subpel.compensate_integer of the prev planes by leaf[pairs][hg][wg][2] at cell size g, sse[pairs] (device, zeroed

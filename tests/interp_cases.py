@@ -53,9 +53,10 @@ def stripes():
 # ---- noise ------------------------------------------------------------------------------------------------------------------
 # (shape, block_size, search_window): frame sizes that are no multiple of the block (48 x 80 at 16 is), the compiled instances
 # (16 and 32) and the run-time one, rows of 12 and 24 bytes, no search at window 0, the largest windows (80 x 80 at 64 and 8),
-# a single block whose every window pixel beyond it is clamped, and the smallest block there is
+# a single block whose every window pixel beyond it is clamped, the smallest block there is, and rows of 6 and 10 bytes, whose
+# last dword holds bytes beyond the block
 NOISE = (((37, 53), 8, 3), ((37, 53), 12, 5), ((48, 80), 16, 8), ((48, 80), 16, 0), ((70, 101), 32, 4), ((70, 101), 24, 8),
-         ((130, 135), 64, 8), ((16, 16), 16, 8), ((4, 4), 4, 1))
+         ((130, 135), 64, 8), ((16, 16), 16, 8), ((4, 4), 4, 1), ((37, 53), 6, 3), ((37, 53), 10, 5))
 
 
 def noise_biases(case, pnorm):
