@@ -15,9 +15,13 @@
 //      against a zero reference (four sliding 4-byte sums) whose accumulator adds up the rows; an
 //      output row is the difference of two of those cumulative sums plus the neighbour lane's
 //      (DPP wave_shl:1), i.e. the other 4-byte half -- no per-frame table, no extra HBM traffic;
-//   B  LB for all NC^2 candidates of the wave's block: four S8 reads, two v_perm_b32 and two
-//      v_sad_u16 per candidate; per lane: min LB of each of its R patches (R rows x 4 columns);
-//   C  UB := SAD of the candidate with the smallest LB and of the zero vector (64 lanes x 1 dword);
+//   B  LB for all NC^2 candidates of the wave's block: per lane and candidate row 2 (R + 2) S8 reads and 4 (R + 2)
+//      v_perm_b32 that pair S8(y, x) with S8(y + 8, x) -- the right-hand pair of candidate column x is the left-hand
+//      pair of column x + 8 -- and two v_sad_u16 per candidate; per lane: the smallest LB of each of its R patches
+//      (R rows x 4 columns), the bound alone, no candidate index;
+//   C  UB := SAD of three real candidates (64 lanes x 1 dword): the zero vector, the vector the workgroup's previous tile
+//      ended with, and the candidate with the smallest LB -- a wave minimum over (LB, lane) names the first lane that
+//      holds it, the wave's lanes then recompute that lane's candidates, one each, and a ballot names the first one;
 //   D  patches with min LB <= UB go to a workgroup-wide list (LDS atomics);
 //   E  the list is processed 64*NB patches at a time, one patch per lane (R x 16 x 4
 //      v_qsad_pk_u16_u8 against the anchor read from LDS -- lanes of one wave may serve different
@@ -40,23 +44,40 @@ using namespace sea;
 //   GUARD_ALL  (frame corners, left and right edge, partial size classes with their padding candidates)  the start
 //       value also takes PENALTY for a column above hi_c: one v_cndmask_b32 per candidate on a lane mask formed
 //       once per column; below lo_c whole patches go (lo_c is a multiple of 4), after the loop.
-// A penalised bound lies above 65280, the largest real one (and SAD), and below 2^18, so its key fits 32 bits
-// and stays above every real key.  The table rows and quads such a candidate reads exist (the table is sized by
-// R, not by the frame); what they hold does not matter.  A patch whose smallest key is a penalised one has no
-// valid candidate: 0xFFFFFFFF, as if no key had been formed.
+// A penalised bound lies above 65280, the largest real one (and SAD), and below 2^18.  The table rows and quads such a
+// candidate reads exist (the table is sized by R, not by the frame); what they hold does not matter.  pmin[k] is the
+// smallest bound of patch k, without an index; a patch whose smallest bound is a penalised one has no valid candidate:
+// 0xFFFFFFFF, as if no bound had been formed.  Shifted by 13 that is 0xFFFFE000, above every real key
+// (FIRST_INVALID_KEY = FIRST_INVALID_BOUND << 13), which is what everything downstream keeps seeing.
 constexpr int GUARD_NONE = 0, GUARD_ROWS = 1, GUARD_ALL = 2;
 constexpr uint32_t PENALTY = 1u << 17;
 constexpr uint32_t FIRST_INVALID_KEY = 65536u << 13;     // above every real key, not above any penalised one
-template <int R, int GUARD>
-__device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int prow, int q, uint32_t a01, uint32_t a23,
-                                             int lo_r, int hi_r, int lo_c, int hi_c, uint32_t (&pkey)[R])
+constexpr uint32_t FIRST_INVALID_BOUND = FIRST_INVALID_KEY >> 13;
+// [lo(t), lo(b)] (odd = false) or [hi(t), hi(b)] of two packed u16 pairs
+__device__ __forceinline__ uint32_t pair_u16(uint32_t t, uint32_t b, bool odd)
+{
+    return __builtin_amdgcn_perm(b, t, odd ? 0x07060302u : 0x05040100u);
+}
+// The two operand pairs of the candidate whose quadrant sums are tl, tr (row y, columns x and x + 8) and bl, br (row y + 8), each
+// in the halves `odd` picks: vertically ([tl, bl], [tr, br]) against the anchor sums [A0, A2] and [A1, A3], or horizontally
+// ([tl, tr], [bl, br]) against [A0, A1] and [A2, A3].  pa / pb below are the anchor sums in the packing of the instance.
+template <bool VERT>
+__device__ __forceinline__ void candidate_pairs(uint32_t tl, uint32_t tr, uint32_t bl, uint32_t br, bool odd, uint32_t* first, uint32_t* second)
+{
+    *first = VERT ? pair_u16(tl, bl, odd) : pair_u16(tl, tr, odd);
+    *second = VERT ? pair_u16(tr, br, odd) : pair_u16(bl, br, odd);
+}
+template <int R, int GUARD, bool VERT>
+__device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int prow, int q, uint32_t pa, uint32_t pb,
+                                             int lo_r, int hi_r, int lo_c, int hi_c, uint32_t (&pmin)[R])
 {
     // R >= 4 keeps the earlier form for every edge block (GUARD_ALL there; GUARD_ROWS is not used), which skips invalid
-    // rows and candidates by compares of their own: in the <5, 7, 38> instance, already at its 80 VGPRs, the column
-    // masks spilled three VGPRs and GUARD_ROWS beside the earlier form one
+    // rows and candidates by compares of their own: in the <5, 7, 38> instance, at 80 VGPRs when that was tried, the column
+    // masks spilled three VGPRs and GUARD_ROWS beside the earlier form one ("Trimmed").  It builds both
+    // operand pairs per candidate, as every instance without vertical pairs does (vertical_pairs below)
     constexpr bool SKIP = GUARD == GUARD_ALL && R >= 4;
 #pragma unroll
-    for (int k = 0; k < R; ++k) pkey[k] = 0xFFFFFFFFu;
+    for (int k = 0; k < R; ++k) pmin[k] = 0xFFFFFFFFu;
     constexpr uint32_t penalty = PENALTY;
     uint32_t seed[R];
 #pragma unroll
@@ -76,18 +97,42 @@ __device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int pr
             uint64_t t[R + 2], b[R + 2];                   // quads k and k + 2 for k < R: R + 2 distinct ones
 #pragma unroll
             for (int k = 0; k < R + 2; ++k) { t[k] = top[k]; b[k] = bot[k]; }
+            if constexpr (SKIP || !VERT) {
+                // both pairs built per candidate (the skip form decides per lane which candidates it needs at all)
 #pragma unroll
-            for (int k = 0; k < R; ++k) {
-                if (SKIP && (4 * k > nhi || 4 * k + 3 < nlo)) continue;
+                for (int k = 0; k < R; ++k) {
+                    if (SKIP && (4 * k > nhi || 4 * k + 3 < nlo)) continue;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (SKIP && (4 * k + e < nlo || 4 * k + e > nhi)) continue;
-                    const uint32_t sel = (e & 1) ? 0x07060302u : 0x05040100u;
-                    const uint32_t tp = __builtin_amdgcn_perm((uint32_t)(t[k + 2] >> (32 * (e >> 1))), (uint32_t)(t[k] >> (32 * (e >> 1))), sel);
-                    const uint32_t bt = __builtin_amdgcn_perm((uint32_t)(b[k + 2] >> (32 * (e >> 1))), (uint32_t)(b[k] >> (32 * (e >> 1))), sel);
-                    const uint32_t start = (GUARD != GUARD_ALL || SKIP || 4 * k + e <= nhi) ? seed[i] : penalty;
-                    const uint32_t lb = __builtin_amdgcn_sad_u16(tp, a01, __builtin_amdgcn_sad_u16(bt, a23, start));
-                    pkey[k] = min(pkey[k], (lb << 13) + (uint32_t)((4 * k + e) * R + i));
+                    for (int e = 0; e < 4; ++e) {
+                        if (SKIP && (4 * k + e < nlo || 4 * k + e > nhi)) continue;
+                        const int sh = 32 * (e >> 1);
+                        uint32_t first, second;
+                        candidate_pairs<VERT>((uint32_t)(t[k] >> sh), (uint32_t)(t[k + 2] >> sh), (uint32_t)(b[k] >> sh), (uint32_t)(b[k + 2] >> sh), e & 1, &first, &second);
+                        const uint32_t start = (GUARD != GUARD_ALL || SKIP || 4 * k + e <= nhi) ? seed[i] : penalty;
+                        pmin[k] = min(pmin[k], __builtin_amdgcn_sad_u16(first, pa, __builtin_amdgcn_sad_u16(second, pb, start)));
+                    }
+                }
+            } else {
+                // vertical pairs: column c = 4m + e of the row gives vp[m][e] = [S(y, c), S(y+8, c)]; candidate column j
+                // matches vp of column j against [A0, A2] and vp of column j + 8 against [A1, A3], so the right-hand pairs
+                // of column group k are the left-hand pairs of group k + 2: 4 (R + 2) pairs per row, each built once, in
+                // the order the groups need them (quads 2 .. R - 1 stay live until their second use)
+                uint32_t vp[R + 2][4];
+#pragma unroll
+                for (int k = 0; k < R; ++k) {
+#pragma unroll
+                    for (int m = (k < 2 ? k : k + 2); m <= k + 2; m += 2)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            vp[m][e] = pair_u16((uint32_t)(t[m] >> (32 * (e >> 1))), (uint32_t)(b[m] >> (32 * (e >> 1))), e & 1);
+                    uint32_t lb[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const uint32_t start = (GUARD != GUARD_ALL || 4 * k + e <= nhi) ? seed[i] : penalty;
+                        lb[e] = __builtin_amdgcn_sad_u16(vp[k][e], pa, __builtin_amdgcn_sad_u16(vp[k + 2][e], pb, start));
+                    }
+                    pmin[k] = min(min(pmin[k], lb[0]), lb[1]);
+                    pmin[k] = min(min(pmin[k], lb[2]), lb[3]);
                 }
             }
         }
@@ -97,8 +142,44 @@ __device__ __forceinline__ void lower_bounds(const uint64_t* sp0, int XQ, int pr
     if constexpr (GUARD != GUARD_NONE && !SKIP) {
 #pragma unroll
         for (int k = 0; k < R; ++k)
-            if (pkey[k] >= FIRST_INVALID_KEY || (GUARD == GUARD_ALL && 4 * k < nlo)) pkey[k] = 0xFFFFFFFFu;
+            if (pmin[k] >= FIRST_INVALID_BOUND || (GUARD == GUARD_ALL && 4 * k < nlo)) pmin[k] = 0xFFFFFFFFu;
     }
+}
+
+// C: the candidate phase B's minimum names, recovered once per wave.  `bl` is the first lane that holds the block's
+// smallest bound `mb`; lane l of the wave recomputes candidate `local = l` of that lane ((4k + e) R + i, the numbering the
+// per-candidate keys used; two rounds at R = 5, where a lane has 100) from the four table entries, with the validity the
+// lane applied, and the first lane that finds `mb` on a valid candidate names it: smallest bound, then smallest lane,
+// then smallest local index.  Returns the scan index.  Wave-uniform; every lane must call it (ballot).
+template <int R, bool VERT>
+__device__ __forceinline__ int min_bound_candidate(const uint64_t* s8blk, int XQ, int NC, int bl, uint32_t mb, uint32_t pa, uint32_t pb,
+                                                   int lo_r, int hi_r, int lo_c, int hi_c, int lane)
+{
+    const int col0 = (bl & 3) * 4 * R, row0 = (bl >> 2) * R;
+    const uint16_t* tab = (const uint16_t*)(s8blk + row0 * XQ + (bl & 3) * R);     // S8 as u16: 4 XQ per row
+    int loc = 0;
+    bool found = false;
+#pragma unroll
+    for (int base = 0; base < 4 * R * R; base += 64) {
+        const int l = base + lane;
+        const int ce = l / R, li = l - ce * R;
+        bool hit = false;
+        if (4 * R * R - base >= 64 || l < 4 * R * R) {
+            const uint16_t* p = tab + li * 4 * XQ + ce;
+            uint32_t first, second;
+            candidate_pairs<VERT>(p[0], p[8], p[32 * XQ], p[32 * XQ + 8], false, &first, &second);
+            const uint32_t lb = __builtin_amdgcn_sad_u16(first, pa, __builtin_amdgcn_sad_u16(second, pb, 0u));
+            const int ci = col0 + ce, ri = row0 + li;
+            hit = lb == mb && ci >= lo_c && ci <= hi_c && ri >= lo_r && ri <= hi_r;
+        }
+        const unsigned long long m = __ballot(hit);
+        if (!found && m) {
+            loc = base + __builtin_ctzll(m);
+            found = true;
+        }
+    }
+    const int ce = loc / R, li = loc - ce * R;
+    return (col0 + ce) * NC + row0 + li;
 }
 
 // C2's evaluation, four lanes per patch: lane `sub` of a quad takes anchor rows 4*sub .. 4*sub+3 of the patch's block (R+3 window rows,
@@ -188,9 +269,9 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaGeo& d, int H, int 
 // Returns true (workgroup-uniform) when the tile was handed to the redo kernel instead (SeaDev::redo_list).
 // `d` is the geometry; frame size, ordered evaluation, redo list and result plane come from the argument segment
 // (bbme_sea_common.h: launch_args), once for phases A' .. D and once behind phase D's barrier for the rest.
-template <int R, bool FIXED>
+template <int R, bool FIXED, bool VERT>
 __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                            uint32_t mine, uint32_t a01, uint32_t a23, int tid, int tile_id)
+                                            uint32_t mine, uint32_t pa, uint32_t pb, int tid, int tile_id)
 {
     // phase C2 and phase E with four lanes per patch (a quarter of the latency the other waves wait for) from R = 3 on:
     // +11 % at sw 32, +3 % at sw 16
@@ -222,35 +303,35 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
     uint32_t ub_key = 0xFFFFFFFFu;
     if (wave_ok) {
         const int lo_c = max(0, d.sw - c0), hi_c = min(NC - 1, c->W - 16 - c0 + d.sw);
-        // per patch k: min over its candidates of (LB << 13) + local, local = (4k+e)*R + i (any
-        // consistent index will do here: the bound only has to name one good candidate)
-        uint32_t pkey[R];
-        const uint64_t* sp0 = s8 + (16 * wb.wr + prow * R) * XQ + wb.wc * 4 + q * R;
+        // per patch k: the smallest bound of its candidates, no index (a patch without valid candidates: 0xFFFFFFFF)
+        uint32_t pmin[R];
+        const uint64_t* s8blk = s8 + 16 * wb.wr * XQ + wb.wc * 4;                        // the block's corner of the table
+        const uint64_t* sp0 = s8blk + prow * R * XQ + q * R;
         const bool cols_inside = NC == 16 * R && lo_c == 0 && hi_c == NC - 1;           // and no padding candidates
         if (rows_inside && cols_inside)                                                // wave-uniform, all three
-            lower_bounds<R, GUARD_NONE>(sp0, XQ, prow, q, a01, a23, lo_r, hi_r, lo_c, hi_c, pkey);
+            lower_bounds<R, GUARD_NONE, VERT>(sp0, XQ, prow, q, pa, pb, lo_r, hi_r, lo_c, hi_c, pmin);
         else if (R <= 3 && cols_inside)                                                // R >= 4: see lower_bounds
-            lower_bounds<R, GUARD_ROWS>(sp0, XQ, prow, q, a01, a23, lo_r, hi_r, lo_c, hi_c, pkey);
+            lower_bounds<R, GUARD_ROWS, VERT>(sp0, XQ, prow, q, pa, pb, lo_r, hi_r, lo_c, hi_c, pmin);
         else
-            lower_bounds<R, GUARD_ALL>(sp0, XQ, prow, q, a01, a23, lo_r, hi_r, lo_c, hi_c, pkey);
+            lower_bounds<R, GUARD_ALL, VERT>(sp0, XQ, prow, q, pa, pb, lo_r, hi_r, lo_c, hi_c, pmin);
         // pkd[k] = (smallest bound of patch k) << 13 | scan index of the patch's FIRST candidate: no candidate of the
         // patch can have a smaller key (sad << 13 | scan index).  A patch without valid candidates keeps 0xFFFFE000 | index,
         // above every real key (sad <= 65280 < 2^16).
         const uint32_t first_idx = (uint32_t)((q * 4 * R) * NC + prow * R);
-        uint32_t pkd[R], lb_key = 0xFFFFFFFFu;
+        uint32_t pkd[R], lane_min = 0xFFFFFFFFu;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            pkd[k] = (pkey[k] & 0xFFFFE000u) | (first_idx + (uint32_t)(4 * k * NC));
-            lb_key = min(lb_key, pkey[k]);
+            pkd[k] = (pmin[k] << 13) | (first_idx + (uint32_t)(4 * k * NC));
+            lane_min = min(lane_min, pmin[k]);
         }
-        const uint32_t lane_lb = lb_key;                               // this lane's smallest bound << 13 (| local index)
-        if (lb_key != 0xFFFFFFFFu) lb_key += (uint32_t)lane << 7;      // local < 4R*R <= 100 < 128
-        // ---- C: upper bound from two real candidates (cooperative 16x16 SAD, one dword per lane)
-        lb_key = wave_min_u32(lb_key);
+        const uint32_t lane_lb = lane_min << 13;                       // this lane's smallest bound << 13 (none: 0xFFFFE000)
+        uint32_t lb_key = lane_min != 0xFFFFFFFFu ? lane_lb + ((uint32_t)lane << 7) : 0xFFFFFFFFu;
+        // ---- C: upper bound from three real candidates (cooperative 16x16 SAD, one dword per lane)
+        lb_key = wave_min_u32(lb_key);                                 // smallest bound << 13 | first lane that holds it << 7
         {
-            const int bl = (lb_key >> 7) & 63, loc = lb_key & 127;     // decode lane and local index
-            const int ce = loc / R, li = loc - ce * R;
-            const int idx1 = ((bl & 3) * 4 * R + ce) * NC + (bl >> 2) * R + li;       // min-LB candidate
+            // the zero vector is always valid, so the minimum is a real bound and one of the lane's candidates has it
+            const int idx1 = min_bound_candidate<R, VERT>(s8blk, XQ, NC, (int)(lb_key >> 7) & 63, lb_key >> 13, pa, pb,
+                                                          lo_r, hi_r, lo_c, hi_c, lane);   // min-LB candidate
             const int idx0 = d.sw * NC + d.sw;                                       // zero vector
             const int arow = lane >> 2, aj = lane & 3;
             uint32_t packed = 0;                           // two 16x16 SADs (<= 65280 each) in one register
@@ -291,7 +372,7 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
         if constexpr (E4) {
             // crowded?  Lanes with a surviving patch are counted first (one ballot); the exact count only where it matters
             const int engage = c->engage;
-            if (c->quota > 0 && __popcll(__ballot((lane_lb & 0xFFFFE000u) < ub_key)) > engage / 3) {
+            if (c->quota > 0 && __popcll(__ballot(lane_lb < ub_key)) > engage / 3) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) n_w += __popcll(__ballot(pkd[k] < ub_key));
                 if (n_w > engage) {
@@ -531,22 +612,26 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
 
 // What the shared tile drivers (bbme_sea_common.h: one_tile, persistent_tiles) need from this kernel.
 // FIXED: the geometry-fixed instances (fix_geometry), whose strides are compile-time constants
-template <int R, bool FIXED = false>
+// VERT: phase B pairs its operands vertically (lower_bounds); the anchor sums are packed to match
+template <int R, bool FIXED = false, bool VERT = true>
 struct MaeTile {
-    struct Pre { uint32_t a01, a23; };
+    struct Pre { uint32_t pa, pb; };                       // anchor quadrant sums: [A0, A2], [A1, A3] (VERT) or [A0, A1], [A2, A3]
     static __device__ __forceinline__ Pre prep(uint32_t* lds, const Layout& L, int wave, int lane, bool wave_ok, uint32_t mine)
     {
         Pre p = { 0, 0 };
         if (wave_ok) {
             lds[L.anchor + wave * ANCHOR_STRIDE + lane] = mine;
-            anchor_quadrants(mine, &p.a01, &p.a23);
+            uint32_t a01, a23;
+            anchor_quadrants(mine, &a01, &a23);            // shared with the MSE kernel, which pairs horizontally
+            p.pa = VERT ? pair_u16(a01, a23, false) : a01;
+            p.pb = VERT ? pair_u16(a01, a23, true) : a23;
         }
         return p;
     }
     static __device__ __forceinline__ bool phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
                                                   uint32_t mine, const Pre& p, int tid, int tile_id)
     {
-        return tile_phases<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, tid, tile_id);
+        return tile_phases<R, FIXED, VERT>(d, lds, L, pair, trow, bcol0, mine, p.pa, p.pb, tid, tile_id);
     }
     static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.best + 2 * wave + 1; }
 };
@@ -559,6 +644,10 @@ __global__ void __launch_bounds__(1024) k_exh_sea16(SeaDev d)
     one_tile<MaeTile<R>>(g, lds, layout_of(g, R));
 }
 
+// Which persistent instances pair vertically ("Bound minima"): all but the ones the shared pairs would
+// cost a spilled VGPR of the prefetched tile
+constexpr bool vertical_pairs(int R, int NV) { return !(R == 5 && NV == 16); }
+
 template <int R, int NV, int GEO = 0>
 __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p(SeaDev d)
 {
@@ -567,7 +656,7 @@ __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p(SeaDev d)
     fix_geometry<R, GEO>(g);
     const Layout L = layout_of(g, R);
     if ((threadIdx.x & 63) == 0) lds[L.best + 2 * (threadIdx.x >> 6) + 1] = (uint32_t)(g.sw * (2 * g.sw + 16) + g.sw);   // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MaeTile<R, GEO != 0>>(g, lds, L);
+    persistent_tiles<NV, MaeTile<R, GEO != 0, vertical_pairs(R, NV)>>(g, lds, L);
 }
 
 // What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.
