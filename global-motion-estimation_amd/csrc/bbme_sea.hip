@@ -53,6 +53,36 @@ constexpr int GUARD_NONE = 0, GUARD_ROWS = 1, GUARD_ALL = 2;
 constexpr uint32_t PENALTY = 1u << 17;
 constexpr uint32_t FIRST_INVALID_KEY = 65536u << 13;     // above every real key, not above any penalised one
 constexpr uint32_t FIRST_INVALID_BOUND = FIRST_INVALID_KEY >> 13;
+// *p += v in LDS by the calling lanes, each on its own; returns what the word held.  Written out, because an atomicAdd is
+// rewritten into a wave-wide aggregation (ballot, v_mbcnt, multiply, one lane's add, broadcast) even where the caller has
+// aggregated already and calls it from one lane.  The wait is part of it: the compiler does not count this instruction.
+__device__ __forceinline__ uint32_t lds_add_rtn(uint32_t* p, uint32_t v)
+{
+    uint32_t old;
+    const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)p;
+    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(old) : "v"(addr), "v"(v) : "memory");
+    return old;
+}
+// A list entry (phase D's list, phase C2's own slots): bound | k << 16 | lane << 19 | wave << 25 -- the patch of phase B's
+// lane (prow, q), column group k, of the block of wave `wave` (at most 16: bits 25 .. 28) -- and in bit 29 whether that
+// block's whole window lies inside the frame with no padding candidates (phase B's GUARD_NONE case).  The listing wave
+// knows that as a wave-uniform value; the lanes that score the entry serve different blocks and would each have to
+// work it out from the block's position.
+constexpr uint32_t ENT_INTERIOR = 1u << 29;
+// wave / tc for a wave number below 16 (a list entry's): a shift where the tile's width is a compile-time power of two
+// (the geometry-fixed 2x4 instance), the multiply-shift division otherwise
+__device__ __forceinline__ int wave_row(const SeaGeo& d, int w)
+{
+    if (__builtin_constant_p(d.tc) && (d.tc & (d.tc - 1)) == 0) return w >> __builtin_ctz((unsigned)d.tc);
+    return div_small(w, d.magic_tc);
+}
+// some value, at no instruction: for registers whose content is exchanged but never used (lanes without work in a DPP sum)
+__device__ __forceinline__ uint64_t any_u64()
+{
+    uint32_t lo, hi;
+    asm volatile("" : "=v"(lo), "=v"(hi));
+    return ((uint64_t)hi << 32) | lo;
+}
 // [lo(t), lo(b)] (odd = false) or [hi(t), hi(b)] of two packed u16 pairs
 __device__ __forceinline__ uint32_t pair_u16(uint32_t t, uint32_t b, bool odd)
 {
@@ -186,18 +216,20 @@ __device__ __forceinline__ int min_bound_candidate(const uint64_t* s8blk, int XQ
 // 16*R QSADs); the four partial u16x4 sums are added inside the quad with DPP moves, then lane `sub` turns column `sub`
 // of the patch into keys (sad << 13 | scan index).  Returns the quad's smallest key (0xFFFFFFFF: none).  Every lane of
 // the wave must call it (DPP); a quad is uniform in `ent` and `active`.
-// ent = wave << 25 | lane << 19 | k << 16 | bound: the patch of phase B's lane (prow, q), column group k, of block `wave`.
+// ent: a list entry (ENT_INTERIOR above).
 template <int R>
 __device__ __forceinline__ uint32_t eval_patch_quad(const SeaGeo& d, int H, int W, const uint32_t* win, const uint32_t* anchor, uint32_t ent,
                                                     bool active, int sub, int trow, int bcol0, int NC)
 {
-    const int w2 = ent >> 25, l2 = (ent >> 19) & 63, k2 = (ent >> 16) & 7;
-    const int wr2 = div_small(w2, d.magic_tc), wc2 = w2 - wr2 * d.tc;     // the patch's block inside the tile
+    const int w2 = (ent >> 25) & 15, l2 = (ent >> 19) & 63, k2 = (ent >> 16) & 7;
+    const int wr2 = wave_row(d, w2), wc2 = w2 - wr2 * d.tc;     // the patch's block inside the tile
     const int prow2 = l2 >> 2, q2 = l2 & 3;
     uint64_t acc[R];
 #pragma unroll
-    for (int i = 0; i < R; ++i) acc[i] = 0;
+    for (int i = 0; i < R; ++i) acc[i] = any_u64();          // idle quads add and exchange whatever they hold; nobody reads it
     if (active) {
+#pragma unroll
+        for (int i = 0; i < R; ++i) acc[i] = 0;
         const uint32_t* lrow = win + (16 * wr2 + prow2 * R + 4 * sub) * d.pitch_dw + wc2 * 4 + q2 * R + k2;
         const uint32_t* an = anchor + w2 * ANCHOR_STRIDE + 16 * sub;
 #pragma unroll
@@ -232,13 +264,9 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaGeo& d, int H, int 
     if (active) {
         // every lane of the quad holds the patch's R x 4 sums now; lane `sub` turns column `sub` into keys
         // (R candidates instead of 4 R on one lane)
-        const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
-        const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
-        const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
-        const bool rows_inside2 = NC == 16 * R && lo_r2 == 0 && hi_r2 == NC - 1;
         const int ci = q2 * 4 * R + 4 * k2 + sub, ri0 = prow2 * R;
         const uint32_t shift = (uint32_t)(sub & 1) * 16u;
-        if (rows_inside2 && lo_c == 0 && hi_c == NC - 1) {
+        if (ent & ENT_INTERIOR) {
             // whole window inside the frame: keys relative to the column's first candidate, base added once
 #pragma unroll
             for (int i = 0; i < R; ++i) {
@@ -247,11 +275,15 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaGeo& d, int H, int 
                 key = min(key, (sad << 13) + (uint32_t)i);
             }
             key += (uint32_t)(ci * NC + ri0);
-        } else if (ci >= lo_c && ci <= hi_c) {
+        } else {
+            // an edge block: the window limits are formed here only (lanes of one wave serve different blocks)
+            const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
+            const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
+            const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
 #pragma unroll
             for (int i = 0; i < R; ++i) {
                 const int ri = ri0 + i;
-                if (ri < lo_r2 || ri > hi_r2) continue;
+                if (ci < lo_c || ci > hi_c || ri < lo_r2 || ri > hi_r2) continue;
                 const uint32_t word = (sub & 2) ? (uint32_t)(acc[i] >> 32) : (uint32_t)acc[i];
                 const uint32_t sad = __builtin_amdgcn_ubfe(word, shift, 16u);
                 key = min(key, (sad << 13) | (uint32_t)(ci * NC + ri));
@@ -283,7 +315,7 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
     uint32_t* best = lds + L.best;                         // [NB] keys, 8 bytes apart (low dword used here)
     uint32_t* count = lds + L.count;
     uint64_t* s8 = (uint64_t*)(lds + L.s8);                // [s8_rows][XQ] packed u16 x 4: S8(y, 4s .. 4s+3)
-    uint32_t* work = lds + L.work;                         // [NB*64*R] entries: wave<<25 | lane<<19 | k<<16 | LB
+    uint32_t* work = lds + L.work;                         // [NB*64*R] entries: interior<<29 | wave<<25 | lane<<19 | k<<16 | LB
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const SeaArgs c = launch_args();
@@ -318,6 +350,8 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
         // patch can have a smaller key (sad << 13 | scan index).  A patch without valid candidates keeps 0xFFFFE000 | index,
         // above every real key (sad <= 65280 < 2^16).
         const uint32_t first_idx = (uint32_t)((q * 4 * R) * NC + prow * R);
+        // what this lane's list entries share (ENT_INTERIOR above)
+        const uint32_t ent0 = (rows_inside && cols_inside ? ENT_INTERIOR : 0u) | ((uint32_t)wave << 25) | ((uint32_t)lane << 19);
         uint32_t pkd[R], lane_min = 0xFFFFFFFFu;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -394,7 +428,7 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
                         const unsigned long long m = __ballot(sel);
                         const int rank = base_rank + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                         if (sel && rank < 16) {
-                            own[rank] = ((uint32_t)wave << 25) | ((uint32_t)lane << 19) | ((uint32_t)k << 16) | (pkd[k] >> 13);
+                            own[rank] = ent0 | ((uint32_t)k << 16) | (pkd[k] >> 13);
                             listed_here |= 1u << k;
                         }
                         base_rank += __popcll(m);
@@ -417,18 +451,31 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
         // LB << 13 | index, so a patch whose smallest possible key -- its bound with the scan index of its first
         // candidate -- does not undercut ub_key holds no winner.  On flat content (every cost ties) this
         // leaves nothing behind the first candidate in scan order instead of everything.
+        // One reservation per wave and tile: the R ballots give the wave's total, lane 0 adds it to the list's length, and
+        // lane l writes entry k behind the entries of column groups j < k and of the lanes below it.  (One atomicAdd(count, 1)
+        // per column group is expanded into a ballot, two v_mbcnt, the add by one lane, a wait and a v_readfirstlane each:
+        // R LDS round trips in a row.)  Only the order inside the list differs, which no result depends on.
+        unsigned long long pushes[R];
+        int pushed = 0;
 #pragma unroll
-        for (int k = 0; k < R; ++k)
-            if (pkd[k] < ub_key) {
-                const uint32_t slot = atomicAdd(count, 1u);
-                work[slot] = ((uint32_t)wave << 25) | ((uint32_t)lane << 19) | ((uint32_t)k << 16) | (pkd[k] >> 13);   // LB <= 65280
-            }
-        if (own_lim) {                                     // statistics: what the first bound had left and C2 took or pruned
-            int pushed = 0;
-#pragma unroll
-            for (int k = 0; k < R; ++k) pushed += __popcll(__ballot(pkd[k] < ub_key));
-            if (lane == 0) atomicAdd(count + 4, (uint32_t)(n_w - pushed));
+        for (int k = 0; k < R; ++k) {
+            pushes[k] = __ballot(pkd[k] < ub_key);
+            pushed += __popcll(pushes[k]);
         }
+        if (pushed) {                                      // wave-uniform
+            uint32_t base = 0;
+            if (lane == 0) base = lds_add_rtn(count, (uint32_t)pushed);
+            uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                if (pkd[k] < ub_key)
+                    work[__builtin_amdgcn_mbcnt_hi((uint32_t)(pushes[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pushes[k], slot))] =
+                        ent0 | ((uint32_t)k << 16) | (pkd[k] >> 13);   // LB <= 65280
+                slot += (uint32_t)__popcll(pushes[k]);
+            }
+        }
+        // statistics: what the first bound had left and C2 took or pruned
+        if (own_lim && lane == 0) atomicAdd(count + 4, (uint32_t)(n_w - pushed));
     }
     __syncthreads();
     const SeaArgs ce = launch_args();                      // phases E and F, and the test in front of them
@@ -450,16 +497,19 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
             bool active = e < n;
             uint32_t ent = 0;
             if (active) ent = work[e];
-            const int w2 = ent >> 25, l2 = (ent >> 19) & 63, k2 = (ent >> 16) & 7;
-            const int wr2 = div_small(w2, d.magic_tc), wc2 = w2 - wr2 * d.tc;     // the patch's block inside the tile
+            const int w2 = (ent >> 25) & 15, l2 = (ent >> 19) & 63, k2 = (ent >> 16) & 7;
+            const int wr2 = wave_row(d, w2), wc2 = w2 - wr2 * d.tc;     // the patch's block inside the tile
             const int prow2 = l2 >> 2, q2 = l2 & 3;
             // dropped by a tightened UB (same key rule as phase D); the quad is uniform in `active` (same entry),
             // so the DPP exchange below is safe
-            active = active && (((ent & 0xFFFFu) << 13) | (uint32_t)((q2 * 4 * R + 4 * k2) * NC + prow2 * R)) < best[2 * w2];
+            const uint32_t first2 = (uint32_t)((q2 * 4 * R + 4 * k2) * NC + prow2 * R);     // scan index of the patch's first candidate
+            active = active && (((ent & 0xFFFFu) << 13) | first2) < best[2 * w2];
             uint64_t acc[R];
     #pragma unroll
-            for (int i = 0; i < R; ++i) acc[i] = 0;
+            for (int i = 0; i < R; ++i) acc[i] = any_u64();  // idle quads add and exchange whatever they hold; nobody reads it
             if (active) {
+    #pragma unroll
+                for (int i = 0; i < R; ++i) acc[i] = 0;
                 const uint32_t* lrow = win + (16 * wr2 + prow2 * R + 4 * sub) * d.pitch_dw + wc2 * 4 + q2 * R + k2;
                 const uint32_t* an = anchor + w2 * ANCHOR_STRIDE + 16 * sub;
     #pragma unroll
@@ -493,14 +543,10 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
             if (active) {
                 // every lane of the quad holds the patch's R x 4 sums now; lane `sub` turns column `sub` into keys
                 // (R candidates instead of 4 R on one lane), the quad's minimum goes to the block's best key
-                const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
-                const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
-                const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
-                const bool rows_inside2 = NC == 16 * R && lo_r2 == 0 && hi_r2 == NC - 1;
                 const int ci = q2 * 4 * R + 4 * k2 + sub, ri0 = prow2 * R;
                 const uint32_t shift = (uint32_t)(sub & 1) * 16u;
                 uint32_t key = 0xFFFFFFFFu;
-                if (rows_inside2 && lo_c == 0 && hi_c == NC - 1) {
+                if (ent & ENT_INTERIOR) {
                     // whole window inside the frame: keys relative to the column's first candidate, base added once
     #pragma unroll
                     for (int i = 0; i < R; ++i) {
@@ -508,12 +554,16 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
                         const uint32_t sad = __builtin_amdgcn_ubfe(word, shift, 16u);
                         key = min(key, (sad << 13) + (uint32_t)i);
                     }
-                    key += (uint32_t)(ci * NC + ri0);
-                } else if (ci >= lo_c && ci <= hi_c) {
+                    key += first2 + (uint32_t)(sub * NC);
+                } else {
+                    // an edge block: the window limits are formed here only (lanes of one wave serve different blocks)
+                    const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
+                    const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
+                    const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
     #pragma unroll
                     for (int i = 0; i < R; ++i) {
                         const int ri = ri0 + i;
-                        if (ri < lo_r2 || ri > hi_r2) continue;
+                        if (ci < lo_c || ci > hi_c || ri < lo_r2 || ri > hi_r2) continue;
                         const uint32_t word = (sub & 2) ? (uint32_t)(acc[i] >> 32) : (uint32_t)acc[i];
                         const uint32_t sad = __builtin_amdgcn_ubfe(word, shift, 16u);
                         key = min(key, (sad << 13) | (uint32_t)(ci * NC + ri));
@@ -536,11 +586,11 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
             if (active) {
                 ent = work[e];
                 const uint32_t first = (uint32_t)(((int)((ent >> 19) & 3) * 4 * R + 4 * (int)((ent >> 16) & 7)) * NC + (int)((ent >> 21) & 15) * R);
-                active = (((ent & 0xFFFFu) << 13) | first) < best[2 * (ent >> 25)];      // dropped by a tightened UB
+                active = (((ent & 0xFFFFu) << 13) | first) < best[2 * ((ent >> 25) & 15)];      // dropped by a tightened UB
             }
             if (active) {
-                const int w2 = ent >> 25, l2 = (ent >> 19) & 63, k2 = (ent >> 16) & 7;
-                const int wr2 = div_small(w2, d.magic_tc), wc2 = w2 - wr2 * d.tc;     // the patch's block inside the tile
+                const int w2 = (ent >> 25) & 15, l2 = (ent >> 19) & 63, k2 = (ent >> 16) & 7;
+                const int wr2 = wave_row(d, w2), wc2 = w2 - wr2 * d.tc;     // the patch's block inside the tile
                 const int prow2 = l2 >> 2, q2 = l2 & 3;
                 const uint32_t* lrow = win + (16 * wr2 + prow2 * R) * d.pitch_dw + wc2 * 4 + q2 * R + k2;
                 const uint32_t* an = anchor + w2 * ANCHOR_STRIDE;
@@ -562,13 +612,9 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
                             acc[i] = __builtin_amdgcn_qsad_pk_u16_u8(w[j], ar[j], acc[i]);
                     }
                 }
-                const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
-                const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
-                const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
-                const bool rows_inside2 = NC == 16 * R && lo_r2 == 0 && hi_r2 == NC - 1;
                 const int ci0 = q2 * 4 * R + 4 * k2, ri0 = prow2 * R;
                 uint32_t key = 0xFFFFFFFFu;
-                if (rows_inside2 && lo_c == 0 && hi_c == NC - 1) {
+                if (ent & ENT_INTERIOR) {
                     // whole window inside the frame: keys relative to the patch's first candidate, base added once
     #pragma unroll
                     for (int e4 = 0; e4 < 4; ++e4)
@@ -579,6 +625,9 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
                         }
                     key += (uint32_t)(ci0 * NC + ri0);
                 } else {
+                    const int c02 = (bcol0 + wc2) * 16, r02 = (trow * d.tr + wr2) * 16;
+                    const int lo_c = max(0, d.sw - c02), hi_c = min(NC - 1, W - 16 - c02 + d.sw);
+                    const int lo_r2 = max(0, d.sw - r02), hi_r2 = min(NC - 1, H - 16 - r02 + d.sw);
     #pragma unroll
                     for (int e4 = 0; e4 < 4; ++e4) {
                         const int ci = ci0 + e4;

@@ -261,20 +261,32 @@ __device__ __forceinline__ void box_sums8_ch(const SeaGeo& d, const uint32_t* wi
         // FIXED: both strides are constants, so the reads go by instruction offsets from one base per RB rows and
         // the stores by instruction offsets from a single one.
         int pi = active ? (ch * CH) * d.pitch_dw + sq : 0, oi = (ch * CH) * XQ + sq;
-        uint64_t ring[8], acc = 0;
+        // FIXED: the window rows are read a batch of eight ahead of the rows being summed (all 16 of them at once where a
+        // chunk has no more): every predicated store below is a basic block of its own, which the next read does not
+        // cross, so rows read one by one behind the first store each wait out an LDS round trip.  Run-time geometry
+        // reads row by row: its instances have no registers for rows in flight (the persistent ones would spill).
+        constexpr int ROWS = CH + 7, STEP = FIXED ? 8 : 1, AHEAD = FIXED ? 16 : 1;
+        uint64_t ring[8], acc = 0, w[ROWS];
+        int read = 0;                                              // rows read so far (a constant once unrolled)
 #pragma unroll
-        for (int r = 0; r < CH + 7; ++r) {
-            if constexpr (FIXED) {
-                if (r > 0 && r % RB == 0) {
-                    pi += RB * d.pitch_dw;
-                    asm volatile("" : "+v"(pi));                   // a base register, not an offset too large for the encoding
+        for (int r = 0; r < ROWS; ++r) {
+            if (r % STEP == 0) {
+#pragma unroll
+                for (; read < ROWS && read < r + AHEAD; ++read) {
+                    if constexpr (FIXED) {
+                        if (read > 0 && read % RB == 0) {
+                            pi += RB * d.pitch_dw;
+                            asm volatile("" : "+v"(pi));           // a base register, not an offset too large for the encoding
+                        }
+                        w[read] = *(const u64_a4*)(win + pi + (read % RB) * d.pitch_dw);
+                    } else {
+                        w[read] = *(const u64_a4*)(win + pi);
+                        pi += d.pitch_dw;
+                        asm volatile("" : "+v"(pi));
+                    }
                 }
-                acc = __builtin_amdgcn_qsad_pk_u16_u8(*(const u64_a4*)(win + pi + (r % RB) * d.pitch_dw), 0u, acc);
-            } else {
-                acc = __builtin_amdgcn_qsad_pk_u16_u8(*(const u64_a4*)(win + pi), 0u, acc);
-                pi += d.pitch_dw;
-                asm volatile("" : "+v"(pi));
             }
+            acc = __builtin_amdgcn_qsad_pk_u16_u8(w[r], 0u, acc);
             if (r >= 7) {
                 uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
                 if (r >= 8) { lo -= (uint32_t)ring[r & 7]; hi -= (uint32_t)(ring[r & 7] >> 32); }
@@ -543,7 +555,7 @@ __device__ __forceinline__ void one_tile(const SeaGeo& d, uint32_t* lds, const L
     if (wb.ok) {
         const int pitch = c->pitch;
         const uint8_t* aptr = c->prev + plane + (long long)(wb.brow * 16) * pitch + wb.bcol * 16;
-        mine = *(const uint32_t*)(aptr + (long long)(lane >> 2) * pitch + (lane & 3) * 4);
+        mine = *(const uint32_t*)(aptr + (uint32_t)((lane >> 2) * pitch + (lane & 3) * 4));
     }
     const typename Kern::Pre pre = Kern::prep(lds, L, wave, lane, wb.ok, mine);
     if (lane == 0) lds[Kern::probe_word(L, wave)] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);      // no previous tile: the zero vector
@@ -611,7 +623,10 @@ __device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds,
         // Window rows through a buffer resource over the pair's `cur` plane (H * pitch bytes): rows above or below
         // the frame give offsets outside it and the hardware range check returns 0 -- what the search wants there
         // (bbme.py:157-162 skips such candidates; they never form keys) -- so no per-row guard or branch is left.
-        // Columns outside the plane and threads beyond the staging sweep get an offset that is out of range by itself.
+        // Columns outside the plane and threads beyond the staging sweep get an offset that is out of range by itself,
+        // 2^31, and stays so with the row steps added (u * sstep is far below 2^31; the offset is compared unsigned): no
+        // select per row.  The row step stays in the vector offset -- the range check does not cover the instruction's
+        // scalar offset.
         const int pitch = c->pitch;
         const long long plane = (long long)pair * c->plane_stride;
         const uint8_t* cur = c->cur + plane;
@@ -628,12 +643,14 @@ __device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds,
         const int sstep = d.rstep * pitch;
 #pragma unroll
         for (int u = 0; u < NV; ++u)
-            wv[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, colok ? off0 + u * sstep : off0, 0, 0);
+            wv[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, off0 + u * sstep, 0, 0);
         an_next = 0;
         const WaveBlock wb = wave_block(d, c, trow, bcol0, wave);
         if (wb.ok) {
+            // the block's corner is wave-uniform; the lane's dword lies 15 rows and 12 bytes behind it at most: a 32-bit
+            // offset on a scalar base, no 64-bit multiply-add per lane
             const uint8_t* aptr = c->prev + plane + (long long)(wb.brow * 16) * pitch + wb.bcol * 16;
-            an_next = *(const uint32_t*)(aptr + (long long)(lane >> 2) * pitch + (lane & 3) * 4);
+            an_next = *(const uint32_t*)(aptr + (uint32_t)((lane >> 2) * pitch + (lane & 3) * 4));
         }
     };
     fetch(tile, opaque_tid());
