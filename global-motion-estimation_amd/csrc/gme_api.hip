@@ -1718,7 +1718,8 @@ static int solve_sums(gme_ctx* ctx, int order, int model, const char* who, const
 // The device solve on its own (what gme_seq_gme_device_solve runs between its stages), for callers and tests that hold
 // normal-equation sums: sums[P][15] = F | Sx | Sy -> params_out[P][6] (first components doubled if `project`,
 // motion.py:191-207) and flags_out[P]: bit 1 where a displacement of the h x w model field of those parameters lies within
-// 1e-9 of a rounding tie, bit 4 for a singular system.
+// 1e-9 max(1, S) of a rounding tie (S = |p0| + |p1| (h - 1) + |p2| (w - 1)), bit 4 for a singular system, bit 8 for an
+// ill-conditioned one (k_solve3, gme_kernels.hip).
 extern "C" int gme_solve_fit_sums(gme_ctx* ctx, const double* sums, int pairs, int project, int h, int w, double* params_out,
                                   int32_t* flags_out)
 {
@@ -1778,10 +1779,11 @@ static int seq_device_solve(gme_seq* s, int order, int model, const char* who, i
 // motion.global_motion_estimation + get_motion_field_affine + compensate_frame + the squared error of results.py:50-59,109
 // for every pair in ONE call with ONE host round trip: the 3x3 solves of motion.py:262-264,280-282 run on the device
 // (k_solve3, gme_kernels.hip).  Opt-in (the package uses it under GME_DEVICE_SOLVE=1): LAPACK's last bits are not
-// reproduced, parameters are within rtol 1e-10 of the host path's; flags_out[p] != 0 names the pairs the caller must
-// redo through the host path (a model displacement within 1e-9 of a rounding tie: bit 1 at level 2, bit 2 in the final
-// field; bit 4: a singular system, numpy.linalg.LinAlgError upstream) -- for all other pairs model fields, masks,
-// compensated frames and squared errors are bit-equal to the staged calls'.  Split-phase like them.
+// reproduced, parameters are within 1e-10 max(1, S) of the host path's per term (the header has the bound); flags_out[p] != 0
+// names the pairs the caller must redo through the host path (a model displacement within 1e-9 max(1, S) of a rounding tie:
+// bit 1 at level 2, bit 2 in the final field; bit 4: a singular system, numpy.linalg.LinAlgError upstream; bit 8: an
+// ill-conditioned one) -- for all other pairs model fields, masks, compensated frames and squared errors are bit-equal to
+// the staged calls'.  Split-phase like them.
 extern "C" int gme_seq_gme_device_solve(gme_seq* s, int fd, int bbme_bs, int procedure, int sw, double outlier_fraction,
                                         double* params_out, int64_t* sse_out, int32_t* flags_out)
 {

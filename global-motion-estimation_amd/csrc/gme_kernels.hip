@@ -345,61 +345,97 @@ __device__ __forceinline__ int16_t model_component(double p0, double p1, double 
 // ---------------------------------------------------------------------------
 // Opt-in (GME_DEVICE_SOLVE=1, gme_seq_gme_device_solve): the two 3x3 solves of motion.py:262-264,280-282 on the device, so
 // that a whole estimate is ONE host round trip instead of three.  The reference inverts F with LAPACK (np.linalg.inv); a
-// device solve cannot reproduce LAPACK's last bits (builds already differ by ~1e-13 among themselves), so:
-//   * parameters are promised to rtol 1e-10 only (the tolerance every parity test uses for them anyway);
+// device solve cannot reproduce LAPACK's last bits (builds already differ by ~1e-13 among themselves), so
+// the contract is k_solve_model2's (below), with m_k = (1, h - 1, w - 1) and S = |p0| + |p1| (h - 1) + |p2| (w - 1) over the
+// three terms of one displacement:
+//   * the parameters of an unflagged pair are promised to |dp_k| m_k <= 1e-10 max(1, S) only;
 //   * everything DOWNSTREAM of a solve must stay bit-equal -- model fields, masks, compensated frames.  Those depend on
-//     the parameters only through round-half-even of the model displacements (model_component below), so the kernel
-//     evaluates the field the parameters will be used for and raises the pair's flag when any displacement lies within
-//     `margin` (1e-9) of k + 0.5: such a pair -- and a singular system, for which upstream raises LinAlgError -- is
-//     redone through the host path by the caller.  Elsewhere a 1e-10 relative parameter error cannot move a rounding.
-// One workgroup per pair: thread 0 solves (Gaussian elimination with partial pivoting, every product and sum rounded
-// separately), all threads scan the field.
+//     the parameters only through round-half-even of the model displacements (model_component above), so the kernel
+//     evaluates the field the parameters will be used for and raises the pair's flag for the host path:
+//   4         a non-positive diagonal entry or a zero pivot: a singular system (numpy.linalg.LinAlgError upstream);
+//   8         min |pivot| below SOLVE_PIVOT_RATIO max |pivot| in the equilibrated system: the inliers leave one direction
+//             of the plane almost undetermined and the parameters may be further from LAPACK's than promised (measured,
+//             DESIGN.md "Opt-in device solve");
+//   flag_bit  a displacement of the h x w field of the output within tol = 1e-9 max(1, S) of k + 0.5, or |d| >= 30000, or
+//             NaN.  The three terms of an unflagged displacement, each off by at most 1e-10 max(1, S), cannot move it
+//             across a tie: the field rounds as the host's does.
+// One workgroup per pair: thread 0 solves both right-hand sides in one elimination (Jacobi equilibration D = 1 / sqrt(diag),
+// Gaussian elimination with partial pivoting, x = D z, every operation rounded separately: tests/solve_cases.py restates
+// it bit for bit), all threads scan the field.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ bool solve3(const double* F, const double* S, double* x)
+constexpr double SOLVE_PIVOT_RATIO = 3e-5;       // both device solves: k_solve3 and k_solve_model2
+
+// F x = Sx, F y = Sy -> false (x, y untouched) for a singular system; *pmin / *pmax: the smallest and largest |pivot|
+__device__ __forceinline__ bool solve3(const double* F, const double* Sx, const double* Sy, double* x, double* y, double* pmin,
+                                       double* pmax)
 {
-    double a[3][4];
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) a[r][c] = F[3 * r + c]; a[r][3] = S[r]; }
+    double a[3][5], dsc[3];
+    for (int k = 0; k < 3; ++k) {
+        const double d = F[4 * k];
+        if (!(d > 0.0)) return false;
+        dsc[k] = __ddiv_rn(1.0, __dsqrt_rn(d));
+    }
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) a[r][c] = __dmul_rn(__dmul_rn(F[3 * r + c], dsc[r]), dsc[c]);
+        a[r][3] = __dmul_rn(Sx[r], dsc[r]);
+        a[r][4] = __dmul_rn(Sy[r], dsc[r]);
+    }
+    double lo = INFINITY, hi = 0.0;
     for (int k = 0; k < 3; ++k) {
         int piv = k;
         for (int r = k + 1; r < 3; ++r) if (fabs(a[r][k]) > fabs(a[piv][k])) piv = r;
         if (a[piv][k] == 0.0) return false;
-        if (piv != k) for (int c = 0; c < 4; ++c) { const double t = a[k][c]; a[k][c] = a[piv][c]; a[piv][c] = t; }
+        if (piv != k) for (int c = 0; c < 5; ++c) { const double t = a[k][c]; a[k][c] = a[piv][c]; a[piv][c] = t; }
+        lo = fmin(lo, fabs(a[k][k]));
+        hi = fmax(hi, fabs(a[k][k]));
         for (int r = k + 1; r < 3; ++r) {
             const double m = __ddiv_rn(a[r][k], a[k][k]);
-            for (int c = k; c < 4; ++c) a[r][c] = __dsub_rn(a[r][c], __dmul_rn(m, a[k][c]));
+            for (int c = k; c < 5; ++c) a[r][c] = __dsub_rn(a[r][c], __dmul_rn(m, a[k][c]));
         }
     }
-    for (int k = 2; k >= 0; --k) {
-        double t = a[k][3];
-        for (int c = k + 1; c < 3; ++c) t = __dsub_rn(t, __dmul_rn(a[k][c], x[c]));
-        x[k] = __ddiv_rn(t, a[k][k]);
+    for (int s = 0; s < 2; ++s) {
+        double z[3];
+        for (int k = 2; k >= 0; --k) {
+            double t = a[k][3 + s];
+            for (int c = k + 1; c < 3; ++c) t = __dsub_rn(t, __dmul_rn(a[k][c], z[c]));
+            z[k] = __ddiv_rn(t, a[k][k]);
+        }
+        double* out = s ? y : x;
+        for (int k = 0; k < 3; ++k) out[k] = __dmul_rn(z[k], dsc[k]);
     }
+    *pmin = lo;
+    *pmax = hi;
     return true;
 }
 
-__global__ void __launch_bounds__(256) k_solve3(const double* sums, int pairs, int project, int h, int w, double margin,
-                                                double* params_out, int32_t* flags, int flag_bit)
+__global__ void __launch_bounds__(256) k_solve3(const double* sums, int pairs, int project, int h, int w, double* params_out,
+                                                int32_t* flags, int flag_bit)
 {
     __shared__ double p[6];
     __shared__ int bad;
     const int pair = blockIdx.x;
     if (threadIdx.x == 0) {
         const double* s = sums + (long long)pair * 15;
-        double ax[3] = { 0, 0, 0 }, ay[3] = { 0, 0, 0 };
-        bad = (solve3(s, s + 9, ax) && solve3(s, s + 12, ay)) ? 0 : 4;           // 4: singular system (numpy.linalg.LinAlgError upstream)
+        double ax[3] = { 0, 0, 0 }, ay[3] = { 0, 0, 0 }, pmin = 0.0, pmax = 0.0;
+        int b = solve3(s, s + 9, s + 12, ax, ay, &pmin, &pmax) ? 0 : 4;
+        if (b == 0 && !(pmin >= __dmul_rn(SOLVE_PIVOT_RATIO, pmax))) b = 8;
         if (project) { ax[0] = __dmul_rn(ax[0], 2.0); ay[0] = __dmul_rn(ay[0], 2.0); }     // motion.py:191-207
         p[0] = ax[0]; p[1] = ax[1]; p[2] = ax[2]; p[3] = ay[0]; p[4] = ay[1]; p[5] = ay[2];
         for (int k = 0; k < 6; ++k) params_out[(long long)pair * 6 + k] = p[k];
+        bad = b;
     }
     __syncthreads();
+    const double hm = (double)(h - 1), wm = (double)(w - 1);
     int near_half = 0;
-    for (int b = threadIdx.x; b < h * w; b += blockDim.x) {
-        const int i = b / w, j = b - i * w;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const double d = __dadd_rn(__dadd_rn(p[3 * c], __dmul_rn(p[3 * c + 2], (double)j)), __dmul_rn(p[3 * c + 1], (double)i));
-            const double fr = d - floor(d);
-            if (fabs(fr - 0.5) < margin || !(fabs(d) < 30000.0)) near_half = 1;    // (also: outside int16's comfortable range, NaN)
+    for (int c = 0; c < 2; ++c) {
+        const double p0 = p[3 * c], p1 = p[3 * c + 1], p2 = p[3 * c + 2];
+        const double scale = __dadd_rn(__dadd_rn(fabs(p0), __dmul_rn(fabs(p1), hm)), __dmul_rn(fabs(p2), wm));
+        const double tol = __dmul_rn(1e-9, fmax(1.0, scale));
+        for (int b = threadIdx.x; b < h * w; b += blockDim.x) {
+            const int i = b / w, j = b - i * w;
+            const double d = __dadd_rn(__dadd_rn(p0, __dmul_rn(p2, (double)j)), __dmul_rn(p1, (double)i));
+            if (fabs(d - floor(d) - 0.5) <= tol || !(fabs(d) < 30000.0)) near_half = 1;    // (also: outside int16's comfortable range, NaN)
         }
     }
     if (near_half) atomicOr(&bad, flag_bit);
@@ -470,7 +506,7 @@ __global__ void __launch_bounds__(256) k_model2_field(const double* params, int 
 // Jacobi equilibration (D = 1 / sqrt(diag)), Gaussian elimination with partial pivoting and x = D z, every product and sum
 // rounded separately.  LAPACK's last bits are not reproduced, so the pair is flagged for the host path:
 //   4         a non-positive diagonal entry (roadmap raises LinAlgError there) or a zero pivot;
-//   8         min |pivot| / max |pivot| of the equilibrated system below 1e-12: the parameters may then be further from
+//   8         min |pivot| / max |pivot| of the equilibrated system below SOLVE_PIVOT_RATIO (3e-5): the parameters may then be further from
 //             LAPACK's than the contract allows;
 //   flag_bit  a displacement of the h x w order-2 field of the output (model2_value: k_model2_field's arithmetic) within
 //             tol = 1e-9 max(1, sum_k |p_k| m_k) of k + 0.5, m_k = max |phi_k(i, j)| over the field, or |d| >= 30000, or NaN.
@@ -534,7 +570,7 @@ __global__ void __launch_bounds__(256) k_solve_model2(const double* sums, int mo
     if (t == 0) {
         int b = bad;
         if (pmin == 0.0) b |= 4;
-        if (!(__ddiv_rn(pmin, pmax) >= 1e-12)) b |= 8;
+        if (!(__ddiv_rn(pmin, pmax) >= SOLVE_PIVOT_RATIO)) b |= 8;
         for (int k = 0; k < 12; ++k) p[k] = 0.0;
         if (pp) {
             for (int k = 0; k < 6; ++k) p[k] = __dmul_rn(z[0][k], dsc[k]);
@@ -1237,7 +1273,7 @@ int launch_sse(gme_ctx* ctx, const uint8_t* a, int64_t a_stride, int a_pitch, co
 int launch_solve3(gme_ctx* ctx, const double* sums, int pairs, int project, int h, int w, double* params_out, int32_t* flags, int flag_bit)
 {
     if (pairs == 0) return GME_OK;
-    hipLaunchKernelGGL(k_solve3, dim3((unsigned)pairs), dim3(256), 0, ctx->stream, sums, pairs, project, h, w, 1e-9, params_out, flags, flag_bit);
+    hipLaunchKernelGGL(k_solve3, dim3((unsigned)pairs), dim3(256), 0, ctx->stream, sums, pairs, project, h, w, params_out, flags, flag_bit);
     GME_HIP_TRY(hipGetLastError());
     return GME_OK;
 }

@@ -219,7 +219,7 @@ def normal_matrix(s):
 def solve(s):
     """JtJ delta = Jte by the device's elimination (gme_internal.h: Jacobi equilibration, then Gaussian elimination with
     partial pivoting, first largest pivot) -> (delta float64[8], ok); not ok for a non-positive diagonal, a zero pivot or a
-    pivot ratio below 1e-12 (the criteria of k_solve_model2)."""
+    pivot ratio below 1e-12 (the criteria of k_direct_state, gme_direct.hip)."""
     N, rhs = normal_matrix(s)
     n = 8
     if not all(N[k, k] > 0.0 for k in range(n)):

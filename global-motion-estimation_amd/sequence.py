@@ -598,9 +598,9 @@ class ShardedSequence:
     def _device_solved(self, procedure, search_window, exact_psnr=False, model="affine"):
         """estimate_and_compensate() with the solves on the device (roadmap.device_stages, round robin): one call and one
         wait per lane -> (params, psnr), or None when the library flags a pair (near a rounding tie, singular or
-        ill-conditioned) and the caller must run the host path.  Affine parameters are within rtol 1e-10 of the host path's;
-        model fields, masks, compensated frames and PSNR are bit-equal to it (the order-2 contract:
-        gme_seq_gme_device_solve2 in the header)."""
+        ill-conditioned) and the caller must run the host path.  Both orders keep one contract (gme_seq_gme_device_solve and
+        gme_seq_gme_device_solve2 in the header): each parameter within 1e-10 max(1, S) of the host path's, scaled by its
+        term's largest factor over the field; model fields, masks, compensated frames and PSNR bit-equal to it."""
         parts = self._round_robin(lambda lane: roadmap.device_stages(lane.seq, self.fd, model, procedure, search_window))
         if any(np.any(f[:lane.hi - lane.lo]) for lane, (_, _, f) in zip(self.lanes, parts)):
             return None

@@ -244,7 +244,8 @@ enum { GME_MODEL_BILINEAR = 3, GME_MODEL_PSEUDO_PERSPECTIVE = 4, GME_MODEL_QUADR
  * terms of one displacement, every parameter of an unflagged pair satisfies |p_dev - p_host| m_k <= 1e-10 max(1, S).
  * flags_out: bit 1 -- a displacement of the h x w order-2 field of the output within 1e-9 max(1, S) of k + 0.5 (or
  * |d| >= 30000, or NaN); bit 4 -- singular (a non-positive diagonal entry: LinAlgError in roadmap; or a zero pivot); bit 8 --
- * ill-conditioned (min / max |pivot| of the equilibrated system below 1e-12).  Host pointers. */
+ * ill-conditioned (min / max |pivot| of the equilibrated system below 3e-5: the inliers leave a direction of the model almost
+ * undetermined and the bound above is not assured; DESIGN.md gives the measurement).  Host pointers. */
 GME_API int gme_solve_model2_sums(gme_ctx *ctx, int model, const double *sums, int pairs, int project, int h, int w,
                                   double *params_out, int32_t *flags_out);
 /* gme_seq_gme_device_solve for a second-order model: begin_fit2 -> device solve + projection -> fit2(2) -> device solve ->
@@ -291,14 +292,19 @@ GME_API int gme_seq_refine_projective(gme_seq *seq, int frame_distance, const do
 GME_API int gme_seq_compensate_projective(gme_seq *seq, int frame_distance, const double *params, int64_t *sse_out);
 /* Opt-in one-call form of begin_fit -> solve -> fit(2) -> solve -> compensate with the two 3x3 solves of
  * motion.py:262-264,280-282 on the device: one host round trip per estimate instead of three.  LAPACK's last bits are not
- * reproduced: params_out[P][6] is within rtol 1e-10 of the staged path's (motion.py:109-136); model fields, masks,
- * compensated frames (results.py:52-59) and sse_out[P] (may be NULL) are bit-equal to it for every pair whose flags_out[p]
- * is 0.  A non-zero flag -- bit 1 / 2: a model displacement within 1e-9 of a rounding tie at level 2 / in the final field;
- * bit 4: a singular system (numpy.linalg.LinAlgError upstream, motion.py:262) -- tells the caller to redo that pair through
- * the staged calls.  Split-phase like them (gme_seq_set_split_phase). */
+ * reproduced.  With m_k = (1, h-1, w-1) over the H/bs x W/bs field and S = |p0| + |p1| (h-1) + |p2| (w-1) over the three terms
+ * of one displacement, every parameter of a pair whose flags_out[p] is 0 satisfies |p_dev - p_host| m_k <= 1e-10 max(1, S)
+ * against the staged path's (motion.py:109-136), and its model fields, masks, compensated frame (results.py:52-59) and
+ * sse_out[p] (may be NULL) are bit-equal to that path's.  A non-zero flag -- bit 1 / 2: a model displacement within
+ * 1e-9 max(1, S) of a rounding tie at level 2 / in the final field; bit 4: a singular system (numpy.linalg.LinAlgError
+ * upstream, motion.py:262); bit 8: an ill-conditioned one (below) -- tells the caller to redo that pair through the staged
+ * calls.  Split-phase like them (gme_seq_set_split_phase). */
 /* The device solve by itself: sums[P][15] = F (9, row-major) | Sx | Sy -> params_out[P][6] (motion.py:262-286; first
- * components doubled if `project`, motion.py:191-207) and flags_out[P] (bit 1: a displacement of the h x w model field of
- * those parameters within 1e-9 of a rounding tie, motion.py:139-157; bit 4: singular).  Host pointers. */
+ * components doubled if `project`, motion.py:191-207) and flags_out[P].  Both systems are Jacobi-equilibrated and solved by
+ * Gaussian elimination with partial pivoting.  bit 1: a displacement of the h x w model field of those parameters
+ * (motion.py:139-157) within 1e-9 max(1, S) of k + 0.5, or |d| >= 30000, or NaN; bit 4: singular (a non-positive diagonal
+ * entry or a zero pivot); bit 8: ill-conditioned (min / max |pivot| of the equilibrated system below 3e-5, as in
+ * gme_solve_model2_sums).  The parameters of an unflagged pair meet the bound above.  Host pointers. */
 GME_API int gme_solve_fit_sums(gme_ctx *ctx, const double *sums, int pairs, int project, int h, int w, double *params_out,
                        int32_t *flags_out);
 GME_API int gme_seq_gme_device_solve(gme_seq *seq, int frame_distance, int bbme_block_size, int procedure, int search_window,
