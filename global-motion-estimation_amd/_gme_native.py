@@ -132,6 +132,8 @@ _SIGNATURES = {
     "gme_seq_read_prop": (_i, [_vp, _i, _i, _c_i32p, _c_i64p, _c_u8p]),
     "gme_interp_u8": (_i, [_vp, _c_u8p, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
     "gme_seq_interp": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
+    "gme_obmc_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _c_i32p, _i, _c_u8p, _c_i64p]),
+    "gme_seq_obmc": (_i, [_vp, _i, _i, _i, _i, _i, _c_u8p, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -516,6 +518,37 @@ class Context:
                                       search_window, pnorm, bias, _p(mv, _c_i32p), _p(cost, _c_i64p), _p(dist, _c_i64p), _p(made, _c_u8p),
                                       ctypes.byref(sse)), self.lib)
         return mv, cost, dist, made, sse.value
+
+    def obmc(self, prev, field, block_size, quarter=True, cur=None):
+        """``prev`` compensated by the block field with overlapped blocks (gme_obmc_u8, obmc.compensate) -> (frame uint8[H, W],
+        sse int): ``field`` int32[H // B, W // B, 2] in quarter pixels, or with ``quarter`` false in whole pixels (components within
+        +-2**29); ``sse`` is the squared error against ``cur``, or -1 without one."""
+        import obmc
+        frames = [as_frame(prev, "prev")] + ([] if cur is None else [as_frame(cur, "cur")])
+        if any(a.shape != frames[0].shape for a in frames):
+            raise AssertionError("the frames differ in shape (bbme.py:59)")
+        H, W = frames[0].shape
+        block_size = obmc.check_block_size(block_size)
+        obmc.check_shape(H, W, block_size)
+        field = _obmc_field(field, H, W, block_size, quarter)
+        if any(a.strides[0] != frames[0].strides[0] for a in frames):
+            frames = [np.ascontiguousarray(a) for a in frames]
+        made = np.empty((H, W), np.uint8)
+        sse = ctypes.c_int64(0)
+        _check(self.lib.gme_obmc_u8(self.handle, _p(frames[0], _c_u8p), None if cur is None else _p(frames[1], _c_u8p), H, W,
+                                    frames[0].strides[0], block_size, _p(field, _c_i32p), 1 if quarter else 4, _p(made, _c_u8p),
+                                    ctypes.byref(sse)), self.lib)
+        return made, sse.value
+
+
+def _obmc_field(field, H, W, block_size, quarter):
+    """obmc.check_field and the range of an integer field: ValueError before the library is asked -> contiguous int32."""
+    import obmc
+    field = obmc.check_field(field, H, W, block_size)
+    limit = (1 << 31) - 1 if quarter else obmc.MAX_INTEGER_VECTOR
+    if field.size and (int(field.min()) < (-limit - 1 if quarter else -limit) or int(field.max()) > limit):
+        raise ValueError("a vector component beyond %s" % ("int32" if quarter else "+-2**29 whole pixels"))
+    return np.ascontiguousarray(field, dtype=np.int32)
 
 
 def _interp_args(block_size, search_window, pnorm, bias, H, W):
@@ -1170,6 +1203,24 @@ class Sequence:
         _check(self.lib.gme_seq_interp(self.handle, fd, block_size, search_window, pnorm, bias, first, count, _p(mv, _c_i32p),
                                        _p(cost, _c_i64p), _p(dist, _c_i64p), _p(frames, _c_u8p), _p(sse, _c_i64p)), self.lib)
         return mv, cost, dist, frames, sse[:n]
+
+    # ---- overlapped block motion compensation (bbme_obmc.hip, obmc.py)
+    def obmc(self, frame_distance, block_size, quarter=False, first=0, count=None):
+        """Frame k compensated with overlapped blocks for the pairs k = first .. first+count-1 (gme_seq_obmc, obmc.compensate) ->
+        (frames uint8[count, H, W], sse int64[count]) by the sequence's motion field, or with ``quarter`` by its quarter-pel field;
+        ``sse`` is the squared error against frame k + fd.  One blocking call, also in split-phase mode, that keeps nothing and
+        leaves everything the sequence holds as it was.  A range outside the field's pairs is an IndexError."""
+        import obmc
+        fd = int(frame_distance)
+        block_size = obmc.check_block_size(block_size)
+        obmc.check_shape(self.H, self.W, block_size)
+        first = int(first)
+        count = self.N - fd - first if count is None else int(count)
+        n = max(count, 0)                      # a refused range writes nothing
+        frames, sse = np.empty((n, self.H, self.W), np.uint8), np.zeros(max(n, 1), np.int64)
+        _check(self.lib.gme_seq_obmc(self.handle, fd, block_size, 1 if quarter else 4, first, count, _p(frames, _c_u8p),
+                                     _p(sse, _c_i64p)), self.lib)
+        return frames, sse[:n]
 
 
 _default = None

@@ -784,6 +784,36 @@ extern "C" int gme_interp_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* n
     return rc;
 }
 
+// Overlapped block motion compensation of one pair (bbme_obmc.hip): `prev`, `cur` where the caller has one
+// and the compensated frame as one stack of three planes in the scratch.
+extern "C" int gme_obmc_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int H, int W, int stride, int block_size,
+                           const int32_t* field, int unit, uint8_t* frame_out, int64_t* sse_out)
+{
+    GME_ENTER(ctx);
+    int rc = oneshot_check("gme_obmc_u8", prev && field, H, W, stride);
+    if (rc) return rc;
+    rc = obmc_check_args("gme_obmc_u8", H, W, block_size, unit);
+    if (rc) return rc;
+    const size_t n = (size_t)(H / block_size) * (W / block_size);
+    Plane st = plane_shape(H, W, 3);                           // prev, cur, compensated
+    int32_t* d_field = nullptr;
+    unsigned long long* d_sse = nullptr;
+    Carver c;
+    c.take(&st, true); c.take(&d_field, n * 2); c.take(&d_sse, 1);
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_field - st.ptr, ctx->stream));
+    rc = put_planes(ctx, st, { prev, cur ? cur : prev }, stride);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(d_field, field, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    int64_t sse = -1;                                          // without `cur` there is no error to report
+    rc = oneshot_predict(ctx, st, 2, d_sse, frame_out, cur && sse_out ? &sse : nullptr, [&] {
+        return launch_obmc(ctx, st.at(0), st.at(1), 0, 1, H, W, st.pitch, block_size, d_field, unit, st.at(2), 0, st.pitch, d_sse);
+    });
+    if (sse_out) *sse_out = sse;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -2563,6 +2593,51 @@ extern "C" int gme_seq_interp(gme_seq* s, int fd, int bs, int sw, int pnorm, int
             if (sse_out && truth)
                 GME_HIP_TRY(hipMemcpyAsync(sse_out + k, sse.get(), (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         }
+        rc = ctx_finish(ctx);                                  // the next chunk writes the same buffers
+        if (rc) return rc;
+    }
+    return GME_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Overlapped block motion compensation (bbme_obmc.hip): one blocking call that computes and returns, in the
+// form of gme_seq_interp.  It reads the sequence's motion field (unit 4) or its quarter-pel field (unit 1), works in buffers of its
+// own that live as long as the call and keeps nothing: it writes neither the compensated planes nor any field, so there is
+// nothing of it that a later call could read stale.
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_obmc(gme_seq* s, int fd, int bs, int unit, int first_pair, int count, uint8_t* frames_out, int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_obmc: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(fd >= 1 && fd < s->N, GME_ERR_ARG, "gme_seq_obmc: frame_distance %d needs at least %d frames", fd, fd + 1);
+    int rc = obmc_check_args("gme_seq_obmc", s->H, s->W, bs, unit);
+    if (rc) return rc;
+    GME_REQUIRE(unit == 4 || s->qmv_valid, GME_ERR_STATE, "gme_seq_obmc with the quarter-pel field before gme_seq_subpel");
+    rc = subpel_field(s, "gme_seq_obmc", fd, bs);
+    if (rc) return rc;
+    GME_REQUIRE(first_pair >= 0 && count >= 0 && first_pair + count <= s->mv_pairs, GME_ERR_ARG, "gme_seq_obmc: pairs [%d, %d) outside [0, %d)",
+                first_pair, first_pair + count, s->mv_pairs);
+    const size_t per = (size_t)s->mv_h * s->mv_w, image = (size_t)s->H * s->W;
+    const int32_t* field = unit == 4 ? s->mv.get() : s->qmv.get();
+    const int step = max_grid_planes(), most = count < step ? count : step;
+    DevBuf<unsigned long long> sse;
+    PlaneBuf made;
+    rc = sse.ensure((size_t)most, "overlapped compensation errors");
+    if (rc) return rc;
+    rc = plane_alloc(ctx, &made, most, s->H, s->W);
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    for (int k = 0; k < count; k += step) {
+        const int n = count - k < step ? count - k : step, at = first_pair + k;
+        rc = launch_obmc(ctx, p.at(at), p.at(at + fd), p.stride, n, s->H, s->W, p.pitch, bs, field + per * 2 * at, unit, made.ptr, made.stride,
+                         made.pitch, sse);
+        if (rc) return rc;
+        if (frames_out) {
+            rc = read_planes(ctx, made, 0, n, frames_out + image * k);
+            if (rc) return rc;
+        }
+        if (sse_out) GME_HIP_TRY(hipMemcpyAsync(sse_out + k, sse.get(), (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         rc = ctx_finish(ctx);                                  // the next chunk writes the same buffers
         if (rc) return rc;
     }

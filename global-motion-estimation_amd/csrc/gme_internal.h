@@ -515,6 +515,15 @@ int launch_interp_frame(gme_ctx* ctx, const uint8_t* past, const uint8_t* next, 
                         int H, int W, int pitch, int bs, const int32_t* mv, uint8_t* out, long long out_stride, int out_pitch,
                         unsigned long long* sse);
 
+// ---- bbme_obmc.hip: overlapped block motion compensation ---------------------------------------------
+// the argument rules of obmc.py for H x W frames (GME_ERR_ARG)
+int obmc_check_args(const char* who, int H, int W, int bs, int unit);
+// out planes = obmc.compensate of the prev planes by field [pairs][H / bs][W / bs][2] in units of unit / 4 pixels (4: whole
+// pixels, 1: quarter pixels), sse[pairs] (device) = squared error of each against its cur plane.  Names the kernel in the context's
+// plan.
+int launch_obmc(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W, int pitch, int bs,
+                const int32_t* field, int unit, uint8_t* out, long long out_stride, int out_pitch, unsigned long long* sse);
+
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);
 int launch_synth_frames(gme_ctx* ctx, uint64_t seed, int t0, const uint8_t* canvas, const Plane& dst);

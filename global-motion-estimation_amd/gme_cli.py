@@ -17,7 +17,8 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py gmc -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--penalty N] [--estimator projective|affine] [-o OUTDIR]   # global motion compensation of one pair
     python gme_cli.py prop -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 3] [-pn 0] [--rounds 2] [--steps 1] [--no-temporal] [--camera projective|affine|none] [--hier] [-o OUTDIR]   # vector propagation search of one pair
     python gme_cli.py interp -p <video|frame dir> -fi 2 [-fd 2] [-bs 16] [-sw 8] [-pn 0] [--bias N] [-o OUTDIR] [--upconvert]   # the frame between two frames; frame-rate doubling
-    python gme_cli.py info                                                          # searches, norms, models, device
+    python gme_cli.py obmc -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--subpel 0|1|2] [--hier] [-o OUTDIR]   # overlapped block motion compensation of one pair
+    python gme_cli.py info                                                       # searches, norms, models, device
 """
 import argparse
 import sys
@@ -173,6 +174,18 @@ def _parser():
                          "tool and not a tuned value")
     ip.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for interp.json, interp.png and upconverted/%%04d.png")
     ip.add_argument("--upconvert", action="store_true", help="also double the frame rate of the whole clip into OUTDIR/upconverted/%%04d.png")
+    op = sub.add_parser("obmc", help="overlapped block motion compensation of one frame pair: search, optional sub-pel refinement, the plain and the overlapped compensation (obmc.py, DESIGN.md 7o)")
+    op.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    op.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the current frame")
+    op.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=1, help="the previous frame is fi - fd")
+    op.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="4 .. 64")
+    op.add_argument("-sw", "--search-window", dest="search_window", type=int, default=16, help="search window (with --hier: the coarse window, 0 .. 8)")
+    op.add_argument("-sp", "--searching-procedure", dest="searching_procedure", type=int, default=0,
+                    help="0: exhaustive, 1: three-step, 2: 2-D log, 3: diamond")
+    op.add_argument("-pn", "--pnorm-distance", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    op.add_argument("--subpel", type=int, default=0, help="refine the field afterwards: 0 no, 1 half-pel, 2 quarter-pel")
+    op.add_argument("--hier", action="store_true", help="take the field from the hierarchical search (three levels, radius 1)")
+    op.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for obmc.json and obmc.png")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -380,6 +393,39 @@ def _interp(args):
     return res
 
 
+def _obmc(args):
+    """The PSNR of the plain and of the overlapped compensation of one pair, by the integer field and, with --subpel above 0, by the
+    refined field; the same record into OUTDIR/obmc.json and the overlapped compensation by the finest field into OUTDIR/obmc.png."""
+    import json
+    import os
+    import obmc
+    import utils
+    frames = utils.get_video_frames(args.path)
+    if not args.fd <= args.fi < len(frames) or args.fd < 1:
+        raise IndexError("frames %d and %d of %d" % (args.fi - args.fd, args.fi, len(frames)))
+    if args.hier:
+        args.search_window = min(args.search_window, 8)
+    res = obmc.report(frames[args.fi - args.fd], frames[args.fi], args.block_size, args.search_window, args.searching_procedure,
+                      args.pnorm, args.subpel, args.hier)
+    record = {"options": {"path": args.path, "frame_index": args.fi, "frame_distance": args.fd, "block_size": args.block_size,
+                          "search_window": args.search_window, "searching_procedure": args.searching_procedure,
+                          "pnorm": args.pnorm, "subpel": args.subpel, "hier": bool(args.hier)},
+              "shape": list(res["mf"].shape[:2])}
+    print("frames {} -> {}: {} x {} blocks of {}".format(args.fi - args.fd, args.fi, record["shape"][0], record["shape"][1],
+                                                         args.block_size))
+    for key, name in (("integer", "integer field"), ("qpel", "refined field")):
+        if key in res:
+            record[key] = res[key]
+            print("psnr {}: plain {:.4f} dB, overlapped {:.4f} dB  (gain {:+.4f} dB)".format(
+                name, res[key]["psnr_plain"], res[key]["psnr_obmc"], res[key]["psnr_gain"]))
+    if args.outdir:
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "obmc.json"), "w") as f:
+            json.dump(record, f, indent=1)
+        utils.write_image(os.path.join(args.outdir, "obmc.png"), res["frame"])
+    return res
+
+
 def _gmc(args):
     """The penalty, the mode shares and the PSNR of the global-only, the local-only and the chosen prediction of one frame; the
     same record into OUTDIR/gmc.json and the mode map (0 / 128 / 255 per block, scaled up to the frame) into OUTDIR/modes.png."""
@@ -584,6 +630,8 @@ def main(argv=None):
         return _prop(args)
     if args.command == "interp":
         return _interp(args)
+    if args.command == "obmc":
+        return _obmc(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")
@@ -596,6 +644,7 @@ def main(argv=None):
     print("global motion compensation (gme_cli.py gmc): -bs 4 .. 64, --penalty 0 .. 2^30, --estimator projective | affine; per block the camera warp or the block's own vector   (gmc.py)")
     print("vector propagation search (gme_cli.py prop): -bs 4 .. 64, --rounds 1 .. 4, --steps 0 .. 4, --camera projective | affine | none; own, neighbour, temporal, camera and zero vectors on a prior field, refined by one pixel   (propagate.py)")
     print("frame interpolation (gme_cli.py interp): -bs 4 .. 64, -sw 0 .. 8, --bias 0 .. 2^16, --upconvert; the frame halfway between two frames by a bilateral search, borders replicated   (interp.py)")
+    print("overlapped block compensation (gme_cli.py obmc): -bs 4 .. 64, --subpel 0 .. 2, --hier; every pixel blended from its block's and the nearest neighbours' predictions under a linear ramp, borders replicated   (obmc.py)")
     try:
         print("device: " + _gme_native.default_context().info()["name"])
     except Exception as e:      # noqa: BLE001 -- no GPU: say so, the listing above is still useful

@@ -77,6 +77,12 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    ``interp.upconvert`` doubles the frame rate of a clip.  A block's whole search runs in one wave of one kernel (k_interp,
    csrc/bbme_interp.hip; host definition interp.py); ``Sequence.interp`` computes and returns in one call and
    keeps nothing.
+   **Overlapped block motion compensation.**  ``obmc.frame`` compensates a frame by a block field, whole or quarter pixels,
+   without the jump at block edges where two neighbours disagree: every pixel is blended from the prediction of its own block and
+   of the nearest vertical, horizontal and diagonal neighbour under a linear ramp, the border replicated per pixel so that no
+   vector is unavailable.  One wave per row of one kernel (k_obmc, csrc/bbme_obmc.hip; host definition obmc.py; DESIGN.md §7o);
+   ``Sequence.obmc`` takes the sequence's motion field or its quarter-pel field, computes and returns in one call and keeps
+   nothing.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

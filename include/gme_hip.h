@@ -575,6 +575,34 @@ GME_API int gme_seq_interp(gme_seq *seq, int frame_distance, int block_size, int
                            int count, int32_t *mv_out, int64_t *cost_out, int64_t *dist_out, uint8_t *frames_out, int64_t *sse_out);
 
 /* ---------------------------------------------------------------------------
+ * Overlapped block motion compensation (csrc/bbme_obmc.hip; host definition: obmc.py): `prev` compensated
+ * by a block field, every pixel blended from the predictions of its own block and of the nearest vertical, horizontal and
+ * diagonal neighbour blocks under a linear ramp, so the prediction does not jump where two neighbours disagree.  field is
+ * int32[H/B][W/B][2] (column, row; sign and axes of the quarter-pel section); unit 4: whole pixels, unit 1: quarter pixels (the
+ * product is formed in 64 bits).  A prediction of pixel (u, v) under the vector q is the four-tap blend of the quarter-pel
+ * section at (4 u - q0, 4 v - q1) with every tap's coordinates clamped to the frame (border replication): no vector is
+ * unavailable, INT32_MIN and INT32_MAX included.  With ty = 2 (v mod B) + 1 - B the vertical neighbour is the block row above
+ * (ty < 0) or below, clamped to the grid, and the two rows weigh 2B - |ty| and |ty|; the same for the columns; the pixel is
+ * (sum of the four weighted 8-bit predictions + 2 B^2) / (4 B^2), rounded down.  Beyond the last whole block the pixel is the
+ * copy of `prev`.  All integer, byte-equal to obmc.compensate.  block_size 4 .. 64 (H >= block_size and W >= block_size), unit 1
+ * or 4; anything else is GME_ERR_ARG.
+ * gme_obmc_u8: one pair on host buffers -> frame_out uint8[H][W] (tight), *sse_out = exact squared error against `cur`, or -1
+ *   where cur is NULL.  Either output may be NULL.
+ * gme_seq_obmc: the pairs (k, k + frame_distance), k = first_pair .. first_pair + count - 1 (a range outside the field's pairs is
+ *   GME_ERR_ARG) -> frames_out uint8[count][H][W] (tight), sse_out[count] = exact squared error against frame k + frame_distance.
+ *   Either output may be NULL.  unit 4 takes the sequence's motion field as gme_seq_vbs takes it (the field survives new frame
+ *   data; GME_ERR_STATE without a field, or for another frame distance or block size than the field's); unit 1 takes the
+ *   quarter-pel field and is GME_ERR_STATE wherever gme_seq_compensate_qpel is.  It computes and returns in one call, in buffers
+ *   of its own that live as long as the call: it keeps nothing, writes neither the compensated planes nor any field, and leaves
+ *   every kept result readable and byte-identical, so it is no part of the result lifetimes above.
+ * Blocking calls, also in split-phase mode.  gme_last_bbme_info names the kernel: k_obmc. */
+GME_API int gme_obmc_u8(gme_ctx *ctx, const uint8_t *prev, const uint8_t *cur /* may be NULL */, int H, int W, int stride,
+                        int block_size, const int32_t *field, int unit /* 4: whole pixels, 1: quarter pixels */,
+                        uint8_t *frame_out, int64_t *sse_out);
+GME_API int gme_seq_obmc(gme_seq *seq, int frame_distance, int block_size, int unit, int first_pair, int count,
+                         uint8_t *frames_out, int64_t *sse_out);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
  * the context's stream.  The reference has no distributed code; SURVEY.md §8(e) defines this split.
