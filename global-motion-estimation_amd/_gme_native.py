@@ -134,6 +134,9 @@ _SIGNATURES = {
     "gme_seq_interp": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
     "gme_obmc_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _c_i32p, _i, _c_u8p, _c_i64p]),
     "gme_seq_obmc": (_i, [_vp, _i, _i, _i, _i, _i, _c_u8p, _c_i64p]),
+    "gme_denoise_u8": (_i, [_vp, _c_u8p, ctypes.POINTER(_c_u8p), ctypes.POINTER(_c_i32p), _i, _i, _i, _i, _i, _i, _i, _c_u8p, _c_u8p,
+                            _c_i64p]),
+    "gme_seq_denoise": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c_u8p, _c_i64p]),
     "gme_seq_set_split_phase": (_i, [_vp, _i]),
     "gme_seq_wait": (_i, [_vp]),
     "gme_seq_poll": (_i, [_vp]),
@@ -538,6 +541,36 @@ class Context:
         _check(self.lib.gme_obmc_u8(self.handle, _p(frames[0], _c_u8p), None if cur is None else _p(frames[1], _c_u8p), H, W,
                                     frames[0].strides[0], block_size, _p(field, _c_i32p), 1 if quarter else 4, _p(made, _c_u8p),
                                     ctypes.byref(sse)), self.lib)
+        return made, sse.value
+
+
+    def denoise(self, cur, refs, fields, block_size, quarter=False, strength=24, truth=None):
+        """``cur`` filtered with the overlapped predictions of it from ``refs`` (gme_denoise_u8, denoise.frame) -> (frame
+        uint8[H, W], sse int): ``fields[r]`` int32[H // B, W // B, 2] says where the blocks of ``cur`` are found in ``refs[r]``, in
+        whole pixels (components within +-2**29) or with ``quarter`` in quarter pixels; ``sse`` is the squared error against
+        ``truth``, or -1 without one.  The default strength is a convention of the tool, not a tuned value."""
+        import denoise
+        import obmc
+        refs, fields = list(refs), list(fields)
+        R, strength = denoise.check_args(len(refs), strength)
+        if len(fields) != R:
+            raise ValueError("%d references, %d fields" % (R, len(fields)))
+        frames = [as_frame(cur, "cur")] + [as_frame(a, "ref") for a in refs] + ([] if truth is None else [as_frame(truth, "truth")])
+        if any(a.shape != frames[0].shape for a in frames):
+            raise AssertionError("the frames differ in shape (bbme.py:59)")
+        H, W = frames[0].shape
+        block_size = obmc.check_block_size(block_size)
+        obmc.check_shape(H, W, block_size)
+        fields = [_obmc_field(f, H, W, block_size, quarter) for f in fields]
+        if any(a.strides[0] != frames[0].strides[0] for a in frames):
+            frames = [np.ascontiguousarray(a) for a in frames]
+        ref_ptrs = (_c_u8p * R)(*[_p(a, _c_u8p) for a in frames[1:1 + R]])
+        field_ptrs = (_c_i32p * R)(*[_p(f, _c_i32p) for f in fields])
+        made = np.empty((H, W), np.uint8)
+        sse = ctypes.c_int64(0)
+        _check(self.lib.gme_denoise_u8(self.handle, _p(frames[0], _c_u8p), ref_ptrs, field_ptrs, R, H, W, frames[0].strides[0], block_size,
+                                       1 if quarter else 4, strength, None if truth is None else _p(frames[-1], _c_u8p), _p(made, _c_u8p),
+                                       ctypes.byref(sse)), self.lib)
         return made, sse.value
 
 
@@ -1221,6 +1254,29 @@ class Sequence:
         _check(self.lib.gme_seq_obmc(self.handle, fd, block_size, 1 if quarter else 4, first, count, _p(frames, _c_u8p),
                                      _p(sse, _c_i64p)), self.lib)
         return frames, sse[:n]
+
+
+    # ---- motion-compensated temporal denoising (bbme_denoise.hip, denoise.py)
+    def denoise(self, frame_distance, block_size=16, search_window=8, procedure=0, pnorm=0, radius=1, levels=0, strength=24, first=0,
+                count=None):
+        """The interior targets t = radius fd + first + k, k < count, each filtered with its 2 radius references t -+ d fd
+        (gme_seq_denoise, denoise.frame over searches from the target) -> (frames uint8[count, H, W], change int64[count]);
+        ``change`` is the squared difference between the filtered frame and the target.  One blocking call, also in split-phase
+        mode, that keeps nothing and leaves everything the sequence holds as it was.  A range outside the interior targets is an
+        IndexError.  The default strength is a convention of the tool, not a tuned value."""
+        import denoise
+        import obmc
+        fd, radius = int(frame_distance), denoise.check_radius(radius)
+        _, strength = denoise.check_args(2 * radius, strength)
+        block_size = obmc.check_block_size(block_size)
+        obmc.check_shape(self.H, self.W, block_size)
+        first = int(first)
+        count = self.N - 2 * radius * fd - first if count is None else int(count)
+        n = max(count, 0)                      # a refused range writes nothing
+        frames, change = np.empty((n, self.H, self.W), np.uint8), np.zeros(max(n, 1), np.int64)
+        _check(self.lib.gme_seq_denoise(self.handle, fd, block_size, int(search_window), int(procedure), int(pnorm), radius, int(levels),
+                                        strength, first, count, _p(frames, _c_u8p), _p(change, _c_i64p)), self.lib)
+        return frames, change[:n]
 
 
 _default = None

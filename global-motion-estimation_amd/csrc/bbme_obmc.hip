@@ -89,9 +89,10 @@ int obmc_check_args(const char* who, int H, int W, int bs, int unit)
 }
 
 // out planes = obmc.compensate of the prev planes by field[pairs][hb][wb][2], sse[pairs] (device, zeroed here) = squared error of
-// each against its cur plane
+// each against its cur plane.  negate: by the negated field (the product with the unit is formed in 64 bits, so INT32_MIN negates
+// too): the field is anchored at the predicted frame, as denoise.predict takes it.
 int launch_obmc(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W, int pitch, int bs,
-                const int32_t* field, int unit, uint8_t* out, long long out_stride, int out_pitch, unsigned long long* sse)
+                const int32_t* field, int unit, uint8_t* out, long long out_stride, int out_pitch, unsigned long long* sse, bool negate)
 {
     int rc = obmc_check_args("overlapped compensation", H, W, bs, unit);
     if (rc) return rc;
@@ -104,7 +105,7 @@ int launch_obmc(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long
     return predict_planes(ctx, pairs, sse, [&](int k, int n) {
         const long long off = (long long)k * plane_stride;
         hipLaunchKernelGGL(k_obmc, predict_grid(H, W, n), dim3(PRED_THREADS), 0, ctx->stream, prev + off, cur + off, plane_stride, H, W,
-                           pitch, bs, hb, wb, field + (long long)hb * wb * 2 * k, unit, recip, out + (long long)k * out_stride, out_stride,
+                           pitch, bs, hb, wb, field + (long long)hb * wb * 2 * k, negate ? -unit : unit, recip, out + (long long)k * out_stride, out_stride,
                            out_pitch, sse + k);
     });
 }

@@ -814,6 +814,50 @@ extern "C" int gme_obmc_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur
     return rc;
 }
 
+// Motion-compensated temporal denoising of one frame (bbme_denoise.hip): `cur`, the comparison plane, the R
+// references, their R overlapped predictions and the filtered frame as one stack of 2 R + 3 planes in the scratch.
+extern "C" int gme_denoise_u8(gme_ctx* ctx, const uint8_t* cur, const uint8_t* const* refs, const int32_t* const* fields, int R, int H, int W,
+                              int stride, int block_size, int unit, int strength, const uint8_t* truth, uint8_t* frame_out, int64_t* sse_out)
+{
+    GME_ENTER(ctx);
+    int rc = oneshot_check("gme_denoise_u8", cur && refs && fields, H, W, stride);
+    if (rc) return rc;
+    rc = denoise_check_args("gme_denoise_u8", R, strength);
+    if (rc) return rc;
+    for (int r = 0; r < R; ++r) GME_REQUIRE(refs[r] && fields[r], GME_ERR_ARG, "gme_denoise_u8: null reference or field %d", r);
+    rc = obmc_check_args("gme_denoise_u8", H, W, block_size, unit);
+    if (rc) return rc;
+    const size_t n = (size_t)(H / block_size) * (W / block_size);
+    Plane st = plane_shape(H, W, 2 * R + 3);                   // cur, truth, R references, R predictions, filtered
+    int32_t* d_field = nullptr;
+    unsigned long long* d_sse = nullptr;                       // [0] of the filter, [1 + r] of prediction r (not reported)
+    Carver c;
+    c.take(&st, true); c.take(&d_field, n * 2 * R); c.take(&d_sse, 1 + (size_t)R);
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_field - st.ptr, ctx->stream));
+    rc = put_planes(ctx, st, { cur, truth ? truth : cur }, stride);
+    if (rc) return rc;
+    for (int r = 0; r < R; ++r) {
+        Plane one = st;
+        one.ptr = st.at(2 + r);
+        GME_HIP_TRY(put_plane(ctx, one, refs[r], stride));
+        GME_HIP_TRY(hipMemcpyAsync(d_field + n * 2 * r, fields[r], n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    int64_t sse = -1;                                          // without `truth` there is no error to report
+    rc = oneshot_predict(ctx, st, 2 * R + 2, d_sse, frame_out, truth && sse_out ? &sse : nullptr, [&] {
+        for (int r = 0; r < R; ++r) {
+            const int e = launch_obmc(ctx, st.at(2 + r), st.at(0), 0, 1, H, W, st.pitch, block_size, d_field + n * 2 * r, unit, st.at(2 + R + r), 0,
+                                      st.pitch, d_sse + 1 + r, true);
+            if (e) return e;
+        }
+        return launch_denoise(ctx, st.at(0), 0, st.at(2 + R), st.stride, 0, 1, R, H, W, st.pitch, strength, st.at(1), 0, st.at(2 * R + 2), 0,
+                              st.pitch, d_sse);
+    });
+    if (sse_out) *sse_out = sse;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // sequences
 // ---------------------------------------------------------------------------
@@ -2638,6 +2682,89 @@ extern "C" int gme_seq_obmc(gme_seq* s, int fd, int bs, int unit, int first_pair
             if (rc) return rc;
         }
         if (sse_out) GME_HIP_TRY(hipMemcpyAsync(sse_out + k, sse.get(), (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        rc = ctx_finish(ctx);                                  // the next chunk writes the same buffers
+        if (rc) return rc;
+    }
+    return GME_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Motion-compensated temporal denoising (bbme_denoise.hip): one blocking call that computes and returns, in
+// the form of gme_seq_obmc.  For every chunk of targets and each of the 2 radius references it runs the search from the target
+// into a field of its own (as gme_seq_bipred and gme_seq_gmc do), the sub-pel refinement where asked for, and the overlapped
+// prediction; then the filter.  All its buffers live as long as the call and it keeps nothing: it writes neither the motion
+// field, the quarter-pel field, the compensated planes nor any other kept result, so there is nothing of it that a later call
+// could read stale.
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_denoise(gme_seq* s, int fd, int bs, int sw, int procedure, int pnorm, int radius, int levels, int strength,
+                               int first_target, int count, uint8_t* frames_out, int64_t* change_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_denoise: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(radius >= 1 && radius <= 2, GME_ERR_ARG, "gme_seq_denoise: radius %d (1 .. 2)", radius);
+    GME_REQUIRE(fd >= 1 && fd <= (s->N - 1) / (2 * radius), GME_ERR_ARG, "gme_seq_denoise: frame_distance %d at radius %d needs at least %lld frames",
+                fd, radius, 2ll * radius * fd + 1);
+    const int R = 2 * radius;
+    int rc = denoise_check_args("gme_seq_denoise", R, strength);
+    if (rc) return rc;
+    rc = obmc_check_args("gme_seq_denoise", s->H, s->W, bs, 4);
+    if (rc) return rc;
+    rc = bbme_check_args(s->H, s->W, bs, sw, procedure, pnorm);
+    if (rc) return rc;
+    rc = subpel_check("gme_seq_denoise", s->H, s->W, bs, pnorm, levels);
+    if (rc) return rc;
+    const int reach = radius * fd, T = s->N - 2 * reach;
+    GME_REQUIRE(first_target >= 0 && count >= 0 && first_target <= T - count, GME_ERR_ARG, "gme_seq_denoise: targets [%d, %lld) outside [0, %d)",
+                first_target, (long long)first_target + count, T);
+    if (count == 0) return GME_OK;
+    const size_t per = (size_t)(s->H / bs) * (s->W / bs), image = (size_t)s->H * s->W;
+    const int step = max_grid_planes(), most = count < step ? count : step;
+    DevBuf<int32_t> mf, qmf;
+    DevBuf<long long> qcost;
+    DevBuf<unsigned long long> sse;                            // [most] of the filter, then [most] of a prediction (not reported)
+    PlaneBuf preds, made;                                      // preds: reference r's planes at r * most
+    rc = mf.ensure(per * 2 * most, "denoising field");
+    if (rc) return rc;
+    if (levels > 0) {
+        rc = qmf.ensure(per * 2 * most, "denoising quarter-pel field");
+        if (rc) return rc;
+        rc = qcost.ensure(per * most, "denoising quarter-pel costs");
+        if (rc) return rc;
+    }
+    rc = sse.ensure((size_t)most * 2, "denoising errors");
+    if (rc) return rc;
+    rc = plane_alloc(ctx, &preds, most * R, s->H, s->W);
+    if (rc) return rc;
+    rc = plane_alloc(ctx, &made, most, s->H, s->W);
+    if (rc) return rc;
+    const Plane& p = s->level[2];
+    for (int k = 0; k < count; k += step) {
+        const int n = count - k < step ? count - k : step, t0 = reach + first_target + k;
+        for (int r = 0; r < R; ++r) {
+            // reference r of target t: t - fd, t + fd, t - 2 fd, t + 2 fd.  The anchor of the search is the target.
+            const int d = (r / 2 + 1) * fd, ref0 = r % 2 == 0 ? t0 - d : t0 + d;
+            BbmeJob job = bbme_job(p, t0, 0, n, bs, sw, procedure, pnorm, mf);
+            job.cur = p.at(ref0);
+            rc = seq_launch_bbme_from(s, 2, ref0, job);
+            if (rc) return rc;
+            if (levels > 0) {
+                rc = launch_subpel_refine(ctx, p.at(t0), p.at(ref0), p.stride, n, s->H, s->W, p.pitch, bs, pnorm, levels, mf, qmf, qcost);
+                if (rc) return rc;
+            }
+            rc = launch_obmc(ctx, p.at(ref0), p.at(t0), p.stride, n, s->H, s->W, p.pitch, bs, levels > 0 ? qmf.get() : mf.get(), levels > 0 ? 1 : 4,
+                             preds.at(r * most), preds.stride, preds.pitch, sse.get() + most, true);
+            if (rc) return rc;
+        }
+        rc = launch_denoise(ctx, p.at(t0), p.stride, preds.ptr, (long long)most * preds.stride, preds.stride, n, R, s->H, s->W, p.pitch, strength,
+                            p.at(t0), p.stride, made.ptr, made.stride, made.pitch, sse);
+        if (rc) return rc;
+        if (frames_out) {
+            rc = read_planes(ctx, made, 0, n, frames_out + image * k);
+            if (rc) return rc;
+        }
+        if (change_out)
+            GME_HIP_TRY(hipMemcpyAsync(change_out + k, sse.get(), (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         rc = ctx_finish(ctx);                                  // the next chunk writes the same buffers
         if (rc) return rc;
     }

@@ -520,9 +520,21 @@ int launch_interp_frame(gme_ctx* ctx, const uint8_t* past, const uint8_t* next, 
 int obmc_check_args(const char* who, int H, int W, int bs, int unit);
 // out planes = obmc.compensate of the prev planes by field [pairs][H / bs][W / bs][2] in units of unit / 4 pixels (4: whole
 // pixels, 1: quarter pixels), sse[pairs] (device) = squared error of each against its cur plane.  Names the kernel in the context's
-// plan.
+// plan.  negate: by the negated field, for a field anchored at the predicted frame (denoise.predict).
 int launch_obmc(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, long long plane_stride, int pairs, int H, int W, int pitch, int bs,
-                const int32_t* field, int unit, uint8_t* out, long long out_stride, int out_pitch, unsigned long long* sse);
+                const int32_t* field, int unit, uint8_t* out, long long out_stride, int out_pitch, unsigned long long* sse,
+                bool negate = false);
+
+// ---- bbme_denoise.hip: motion-compensated temporal denoising -----------------------------------------
+// the argument rules of denoise.py (GME_ERR_ARG)
+int denoise_check_args(const char* who, int R, int strength);
+// out planes = denoise.blend of the cur planes (cur_stride apart) with R prediction planes each: target k reads prediction r at
+// preds + k * plane_stride + r * pred_stride; sse[targets] (device) = squared difference of each output against its truth plane
+// (truth_stride apart).  Every input plane has the row pitch `pitch`.  Names the kernel in the context's plan; GME_OK for zero
+// targets.
+int launch_denoise(gme_ctx* ctx, const uint8_t* cur, long long cur_stride, const uint8_t* preds, long long pred_stride, long long plane_stride,
+                   int targets, int R, int H, int W, int pitch, int strength, const uint8_t* truth, long long truth_stride, uint8_t* out,
+                   long long out_stride, int out_pitch, unsigned long long* sse);
 
 // ---- synth_kernels.hip ------------------------------------------------------
 int launch_synth_canvas(gme_ctx* ctx, uint64_t seed, uint8_t* canvas);

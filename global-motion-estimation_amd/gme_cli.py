@@ -18,6 +18,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py prop -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 3] [-pn 0] [--rounds 2] [--steps 1] [--no-temporal] [--camera projective|affine|none] [--hier] [-o OUTDIR]   # vector propagation search of one pair
     python gme_cli.py interp -p <video|frame dir> -fi 2 [-fd 2] [-bs 16] [-sw 8] [-pn 0] [--bias N] [-o OUTDIR] [--upconvert]   # the frame between two frames; frame-rate doubling
     python gme_cli.py obmc -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--subpel 0|1|2] [--hier] [-o OUTDIR]   # overlapped block motion compensation of one pair
+    python gme_cli.py denoise -p <video|frame dir> -o OUTDIR [-fd 1] [-bs 16] [-sw 8] [-sp 0] [-pn 0] [--radius 1] [--subpel 0|1|2] [--strength 24] [--noise SIGMA [--seed N]]   # motion-compensated temporal denoising of a clip
     python gme_cli.py info                                                       # searches, norms, models, device
 """
 import argparse
@@ -186,6 +187,22 @@ def _parser():
     op.add_argument("--subpel", type=int, default=0, help="refine the field afterwards: 0 no, 1 half-pel, 2 quarter-pel")
     op.add_argument("--hier", action="store_true", help="take the field from the hierarchical search (three levels, radius 1)")
     op.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for obmc.json and obmc.png")
+    dp = sub.add_parser("denoise", help="motion-compensated temporal denoising of a clip: every frame averaged with the overlapped predictions of it from its neighbours, gated per pixel (denoise.py, DESIGN.md 7p)")
+    dp.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    dp.add_argument("-o", "--output", dest="outdir", type=str, required=True, help="directory for denoise.json and denoised/%%04d.png")
+    dp.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=1, help="the references of frame t are t -+ d fd, d = 1 .. radius")
+    dp.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="4 .. 64")
+    dp.add_argument("-sw", "--search-window", dest="search_window", type=int, default=8)
+    dp.add_argument("-sp", "--searching-procedure", dest="searching_procedure", type=int, default=0,
+                    help="0: exhaustive, 1: three-step, 2: 2-D log, 3: diamond")
+    dp.add_argument("-pn", "--pnorm-distance", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    dp.add_argument("--radius", type=int, default=1, help="1 .. 2: references on each side of a frame")
+    dp.add_argument("--subpel", type=int, default=0, help="refine the fields: 0 no, 1 half-pel, 2 quarter-pel")
+    dp.add_argument("--strength", type=int, default=24,
+                    help="1 .. 64 grey levels: a prediction's weight reaches zero where the mean absolute difference over the 3 x 3 window "
+                         "reaches it; the default is a convention of the tool and not a tuned value")
+    dp.add_argument("--noise", type=float, default=None, help="add Gaussian noise of this sigma to the clip first and report PSNR against the clean clip")
+    dp.add_argument("--seed", type=int, default=0, help="seed of --noise")
     sub.add_parser("info", help="list searches, norms, motion models and the device")
     return ap
 
@@ -426,6 +443,43 @@ def _obmc(args):
     return res
 
 
+def _denoise(args):
+    """The filtered clip into OUTDIR/denoised/%04d.png and the record into OUTDIR/denoise.json: per frame the squared difference
+    to the input, and with --noise (seeded Gaussian noise added to the clip first) the squared errors and the PSNR of the noisy and
+    of the filtered clip against the clean one."""
+    import json
+    import os
+    import numpy as np
+    import denoise
+    import utils
+    frames = np.stack([np.ascontiguousarray(f) for f in utils.get_video_frames(args.path)])
+    clean = None
+    if args.noise is not None:
+        clean = frames
+        rng = np.random.default_rng(args.seed)
+        frames = np.clip(np.rint(clean + rng.normal(scale=args.noise, size=clean.shape)), 0, 255).astype(np.uint8)
+    res = denoise.report(frames, clean, frame_distance=args.fd, block_size=args.block_size, search_window=args.search_window,
+                         searching_procedure=args.searching_procedure, pnorm_distance=args.pnorm, radius=args.radius, levels=args.subpel,
+                         strength=args.strength)
+    record = {"options": {"path": args.path, "frame_distance": args.fd, "block_size": args.block_size, "search_window": args.search_window,
+                          "searching_procedure": args.searching_procedure, "pnorm": args.pnorm, "radius": args.radius,
+                          "subpel": args.subpel, "strength": args.strength, "noise": args.noise, "seed": args.seed},
+              "frames": len(frames), "shape": list(frames.shape[1:])}
+    record.update({k: v for k, v in res.items() if k != "frames"})
+    print("{} frames of {} x {}: strength {}, radius {}, changed by {} in all".format(len(frames), frames.shape[1], frames.shape[2],
+                                                                                    args.strength, args.radius, sum(res["change"])))
+    if clean is not None:
+        print("psnr against the clean clip: noisy {:.4f} dB, filtered {:.4f} dB  (gain {:+.4f} dB)".format(
+            res["psnr_noisy"], res["psnr_filtered"], res["psnr_filtered"] - res["psnr_noisy"]))
+    os.makedirs(os.path.join(args.outdir, "denoised"), exist_ok=True)
+    with open(os.path.join(args.outdir, "denoise.json"), "w") as f:
+        json.dump(record, f, indent=1)
+    for k, made in enumerate(res["frames"]):
+        utils.write_image(os.path.join(args.outdir, "denoised", "%04d.png" % k), made)
+    res["noisy"] = frames
+    return res
+
+
 def _gmc(args):
     """The penalty, the mode shares and the PSNR of the global-only, the local-only and the chosen prediction of one frame; the
     same record into OUTDIR/gmc.json and the mode map (0 / 128 / 255 per block, scaled up to the frame) into OUTDIR/modes.png."""
@@ -632,6 +686,8 @@ def main(argv=None):
         return _interp(args)
     if args.command == "obmc":
         return _obmc(args)
+    if args.command == "denoise":
+        return _denoise(args)
     import _gme_native
     import roadmap
     print("searching procedures (-sp): 0 exhaustive, 1 three-step, 2 2-D log, 3 diamond   (bbme.py:609-614)")
@@ -645,6 +701,7 @@ def main(argv=None):
     print("vector propagation search (gme_cli.py prop): -bs 4 .. 64, --rounds 1 .. 4, --steps 0 .. 4, --camera projective | affine | none; own, neighbour, temporal, camera and zero vectors on a prior field, refined by one pixel   (propagate.py)")
     print("frame interpolation (gme_cli.py interp): -bs 4 .. 64, -sw 0 .. 8, --bias 0 .. 2^16, --upconvert; the frame halfway between two frames by a bilateral search, borders replicated   (interp.py)")
     print("overlapped block compensation (gme_cli.py obmc): -bs 4 .. 64, --subpel 0 .. 2, --hier; every pixel blended from its block's and the nearest neighbours' predictions under a linear ramp, borders replicated   (obmc.py)")
+    print("temporal denoising (gme_cli.py denoise): -bs 4 .. 64, --radius 1 .. 2, --subpel 0 .. 2, --strength 1 .. 64 (default 24, a convention); every frame averaged with the overlapped predictions of it from its neighbours, each pixel gated by its 3 x 3 prediction error   (denoise.py)")
     try:
         print("device: " + _gme_native.default_context().info()["name"])
     except Exception as e:      # noqa: BLE001 -- no GPU: say so, the listing above is still useful

@@ -83,6 +83,12 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    vector is unavailable.  One wave per row of one kernel (k_obmc, csrc/bbme_obmc.hip; host definition obmc.py; DESIGN.md §7o);
    ``Sequence.obmc`` takes the sequence's motion field or its quarter-pel field, computes and returns in one call and keeps
    nothing.
+   **Motion-compensated temporal denoising.**  ``denoise.clip`` cleans a noisy clip: every frame is averaged with the overlapped
+   predictions of it from its neighbour frames (``radius`` 1 or 2 on each side), each pixel gated by the prediction error over
+   its 3 x 3 window, so the filter follows local motion and leaves the frame alone where the prediction fails; the fields are
+   searched from the frame being filtered and applied negated.  ``denoise.blend`` and ``denoise.frame`` are the host definition;
+   one wave per row of one kernel (k_denoise, csrc/bbme_denoise.hip); ``Sequence.denoise`` searches, predicts and
+   filters in one call and keeps nothing.  The default strength 24 is a convention of the tool, not a tuned value.
 2. **Parameter heuristics** (``suggest_parameters``): block size from the frame height (the authors'
    slide settings, docs/presentation/main.tex:382-558, follow ``H / 20`` in 4 of 5 cases), search window
    from the dense coarse field, outlier fraction from the spread of the block vectors.

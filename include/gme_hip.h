@@ -603,6 +603,38 @@ GME_API int gme_seq_obmc(gme_seq *seq, int frame_distance, int block_size, int u
                          uint8_t *frames_out, int64_t *sse_out);
 
 /* ---------------------------------------------------------------------------
+ * Motion-compensated temporal denoising (csrc/bbme_denoise.hip; host definition: denoise.py): a frame
+ * averaged with R = 1 .. 4 overlapped predictions of it from neighbour frames, every pixel gated by how well its neighbourhood
+ * was predicted.  With S = 9 strength (strength 1 .. 64 grey levels) and D_r the sum of |prediction_r - cur| over the pixel's
+ * 3 x 3 window (both coordinates clamped to the frame), prediction r weighs w_r = max(0, S - D_r) and the pixel itself S:
+ * out = (S cur + sum w_r p_r + tot / 2) / tot, tot = S + sum w_r, rounded down.  All integer, byte-equal to denoise.blend.
+ * A prediction is the overlapped compensation of the section above by the NEGATED field: field r is int32[H/B][W/B][2] (column,
+ * row) on the block grid of the frame being filtered and says where that frame's block is found in reference r (what
+ * gme_bbme_u8 returns with the frame as `prev` and the reference as `cur`; f0 and f1 of the bidirectional section), so pixel
+ * (u, v) reads the reference at (4 u + q0, 4 v + q1) quarter pixels, every tap clamped; any int32 vector is valid.  unit 4: whole
+ * pixels, unit 1: quarter pixels.  R outside 1 .. 4, strength outside 1 .. 64, unit not 1 or 4, block_size outside 4 .. 64 or
+ * above H or W: GME_ERR_ARG.
+ * gme_denoise_u8: one frame on host buffers (refs and fields: R pointers each, all images with the row stride `stride`) ->
+ *   frame_out uint8[H][W] (tight), *sse_out = exact squared error of the filtered frame against `truth`, or -1 where truth is
+ *   NULL.  Either output may be NULL.
+ * gme_seq_denoise: the interior targets t = radius * frame_distance + first_target + k, k < count, of a resident sequence, each
+ *   with the 2 radius references t -+ d frame_distance, d = 1 .. radius (radius 1 .. 2; fewer than 2 radius frame_distance + 1
+ *   frames, or a target range outside [0, N - 2 radius frame_distance), is GME_ERR_ARG; the rules of gme_seq_bbme apply to the
+ *   search arguments).  Per reference it runs the named search from the target into a field of its own, with levels 1 or 2 the
+ *   sub-pel refinement of the quarter-pel section, and the overlapped prediction; then the filter -> frames_out
+ *   uint8[count][H][W] (tight), change_out[count] = sum (out - target)^2, the energy the filter removed.  Either output may be
+ *   NULL.  It computes and returns in one call, in buffers of its own that live as long as the call: it keeps nothing, writes
+ *   neither a field nor the compensated planes, and leaves every kept result readable and byte-identical, so it is no part of the
+ *   result lifetimes above.
+ * Blocking calls, also in split-phase mode.  gme_last_bbme_info names the kernel: k_denoise. */
+GME_API int gme_denoise_u8(gme_ctx *ctx, const uint8_t *cur, const uint8_t *const *refs, const int32_t *const *fields, int R,
+                           int H, int W, int stride, int block_size, int unit /* 4: whole pixels, 1: quarter pixels */,
+                           int strength, const uint8_t *truth /* may be NULL */, uint8_t *frame_out, int64_t *sse_out);
+GME_API int gme_seq_denoise(gme_seq *seq, int frame_distance, int block_size, int search_window, int procedure, int pnorm,
+                            int radius, int levels, int strength, int first_target, int count, uint8_t *frames_out,
+                            int64_t *change_out);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, contiguous pair ranges per rank (results.py:41-50 carries no state
  * between pairs), and ONE exchange: the all-gather of the per-pair parameter rows over RCCL / xGMI on
  * the context's stream.  The reference has no distributed code; SURVEY.md §8(e) defines this split.
