@@ -103,6 +103,7 @@ _SIGNATURES = {
     "gme_seq_warp_frames": (_i, [_vp, _i, _i, _c_f64p, _i, _i, _c_i64p]),
     "gme_seq_read_warped_range": (_i, [_vp, _i, _i, _c_u8p]),
     "gme_seq_frame_sse": (_i, [_vp, _i, _i, _i, _c_i64p]),
+    "gme_seq_warp_fill": (_i, [_vp, _i, _i, _i, _c_i32p, _c_f64p, _i, _i, _c_u8p, _c_u8p, _c_i64p, _c_i64p, _c_i64p]),
     "gme_seq_mosaic": (_i, [_vp, _i, _i, _c_f64p, _c_u8p, _i, _i, _i, _i, _i, _i]),
     "gme_seq_read_mosaic": (_i, [_vp, _c_u8p, _c_u16p]),
     "gme_seq_moving_masks": (_i, [_vp, _i, _i, _c_f64p, _c_u8p, _i, _i, _i, _i, _c_i64p, _c_i64p]),
@@ -1009,6 +1010,26 @@ class Sequence:
         sse = np.zeros(int(count), np.int64)
         _check(self.lib.gme_seq_frame_sse(self.handle, int(warped), int(first), int(count), _p(sse, _c_i64p)), self.lib)
         return sse
+
+    def warp_fill(self, first, sources, warps, border=0, fill=0, want_source=False):
+        """Output frames first .. first+count-1, each pixel from the first of its frame's candidates (sources int32[count, n]
+        absolute frame indices or -1, warps float64[count, n, 8], n in 1 .. 17) whose sample point lies in its frame, the border
+        rule on candidate 0 elsewhere (gme_seq_warp_fill, stabilize.warp_fill) -> (frames uint8[count, H, W], source
+        uint8[count, H, W] or None, valid int64[count], filled int64[count], sse int64[count - 1]).  One blocking call, also in
+        split-phase mode, that keeps nothing and leaves everything the sequence holds as it was."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        if src.ndim != 2:
+            raise ValueError("sources must be int32[count, n], not of shape %r" % (src.shape,))
+        count, n = src.shape
+        w = np.ascontiguousarray(np.asarray(warps, dtype=np.float64).reshape(count, n, 8))
+        frames = np.empty((count, self.H, self.W), np.uint8)
+        who = np.empty((count, self.H, self.W), np.uint8) if want_source else None
+        valid, filled = np.zeros(max(count, 1), np.int64), np.zeros(max(count, 1), np.int64)
+        sse = np.zeros(max(count - 1, 1), np.int64)
+        _check(self.lib.gme_seq_warp_fill(self.handle, int(first), count, n, _p(src, _c_i32p), _p(w, _c_f64p), int(border), int(fill),
+                                          _p(frames, _c_u8p), None if who is None else _p(who, _c_u8p), _p(valid, _c_i64p),
+                                          _p(filled, _c_i64p), _p(sse, _c_i64p)), self.lib)
+        return frames, who, valid[:count], filled[:count], sse[:max(count - 1, 0)]
 
     # ---- background mosaic and moving-object masks (gme_mosaic.hip, mosaic.py, DESIGN.md section 7d)
     def _blocking(self, what):

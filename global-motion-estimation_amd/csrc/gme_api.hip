@@ -2076,6 +2076,71 @@ extern "C" int gme_seq_frame_sse(gme_seq* s, int warped, int first, int count, i
 }
 
 // ---------------------------------------------------------------------------
+// Full-frame stabilization (gme_stab_fill.hip): one blocking call that computes and returns, in the form
+// of gme_seq_obmc.  The output frames, the winning candidates, the counts and the candidate rows live in buffers of the
+// call's own; it touches neither the sequence's warped planes and their written flags nor any other kept result, so there
+// is nothing of it that a later call could read stale.  The source frames are absolute resident indices, so the whole
+// range is warped into one buffer (chunked over output frames by the launcher) and the squared errors are taken there.
+// ---------------------------------------------------------------------------
+extern "C" int gme_seq_warp_fill(gme_seq* s, int first, int count, int n_cand, const int32_t* sources, const double* warps, int border,
+                                 int fill, uint8_t* frames_out, uint8_t* source_out, int64_t* valid_out, int64_t* filled_out,
+                                 int64_t* sse_out)
+{
+    GME_REQUIRE(s != nullptr, GME_ERR_ARG, "gme_seq_warp_fill: null sequence");
+    gme_ctx* ctx = s->ctx;
+    GME_ENTER(ctx);
+    GME_REQUIRE(first >= 0 && count >= 0 && first <= s->N - count, GME_ERR_ARG, "gme_seq_warp_fill: frames [%d, %lld) outside [0, %d)",
+                first, (long long)first + count, s->N);
+    GME_REQUIRE(n_cand >= 1 && n_cand <= 17, GME_ERR_ARG, "gme_seq_warp_fill: %d candidates (1 .. 17)", n_cand);
+    GME_REQUIRE((sources != nullptr && warps != nullptr) || count == 0, GME_ERR_ARG, "gme_seq_warp_fill: null sources or warps");
+    GME_REQUIRE(border == 0 || border == 1, GME_ERR_ARG, "gme_seq_warp_fill: border %d (0 constant, 1 replicate)", border);
+    GME_REQUIRE(fill >= 0 && fill <= 255, GME_ERR_ARG, "gme_seq_warp_fill: fill %d (0 .. 255)", fill);
+    const size_t rows = (size_t)count * n_cand;
+    for (size_t i = 0; i < rows; ++i) {
+        GME_REQUIRE(sources[i] >= -1 && sources[i] < s->N, GME_ERR_ARG, "gme_seq_warp_fill: source %d of frame %d outside -1 .. %d",
+                    sources[i], first + (int)(i / n_cand), s->N - 1);
+        GME_REQUIRE(i % n_cand != 0 || sources[i] >= 0, GME_ERR_ARG, "gme_seq_warp_fill: candidate 0 of frame %d is not a frame",
+                    first + (int)(i / n_cand));
+    }
+    if (count == 0) return GME_OK;
+    DevBuf<int32_t> cand;
+    DevBuf<double> par;
+    DevBuf<unsigned long long> counts;                         // valid [count] | filled [count] | sse [count - 1]
+    PlaneBuf made, who;
+    int rc = dev_ensure_all("fill candidates", { { cand, rows }, { par, rows * 8 }, { counts, (size_t)count * 3 } });
+    if (rc) return rc;
+    rc = plane_alloc(ctx, &made, count, s->H, s->W);
+    if (rc) return rc;
+    if (source_out) {
+        rc = plane_alloc(ctx, &who, count, s->H, s->W);
+        if (rc) return rc;
+    }
+    GME_HIP_TRY(hipMemcpyAsync(cand.get(), sources, rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    GME_HIP_TRY(hipMemcpyAsync(par.get(), warps, rows * 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    unsigned long long *valid = counts.get(), *filled = valid + count, *sse = filled + count;
+    rc = launch_warp_fill(ctx, s->level[2], made, who, count, n_cand, cand, par, border, fill, valid, filled);
+    if (rc) return rc;
+    if (sse_out) {
+        rc = launch_frame_sse(ctx, made, 0, count - 1, sse);
+        if (rc) return rc;
+    }
+    const hipStream_t st = ctx->stream;
+    if (frames_out) {
+        rc = read_planes(ctx, made, 0, count, frames_out);
+        if (rc) return rc;
+    }
+    if (source_out) {
+        rc = read_planes(ctx, who, 0, count, source_out);
+        if (rc) return rc;
+    }
+    if (valid_out) GME_HIP_TRY(hipMemcpyAsync(valid_out, valid, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (filled_out) GME_HIP_TRY(hipMemcpyAsync(filled_out, filled, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (sse_out && count > 1)
+        GME_HIP_TRY(hipMemcpyAsync(sse_out, sse, (size_t)(count - 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    return ctx_finish(ctx);                                    // the buffers are freed behind a drained stream
+}
+
+// ---------------------------------------------------------------------------
 // Background mosaic and moving-object masks (gme_mosaic.hip): blocking calls on the resident frames.
 // ---------------------------------------------------------------------------
 static int mosaic_rows(gme_seq* s)

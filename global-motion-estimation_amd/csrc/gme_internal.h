@@ -412,6 +412,14 @@ int launch_warp_frames(gme_ctx* ctx, const Plane& src, const Plane& dst, int fir
 // sse[k] = sum (p[first + k + 1] - p[first + k])^2, k < count (device)
 int launch_frame_sse(gme_ctx* ctx, const Plane& p, int first, int count, unsigned long long* sse);
 
+// ---- gme_stab_fill.hip: full-frame stabilization ----------------------------------------------
+// output frames 0 .. count - 1 of dst, each pixel from the first of its frame's n_cand candidates (sources[count][n_cand]
+// absolute frames of src or -1, params[count][n_cand][8]; device) whose sample point lies in its frame, the border rule on
+// candidate 0 elsewhere; who (same geometry as dst; no memory: not wanted) the winning candidate or 255 per pixel;
+// valid / filled [count] (device) the pixels won by candidate 0 / by a later one.  The caller has checked the indices.
+int launch_warp_fill(gme_ctx* ctx, const Plane& src, const Plane& dst, const Plane& who, int count, int n_cand, const int* sources,
+                     const double* params, int border, int fill, unsigned long long* valid, unsigned long long* filled);
+
 // ---- gme_mosaic.hip: background mosaic and moving-object masks --------------------------------
 // sprite / cnt [Hc][out_pitch] = lower median / number of the in-frame samples of frames first .. first + count - 1 of src at
 // every canvas pixel (fill where there is none); G[count][8] and usable[count] on the device; cull 0 samples every frame

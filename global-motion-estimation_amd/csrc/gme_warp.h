@@ -1,5 +1,5 @@
 // The per-pixel arithmetic of direct.py (warp, taps, blend), shared by the direct refinement (gme_direct.hip) and the
-// per-frame warp of the stabilizer (gme_stab.hip): one rounding per operation, in the order direct.py writes it, so that
+// per-frame warps of the stabilizer (gme_stab.hip, gme_stab_fill.hip): one rounding per operation, in the order direct.py writes it, so that
 // host and device agree bit for bit (the library builds with -ffp-contract=off).
 #pragma once
 #include "gme_internal.h"

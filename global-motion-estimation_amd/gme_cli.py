@@ -8,7 +8,7 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py results -v <name under resources/videos> -f 1 [--model quadratic] [--suggest]    # results.py main
     python gme_cli.py suggest -p <video|frame dir> [-fi 1] [-f 1]                 # parameter heuristics
     python gme_cli.py projective -p <video|frame dir> -fi 1 [-f 1]                # direct projective refinement of one pair
-    python gme_cli.py stabilize -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--radius 15]   # video stabilization
+    python gme_cli.py stabilize -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--radius 15] [--neighbours 0]   # video stabilization
     python gme_cli.py mosaic -p <video|frame dir> -o OUTDIR [--estimator projective|affine] [--anchor 0] [--threshold 16] [--min-count 3] [--no-masks]   # background mosaic, moving-object masks
     python gme_cli.py subpel -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--levels 2] [-o OUTDIR]   # quarter-pel block matching of one pair
     python gme_cli.py hier -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-cw 8] [-r 1] [-pn 0] [--levels 3] [--subpel 0|1|2] [-o OUTDIR]   # hierarchical block matching of one pair
@@ -72,7 +72,9 @@ def _parser():
     st.add_argument("--max-crop", type=float, default=0.25, help="cap of the auto crop")
     st.add_argument("--border", choices=("constant", "replicate"), default="constant")
     st.add_argument("--fill", type=int, default=0, help="value of border pixels under --border constant")
-    mo = sub.add_parser("mosaic", help="background mosaic and moving-object masks from the estimated camera path (mosaic.py, DESIGN.md 7d)")
+    st.add_argument("--neighbours", type=int, default=0,
+                    help="fill the border of each frame from this many frames a side (0 .. 8; crop auto then means 0)")
+    mo =sub.add_parser("mosaic", help="background mosaic and moving-object masks from the estimated camera path (mosaic.py, DESIGN.md 7d)")
     mo.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
     mo.add_argument("-o", "--output", dest="outdir", type=str, required=True,
                     help="directory for mosaic.png, masks/%%04d.png and mosaic.json")
@@ -220,7 +222,7 @@ def _stabilize(args):
     import utils
     frames = np.stack([np.asarray(f, dtype=np.uint8) for f in utils.get_video_frames(args.path)])
     out, res = stabilize.stabilize(frames, estimator=args.estimator, radius=args.radius, sigma=args.sigma, crop=args.crop,
-                                   max_crop=args.max_crop, border=args.border, fill=args.fill)
+                                   max_crop=args.max_crop, border=args.border, fill=args.fill, neighbours=args.neighbours)
     d = os.path.join(args.outdir, "stabilized")
     os.makedirs(d, exist_ok=True)
     for k, f in enumerate(out):
@@ -230,6 +232,9 @@ def _stabilize(args):
               "frames": int(len(out)), "crop": res["crop"], "itf_before": res["itf_before"], "itf_after": res["itf_after"],
               "pair_params": res["h"].tolist(), "pair_flags": res["pair_flags"].tolist(), "W": res["W"].tolist(),
               "frame_flags": res["flags"].tolist(), "valid": res["valid"].tolist()}
+    if args.neighbours:
+        record["options"]["neighbours"] = args.neighbours
+        record.update(neighbours=res["neighbours"], filled=res["filled"].tolist(), unfilled=res["unfilled"].tolist())
     with open(os.path.join(args.outdir, "stabilize.json"), "w") as f:
         json.dump(record, f, indent=1)
     print("{} frames of shape {}, crop {:.4f}".format(len(out), out.shape[1:], res["crop"]))

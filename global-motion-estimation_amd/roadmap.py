@@ -46,7 +46,9 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    Gauss-Newton under a truncated quadratic (k_direct_sums / k_direct_state, csrc/gme_direct.hip; host definition
    direct.py), with dense sub-pixel compensation under it.  It is a separate estimator, not an entry of ``MODELS``.
    **Stabilization.**  ``stabilize.stabilize`` chains the pair warps of either estimator into a camera path, smooths it and
-   warps every frame on the device (k_warp_frames, csrc/gme_stab.hip).
+   warps every frame on the device (k_warp_frames, csrc/gme_stab.hip).  With ``neighbours=K`` the border of
+   frame t is filled from frames t-1, t+1, .. t-K, t+K instead of being cropped away (k_warp_fill, csrc/gme_stab_fill.hip;
+   host definition stabilize.warp_fill / fill_candidates).
    **Quarter-pel block matching.**  ``subpel.motion_field`` refines the integer field of any search to half and quarter
    pixels and ``Sequence.compensate_qpel`` compensates with it (k_subpel_refine / k_compensate_qpel, csrc/bbme_subpel.hip;
    host definition subpel.py).  The fits above still take integer vectors.

@@ -399,6 +399,7 @@ class ShardedSequence:
             self.lanes.append(_Lane(c, _native.Sequence(c, n_fr, self.H, self.W), lo, hi))
         self.seq = self.lanes[0].seq if len(self.lanes) == 1 else None     # single-stream shards: the sequence itself
         self._pool = None
+        self._stabilized = None       # the frames of the last stabilize(neighbours >= 1), which keeps nothing on the device
 
     @property
     def n_pairs(self):
@@ -687,13 +688,19 @@ class ShardedSequence:
 
     # ---- video stabilization (stabilize.py, gme_stab.hip)
     def stabilize(self, estimator="projective", radius=15, sigma=None, crop="auto", max_crop=0.25, border="constant", fill=0,
-                  procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10):
+                  procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10, neighbours=0):
         """Stabilize the whole video from its estimated camera path -> result dict (stabilize.stabilize).  Each lane estimates
         its pairs; the pair warps are all-gathered (gather, k = 8), so every rank and lane computes the same path, crop and
         corrections in host float64; each lane then warps all of its resident frames lo .. hi (the frame shared at a lane
         boundary twice, identically) and the consecutive-frame squared errors of its pairs.  read_stabilized reads the
-        frames.  Results do not depend on ``streams``."""
+        frames.  Results do not depend on ``streams``.  With ``neighbours`` K >= 1 the border of frame t is filled from frames
+        t-1, t+1, .. t-K, t+K (stabilize.fill_candidates, gme_seq_warp_fill), which reads frames across lane boundaries: one
+        rank, one lane; the call returns the frames and read_stabilized serves them from host memory."""
         import stabilize as stab
+        neighbours = int(neighbours)
+        if neighbours and (self.world > 1 or len(self.lanes) > 1):
+            raise ValueError("stabilize with neighbours needs the whole video in one sequence: world %d, streams %d (a border is "
+                             "filled from frames of other shards; use world = 1 and streams = 1)" % (self.world, len(self.lanes)))
         if self.fd != 1:
             raise ValueError("stabilize needs frame_distance 1 (this sequence has %d)" % self.fd)
         if estimator not in stab.ESTIMATORS:
@@ -703,8 +710,16 @@ class ShardedSequence:
             raise ValueError("fill %d outside 0 .. 255" % fill)
         h_loc, f_loc = self._pair_warps(estimator, procedure, search_window, outlier_fraction, max_iters)
         h = self.gather(h_loc)
-        out = stab.plan(h, self.H, self.W, radius, sigma, crop, max_crop)
+        out = stab.plan(h, self.H, self.W, radius, sigma, crop, max_crop, neighbours)
         Wt = out["W"]
+        self._stabilized = None
+        if neighbours:
+            n = self.n_pairs_total
+            self._stabilized, _, valid, filled, sse = self.seq.warp_fill(0, out["sources"], out["fill_warps"], bid, int(fill))
+            out.update(h=h, pair_flags=f_loc, estimator=estimator, valid=valid, filled=filled,
+                       unfilled=self.H * self.W - valid - filled, itf_before=stab.itf(self.seq.frame_sse(0, 0, n), self.H, self.W),
+                       itf_after=stab.itf(sse, self.H, self.W))
+            return out
 
         def warp(lane):
             n = lane.hi - lane.lo
@@ -730,11 +745,17 @@ class ShardedSequence:
 
     def read_stabilized(self, frame):
         """Stabilized frame ``frame`` (global index) from the lane that owns it (stabilized_owners) -> uint8[H, W]."""
+        if self._stabilized is not None:
+            return self._stabilized[frame].copy()
         lane, k, _ = self._owner(frame)
         return lane.seq.read_warped_range(k, 1)[0]
 
     def read_stabilized_range(self, first, count):
         """Stabilized frames first .. first+count-1, all owned by this rank -> uint8[count, H, W]."""
+        if self._stabilized is not None:
+            if not 0 <= first <= first + count <= len(self._stabilized):
+                raise IndexError("frames [%d, %d) outside [0, %d)" % (first, first + count, len(self._stabilized)))
+            return self._stabilized[first:first + count].copy()
         out = np.empty((int(count), self.H, self.W), np.uint8)
         k = 0
         while k < count:

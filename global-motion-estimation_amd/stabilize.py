@@ -14,6 +14,9 @@ M(h) = [[h0 h1 h2] [h3 h4 h5] [h6 h7 1]]; a warp maps a pixel of the frame being
 * ``smooth``: S_t, the Gaussian average of C_{t-r_t} .. C_{t+r_t}, r_t = min(radius, t, N-1-t) (symmetric at the ends).
 * Correction of frame t: W_t = C_t^-1 S_t Z(crop), [2,2] = 1, where Z zooms by s = 1 - crop about the frame centre.  Output
   pixel (u, v) of stabilized frame t samples source frame t at direct.warp(W_t, u, v).
+* Full-frame form: frame s sees output pixel (u, v) of stabilized frame t at C_s^-1 S_t Z (u, v), so what
+  W_t misses of frame t is taken from frames t-1, t+1, t-2, ... (``fill_candidates``) by ``warp_fill``, the definition of
+  ``gme_seq_warp_fill`` (``csrc/gme_stab_fill.hip``): per pixel, the first candidate whose point lies in its frame.
 * Frame flags: FLAG_FALLBACK (1) -- W_t was non-finite or had d <= 0 at an output corner and was replaced by Z;
   FLAG_BORDER (2) -- an output corner maps outside the frame, so the frame has border pixels (informational).
 """
@@ -204,6 +207,107 @@ def warp_frames(frames, warps, border="constant", fill=0):
     return out, valid
 
 
+MAX_NEIGHBOURS = 8            # fill_candidates: neighbours a side
+MAX_CANDIDATES = 2 * MAX_NEIGHBOURS + 1
+NO_SOURCE = 255               # warp_fill's `source` where no candidate gave the pixel
+
+
+def warp_fill(frames, sources, warps, border="constant", fill=0):
+    """The definition of gme_seq_warp_fill: uint8[N, H, W] frames, int32[N, n] candidate frames and
+    float64[N, n, 8] candidate warps, 1 <= n <= 17 -> (out uint8[N, H, W], source uint8[N, H, W], valid int64[N],
+    filled int64[N], sse int64[N-1]).  Output pixel (u, v) of frame t walks its candidates j = 0 .. n-1 in order; a candidate
+    with sources[t, j] == -1 is skipped; the first one whose point direct.warp(warps[t, j], u, v) is valid in frame
+    sources[t, j] (warp_frames' test) gives the pixel, floor(bilinear + 0.5).  Where none is valid the pixel follows
+    ``border`` as warp_frames does for candidate 0 (which must be a frame).  ``source``: the winning j, NO_SOURCE where there
+    is none; ``valid`` / ``filled``: the pixels won by candidate 0 / by a later one; sse[k] = sum (out[k+1] - out[k])^2."""
+    bid = border_id(border)
+    fill = int(fill)
+    if not 0 <= fill <= 255:
+        raise ValueError("fill %d outside 0 .. 255" % fill)
+    frames = np.asarray(frames, dtype=np.uint8)
+    N, H, W = frames.shape
+    sources = np.asarray(sources)
+    if sources.ndim != 2 or len(sources) != N or not 1 <= sources.shape[1] <= MAX_CANDIDATES:
+        raise ValueError("sources of shape %r: need [%d, n] with n in 1 .. %d" % (sources.shape, N, MAX_CANDIDATES))
+    n = sources.shape[1]
+    if N and (sources.min() < -1 or sources.max() >= N):
+        raise ValueError("a source outside -1 .. %d" % (N - 1))
+    if np.any(sources[:, 0] < 0):
+        raise ValueError("candidate 0 must be a frame")
+    sources = sources.astype(np.int32)
+    warps = np.asarray(warps, dtype=np.float64).reshape(N, n, 8)
+    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    u, v = u.ravel(), v.ravel()
+    out = np.empty_like(frames)
+    source = np.empty_like(frames)
+    valid, filled = np.zeros(N, np.int64), np.zeros(N, np.int64)
+    for t in range(N):
+        val = np.full(H * W, float(fill))
+        who = np.full(H * W, NO_SOURCE, np.uint8)
+        if bid == 1:
+            with np.errstate(all="ignore"):
+                up, vp, _ = direct.warp(warps[t, 0], u, v)
+            up = np.where(up > 0.0, np.where(up < W - 1.0, up, W - 1.0), 0.0)
+            vp = np.where(vp > 0.0, np.where(vp < H - 1.0, vp, H - 1.0), 0.0)
+            val = np.floor(direct.bilinear(frames[sources[t, 0]], up, vp) + 0.5)
+        for j in range(n):
+            s = int(sources[t, j])
+            if s < 0:
+                continue
+            with np.errstate(all="ignore"):
+                up, vp, _ = direct.warp(warps[t, j], u, v)
+                ins = (up >= 0.0) & (up <= W - 1.0) & (vp >= 0.0) & (vp <= H - 1.0)
+            win = ins & (who == NO_SOURCE)
+            if not np.any(win):
+                continue
+            val[win] = np.floor(direct.bilinear(frames[s], up[win], vp[win]) + 0.5)
+            who[win] = j
+        out[t] = val.astype(np.uint8).reshape(H, W)
+        source[t] = who.reshape(H, W)
+        valid[t] = int((who == 0).sum())
+        filled[t] = int(((who != 0) & (who != NO_SOURCE)).sum())
+    d = out[1:].astype(np.int64) - out[:-1].astype(np.int64)
+    return out, source, valid, filled, (d * d).sum(axis=(1, 2))
+
+
+def fill_candidates(C, S, H, W, crop=0.0, neighbours=1):
+    """The candidates of warp_fill for a stabilization -> (sources int32[N, 2K+1], warps float64[N, 2K+1, 8], flags int32[N]),
+    K = ``neighbours`` in 0 .. MAX_NEIGHBOURS.  Candidate 0 is frame t itself with corrections(C, S, H, W, crop)'s W_t and
+    flags, exactly; candidates 1, 2, 3, 4, ... are frames t-1, t+1, t-2, t+2, ..., frame s under
+    params(C_s^-1 S_t Z(crop)): where frame s saw what the stabilized pose of frame t looks at.  A neighbour is dropped
+    (source -1; the slots do not move) where s is outside [0, N), its warp is non-finite or has d <= 0 at an output corner, or
+    frame t carries FLAG_FALLBACK (its own warp is no longer the stabilized pose)."""
+    K = int(neighbours)
+    if not 0 <= K <= MAX_NEIGHBOURS:
+        raise ValueError("neighbours %d outside 0 .. %d" % (K, MAX_NEIGHBOURS))
+    C, S = np.asarray(C, np.float64), np.asarray(S, np.float64)
+    N = len(C)
+    w0, flags = corrections(C, S, H, W, crop)
+    sources = np.full((N, 2 * K + 1), -1, np.int32)
+    warps = np.zeros((N, 2 * K + 1, 8))
+    sources[:, 0] = np.arange(N)
+    warps[:, 0] = w0
+    Z = zoom(crop, H, W)
+    u, v = _corners(H, W)
+    for t in range(N):
+        if flags[t] & FLAG_FALLBACK:
+            continue
+        for j in range(1, 2 * K + 1):
+            s = t - (j + 1) // 2 if j % 2 else t + j // 2
+            if not 0 <= s < N:
+                continue
+            with np.errstate(all="ignore"):
+                try:
+                    w = params(np.linalg.solve(C[s], S[t] @ Z))
+                except np.linalg.LinAlgError:
+                    continue
+                d = direct.warp(w, u, v)[2]
+            if np.all(np.isfinite(w)) and np.all(d > 0.0):
+                sources[t, j] = s
+                warps[t, j] = w
+    return sources, warps, flags
+
+
 def itf(sse, H, W):
     """Inter-frame transformation fidelity: the mean PSNR of consecutive frames from their squared errors
     (sequence.psnr_from_sse on full frames)."""
@@ -212,25 +316,37 @@ def itf(sse, H, W):
     return float(np.mean(sequence.psnr_from_sse(sse, H, W))) if len(sse) else 0.0
 
 
-def plan(h, H, W, radius=15, sigma=None, crop="auto", max_crop=0.25):
-    """The host half of a stabilization from the pair warps float64[P, 8] -> dict(C, S, crop, W, flags)."""
+def plan(h, H, W, radius=15, sigma=None, crop="auto", max_crop=0.25, neighbours=0):
+    """The host half of a stabilization from the pair warps float64[P, 8] -> dict(C, S, crop, W, flags).  With
+    ``neighbours`` >= 1 (the border filled from that many frames a side, fill_candidates) nothing has to be cropped away, so
+    crop "auto" means 0.0, and the dict gains ``neighbours``, ``sources`` and ``fill_warps``; W is candidate 0's warp."""
+    K = int(neighbours)
+    if not 0 <= K <= MAX_NEIGHBOURS:
+        raise ValueError("neighbours %d outside 0 .. %d" % (K, MAX_NEIGHBOURS))
     C = trajectory(h)
     S = smooth(C, radius, sigma)
     if crop == "auto":
-        c = auto_crop(C, S, H, W, max_crop)
+        c = auto_crop(C, S, H, W, max_crop) if K == 0 else 0.0
     else:
         c = float(crop)
         if not 0.0 <= c < 1.0:
             raise ValueError("crop %r outside [0, 1)" % crop)
-    w, flags = corrections(C, S, H, W, c)
-    return {"C": C, "S": S, "crop": c, "W": w, "flags": flags}
+    if K == 0:
+        w, flags = corrections(C, S, H, W, c)
+        return {"C": C, "S": S, "crop": c, "W": w, "flags": flags}
+    sources, warps, flags = fill_candidates(C, S, H, W, c, K)
+    return {"C": C, "S": S, "crop": c, "W": warps[:, 0].copy(), "flags": flags, "neighbours": K, "sources": sources,
+            "fill_warps": warps}
 
 
 def stabilize(frames, estimator="projective", radius=15, sigma=None, crop="auto", max_crop=0.25, border="constant", fill=0,
-              procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10):
+              procedure=3, search_window=2, outlier_fraction=0.1, max_iters=10, neighbours=0):
     """One call for a video in host memory (uint8[N, H, W] or a list of frames) -> (uint8[N, H, W], result).  ``result``
     (dict): pair ``h`` and ``pair_flags``, ``C``, ``S``, ``W``, ``crop``, frame ``flags``, ``valid`` and ``itf_before`` /
-    ``itf_after``.  ``estimator``: "projective" (the direct refinement) or "affine" (the reference's indirect estimate)."""
+    ``itf_after``.  ``estimator``: "projective" (the direct refinement) or "affine" (the reference's indirect estimate).
+    ``neighbours`` K >= 1 fills what the corrected view of frame t misses from frames t-1, t+1, .. t-K, t+K (plan;
+    ``border`` / ``fill`` decide what none of them reaches) and adds ``neighbours``, ``sources``, ``filled`` and ``unfilled``
+    per frame to the result."""
     import sequence
     frames = np.ascontiguousarray(np.stack([np.asarray(f, dtype=np.uint8) for f in frames])
                                   if not isinstance(frames, np.ndarray) else frames, dtype=np.uint8)
@@ -240,7 +356,7 @@ def stabilize(frames, estimator="projective", radius=15, sigma=None, crop="auto"
         sh.load(frames)
         res = sh.stabilize(estimator=estimator, radius=radius, sigma=sigma, crop=crop, max_crop=max_crop, border=border,
                            fill=fill, procedure=procedure, search_window=search_window, outlier_fraction=outlier_fraction,
-                           max_iters=max_iters)
+                           max_iters=max_iters, neighbours=neighbours)
         out = sh.read_stabilized_range(0, N)
     finally:
         sh.close()

@@ -336,6 +336,21 @@ GME_API int gme_seq_read_warped_range(gme_seq *seq, int first, int count, uint8_
 /* sse_out[k] = sum (f[first+k+1] - f[first+k])^2, k < count; warped 0: the resident frames, 1: the warped ones */
 GME_API int gme_seq_frame_sse(gme_seq *seq, int warped, int first, int count, int64_t *sse_out);
 
+/* Full-frame stabilization (host definition stabilize.warp_fill): the border of a stabilized frame filled
+ * from what neighbouring frames saw.  Output pixel (u, v) of frame first+k walks its n_cand candidates in order: candidate j is
+ * frame sources[k][j] (an absolute index of the resident frames, or -1: skipped) sampled at direct.warp(warps[k][j], u, v).  The
+ * first candidate whose point lies in its frame (gme_seq_warp_frames' test) gives the pixel, bilinear and rounded to nearest.
+ * Where none does, the pixel follows `border` / `fill` as gme_seq_warp_frames does for candidate 0, which must be a frame.
+ * frames_out[count][H][W]; source_out[count][H][W] the winning j per pixel, 255 where there is none; valid_out[count] the pixels
+ * won by candidate 0, filled_out[count] those won by a later one; sse_out[count - 1] the squared errors of consecutive output
+ * frames.  Every output pointer may be NULL.
+ * One blocking call, also in split-phase mode, that computes and returns: it works in buffers of its own and keeps nothing, so
+ * the warped frames of gme_seq_warp_frames and every other kept result stay as they were.  A range outside [0, N), n_cand
+ * outside 1 .. 17, a source outside -1 .. N-1, sources[k][0] < 0, or a bad border or fill is GME_ERR_ARG. */
+GME_API int gme_seq_warp_fill(gme_seq *seq, int first, int count, int n_cand, const int32_t *sources, const double *warps,
+                              int border, int fill, uint8_t *frames_out, uint8_t *source_out, int64_t *valid_out,
+                              int64_t *filled_out, int64_t *sse_out);
+
 /* Background mosaic and moving-object masks (host definition mosaic.py).  Blocking calls on the
  * resident frames; sprite, counts and masks are kept in the sequence (allocated on first use).
  * gme_seq_mosaic: canvas pixel (x, y) of the Hc x Wc canvas with origin (ox, oy) samples frame first+k at direct.warp(
