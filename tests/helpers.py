@@ -1,4 +1,5 @@
-"""Shared test plumbing: golden fixtures, the C oracle through ctypes, the NumPy oracle."""
+"""Shared test plumbing: golden fixtures, the C oracle through ctypes, the NumPy oracle, and the restatements and comparisons
+that more than one test file uses (the order-2 fit stage, the device-solve contracts, the direct refinement)."""
 import ctypes
 import os
 import subprocess
@@ -191,3 +192,117 @@ def mv_summary_rows(mf):
         wgt = np.arange(len(x), dtype=np.int64) % 251 + 1
         out[p, 3:] = (x.sum(), y.sum(), int((wgt * (3 * x + 5 * y)).sum()))
     return out
+
+
+# ---- the order-2 fit stage (test_gpu_models2.py, reuse_cases.py) ------------------------------------------------------------------
+MOMENTS = [(0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (3, 0), (2, 1), (1, 2), (0, 3), (4, 0), (3, 1), (2, 2), (1, 3), (0, 4)]
+PHI = [(0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2)]
+
+
+def field2_np(params, h, w):
+    """The order-2 field in the device's evaluation order: ((p0 + p2 j) + p1 i) + ((a3 (i i) + a4 (i j)) + a5 (j j)),
+    round-half-even, int16 wrap."""
+    p = np.asarray(params, np.float64)
+    i, j = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    out = np.empty((h, w, 2), np.int16)
+    for c in range(2):
+        q0, q1, q2, s0, s1, s2 = p[3 * c], p[3 * c + 1], p[3 * c + 2], p[6 + 3 * c], p[7 + 3 * c], p[8 + 3 * c]
+        d = ((q0 + q2 * j) + q1 * i) + ((s0 * (i * i) + s1 * (i * j)) + s2 * (j * j))
+        out[:, :, c] = np.rint(d).astype(np.int64).astype(np.int16)
+    return out
+
+
+def stage_np(gt, model, frac, level_hw):
+    """Threshold, mask (motion.py:240-244) and the 27 sequential sums over the ordered inliers, each started at +0.0 (so that
+    a chain of -0.0 terms sums to +0.0, as the reference's accumulators do)."""
+    h, w = gt.shape[:2]
+    n = h * w
+    diff = (np.abs(gt[:, :, 0].astype(np.int64) - model[:, :, 0]) + np.abs(gt[:, :, 1].astype(np.int64) - model[:, :, 1])).ravel()
+    if frac < 0:
+        thr = 0x7FFFFFFF
+    else:
+        drop = int(frac * n)
+        thr = int(np.sort(diff)[n - drop if drop > 0 else 0])
+    mask = diff > thr
+    k = np.nonzero(~mask)[0]
+    x, y = 4.0 * (k // w), 4.0 * (k % w)
+    g0, g1 = gt.reshape(-1, 2)[k, 0].astype(np.float64), gt.reshape(-1, 2)[k, 1].astype(np.float64)
+    wgt = 1.0 / (float(level_hw[0]) * float(level_hw[1]))
+    cols = [x ** p * y ** q for p, q in MOMENTS] + [x ** p * y ** q * g0 for p, q in PHI] + [x ** p * y ** q * g1 for p, q in PHI]
+    sums = np.array([np.cumsum(np.concatenate([[0.0], c * wgt]))[-1] for c in cols])      # from +0.0, as the reference
+    return thr, mask.reshape(h, w), sums
+
+
+# ---- the device-solve contracts (test_gpu_models2_solve.py, reuse_cases.py) ------------------------------------
+DX, DY = [0, 1, 2, 6, 7, 8], [3, 4, 5, 9, 10, 11]        # parameter slots of phi_0 .. phi_5 in dx and dy
+
+
+def m_k(h, w):
+    """max |phi_k(i, j)| over an h x w field, per parameter slot."""
+    m6 = np.array([1.0, h - 1, w - 1, (h - 1) ** 2, (h - 1) * (w - 1), (w - 1) ** 2])
+    m = np.empty(12)
+    m[DX], m[DY] = m6, m6
+    return m
+
+
+def contract_violations2(dev, host, h, w):
+    """Order 2: pairs / slots where |dev - host| m_k > 1e-10 max(1, sum over the displacement's six terms of |host| m_k)."""
+    dev, host = np.atleast_2d(dev), np.atleast_2d(host)
+    m = m_k(h, w)
+    bad = []
+    for slots in (DX, DY):
+        scale = np.maximum(1.0, (np.abs(host[:, slots]) * m[slots]).sum(axis=1))
+        err = np.abs(dev[:, slots] - host[:, slots]) * m[slots]
+        for p, k in zip(*np.nonzero(err > 1e-10 * scale[:, None])):
+            bad.append((int(p), slots[k], float(err[p, k] / scale[p])))
+    return bad
+
+
+def clear_of_ties2(params, h, w):
+    """Order 2: pairs whose h x w field (NumPy, float64) keeps 1e-8 max(1, S) away from every k + 0.5: there an unflagged device
+    solve is required; closer, a flag is legitimate."""
+    params = np.atleast_2d(params)
+    i, j = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    phi = np.stack([np.ones_like(i), i, j, i * i, i * j, j * j]).reshape(6, -1)
+    m = m_k(h, w)
+    ok = np.ones(len(params), bool)
+    for slots in (DX, DY):
+        d = params[:, slots] @ phi
+        scale = np.maximum(1.0, (np.abs(params[:, slots]) * m[slots]).sum(axis=1))
+        ok &= np.abs(d - np.floor(d) - 0.5).min(axis=1) > 1e-8 * scale
+    return ok
+
+
+# ---- the direct refinement (test_gpu_direct.py, reuse_cases.py) ---------------------------------------------------------------------
+def corner_error(a, b, H, W):
+    """The largest distance, per axis, between where two warps send the corners of an H x W frame."""
+    import direct
+    u = np.array([0.0, W - 1.0, 0.0, W - 1.0])
+    v = np.array([0.0, 0.0, H - 1.0, H - 1.0])
+    ua, va, _ = direct.warp(np.asarray(a, np.float64), u, v)
+    ub, vb, _ = direct.warp(np.asarray(b, np.float64), u, v)
+    return float(max(np.abs(ua - ub).max(), np.abs(va - vb).max()))
+
+
+def check_eval(got, p, want, what):
+    """One pair of direct_eval against direct.evaluate: threshold, n_valid and n_in bit-equal; cost and sums within 1e-9
+    of the sums of absolute values, bounded by Cauchy-Schwarz from the diagonal."""
+    import direct
+    assert got["threshold"][p] == want["threshold"], what
+    assert tuple(got["counts"][p]) == (want["n_valid"], want["n_in"]), what
+    assert abs(got["cost"][p] - want["cost"]) <= 1e-9 * want["cost"], what
+    N, rhs = direct.normal_matrix(want["sums"])
+    d = np.sqrt(np.diag(N))
+    se2 = want["cost"] * want["n_valid"]                               # >= sum of e^2 over the inliers
+    scale = np.concatenate([np.outer(d, d)[np.triu_indices(8)], d * np.sqrt(se2)])
+    assert np.all(np.abs(got["sums"][p] - want["sums"]) <= 1e-9 * scale), what
+
+
+def check_refine(h, flags, want, want_flags, init, H, W, what):
+    """One pair of refine_projective against direct.refine: the flags identical, the corners within 0.01 px, a flagged start
+    comes back unchanged."""
+    import direct
+    assert flags == want_flags, (what, flags, want_flags)
+    assert corner_error(h, want, H, W) < 0.01, (what, h, want)
+    if want_flags & ~direct.FLAG_MAX_ITERS:
+        assert np.array_equal(h, init), what

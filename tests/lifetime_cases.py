@@ -157,7 +157,7 @@ def memo(fn):
     """Computed once per argument values (arrays by content): the tests share every host result and leave it unchanged."""
     @functools.wraps(fn)
     def wrapper(*args):
-        key = _digest((fn.__name__,) + args)
+        key = _digest((fn.__module__, fn.__name__) + args)
         if key not in _MEMO:
             _MEMO[key] = _freeze(fn(*args))
         return _MEMO[key]

@@ -7,6 +7,8 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import corner_error
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -30,15 +32,6 @@ def known_warps(width=160):
     return {"subpixel_shift": np.array([1, 0, 1.3, 0, 1, -0.7, 0, 0], np.float64),
             "zoom_rotation": np.array([z * np.cos(th), -z * np.sin(th), 2.0, z * np.sin(th), z * np.cos(th), -1.5, 0, 0]),
             "perspective": np.array([1, 0, 0.5, 0, 1, 0.3, 2e-4 * 160 / width, 0], np.float64)}
-
-
-def corner_error(a, b, H, W):
-    import direct
-    u = np.array([0.0, W - 1.0, 0.0, W - 1.0])
-    v = np.array([0.0, 0.0, H - 1.0, H - 1.0])
-    ua, va, _ = direct.warp(np.asarray(a, np.float64), u, v)
-    ub, vb, _ = direct.warp(np.asarray(b, np.float64), u, v)
-    return float(max(np.abs(ua - ub).max(), np.abs(va - vb).max()))
 
 
 def flag_cases(H=99, W=131):

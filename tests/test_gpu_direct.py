@@ -5,6 +5,7 @@ determinism, real frames, the sharded surface and the CLI.  Needs an MI355X."""
 import numpy as np
 import pytest
 
+from helpers import check_eval, check_refine
 from test_direct_host import corner_error, flag_cases, full_hd_case, known_warps, warp_canvas
 
 pytestmark = pytest.mark.gpu
@@ -62,20 +63,6 @@ def test_compensation_equals_host(native, g9, source):
         assert np.array_equal(comp[p], want), (source, p)
         assert sse[p] == want_sse, (source, p)
     seq.close()
-
-
-def check_eval(got, p, want, what):
-    """One pair of direct_eval against direct.evaluate: threshold, n_valid and n_in bit-equal; cost and sums within 1e-9
-    of the sums of absolute values, bounded by Cauchy-Schwarz from the diagonal."""
-    import direct
-    assert got["threshold"][p] == want["threshold"], what
-    assert tuple(got["counts"][p]) == (want["n_valid"], want["n_in"]), what
-    assert abs(got["cost"][p] - want["cost"]) <= 1e-9 * want["cost"], what
-    N, rhs = direct.normal_matrix(want["sums"])
-    d = np.sqrt(np.diag(N))
-    se2 = want["cost"] * want["n_valid"]                               # >= sum of e^2 over the inliers
-    scale = np.concatenate([np.outer(d, d)[np.triu_indices(8)], d * np.sqrt(se2)])
-    assert np.all(np.abs(got["sums"][p] - want["sums"]) <= 1e-9 * scale), what
 
 
 def test_eval_equals_host(native, g9):
@@ -191,10 +178,7 @@ def refine_parity(native, cases):
             n = names[k]
             want, want_flags = direct.refine(pyramids(seq, 2 * k), pyramids(seq, 2 * k + 1), init[2 * k], **dict(kw))
             assert want_flags == cases[n][4], (n, want_flags)
-            assert flags[2 * k] == want_flags, (n, flags[2 * k], want_flags)
-            assert corner_error(h[2 * k], want, H, W) < 0.01, (n, h[2 * k], want)
-            if want_flags & ~direct.FLAG_MAX_ITERS:
-                assert np.array_equal(h[2 * k], init[2 * k]), n
+            check_refine(h[2 * k], flags[2 * k], want, want_flags, init[2 * k], H, W, n)
     seq.close()
 
 

@@ -6,13 +6,9 @@ import os
 import numpy as np
 import pytest
 
-from helpers import c_oracle
+from helpers import c_oracle, field2_np, stage_np
 
 pytestmark = pytest.mark.gpu
-
-MOMENTS = [(0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (3, 0), (2, 1), (1, 2), (0, 3), (4, 0), (3, 1), (2, 2), (1, 3), (0, 4)]
-PHI = [(0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2)]
-
 
 @pytest.fixture(scope="module")
 def native():
@@ -29,40 +25,6 @@ def bits(a):
 def pad12(p):
     p = np.asarray(p, np.float64).reshape(-1, 6)
     return np.concatenate([p, np.zeros_like(p)], axis=1)
-
-
-def field2_np(params, h, w):
-    """The order-2 field in the device's evaluation order: ((p0 + p2 j) + p1 i) + ((a3 (i i) + a4 (i j)) + a5 (j j)),
-    round-half-even, int16 wrap."""
-    p = np.asarray(params, np.float64)
-    i, j = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
-    out = np.empty((h, w, 2), np.int16)
-    for c in range(2):
-        q0, q1, q2, s0, s1, s2 = p[3 * c], p[3 * c + 1], p[3 * c + 2], p[6 + 3 * c], p[7 + 3 * c], p[8 + 3 * c]
-        d = ((q0 + q2 * j) + q1 * i) + ((s0 * (i * i) + s1 * (i * j)) + s2 * (j * j))
-        out[:, :, c] = np.rint(d).astype(np.int64).astype(np.int16)
-    return out
-
-
-def stage_np(gt, model, frac, level_hw):
-    """Threshold, mask (motion.py:240-244) and the 27 sequential sums over the ordered inliers, each started at +0.0 (so that
-    a chain of -0.0 terms sums to +0.0, as the reference's accumulators do)."""
-    h, w = gt.shape[:2]
-    n = h * w
-    diff = (np.abs(gt[:, :, 0].astype(np.int64) - model[:, :, 0]) + np.abs(gt[:, :, 1].astype(np.int64) - model[:, :, 1])).ravel()
-    if frac < 0:
-        thr = 0x7FFFFFFF
-    else:
-        drop = int(frac * n)
-        thr = int(np.sort(diff)[n - drop if drop > 0 else 0])
-    mask = diff > thr
-    k = np.nonzero(~mask)[0]
-    x, y = 4.0 * (k // w), 4.0 * (k % w)
-    g0, g1 = gt.reshape(-1, 2)[k, 0].astype(np.float64), gt.reshape(-1, 2)[k, 1].astype(np.float64)
-    wgt = 1.0 / (float(level_hw[0]) * float(level_hw[1]))
-    cols = [x ** p * y ** q for p, q in MOMENTS] + [x ** p * y ** q * g0 for p, q in PHI] + [x ** p * y ** q * g1 for p, q in PHI]
-    sums = np.array([np.cumsum(np.concatenate([[0.0], c * wgt]))[-1] for c in cols])      # from +0.0, as the reference
-    return thr, mask.reshape(h, w), sums
 
 
 def pairs_under_test(golden):

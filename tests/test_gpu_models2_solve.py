@@ -7,11 +7,11 @@ from contextlib import contextmanager
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from helpers import DX, DY, MOMENTS, PHI
+from helpers import clear_of_ties2 as clear_of_ties
+from helpers import contract_violations2 as contract_violations
 
-MOMENTS = [(0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (3, 0), (2, 1), (1, 2), (0, 3), (4, 0), (3, 1), (2, 2), (1, 3), (0, 4)]
-PHI = [(0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2)]
-DX, DY = [0, 1, 2, 6, 7, 8], [3, 4, 5, 9, 10, 11]        # parameter slots of phi_0 .. phi_5 in dx and dy
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -35,27 +35,6 @@ def _with_env(name, value):
             os.environ[name] = old
 
 
-def m_k(h, w):
-    """max |phi_k(i, j)| over an h x w field, per parameter slot."""
-    m6 = np.array([1.0, h - 1, w - 1, (h - 1) ** 2, (h - 1) * (w - 1), (w - 1) ** 2])
-    m = np.empty(12)
-    m[DX], m[DY] = m6, m6
-    return m
-
-
-def contract_violations(dev, host, h, w):
-    """Pairs / slots where |dev - host| m_k > 1e-10 max(1, sum over the displacement's six terms of |host| m_k)."""
-    dev, host = np.atleast_2d(dev), np.atleast_2d(host)
-    m = m_k(h, w)
-    bad = []
-    for slots in (DX, DY):
-        scale = np.maximum(1.0, (np.abs(host[:, slots]) * m[slots]).sum(axis=1))
-        err = np.abs(dev[:, slots] - host[:, slots]) * m[slots]
-        for p, k in zip(*np.nonzero(err > 1e-10 * scale[:, None])):
-            bad.append((int(p), slots[k], float(err[p, k] / scale[p])))
-    return bad
-
-
 def sums_of_field(params, h, w, bs, cols=None):
     """The 27 order-2 sums of the fit (x = 4 i, y = 4 j, uniform weight 1 / (H W)) over the blocks of an h x w field whose
     displacements are the float64 values of `params`; `cols` restricts the inliers to those block columns."""
@@ -70,21 +49,6 @@ def sums_of_field(params, h, w, bs, cols=None):
     dx, dy = phi @ p[DX], phi @ p[DY]
     mono = np.stack([x ** a * y ** b for a, b in MOMENTS], axis=1)
     return np.concatenate([(mono * wgt).sum(0), (phi * dx[:, None] * wgt).sum(0), (phi * dy[:, None] * wgt).sum(0)])
-
-
-def clear_of_ties(params, h, w):
-    """Pairs whose h x w field (NumPy, float64) keeps 1e-8 max(1, S) away from every k + 0.5: there an unflagged device solve
-    is required; closer, a flag is legitimate."""
-    params = np.atleast_2d(params)
-    i, j = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
-    phi = np.stack([np.ones_like(i), i, j, i * i, i * j, j * j]).reshape(6, -1)
-    m = m_k(h, w)
-    ok = np.ones(len(params), bool)
-    for slots in (DX, DY):
-        d = params[:, slots] @ phi
-        scale = np.maximum(1.0, (np.abs(params[:, slots]) * m[slots]).sum(axis=1))
-        ok &= np.abs(d - np.floor(d) - 0.5).min(axis=1) > 1e-8 * scale
-    return ok
 
 
 def _synthetic_sums(h, w, bs, n, seed):

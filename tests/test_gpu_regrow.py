@@ -1,8 +1,9 @@
 """One Sequence asked for more than it has allocated: every call that keeps device buffers in the sequence runs first at a
 small demand and then at a larger one on the SAME sequence, so its buffers grow, its groups are sized anew and the borrowed
 motion field of the level -1 fit moves.  Every output is compared byte for byte with the same call on a freshly created
-sequence of the same frames (the rest of the suite makes a fresh sequence per shape and never grows anything).  Successful
-calls only: allocation failures are the business of tests/test_dev_buf_host.py.  Needs an MI355X."""
+sequence of the same frames (tests/test_gpu_reuse.py takes every pass through growing and shrinking demands against its
+definition; the rest of the suite makes a fresh sequence per shape).  Successful calls only: allocation failures are the
+business of tests/test_dev_buf_host.py.  Needs an MI355X."""
 import numpy as np
 import pytest
 
