@@ -303,7 +303,7 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaGeo& d, int H, int 
 // (bbme_sea_common.h: launch_args), once for phases A' .. D and once behind phase D's barrier for the rest.
 template <int R, bool FIXED, bool VERT>
 __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                            uint32_t mine, uint32_t pa, uint32_t pb, int tid, int tile_id)
+                                            uint32_t mine, uint32_t pa, uint32_t pb, int tid, int tile_id, PhaseClock& clk)
 {
     // phase C2 and phase E with four lanes per patch (a quarter of the latency the other waves wait for) from R = 3 on:
     // +11 % at sw 32, +3 % at sw 16
@@ -327,7 +327,9 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
 
     // ---- A': 8x8 box sums of the window (bbme_sea_common.h) ------------------------------------
     box_sums8<R, FIXED>(d, win, s8, tid);
+    clk.mark(ST_BOX, lane);
     __syncthreads();
+    clk.mark(ST_BOX_WAIT, lane);
 
     // ---- B: lower bounds of the wave's own block --------------------------------------------
     const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, c->H - 16 - r0 + d.sw);
@@ -403,6 +405,7 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
         // (bbme.py:171: only a smaller key replaces the best one).
         uint32_t own_lim = 0;                              // keys below it were scored here (wave-uniform)
         int n_w = 0;                                       // patches the first upper bound leaves (statistics)
+        clk.mark(ST_BC, lane);
         if constexpr (E4) {
             // crowded?  Lanes with a surviving patch are counted first (one ballot); the exact count only where it matters
             const int engage = c->engage;
@@ -445,6 +448,7 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
                 }
             }
         }
+        clk.mark(ST_C2, lane);
         if (lane == 0) best[2 * wave] = ub_key;
         // ---- D: surviving patches -> workgroup list.  A candidate replaces the best one only with a smaller
         // key (sad << 13 | scan index: bbme.py:171 keeps the FIRST strict minimum), and its key is at least
@@ -477,7 +481,9 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
         // statistics: what the first bound had left and C2 took or pruned
         if (own_lim && lane == 0) atomicAdd(count + 4, (uint32_t)(n_w - pushed));
     }
+    clk.mark(ST_D, lane);
     __syncthreads();
+    clk.mark(ST_D_WAIT, lane);
     const SeaArgs ce = launch_args();                      // phases E and F, and the test in front of them
     if (ce->redo_list && (int)*count > ce->redo_threshold) {     // workgroup-uniform: hostile tile, brute force is cheaper
         if (tid == 0) push_redo(ce, tile_id, (int)(blockIdx.x & 7));
@@ -574,7 +580,9 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
                 key = min(key, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)key, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
                 if (sub == 0 && key != 0xFFFFFFFFu) atomicMin(&best[2 * w2], key);
             }
+            clk.mark(ST_E, lane);
             __syncthreads();
+            clk.mark(ST_E_WAIT, lane);
         }
     } else {
         // ---- E: evaluate the listed patches, one per lane ---------------------------------------
@@ -643,7 +651,9 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
                 }
                 if (key != 0xFFFFFFFFu) atomicMin(&best[2 * w2], key);
             }
+            clk.mark(ST_E, lane);
             __syncthreads();
+            clk.mark(ST_E_WAIT, lane);
         }
 
     }
@@ -678,9 +688,9 @@ struct MaeTile {
         return p;
     }
     static __device__ __forceinline__ bool phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                                  uint32_t mine, const Pre& p, int tid, int tile_id)
+                                                  uint32_t mine, const Pre& p, int tid, int tile_id, PhaseClock& clk)
     {
-        return tile_phases<R, FIXED, VERT>(d, lds, L, pair, trow, bcol0, mine, p.pa, p.pb, tid, tile_id);
+        return tile_phases<R, FIXED, VERT>(d, lds, L, pair, trow, bcol0, mine, p.pa, p.pb, tid, tile_id, clk);
     }
     static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.best + 2 * wave + 1; }
 };
@@ -750,6 +760,16 @@ bool bbme_sea_applies(int bs, int sw, int procedure, int pnorm)
     const int NC = 2 * sw + 16;
     return (NC + 15) / 16 <= 5 && NC * NC <= 8192 && !getenv("GME_FORCE_GENERIC") && !getenv("GME_EXH_BRUTE");
 }
+
+#ifdef SEA_PHASE_STAMPS
+// Phase-stamp variant only (bbme_sea_common.h: PhaseClock): the totals of the persistent kernels since the last reset,
+// out[16 waves][ST_SLOTS] cycles; norm 0: MAE, 1: MSE
+int sea_stamps_read_mse(unsigned long long* out, int reset);
+extern "C" GME_API int gme_sea_phase_stamps(int norm, unsigned long long* out, int reset)
+{
+    return norm ? sea_stamps_read_mse(out, reset) : sea::sea_stamps_read(out, reset);
+}
+#endif
 
 int launch_bbme_sea(gme_ctx* ctx, const BbmeJob& job, bool* handled)
 {

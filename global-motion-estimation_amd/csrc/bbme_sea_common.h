@@ -101,6 +101,70 @@ __device__ __forceinline__ int launch_groups_x(SeaArgs c)
 
 typedef uint64_t u64_a4 __attribute__((aligned(4)));
 
+// Phase stamps (diagnostic variant, tools/build_variant.sh <name> -DSEA_PHASE_STAMPS; tools/sea_phase_stamps.py prints the table):
+// where a wave's time goes inside a tile.  Lane 0 of every wave reads the shader clock (s_memtime) at the end of each span
+// below and adds the cycles since the previous reading to the wave's total of that span, in LDS behind the tile's own
+// data (Layout::stamps, [nb][ST_SLOTS]); persistent_tiles adds the workgroup's totals to stamp_totals (a device array per
+// norm, [16 waves][ST_SLOTS]) when it has walked its tiles, and sea_stamps_read() hands that to the host.  Every reading
+// waits for the wave's outstanding LDS and scalar loads (s_waitcnt lgkmcnt(0)), so the stamped kernel is slower than the
+// tree's and its figures attribute time, they do not measure it.  Without the macro PhaseClock is empty and every mark()
+// compiles to nothing: the tree's library has neither the array nor the reader.
+enum {
+    ST_HEAD,        // tile head: prefetched registers -> LDS, anchor statistics, thread 0's counters
+    ST_HEAD_WAIT,   // the barrier behind it
+    ST_FETCH,       // the next tile's number and the issue of its prefetch
+    ST_BOX,         // A': box sums
+    ST_BOX_WAIT,    // A's barrier
+    ST_BC,          // B and C: bounds, the three probes
+    ST_C2,          // C2: ordered evaluation of a crowded block (0 where it does not engage)
+    ST_D,           // D: listing
+    ST_D_WAIT,      // D's barrier
+    ST_E,           // E: the chunks' work (MSE: with level 2 of the bound)
+    ST_E_WAIT,      // E: the chunks' barriers
+    ST_F_TAIL,      // F, the loop tail (hostile streaks), up to the next tile's head
+    ST_TILES,       // tiles this wave walked
+    ST_SLOTS = 16
+};
+#ifdef SEA_PHASE_STAMPS
+static __device__ unsigned long long stamp_totals[16 * ST_SLOTS];
+struct PhaseClock {
+    uint32_t slot, last;                                   // LDS byte address of the wave's totals; the previous reading (both wave-uniform)
+    __device__ __forceinline__ void start(uint32_t* totals, int wave)
+    {
+        slot = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)(totals + wave * ST_SLOTS);
+        last = (uint32_t)__builtin_amdgcn_s_memtime();
+    }
+    __device__ __forceinline__ void add(int span, int lane, uint32_t v)
+    {
+        // written out: an atomicAdd from one lane is rewritten into a wave-wide aggregation (lds_add_rtn in bbme_sea.hip)
+        if (lane == 0) asm volatile("ds_add_u32 %0, %1" : : "v"(slot + 4u * (uint32_t)span), "v"(v) : "memory");
+    }
+    __device__ __forceinline__ void mark(int span, int lane)
+    {
+        const uint32_t now = (uint32_t)__builtin_amdgcn_s_memtime();
+        add(span, lane, now - last);
+        last = now;
+    }
+};
+inline int sea_stamps_read(unsigned long long* out, int reset)
+{
+    GME_HIP_TRY(hipDeviceSynchronize());
+    GME_HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(stamp_totals), sizeof(stamp_totals)));
+    if (reset) {
+        void* p = nullptr;
+        GME_HIP_TRY(hipGetSymbolAddress(&p, HIP_SYMBOL(stamp_totals)));
+        GME_HIP_TRY(hipMemset(p, 0, sizeof(stamp_totals)));
+    }
+    return GME_OK;
+}
+#else
+struct PhaseClock {
+    __device__ __forceinline__ void add(int, int, uint32_t) {}
+    __device__ __forceinline__ void mark(int, int) {}
+};
+#endif
+
+
 // wave_min_u32 / wave_sum_u32 (DPP reductions): gme_internal.h
 #define SEA_DPP(v, ctrl) GME_DPP(v, ctrl)
 
@@ -137,6 +201,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct Layout {
     int win, anchor, best, count, a2, prev, own, s8, work, total;
+#ifdef SEA_PHASE_STAMPS
+    int stamps;                                            // [nb][ST_SLOTS] PhaseClock totals, behind everything else
+#endif
 };
 
 __host__ __device__ constexpr Layout make_layout(int R, int nb, int win_rows, int pitch_dw, int xq, int s8_rows)
@@ -154,6 +221,10 @@ __host__ __device__ constexpr Layout make_layout(int R, int nb, int win_rows, in
     l.s8 = (l.own + 16 * nb + 1) & ~1;                 // 8-byte aligned, [s8_rows][xq] u16x4
     l.work = l.s8 + 2 * s8_rows * xq;                  // [nb*64*R] entries
     l.total = l.work + nb * 64 * R;
+#ifdef SEA_PHASE_STAMPS
+    l.stamps = l.total;
+    l.total += nb * ST_SLOTS;
+#endif
     return l;
 }
 
@@ -253,6 +324,12 @@ __device__ __forceinline__ void box_sums8_ch(const SeaGeo& d, const uint32_t* wi
     // FIXED: rows a ds_read2_b32 reaches from one base register (its second offset, in dwords, ends at 255)
     const int RB = FIXED ? 254 / d.pitch_dw + 1 : 1;
     for (int u = wave * SEG; u < units; u += d.nb * SEG) {
+        // A wave that holds chunks is one the whole workgroup waits for at the barrier behind this pass (at the 2x4 tiles
+        // of R = 3: waves 0 .. 3, the other four go straight there), and it shares its SIMD's vector issue, by priority
+        // first and age second, with the waves of other workgroups whom nobody waits for: it runs the pass at priority 1.
+        // `u`, SEG and `units` are scalars (the wave number is a v_readfirstlane_b32), so the loop is a scalar branch and
+        // only such a wave executes the pair; the lower is the last instruction of every trip, in front of the barrier.
+        __builtin_amdgcn_s_setprio(1);
         const int ch = wide ? (u & 7) : u + ls;
         const int sq = wide ? (u >> 3) * 63 + lane : lane - ls * SL;
         const bool active = wide ? sq < SL : (ls < SEG && ch < 8);
@@ -305,6 +382,7 @@ __device__ __forceinline__ void box_sums8_ch(const SeaGeo& d, const uint32_t* wi
             }
             ring[r & 7] = acc;
         }
+        __builtin_amdgcn_s_setprio(0);
     }
 }
 
@@ -530,7 +608,7 @@ __device__ __forceinline__ int tile_number(const SeaGeo& d, SeaArgs c, int pair,
 
 // Kern (MaeTile in bbme_sea.hip, MseTile in bbme_sea_mse.hip) supplies what the two drivers below call per tile:
 //   Pre prep(lds, L, wave, lane, wave_ok, mine)             the wave's anchor dword -> LDS, per-wave anchor statistics
-//   bool phases(d, lds, L, pair, trow, bcol0, mine, pre, tid, tile_id)   phases A' .. F; true: the tile went to redo_list
+//   bool phases(d, lds, L, pair, trow, bcol0, mine, pre, tid, tile_id, clk)   phases A' .. F; true: the tile went to redo_list
 //   int probe_word(L, wave)                                 LDS word of the wave's third probe: the vector its block of the
 //                                                           previous tile ended with (one_tile seeds it with the zero
 //                                                           vector; the persistent kernels seed the same word themselves)
@@ -561,7 +639,11 @@ __device__ __forceinline__ void one_tile(const SeaGeo& d, uint32_t* lds, const L
     if (lane == 0) lds[Kern::probe_word(L, wave)] = (uint32_t)(d.sw * (2 * d.sw + 16) + d.sw);      // no previous tile: the zero vector
     if (threadIdx.x == 0) { lds[L.count] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0; }
     __syncthreads();
-    Kern::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, c, pair, trow, bcol0));
+    PhaseClock clk;
+#ifdef SEA_PHASE_STAMPS
+    clk.start(lds + L.stamps, wave);                       // totals nobody reads: the one-tile form has no flush
+#endif
+    Kern::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, c, pair, trow, bcol0), clk);
     if (threadIdx.x == 0) {                                // the counts are final behind phase D's barrier
         uint32_t* stats = launch_args()->status + GME_STATUS_STATS + 16 * (blockIdx.x & 7);
         atomicAdd(stats, lds[L.count] + lds[L.count + 5]);
@@ -660,6 +742,15 @@ __device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds,
         lds[L.count] = 0; lds[L.count + 3] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0;
     }
     uint32_t stat_scored = 0, stat_listed = 0;             // thread 0's: patches scored exactly / left by the first upper bounds
+    PhaseClock clk;
+#ifdef SEA_PHASE_STAMPS
+    {
+        const int tid = opaque_tid();
+        if (tid < d.nb * ST_SLOTS) lds[L.stamps + tid] = 0;
+        __syncthreads();
+        clk.start(lds + L.stamps, __builtin_amdgcn_readfirstlane(tid >> 6));
+    }
+#endif
     for (;;) {
         const int tid = opaque_tid();
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -685,7 +776,9 @@ __device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds,
             lds[L.count] = 0; lds[L.count + 4] = 0; lds[L.count + 5] = 0; lds[L.count + 7] = 0;
             lds[L.count + 1] = (uint32_t)gx + drawn;       // dynamic schedule: the next tile (static: not read)
         }
+        clk.mark(ST_HEAD, lane);
         __syncthreads();
+        clk.mark(ST_HEAD_WAIT, lane);
         bool more, dynamic;
         {   // loop tail, first half: the next tile, prefetched behind this one's phases
             const SeaArgs c = launch_args();
@@ -697,12 +790,13 @@ __device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds,
                 if (dynamic && tid == 0) drawn = atomicInc(c->status + GME_STATUS_TILECTR + 16 * xcd, 0xFFFFFFFFu);
             }
         }
+        clk.mark(ST_FETCH, lane);
         // A hostile tile is handed to the redo kernel.  When the tile this workgroup processed just before was
         // hostile too (a scene cut, a noisy shot: not an isolated occlusion), thread 0's wave also draws the next
         // tile numbers of this XCD -- consecutive tiles of the same pairs -- and lists them unseen: 3 of them, then
         // 7, then REDO_BURST while the streak lasts.  Where every tile is hostile only one in REDO_BURST + 1 pays
         // for the bound phases before brute force does the work anyway; friendly content never takes the branch.
-        if (!Kern::phases(d, lds, L, pair_c, trow_c, bcol0_c, mine, pre, tid, tile_c)) {
+        if (!Kern::phases(d, lds, L, pair_c, trow_c, bcol0_c, mine, pre, tid, tile_c, clk)) {
             if (tid == 0) lds[L.count + 3] = 0;            // streak of hostile tiles (thread 0's word)
         } else if (dynamic && wave == 0) {
             const int streak = (int)lds[L.count + 3];      // same address for the whole wave; only thread 0 writes it
@@ -719,12 +813,22 @@ __device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds,
             }
             if (lane == 0) lds[L.count + 3] = (uint32_t)(streak + 1);
         }
+        clk.mark(ST_F_TAIL, lane);
+        clk.add(ST_TILES, lane, 1u);
         if (!more) break;
         // No barrier here (round 4): every wave has passed phase D's barrier, and phase E's chunks end in one each, so
         // nobody still reads the window, the anchors, the box sums or the list when the next tile's staging overwrites them;
         // what is touched between here and the next tile's first barrier is per wave (best[], prev[]) or thread 0's
         // (the count words: a wave that has not read the list length yet can only be in a tile whose list is empty).
     }
+#ifdef SEA_PHASE_STAMPS
+    {   // the workgroup's totals -> stamp_totals
+        asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");            // PhaseClock::add's ds_add_u32: the compiler does not count it
+        __syncthreads();
+        const int tid = opaque_tid();
+        if (tid < d.nb * ST_SLOTS) atomicAdd(stamp_totals + tid, (unsigned long long)lds[L.stamps + tid]);
+    }
+#endif
     // thread 0 has passed the barrier behind phase D: the last tile's counts are final
     if (opaque_tid() == 0) {
         uint32_t* stats = launch_args()->status + GME_STATUS_STATS + 16 * xcd;

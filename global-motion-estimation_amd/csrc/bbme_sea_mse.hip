@@ -144,7 +144,7 @@ __device__ __forceinline__ uint32_t bounds2_patch(const uint64_t* sp, int XQ, in
 // Phases A' .. F of one tile (entry conditions as tile_phases() of bbme_sea.hip, plus a2s[] filled).
 template <int R, bool FIXED>
 __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                                uint32_t mine, uint32_t a01, uint32_t a23, uint32_t mine2, int tid, int tile_id)
+                                                uint32_t mine, uint32_t a01, uint32_t a23, uint32_t mine2, int tid, int tile_id, PhaseClock& clk)
 {
     constexpr bool TWO = R >= TWO_LEVEL_FROM;     // two-level bound: L1 form for every candidate, squared form for the listed patches
     const int T = blockDim.x;
@@ -167,7 +167,9 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, 
 
     // ---- A'
     box_sums8<R, FIXED>(d, win, s8, tid);
+    clk.mark(ST_BOX, lane);
     __syncthreads();
+    clk.mark(ST_BOX_WAIT, lane);
 
     // ---- B
     const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, c->H - 16 - r0 + d.sw);
@@ -234,6 +236,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, 
                 ub_key = u64min_(ub_key, ((unsigned long long)wave_sum_u32(part) << 13) | (unsigned)idxp);
             }
         }
+        clk.mark(ST_BC, lane);
         if (lane == 0) best[wave] = ub_key;
         // ---- D
         const uint32_t ub25 = (uint32_t)(ub_key >> 12);                // 2 ssd = floor(64 * ssd / 32); ssd < 2^24
@@ -261,7 +264,9 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, 
         }
         (void)ub25;
     }
+    clk.mark(ST_D, lane);
     __syncthreads();
+    clk.mark(ST_D_WAIT, lane);
     const SeaArgs ce = launch_args();                      // phases D2 .. F, and the test in front of them
     if (ce->redo_list && (int)*count > ce->redo_threshold) {     // workgroup-uniform: hostile tile, brute force is cheaper
         if (tid == 0) push_redo(ce, tile_id, (int)(blockIdx.x & 7));
@@ -288,7 +293,9 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, 
                         work[d.nb * 64 * R - 1 - (int)atomicAdd(count + 7, 1u)] = (ent & 0xFFF80000u) | (lb25 >> 6);
                 }
             }
+            clk.mark(ST_E, lane);
             __syncthreads();
+            clk.mark(ST_E_WAIT, lane);
             n = (int)count[7];
             list = work + d.nb * 64 * R - n;                       // entries were stored downwards: any order will do
             if (tid == 0) count[0] = (uint32_t)n;                  // statistics: patches scored (count[7] is cleared with the other counters at the next tile's start)
@@ -396,7 +403,9 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, 
             }
             if (key != ~0ull) atomicMin(&best[w2], key);
         }
+        clk.mark(ST_E, lane);
         __syncthreads();
+        clk.mark(ST_E_WAIT, lane);
     }
 
     // ---- F
@@ -432,9 +441,9 @@ struct MseTile {
         return p;
     }
     static __device__ __forceinline__ bool phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                                  uint32_t mine, const Pre& p, int tid, int tile_id)
+                                                  uint32_t mine, const Pre& p, int tid, int tile_id, PhaseClock& clk)
     {
-        return tile_phases_mse<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id);
+        return tile_phases_mse<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id, clk);
     }
     static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.prev + wave; }
 };
@@ -485,6 +494,10 @@ struct MseLaunch {
 };
 
 }  // namespace
+
+#ifdef SEA_PHASE_STAMPS
+int sea_stamps_read_mse(unsigned long long* out, int reset) { return sea::sea_stamps_read(out, reset); }     // bbme_sea.hip: gme_sea_phase_stamps
+#endif
 
 int launch_bbme_sea_mse(gme_ctx* ctx, const BbmeJob& job, bool* handled)
 {
