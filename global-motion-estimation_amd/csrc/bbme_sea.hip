@@ -301,9 +301,11 @@ __device__ __forceinline__ uint32_t eval_patch_quad(const SeaGeo& d, int H, int 
 // Returns true (workgroup-uniform) when the tile was handed to the redo kernel instead (SeaDev::redo_list).
 // `d` is the geometry; frame size, ordered evaluation, redo list and result plane come from the argument segment
 // (bbme_sea_common.h: launch_args), once for phases A' .. D and once behind phase D's barrier for the rest.
-template <int R, bool FIXED, bool VERT>
+// behind_box_sums: what the driver has every wave do right behind the barrier that follows phase A' (Kern, bbme_sea_common.h).
+template <int R, bool FIXED, bool VERT, class Behind>
 __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                            uint32_t mine, uint32_t pa, uint32_t pb, int tid, int tile_id, PhaseClock& clk)
+                                            uint32_t mine, uint32_t pa, uint32_t pb, int tid, int tile_id, PhaseClock& clk,
+                                            Behind&& behind_box_sums)
 {
     // phase C2 and phase E with four lanes per patch (a quarter of the latency the other waves wait for) from R = 3 on:
     // +11 % at sw 32, +3 % at sw 16
@@ -330,6 +332,7 @@ __device__ __forceinline__ bool tile_phases(const SeaGeo& d, uint32_t* lds, cons
     clk.mark(ST_BOX, lane);
     __syncthreads();
     clk.mark(ST_BOX_WAIT, lane);
+    behind_box_sums();                                     // persistent_tiles: the next tile's prefetch of the waves that held chunks
 
     // ---- B: lower bounds of the wave's own block --------------------------------------------
     const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, c->H - 16 - r0 + d.sw);
@@ -687,11 +690,13 @@ struct MaeTile {
         }
         return p;
     }
+    template <class Behind>
     static __device__ __forceinline__ bool phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                                  uint32_t mine, const Pre& p, int tid, int tile_id, PhaseClock& clk)
+                                                  uint32_t mine, const Pre& p, int tid, int tile_id, PhaseClock& clk, Behind&& behind_box_sums)
     {
-        return tile_phases<R, FIXED, VERT>(d, lds, L, pair, trow, bcol0, mine, p.pa, p.pb, tid, tile_id, clk);
+        return tile_phases<R, FIXED, VERT>(d, lds, L, pair, trow, bcol0, mine, p.pa, p.pb, tid, tile_id, clk, behind_box_sums);
     }
+    static __device__ __forceinline__ bool holds_chunks(const SeaGeo& d, int wave) { return holds_box_chunks<R>(d, wave); }
     static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.best + 2 * wave + 1; }
 };
 
@@ -707,6 +712,12 @@ __global__ void __launch_bounds__(1024) k_exh_sea16(SeaDev d)
 // cost a spilled VGPR of the prefetched tile
 constexpr bool vertical_pairs(int R, int NV) { return !(R == 5 && NV == 16); }
 
+// Which persistent instances order the next tile's prefetch by who holds box-sum chunks (persistent_tiles, LATE): all but the
+// run-time-geometry ones of R = 3.  Those sit at the 64 VGPRs and 80 SGPRs of eight waves per SIMD: for the second copy of
+// the prefetch <3, 6, 0> spills 20 more SGPRs to VGPR lanes (read back on every tile), <3, 8, 0> three VGPRs, <3, 16, 0>
+// eight ("Order")
+constexpr bool late_prefetch(int R, int GEO) { return !(R == 3 && GEO == 0); }
+
 template <int R, int NV, int GEO = 0>
 __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p(SeaDev d)
 {
@@ -715,7 +726,7 @@ __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p(SeaDev d)
     fix_geometry<R, GEO>(g);
     const Layout L = layout_of(g, R);
     if ((threadIdx.x & 63) == 0) lds[L.best + 2 * (threadIdx.x >> 6) + 1] = (uint32_t)(g.sw * (2 * g.sw + 16) + g.sw);   // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MaeTile<R, GEO != 0, vertical_pairs(R, NV)>>(g, lds, L);
+    persistent_tiles<NV, MaeTile<R, GEO != 0, vertical_pairs(R, NV)>, late_prefetch(R, GEO)>(g, lds, L);
 }
 
 // What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.

@@ -146,7 +146,9 @@ struct PhaseClock {
         last = now;
     }
 };
-inline int sea_stamps_read(unsigned long long* out, int reset)
+// static: each norm's file reads its own stamp_totals (as one inline function of both files the linker kept a single copy,
+// and the MSE reader returned the MAE array)
+static inline int sea_stamps_read(unsigned long long* out, int reset)
 {
     GME_HIP_TRY(hipDeviceSynchronize());
     GME_HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(stamp_totals), sizeof(stamp_totals)));
@@ -281,6 +283,27 @@ __device__ __forceinline__ void stage_window(const SeaGeo& d, SeaArgs c, uint32_
     }
 }
 
+// How the box-sum pass below (box_sums8_ch, "Lanes") deals its work to the waves, from shape_of's constants alone: compile-time
+// in a geometry-fixed instance.  In one place, because holds_box_chunks() asks the same question for the tile driver.
+struct BoxDeal {
+    int SL;                       // lanes per segment: its quads, and a donor if the last one is read
+    bool wide;                    // pieces: one per wave and pass
+    uint32_t magic_sl;
+    int SEG;                      // whole segments per wave
+    int units;                    // pieces (unit = piece * 8 + chunk) or chunks
+};
+__device__ __forceinline__ BoxDeal box_deal(const SeaGeo& d, int need)
+{
+    BoxDeal b;
+    const int XQ = d.xq;
+    b.SL = XQ == need ? XQ + 1 : XQ;
+    b.wide = b.SL > 64;
+    b.magic_sl = XQ == need ? div_magic(b.SL) : d.magic_xq;
+    b.SEG = b.wide ? 1 : div_small(64, b.magic_sl);
+    b.units = b.wide ? 8 * div_small(XQ + 62, div_magic(63)) : 8;
+    return b;
+}
+
 // A': 8x8 box sums of the staged window.  Lane (row chunk ch, column quad sq) walks CH+7 window rows.  Per row ONE
 // QSAD against a zero reference gives the four sliding 4-byte sums h4(4sq .. 4sq+3) of the lane's own quad (packed
 // u16), and its accumulator operand adds them up over the rows for nothing: C(r) = h4 of rows 0 .. r (at most 24 rows
@@ -315,11 +338,10 @@ __device__ __forceinline__ void box_sums8_ch(const SeaGeo& d, const uint32_t* wi
     static_assert((CH + 7) * 1020 < 65536, "cumulative 4-byte sums must fit 16 bits");
     const int XQ = d.xq;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int SL = XQ == need ? XQ + 1 : XQ;                       // lanes per segment: its quads, and a donor if the last one is read
-    const bool wide = SL > 64;                                     // pieces: one per wave and pass
-    const uint32_t magic_sl = XQ == need ? div_magic(SL) : d.magic_xq;
-    const int SEG = wide ? 1 : div_small(64, magic_sl);            // whole segments per wave
-    const int units = wide ? 8 * div_small(XQ + 62, div_magic(63)) : 8;       // pieces (unit = piece * 8 + chunk) or chunks
+    const BoxDeal deal = box_deal(d, need);
+    const int SL = deal.SL, SEG = deal.SEG, units = deal.units;
+    const bool wide = deal.wide;
+    const uint32_t magic_sl = deal.magic_sl;
     const int ls = wide ? 0 : div_small(lane, magic_sl);           // the lane's segment inside its wave
     // FIXED: rows a ds_read2_b32 reaches from one base register (its second offset, in dwords, ends at 255)
     const int RB = FIXED ? 254 / d.pitch_dw + 1 : 1;
@@ -390,13 +412,25 @@ __device__ __forceinline__ void box_sums8_ch(const SeaGeo& d, const uint32_t* wi
 // (four chunks of twice the rows for two-row tiles were measured too -- 7 warm-up rows per chunk are 44 % of a 9-row
 // chunk's work and 28 % of an 18-row one's, but half as many lanes share it; A/B in DESIGN.md)
 // FIXED: the caller is a geometry-fixed instance (fix_geometry): d.pitch_dw and d.xq are compile-time constants there
+template <int R>
+__device__ __forceinline__ int box_quads_needed(const SeaGeo& d) { return 4 * R + 4 * (d.tc - 1) + 2; }     // quads per row the bound phase reads (shape_of); XQ >= need
 template <int R, bool FIXED>
 __device__ __forceinline__ void box_sums8(const SeaGeo& d, const uint32_t* win, uint64_t* s8, int tid)
 {
-    const int need = 4 * R + 4 * (d.tc - 1) + 2;           // quads per row the bound phase reads (shape_of); XQ >= need
+    const int need = box_quads_needed<R>(d);
     if (d.tr == 1) box_sums8_ch<2 * R + 1, FIXED>(d, win, s8, tid, need);
     else if (d.tr == 2) box_sums8_ch<2 * R + 3, FIXED>(d, win, s8, tid, need);
     else box_sums8_ch<2 * R + 7, FIXED>(d, win, s8, tid, need);
+}
+
+// Whether a wave holds chunks of the pass: box_sums8_ch's unit loop has a trip for it.  Wave-uniform, from shape_of's
+// constants and the wave number alone.  Such a wave is one the workgroup waits for at the barrier behind the pass; the
+// others go straight there (persistent_tiles orders the next tile's prefetch by it).
+template <int R>
+__device__ __forceinline__ bool holds_box_chunks(const SeaGeo& d, int wave)
+{
+    const BoxDeal deal = box_deal(d, box_quads_needed<R>(d));
+    return wave * deal.SEG < deal.units;
 }
 
 // quadrant sums of the anchor held one dword per lane (lane = row * 4 + dword): the quad swap pairs
@@ -608,7 +642,11 @@ __device__ __forceinline__ int tile_number(const SeaGeo& d, SeaArgs c, int pair,
 
 // Kern (MaeTile in bbme_sea.hip, MseTile in bbme_sea_mse.hip) supplies what the two drivers below call per tile:
 //   Pre prep(lds, L, wave, lane, wave_ok, mine)             the wave's anchor dword -> LDS, per-wave anchor statistics
-//   bool phases(d, lds, L, pair, trow, bcol0, mine, pre, tid, tile_id, clk)   phases A' .. F; true: the tile went to redo_list
+//   bool phases(d, lds, L, pair, trow, bcol0, mine, pre, tid, tile_id, clk, behind_box_sums)
+//                                                           phases A' .. F; true: the tile went to redo_list.  It calls
+//                                                           behind_box_sums() once, in every wave, right behind the barrier
+//                                                           that follows phase A' (persistent_tiles: the late prefetch)
+//   bool holds_chunks(d, wave)                              holds_box_chunks of the kernel's size class
 //   int probe_word(L, wave)                                 LDS word of the wave's third probe: the vector its block of the
 //                                                           previous tile ended with (one_tile seeds it with the zero
 //                                                           vector; the persistent kernels seed the same word themselves)
@@ -643,7 +681,7 @@ __device__ __forceinline__ void one_tile(const SeaGeo& d, uint32_t* lds, const L
 #ifdef SEA_PHASE_STAMPS
     clk.start(lds + L.stamps, wave);                       // totals nobody reads: the one-tile form has no flush
 #endif
-    Kern::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, c, pair, trow, bcol0), clk);
+    Kern::phases(d, lds, L, pair, trow, bcol0, mine, pre, (int)threadIdx.x, tile_number(d, c, pair, trow, bcol0), clk, [] {});      // no prefetch
     if (threadIdx.x == 0) {                                // the counts are final behind phase D's barrier
         uint32_t* stats = launch_args()->status + GME_STATUS_STATS + 16 * (blockIdx.x & 7);
         atomicAdd(stats, lds[L.count] + lds[L.count + 5]);
@@ -675,7 +713,27 @@ __device__ __forceinline__ uint32_t* tile_counter(SeaArgs c, int xcd) { return c
 // them -- the prefetch, the tile's phases, the loop's head and tail -- and what follows from them alone (tiles of this
 // XCD, G / 8, the counter's address, the plane's extent, the staging stride) is recomputed there by scalar
 // instructions.  Carried, they were 44 to 95 spilled SGPRs per instance, read back from VGPR lanes on every tile.
-template <int NV, class Kern>
+// The loop tail's first half of persistent_tiles: the next tile's number and, if there is one, its prefetch and thread 0's
+// draw.  A function with reference parameters, not a closure of the driver: called from two sites through a closure the
+// instances at their register limit compiled to more spilled VGPRs, or a wave per SIMD less, than with the block in place.
+template <class Fetch>
+__device__ __forceinline__ void next_tile_of(const uint32_t* lds, const Layout& L, int xcd, int tid, int& tile, bool& more, bool& dynamic,
+                                             uint32_t& drawn, Fetch& fetch)
+{
+    const SeaArgs c = launch_args();
+    dynamic = c->dynamic != 0;
+    tile = dynamic ? (int)lds[L.count + 1] : tile + (launch_groups_x(c) >> 3);
+    more = tile < tiles_of_xcd(c, xcd);                    // workgroup-uniform
+    if (more) {
+        fetch(tile, tid);
+        if (dynamic && tid == 0) drawn = atomicInc(c->status + GME_STATUS_TILECTR + 16 * xcd, 0xFFFFFFFFu);
+    }
+}
+
+// LATE: whether the waves that hold box-sum chunks prefetch behind that pass's barrier (below); false keeps every wave's
+// prefetch in front of the pass (`holds` is then false for every wave), for the instances where the second copy of the
+// prefetch would cost spilled registers.
+template <int NV, class Kern, bool LATE = true>
 __device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds, const Layout L)
 {
     const int xcd = blockIdx.x & 7;
@@ -779,24 +837,36 @@ __device__ __forceinline__ void persistent_tiles(const SeaGeo& d, uint32_t* lds,
         clk.mark(ST_HEAD, lane);
         __syncthreads();
         clk.mark(ST_HEAD_WAIT, lane);
-        bool more, dynamic;
-        {   // loop tail, first half: the next tile, prefetched behind this one's phases
-            const SeaArgs c = launch_args();
-            dynamic = c->dynamic != 0;
-            tile = dynamic ? (int)lds[L.count + 1] : tile + (launch_groups_x(c) >> 3);
-            more = tile < tiles_of_xcd(c, xcd);            // workgroup-uniform
-            if (more) {
-                fetch(tile, tid);
-                if (dynamic && tid == 0) drawn = atomicInc(c->status + GME_STATUS_TILECTR + 16 * xcd, 0xFFFFFFFFu);
-            }
+        // Loop tail, first half: the next tile, prefetched behind this one's phases.  Nothing up to phase D reads what it
+        // fetches, but it is 1.5 to 2 thousand cycles of a wave's own time (a chain of scalar loads, two 64-bit
+        // multiply-shift divisions, the buffer descriptor), and the whole workgroup waits at the barrier behind the box-sum
+        // pass for the waves that hold its chunks (holds_box_chunks).  Those waves run the pass first and prefetch behind
+        // its barrier, out of time they would otherwise spend waiting at phase D's; the others, with nothing to do until
+        // that barrier, prefetch in front of it.  Every wave runs it exactly once per tile and reads the same words (thread 0
+        // wrote count[1] in front of the head barrier and nobody writes it again before the next head), so `more`,
+        // `dynamic` and the next `tile` stay workgroup-uniform.  Thread 0's draw goes with wave 0's prefetch, which holds
+        // chunks: behind the barrier, still ahead of the hostile-streak code below that replaces `drawn`.
+        bool more = false, dynamic = false;
+        bool holds = false;                                // wave-uniform
+        if constexpr (LATE) holds = Kern::holds_chunks(d, wave);
+        if (!holds) {
+            next_tile_of(lds, L, xcd, tid, tile, more, dynamic, drawn, fetch);
+            clk.mark(ST_FETCH, lane);                      // charged where the wave runs it
         }
-        clk.mark(ST_FETCH, lane);
+        auto behind_box_sums = [&]() __attribute__((always_inline)) {      // Kern::phases calls it behind the barrier that follows phase A'
+            if constexpr (LATE) {
+                if (holds) {
+                    next_tile_of(lds, L, xcd, tid, tile, more, dynamic, drawn, fetch);
+                    clk.mark(ST_FETCH, lane);
+                }
+            }
+        };
         // A hostile tile is handed to the redo kernel.  When the tile this workgroup processed just before was
         // hostile too (a scene cut, a noisy shot: not an isolated occlusion), thread 0's wave also draws the next
         // tile numbers of this XCD -- consecutive tiles of the same pairs -- and lists them unseen: 3 of them, then
         // 7, then REDO_BURST while the streak lasts.  Where every tile is hostile only one in REDO_BURST + 1 pays
         // for the bound phases before brute force does the work anyway; friendly content never takes the branch.
-        if (!Kern::phases(d, lds, L, pair_c, trow_c, bcol0_c, mine, pre, tid, tile_c, clk)) {
+        if (!Kern::phases(d, lds, L, pair_c, trow_c, bcol0_c, mine, pre, tid, tile_c, clk, behind_box_sums)) {
             if (tid == 0) lds[L.count + 3] = 0;            // streak of hostile tiles (thread 0's word)
         } else if (dynamic && wave == 0) {
             const int streak = (int)lds[L.count + 3];      // same address for the whole wave; only thread 0 writes it

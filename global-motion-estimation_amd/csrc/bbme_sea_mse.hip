@@ -142,9 +142,10 @@ __device__ __forceinline__ uint32_t bounds2_patch(const uint64_t* sp, int XQ, in
 }
 
 // Phases A' .. F of one tile (entry conditions as tile_phases() of bbme_sea.hip, plus a2s[] filled).
-template <int R, bool FIXED>
+template <int R, bool FIXED, class Behind>
 __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                                uint32_t mine, uint32_t a01, uint32_t a23, uint32_t mine2, int tid, int tile_id, PhaseClock& clk)
+                                                uint32_t mine, uint32_t a01, uint32_t a23, uint32_t mine2, int tid, int tile_id, PhaseClock& clk,
+                                                Behind&& behind_box_sums)
 {
     constexpr bool TWO = R >= TWO_LEVEL_FROM;     // two-level bound: L1 form for every candidate, squared form for the listed patches
     const int T = blockDim.x;
@@ -158,7 +159,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, 
     uint32_t* work = lds + L.work;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const SeaArgs c = launch_args();                       // phases A' .. D (bbme_sea.hip: tile_phases)
+    const SeaArgs c = launch_args();
     const WaveBlock wb = wave_block(d, c, trow, bcol0, wave);
     const int brow = wb.brow, bcol = wb.bcol;
     const bool wave_ok = wb.ok;
@@ -170,6 +171,7 @@ __device__ __forceinline__ bool tile_phases_mse(const SeaGeo& d, uint32_t* lds, 
     clk.mark(ST_BOX, lane);
     __syncthreads();
     clk.mark(ST_BOX_WAIT, lane);
+    behind_box_sums();                                     // persistent_tiles: the next tile's prefetch of the waves that held chunks
 
     // ---- B
     const int lo_r = max(0, d.sw - r0), hi_r = min(NC - 1, c->H - 16 - r0 + d.sw);
@@ -440,11 +442,13 @@ struct MseTile {
         }
         return p;
     }
+    template <class Behind>
     static __device__ __forceinline__ bool phases(const SeaGeo& d, uint32_t* lds, const Layout& L, int pair, int trow, int bcol0,
-                                                  uint32_t mine, const Pre& p, int tid, int tile_id, PhaseClock& clk)
+                                                  uint32_t mine, const Pre& p, int tid, int tile_id, PhaseClock& clk, Behind&& behind_box_sums)
     {
-        return tile_phases_mse<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id, clk);
+        return tile_phases_mse<R, FIXED>(d, lds, L, pair, trow, bcol0, mine, p.a01, p.a23, p.mine2, tid, tile_id, clk, behind_box_sums);
     }
+    static __device__ __forceinline__ bool holds_chunks(const SeaGeo& d, int wave) { return holds_box_chunks<R>(d, wave); }
     static __device__ __forceinline__ int probe_word(const Layout& L, int wave) { return L.prev + wave; }
 };
 
@@ -456,6 +460,11 @@ __global__ void __launch_bounds__(1024) k_exh_sea16_mse(SeaDev d)
     one_tile<MseTile<R>>(g, lds, layout_of(g, R));
 }
 
+// Which persistent instances order the next tile's prefetch by who holds box-sum chunks (persistent_tiles, LATE): all but the
+// run-time-geometry ones that the second copy of the prefetch would cost spilled VGPRs (R = 3 and 5 with 13 - 16 staging
+// rows per thread) or a wave per SIMD (R = 4 with 9 - 12)
+constexpr bool late_prefetch_mse(int R, int NV, int GEO) { return !(GEO == 0 && (((R == 3 || R == 5) && NV == 16) || (R == 4 && NV == 12))); }
+
 template <int R, int NV, int GEO = 0>
 __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p_mse(SeaDev d)
 {
@@ -464,7 +473,7 @@ __global__ void __launch_bounds__(1024, (R <= 3 ? 8 : 6)) k_exh_sea16p_mse(SeaDe
     fix_geometry<R, GEO>(g);
     const Layout L = layout_of(g, R);
     if ((threadIdx.x & 63) == 0) lds[L.prev + (threadIdx.x >> 6)] = (uint32_t)(g.sw * (2 * g.sw + 16) + g.sw);    // third probe of the first tile: the zero vector
-    persistent_tiles<NV, MseTile<R, GEO != 0>>(g, lds, L);
+    persistent_tiles<NV, MseTile<R, GEO != 0>, late_prefetch_mse(R, NV, GEO)>(g, lds, L);
 }
 
 // What the shared host launcher (bbme_sea_common.h: launch_sea) needs from this norm.

@@ -8,6 +8,11 @@ the table attributes time, it does not measure it.  Needs an MI355X.
 
     bash tools/build_variant.sh stamps -DSEA_PHASE_STAMPS "bbme_sea.hip bbme_sea_mse.hip"
     python tools/sea_phase_stamps.py [--lib stamps] [--pnorm 0] [--pairs 256] [--out profiles/<tag>_phase_stamps.txt]
+    python tools/sea_phase_stamps.py [--lib stamps] [--pnorm 0] --verify
+
+--verify: no table; the stamped library searches 258 synthetic pairs of 112x176 (2x4 tiles, ragged on both sides, every workgroup
+walks several tiles: the first case of tests/test_gpu_sea_fetch_order.py) under the dynamic and the static schedule, and every
+field must equal the C oracle's bit for bit -- the clock readings sit on every path of a tile and must not change a result.
 """
 import argparse
 import ctypes
@@ -21,9 +26,10 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(REPO, "global-motion-estimation_amd"), REPO]
 
-SPANS = ["head (registers -> LDS)", "head barrier", "prefetch issue", "A' box sums", "A' barrier", "B + C", "C2", "D", "D barrier",
-         "E work", "E barriers", "F + tail"]
-WAITS = (1, 4, 8, 10)
+# (name, slot of the ST_* enum in csrc/bbme_sea_common.h), in the order of a tile
+SPANS = [("head (registers -> LDS)", 0), ("head barrier", 1), ("prefetch issue", 2), ("A' box sums", 3), ("A' barrier", 4),
+         ("B + C", 5), ("C2", 6), ("D", 7), ("D barrier", 8), ("E work", 9), ("E barriers", 10), ("F + tail", 11)]
+WAITS = ("head barrier", "A' barrier", "D barrier", "E barriers")
 ST_TILES, ST_SLOTS = 12, 16
 
 
@@ -63,16 +69,44 @@ def table(tot, nb):
     sums, waits, per = [], [], []
     for _, waves in groups:
         tiles = float(sum(tot[w][ST_TILES] for w in waves)) or 1.0
-        per.append([sum(float(tot[w][s]) for w in waves) / tiles for s in range(len(SPANS))])
+        per.append([sum(float(tot[w][slot]) for w in waves) / tiles for _, slot in SPANS])
         sums.append(sum(per[-1]))
-        waits.append(sum(per[-1][s] for s in WAITS))
-    for s, name in enumerate(SPANS):
+        waits.append(sum(per[-1][s] for s, (name, _) in enumerate(SPANS) if name in WAITS))
+    for s, (name, _) in enumerate(SPANS):
         lines.append("%-26s %s" % (name, "".join("%14.0f %6.1f%%" % (per[g][s], 100.0 * per[g][s] / sums[g]) for g in range(2))))
     lines.append("%-26s %s" % ("tile", "".join("%14.0f %7s" % (sums[g], "") for g in range(2))))
     lines.append("%-26s %s" % ("barrier wait, all four", "".join("%14.0f %6.1f%%" % (waits[g], 100.0 * waits[g] / sums[g]) for g in range(2))))
-    lines.append("%-26s %s" % ("A' + E barriers", "".join("%14.0f %6.1f%%" % (per[g][4] + per[g][10], 100.0 * (per[g][4] + per[g][10]) / sums[g])
+    ia, ie = [n for n, _ in SPANS].index("A' barrier"), [n for n, _ in SPANS].index("E barriers")
+    lines.append("%-26s %s" % ("A' + E barriers", "".join("%14.0f %6.1f%%" % (per[g][ia] + per[g][ie], 100.0 * (per[g][ia] + per[g][ie]) / sums[g])
                                                           for g in range(2))))
     return lines
+
+
+def verify(native, ctx, lib, pnorm):
+    import concurrent.futures
+    import synth
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from helpers import c_oracle
+    frames = np.ascontiguousarray(synth.sequence(4711, 0, 259, 112, 176))
+    co = c_oracle()
+    with concurrent.futures.ThreadPoolExecutor(max_workers=8) as pool:
+        want = np.stack(list(pool.map(lambda p: co.bbme(frames[p], frames[p + 1], 16, 16, 0, pnorm), range(258))))
+    tot = np.zeros((16, ST_SLOTS), np.uint64)
+    for persist in ("2", "1"):
+        os.environ["GME_SEA_PERSIST"] = persist
+        seq = native.Sequence.from_frames(ctx, frames)
+        try:
+            seq.bbme(1, 16, 16, 0, pnorm)
+            mv = seq.read_mv()
+            info = ctx.last_bbme_info()
+        finally:
+            seq.close()
+        assert lib.gme_sea_phase_stamps(pnorm, tot.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), 1) == 0
+        tiles = int(tot[0][ST_TILES])
+        print(info["plan"], "tiles counted for wave 0:", tiles)
+        assert "persistent" in info["plan"] and "geometry-fixed" in info["plan"] and tiles == 258 * 12, (info, tiles)
+        assert np.array_equal(mv, want), "the stamped library's fields differ from the oracle's (GME_SEA_PERSIST=%s)" % persist
+    print("stamped library: 258 pairs bit-exact under both schedules")
 
 
 def main():
@@ -81,6 +115,7 @@ def main():
     ap.add_argument("--pnorm", type=int, default=0, help="0: MAE (k_exh_sea16p), 1: MSE on the vector unit (k_exh_sea16p_mse)")
     ap.add_argument("--pairs", type=int, default=256)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--verify", action="store_true", help="compare the stamped library's fields with the C oracle instead")
     opt = ap.parse_args()
     if opt.pnorm:
         os.environ["GME_EXH_MFMA"] = "0"
@@ -93,6 +128,8 @@ def main():
     lib.gme_sea_phase_stamps.restype = ctypes.c_int
     lib.gme_sea_phase_stamps.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     ctx = _gme_native.default_context()
+    if opt.verify:
+        return verify(_gme_native, ctx, lib, opt.pnorm)
     from bench import host_content
 
     out = ["# phase stamps, %s, %s, %d pairs per content, library libgme_%s.so" % (ctx.info()["name"], "MSE" if opt.pnorm else "MAE", opt.pairs, opt.lib),
