@@ -133,6 +133,8 @@ _SIGNATURES = {
     "gme_seq_read_prop": (_i, [_vp, _i, _i, _c_i32p, _c_i64p, _c_u8p]),
     "gme_interp_u8": (_i, [_vp, _c_u8p, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
     "gme_seq_interp": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
+    "gme_retime_u8": (_i, [_vp, _c_u8p, _c_u8p, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c_i32p, _c_i64p, _c_i64p, _c_u8p, _c_i64p]),
+    "gme_retime_clip_u8": (_i, [_vp, _c_u8p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c_u8p, _c_i32p, _c_i64p, _c_i64p]),
     "gme_obmc_u8": (_i, [_vp, _c_u8p, _c_u8p, _i, _i, _i, _i, _c_i32p, _i, _c_u8p, _c_i64p]),
     "gme_seq_obmc": (_i, [_vp, _i, _i, _i, _i, _i, _c_u8p, _c_i64p]),
     "gme_denoise_u8": (_i, [_vp, _c_u8p, ctypes.POINTER(_c_u8p), ctypes.POINTER(_c_i32p), _i, _i, _i, _i, _i, _i, _i, _c_u8p, _c_u8p,
@@ -522,6 +524,56 @@ class Context:
                                       search_window, pnorm, bias, _p(mv, _c_i32p), _p(cost, _c_i64p), _p(dist, _c_i64p), _p(made, _c_u8p),
                                       ctypes.byref(sse)), self.lib)
         return mv, cost, dist, made, sse.value
+
+    def retime(self, past, next, block_size, search_window=16, pnorm=0, bias=0, n=1, d=2, truth=None):
+        """The frame at phase n / d between ``past`` and ``next`` (gme_retime_u8, retime.search and retime.interpolate) -> (mv
+        int32[h, w, 2], cost int64[h, w], dist int64[h, w], frame uint8[H, W], sse int): ``sse`` is the squared error against
+        ``truth``, the true frame at that time, or -1 without one."""
+        import retime
+        frames = [as_frame(a, name) for a, name in ((past, "past"), (next, "next")) + (() if truth is None else ((truth, "truth"),))]
+        if any(a.shape != frames[0].shape for a in frames):
+            raise AssertionError("the frames differ in shape (bbme.py:59)")
+        H, W = frames[0].shape
+        block_size, search_window, pnorm, bias = retime.check_args(block_size, search_window, pnorm, bias)
+        retime.check_shape(H, W, block_size)
+        n, d = retime.check_phase(n, d)
+        if any(a.strides[0] != frames[0].strides[0] for a in frames):
+            frames = [np.ascontiguousarray(a) for a in frames]
+        h, w = H // block_size, W // block_size
+        mv, cost, dist = np.zeros((h, w, 2), np.int32), np.zeros((h, w), np.int64), np.zeros((h, w), np.int64)
+        made = np.empty((H, W), np.uint8)
+        sse = ctypes.c_int64(0)
+        _check(self.lib.gme_retime_u8(self.handle, _p(frames[0], _c_u8p), _p(frames[1], _c_u8p),
+                                      None if truth is None else _p(frames[2], _c_u8p), H, W, frames[0].strides[0], block_size,
+                                      search_window, pnorm, bias, n, d, _p(mv, _c_i32p), _p(cost, _c_i64p), _p(dist, _c_i64p),
+                                      _p(made, _c_u8p), ctypes.byref(sse)), self.lib)
+        return mv, cost, dist, made, sse.value
+
+    def retime_clip(self, frames, block_size, search_window=16, pnorm=0, bias=0, step=(1, 2), first=0, count=None):
+        """The outputs first .. first + count - 1 (default: all from ``first``) of retime.schedule for the clip ``frames`` uint8[N,
+        H, W] at the step (num, den) input frames per output (gme_retime_clip_u8) -> (frames uint8[count, H, W], mv int32[count, h,
+        w, 2], cost int64[count, h, w], dist int64[count, h, w]); a copy comes with zero vectors and costs.  A range outside the
+        schedule is an IndexError."""
+        import retime
+        frames = np.ascontiguousarray(frames)
+        if frames.ndim != 3 or frames.dtype != np.uint8 or len(frames) < 1:
+            raise TypeError("frames must be uint8[N, H, W], N >= 1")
+        N, H, W = frames.shape
+        block_size, search_window, pnorm, bias = retime.check_args(block_size, search_window, pnorm, bias)
+        retime.check_shape(H, W, block_size)
+        num, den = int(step[0]), int(step[1])
+        M = len(retime.schedule(N, num, den))
+        first = int(first)
+        count = M - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > M:
+            raise IndexError("outputs [%d, %d) outside [0, %d)" % (first, first + count, M))
+        h, w = H // block_size, W // block_size
+        made = np.empty((count, H, W), np.uint8)
+        mv, cost, dist = np.zeros((count, h, w, 2), np.int32), np.zeros((count, h, w), np.int64), np.zeros((count, h, w), np.int64)
+        _check(self.lib.gme_retime_clip_u8(self.handle, _p(frames, _c_u8p), N, H, W, W, block_size, search_window, pnorm, bias, num, den,
+                                           first, count, _p(made, _c_u8p), _p(mv, _c_i32p), _p(cost, _c_i64p), _p(dist, _c_i64p)),
+               self.lib)
+        return made, mv, cost, dist
 
     def obmc(self, prev, field, block_size, quarter=True, cur=None):
         """``prev`` compensated by the block field with overlapped blocks (gme_obmc_u8, obmc.compensate) -> (frame uint8[H, W],

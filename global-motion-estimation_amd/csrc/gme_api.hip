@@ -784,6 +784,163 @@ extern "C" int gme_interp_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* n
     return rc;
 }
 
+// Frame interpolation at any phase of one pair (bbme_retime.hip): the two frames, the true frame at that time
+// where the caller has one and the made frame as one stack of four planes in the scratch, behind them the one row of the phase
+// table.
+extern "C" int gme_retime_u8(gme_ctx* ctx, const uint8_t* past, const uint8_t* next, const uint8_t* truth, int H, int W, int stride,
+                             int block_size, int search_window, int pnorm, int bias, int n, int d, int32_t* mv_out, int64_t* cost_out,
+                             int64_t* dist_out, uint8_t* frame_out, int64_t* sse_out)
+{
+    GME_ENTER(ctx);
+    int rc = oneshot_check("gme_retime_u8", past && next, H, W, stride);
+    if (rc) return rc;
+    rc = retime_check_args("gme_retime_u8", H, W, block_size, search_window, pnorm, bias);
+    if (rc) return rc;
+    rc = retime_check_phase("gme_retime_u8", &n, &d);
+    if (rc) return rc;
+    const size_t blocks = (size_t)(H / block_size) * (W / block_size);
+    Plane st = plane_shape(H, W, 4);                           // past, next, truth, made
+    int32_t* d_mv = nullptr;
+    int32_t* d_table = nullptr;
+    long long* d_cost = nullptr;                               // J, D, then the squared error
+    Carver c;
+    c.take(&st, true); c.take(&d_mv, blocks * 2); c.take(&d_cost, blocks * 2 + 1); c.take(&d_table, (size_t)retime_row_ints());
+    rc = c.commit(ctx);
+    if (rc) return rc;
+    long long* d_dist = d_cost + blocks;
+    unsigned long long* d_sse = (unsigned long long*)(d_cost + blocks * 2);
+    std::vector<int32_t> row((size_t)retime_row_ints());       // read by the copy below before this call returns (ctx_finish)
+    const int wave_lds = retime_row(row.data(), 0, n, d, block_size, search_window);
+    GME_HIP_TRY(hipMemsetAsync(st.ptr, 0, (uint8_t*)d_mv - st.ptr, ctx->stream));
+    rc = put_planes(ctx, st, { past, next, truth ? truth : past }, stride);
+    if (rc) return rc;
+    GME_HIP_TRY(hipMemcpyAsync(d_table, row.data(), row.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_retime(ctx, st.ptr, st.stride, 1, H, W, st.pitch, block_size, search_window, pnorm, bias, d_table, wave_lds, d_mv, d_cost,
+                       d_dist);
+    if (rc) return rc;
+    if (mv_out) GME_HIP_TRY(hipMemcpyAsync(mv_out, d_mv, blocks * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out, d_cost, blocks * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (dist_out) GME_HIP_TRY(hipMemcpyAsync(dist_out, d_dist, blocks * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    int64_t sse = -1;                                          // without a true frame there is no error to report
+    rc = oneshot_predict(ctx, st, 3, d_sse, frame_out, truth && sse_out ? &sse : nullptr, [&] {
+        return launch_retime_frame(ctx, st.ptr, st.stride, 1, H, W, st.pitch, block_size, d_table, d_mv, st.at(2), 0, st.at(3), 0, st.pitch,
+                                   d_sse);
+    });
+    if (sse_out) *sse_out = sse;
+    return rc;
+}
+
+// Rate conversion of a host clip (bbme_retime.hip): the outputs first_out .. first_out + count - 1 of
+// retime.schedule.  Copies are made on the host; the frames the other outputs need are uploaded once into one stack, and the
+// outputs run in chunks of at most one launch's planes, each with its rows of the phase table.  Every buffer lives as long as
+// the call.
+extern "C" int gme_retime_clip_u8(gme_ctx* ctx, const uint8_t* frames, int n_frames, int H, int W, int stride, int block_size,
+                                  int search_window, int pnorm, int bias, int step_num, int step_den, int first_out, int count,
+                                  uint8_t* frames_out, int32_t* mv_out, int64_t* cost_out, int64_t* dist_out)
+{
+    GME_ENTER(ctx);
+    int rc = oneshot_check("gme_retime_clip_u8", frames != nullptr, H, W, stride);
+    if (rc) return rc;
+    GME_REQUIRE(n_frames >= 1, GME_ERR_ARG, "gme_retime_clip_u8: %d frames", n_frames);
+    rc = retime_check_args("gme_retime_clip_u8", H, W, block_size, search_window, pnorm, bias);
+    if (rc) return rc;
+    GME_REQUIRE(step_num >= 1 && step_den >= 1, GME_ERR_ARG, "gme_retime_clip_u8: step %d/%d", step_num, step_den);
+    const long long M = ((long long)(n_frames - 1) * step_den) / step_num + 1;
+    GME_REQUIRE(M <= 0x7FFFFFFF, GME_ERR_ARG, "gme_retime_clip_u8: %lld outputs", M);
+    // the phases of the whole schedule, as retime.schedule checks them: r takes the multiples of gcd(step_num, step_den) that
+    // the M outputs reach
+    for (long long m = 0; m < M && m < step_den; ++m) {
+        int n = (int)((m * step_num) % step_den), d = step_den;
+        if (n == 0) continue;
+        rc = retime_check_phase("gme_retime_clip_u8", &n, &d);
+        if (rc) return rc;
+    }
+    GME_REQUIRE(first_out >= 0 && count >= 0 && (long long)first_out + count <= M, GME_ERR_ARG,
+                "gme_retime_clip_u8: outputs [%d, %lld) outside [0, %lld)", first_out, (long long)first_out + count, M);
+    const size_t per = (size_t)(H / block_size) * (W / block_size), image = (size_t)H * W, frame_bytes = (size_t)H * stride;
+    struct Made { int out, k, n, d; };                         // an output that is not a copy: its index in the range, pair and phase
+    std::vector<Made> made;
+    int k_lo = n_frames, k_hi = -1;
+    for (int i = 0; i < count; ++i) {
+        const long long t = (long long)(first_out + i) * step_num;
+        const int k = (int)(t / step_den);
+        int n = (int)(t % step_den), d = step_den;
+        if (n == 0) {                                          // the frame itself, zero vectors and costs
+            if (frames_out)
+                for (int y = 0; y < H; ++y) memcpy(frames_out + image * i + (size_t)y * W, frames + frame_bytes * k + (size_t)y * stride, (size_t)W);
+            if (mv_out) memset(mv_out + per * 2 * i, 0, per * 2 * sizeof(int32_t));
+            if (cost_out) memset(cost_out + per * i, 0, per * sizeof(int64_t));
+            if (dist_out) memset(dist_out + per * i, 0, per * sizeof(int64_t));
+            continue;
+        }
+        rc = retime_check_phase("gme_retime_clip_u8", &n, &d);
+        if (rc) return rc;
+        made.push_back({ i, k, n, d });
+        if (k < k_lo) k_lo = k;
+        if (k + 1 > k_hi) k_hi = k + 1;
+    }
+    ctx->plan[0] = 0; ctx->plan_patches = 0;
+    if (made.empty()) return GME_OK;
+    // the input frames an output needs, each uploaded once into its plane of one stack (plane = frame - k_lo)
+    PlaneBuf in;
+    rc = plane_alloc(ctx, &in, k_hi - k_lo + 1, H, W);
+    if (rc) return rc;
+    std::vector<uint8_t> needed((size_t)(k_hi - k_lo + 1), 0);
+    for (const Made& o : made) needed[(size_t)(o.k - k_lo)] = needed[(size_t)(o.k + 1 - k_lo)] = 1;
+    for (int k = k_lo; k <= k_hi; ++k)
+        if (needed[(size_t)(k - k_lo)])
+            GME_HIP_TRY(hipMemcpy2DAsync(in.at(k - k_lo), in.pitch, frames + frame_bytes * k, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
+    const int total = (int)made.size(), step = max_grid_planes(), most = total < step ? total : step, ints = retime_row_ints();
+    DevBuf<int32_t> mv, table;
+    DevBuf<long long> cost;                                    // per chunk: J of every block, then D of every block
+    DevBuf<unsigned long long> sse;
+    PlaneBuf out;
+    rc = mv.ensure(per * 2 * most, "retiming vectors");
+    if (rc) return rc;
+    rc = cost.ensure(per * 2 * most, "retiming costs");
+    if (rc) return rc;
+    rc = table.ensure((size_t)ints * most, "retiming phase table");
+    if (rc) return rc;
+    if (frames_out) {
+        rc = sse.ensure((size_t)most, "retiming errors");
+        if (rc) return rc;
+        rc = plane_alloc(ctx, &out, most, H, W);
+        if (rc) return rc;
+    }
+    std::vector<int32_t> rows((size_t)ints * most);            // read by the copy of a chunk before its ctx_finish
+    for (int at = 0; at < total; at += step) {
+        const int n = total - at < step ? total - at : step;
+        int wave_lds = 0;
+        for (int i = 0; i < n; ++i) {
+            const Made& o = made[(size_t)(at + i)];
+            const int lds = retime_row(rows.data() + (size_t)ints * i, o.k - k_lo, o.n, o.d, block_size, search_window);
+            if (lds > wave_lds) wave_lds = lds;
+        }
+        GME_HIP_TRY(hipMemcpyAsync(table.get(), rows.data(), (size_t)ints * n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        long long* dist = cost.get() + per * n;
+        rc = launch_retime(ctx, in.ptr, in.stride, n, H, W, in.pitch, block_size, search_window, pnorm, bias, table, wave_lds, mv, cost, dist);
+        if (rc) return rc;
+        if (frames_out) {                                      // no true frames: the errors against `past` are not used
+            rc = launch_retime_frame(ctx, in.ptr, in.stride, n, H, W, in.pitch, block_size, table, mv, in.ptr, 0, out.ptr, out.stride,
+                                     out.pitch, sse);
+            if (rc) return rc;
+        }
+        for (int i = 0; i < n; ++i) {
+            const size_t o = (size_t)made[(size_t)(at + i)].out;
+            if (mv_out) GME_HIP_TRY(hipMemcpyAsync(mv_out + per * 2 * o, mv.get() + per * 2 * i, per * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+            if (cost_out) GME_HIP_TRY(hipMemcpyAsync(cost_out + per * o, cost.get() + per * i, per * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+            if (dist_out) GME_HIP_TRY(hipMemcpyAsync(dist_out + per * o, dist + per * i, per * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+            if (frames_out) {
+                rc = read_planes(ctx, out, i, 1, frames_out + image * o);
+                if (rc) return rc;
+            }
+        }
+        rc = ctx_finish(ctx);                                  // the next chunk writes the same buffers
+        if (rc) return rc;
+    }
+    return GME_OK;
+}
+
 // Overlapped block motion compensation of one pair (bbme_obmc.hip): `prev`, `cur` where the caller has one
 // and the compensated frame as one stack of three planes in the scratch.
 extern "C" int gme_obmc_u8(gme_ctx* ctx, const uint8_t* prev, const uint8_t* cur, int H, int W, int stride, int block_size,

@@ -523,6 +523,25 @@ int launch_interp_frame(gme_ctx* ctx, const uint8_t* past, const uint8_t* next, 
                         int H, int W, int pitch, int bs, const int32_t* mv, uint8_t* out, long long out_stride, int out_pitch,
                         unsigned long long* sse);
 
+// ---- bbme_retime.hip: frame interpolation at any phase ------------------------------------------------
+// the argument rules of retime.py for H x W frames (GME_ERR_ARG), and retime.check_phase: n / d reduced in place
+int retime_check_args(const char* who, int H, int W, int bs, int sw, int pnorm, int bias);
+int retime_check_phase(const char* who, int* n, int* d);
+// The phase table: one row of retime_row_ints() int32 per output, written on the host by retime_row for the output whose `past`
+// is plane `plane` of the stack (`next` the plane behind it) at the reduced phase n / d -> the LDS a wave of that output needs
+int retime_row_ints();
+int retime_row(int32_t* row, int plane, int n, int d, int bs, int sw);
+// retime.search of `outputs` outputs under their table rows (device; wave_lds: the largest retime_row of them); mv
+// [outputs][H / bs][W / bs][2], cost (J) and dist (D) [outputs][H / bs][W / bs] (device).  Names the kernel instance in the
+// context's plan.
+int launch_retime(gme_ctx* ctx, const uint8_t* frames, long long plane_stride, int outputs, int H, int W, int pitch, int bs, int sw,
+                  int pnorm, int bias, const int32_t* table, int wave_lds, int32_t* mv, long long* cost, long long* dist);
+// out planes = retime.interpolate of each output's planes by mv, sse[outputs] (device) = squared error of each against its cur
+// plane (cur + k * cur_stride: the true frame; any plane where there is none)
+int launch_retime_frame(gme_ctx* ctx, const uint8_t* frames, long long plane_stride, int outputs, int H, int W, int pitch, int bs,
+                        const int32_t* table, const int32_t* mv, const uint8_t* cur, long long cur_stride, uint8_t* out,
+                        long long out_stride, int out_pitch, unsigned long long* sse);
+
 // ---- bbme_obmc.hip: overlapped block motion compensation ---------------------------------------------
 // the argument rules of obmc.py for H x W frames (GME_ERR_ARG)
 int obmc_check_args(const char* who, int H, int W, int bs, int unit);

@@ -16,6 +16,8 @@ argparse scripts (bbme.py:658-714, results.py:117-138); their flags are kept as 
     python gme_cli.py bipred -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [-r 1] [--rounds 1] [--penalty N] [-o OUTDIR]   # bidirectional prediction of one frame
     python gme_cli.py gmc -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--penalty N] [--estimator projective|affine] [-o OUTDIR]   # global motion compensation of one pair
     python gme_cli.py prop -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 3] [-pn 0] [--rounds 2] [--steps 1] [--no-temporal] [--camera projective|affine|none] [--hier] [-o OUTDIR]   # vector propagation search of one pair
+    python gme_cli.py retime -p <video|frame dir> -o OUTDIR (--rate-in 24 --rate-out 60 | --slow 4) [-bs 16] [-sw 16] [-pn 0] [--bias N]   # frame-rate conversion, slow motion
+    python gme_cli.py retime -p <video|frame dir> -fi 0 --phase 1/3 [-fd 3] [-o OUTDIR]   # one frame at a phase between two frames
     python gme_cli.py interp -p <video|frame dir> -fi 2 [-fd 2] [-bs 16] [-sw 8] [-pn 0] [--bias N] [-o OUTDIR] [--upconvert]   # the frame between two frames; frame-rate doubling
     python gme_cli.py obmc -p <video|frame dir> -fi 1 [-fd 1] [-bs 16] [-sw 16] [-sp 0] [-pn 0] [--subpel 0|1|2] [--hier] [-o OUTDIR]   # overlapped block motion compensation of one pair
     python gme_cli.py denoise -p <video|frame dir> -o OUTDIR [-fd 1] [-bs 16] [-sw 8] [-sp 0] [-pn 0] [--radius 1] [--subpel 0|1|2] [--strength 24] [--noise SIGMA [--seed N]]   # motion-compensated temporal denoising of a clip
@@ -177,6 +179,22 @@ def _parser():
                          "tool and not a tuned value")
     ip.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for interp.json, interp.png and upconverted/%%04d.png")
     ip.add_argument("--upconvert", action="store_true", help="also double the frame rate of the whole clip into OUTDIR/upconverted/%%04d.png")
+    rp = sub.add_parser("retime", help="frame interpolation at any phase: frame-rate conversion and slow motion of a clip, or one frame at a phase n/d between two frames (retime.py, DESIGN.md 7r)")
+    rp.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
+    rp.add_argument("--rate-in", dest="rate_in", type=int, default=None, help="frames per second of the clip (with --rate-out)")
+    rp.add_argument("--rate-out", dest="rate_out", type=int, default=None, help="frames per second wanted: 24 -> 60 makes the step 2/5")
+    rp.add_argument("--slow", type=int, default=None, help="slow motion by this factor: the step 1/K")
+    rp.add_argument("-fi", "--frame-index", dest="fi", type=int, default=None, help="one pair: index of the earlier frame (with --phase)")
+    rp.add_argument("--phase", type=str, default=None, help="one pair: n/d, 0 < n/d < 1, d <= 64 once reduced")
+    rp.add_argument("-fd", "--frame-distance", dest="fd", type=int, default=None,
+                    help="one pair: the later frame is fi + fd (default: d of --phase, as written; then frame fi + n is the truth the result is compared with)")
+    rp.add_argument("-bs", "--block-size", dest="block_size", type=int, default=16, help="4 .. 64")
+    rp.add_argument("-sw", "--search-window", dest="search_window", type=int, default=16, help="0 .. 16: how far content may move between the two frames")
+    rp.add_argument("-pn", "--pnorm-distance", dest="pnorm", type=int, default=0, help="0: MAE, 1: MSE")
+    rp.add_argument("--bias", type=int, default=None,
+                    help="cost of one unit of |Vx| + |Vy| (0 .. 2^16); default: bs^2 / 16 for MAE and bs^2 for MSE, a convention of this "
+                         "tool and not a tuned value")
+    rp.add_argument("-o", "--output", dest="outdir", type=str, default=None, help="directory for retime.json and retimed/%%04d.png (a clip) or retime.png (one pair)")
     op = sub.add_parser("obmc", help="overlapped block motion compensation of one frame pair: search, optional sub-pel refinement, the plain and the overlapped compensation (obmc.py, DESIGN.md 7o)")
     op.add_argument("-p", "--video-path", dest="path", type=str, required=True, help="video file, frame directory, .npy or .y4m")
     op.add_argument("-fi", "--frame-index", dest="fi", type=int, required=True, help="index of the current frame")
@@ -413,6 +431,74 @@ def _interp(args):
             res["upconverted"] = clip
             print("up-converted: {} frames into {}".format(len(clip), d))
     return res
+
+
+def _retime(args):
+    """A clip (--rate-in / --rate-out or --slow): the schedule and, per made frame, the median vector and the share of non-zero
+    vectors, into OUTDIR/retime.json, the frames into OUTDIR/retimed/%04d.png.  One pair (-fi, --phase n/d): the same figures
+    and, where the later frame is d frames on, the PSNR of the made frame and of the plain cross-fade against frame fi + n; the
+    record into OUTDIR/retime.json and the frame into OUTDIR/retime.png."""
+    import json
+    import os
+    import numpy as np
+    import retime
+    import utils
+    frames = utils.get_video_frames(args.path)
+    options = {"path": args.path, "block_size": args.block_size, "search_window": args.search_window, "pnorm": args.pnorm % 2}
+    if args.phase is not None:
+        if args.fi is None:
+            raise ValueError("--phase needs -fi, the index of the earlier frame")
+        n, d = (int(t) for t in args.phase.split("/"))
+        fd = d if args.fd is None else args.fd
+        if fd < 1 or not 0 <= args.fi < args.fi + fd < len(frames):
+            raise IndexError("frames %d and %d of %d" % (args.fi, args.fi + fd, len(frames)))
+        truth = frames[args.fi + n] if fd == d and 0 < n < d else None
+        res = retime.report(frames[args.fi], frames[args.fi + fd], n, d, truth, args.block_size, args.search_window, args.pnorm, args.bias)
+        options.update(frame_index=args.fi, frame_distance=fd, phase=res["phase"], bias=res["bias"])
+        record = {"options": options, "shape": list(res["mv"].shape[:2])}
+        record.update({k: res[k] for k in ("median_vector", "nonzero_share", "sse_retime", "sse_crossfade", "psnr_retime", "psnr_crossfade") if k in res})
+        print("the frame at phase {}/{} between {} and {}: {} x {} blocks of {}, window {}, bias {}".format(
+            res["phase"][0], res["phase"][1], args.fi, args.fi + fd, record["shape"][0], record["shape"][1], args.block_size,
+            args.search_window, res["bias"]))
+        print("median vector: ({:g}, {:g})".format(*record["median_vector"]))
+        print("non-zero vectors: {:.2f} %".format(100.0 * record["nonzero_share"]))
+        if truth is not None:
+            print("psnr retimed: {:.4f} dB".format(record["psnr_retime"]))
+            print("psnr plain cross-fade: {:.4f} dB".format(record["psnr_crossfade"]))
+        if args.outdir:
+            os.makedirs(args.outdir, exist_ok=True)
+            with open(os.path.join(args.outdir, "retime.json"), "w") as f:
+                json.dump(record, f, indent=1)
+            utils.write_image(os.path.join(args.outdir, "retime.png"), res["frame"])
+        return res
+    if args.slow is not None:
+        if args.slow < 1:
+            raise ValueError("--slow %d" % args.slow)
+        step = (1, args.slow)
+    elif args.rate_in is not None and args.rate_out is not None:
+        step = retime.rate_step(args.rate_in, args.rate_out)
+    else:
+        raise ValueError("retime wants --rate-in and --rate-out, --slow, or -fi with --phase")
+    if not args.outdir:
+        raise ValueError("retime of a clip wants -o OUTDIR")
+    clip = np.stack([np.asarray(f) for f in frames])
+    rows = retime.schedule(len(clip), *step)
+    made, mv, _, _ = retime.retime_clip(clip, step, args.block_size, args.search_window, args.pnorm, args.bias)
+    bias = retime.default_bias(args.block_size, args.pnorm % 2) if args.bias is None else args.bias
+    options.update(bias=bias)
+    H, W = clip.shape[1:]
+    per_frame = [{"copy_of": int(k)} if n == 0 else dict(retime.summary(mv[m], H, W), pair=[int(k), int(k) + 1], phase=[int(n), int(d)])
+                 for m, (k, n, d) in enumerate(rows)]
+    record = {"options": options, "step": list(step), "schedule": rows.tolist(), "frames": per_frame, "shape": list(mv.shape[1:3])}
+    print("step {}/{}: {} frames from {}, {} x {} blocks of {}, window {}, bias {}".format(
+        step[0], step[1], len(made), len(clip), record["shape"][0], record["shape"][1], args.block_size, args.search_window, bias))
+    d = os.path.join(args.outdir, "retimed")
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(args.outdir, "retime.json"), "w") as f:
+        json.dump(record, f, indent=1)
+    for m, f in enumerate(made):
+        utils.write_image(os.path.join(d, "%04d.png" % m), f)
+    return {"frames": made, "mv": mv, "schedule": rows, "record": record}
 
 
 def _obmc(args):
@@ -689,6 +775,8 @@ def main(argv=None):
         return _prop(args)
     if args.command == "interp":
         return _interp(args)
+    if args.command == "retime":
+        return _retime(args)
     if args.command == "obmc":
         return _obmc(args)
     if args.command == "denoise":
@@ -705,6 +793,7 @@ def main(argv=None):
     print("global motion compensation (gme_cli.py gmc): -bs 4 .. 64, --penalty 0 .. 2^30, --estimator projective | affine; per block the camera warp or the block's own vector   (gmc.py)")
     print("vector propagation search (gme_cli.py prop): -bs 4 .. 64, --rounds 1 .. 4, --steps 0 .. 4, --camera projective | affine | none; own, neighbour, temporal, camera and zero vectors on a prior field, refined by one pixel   (propagate.py)")
     print("frame interpolation (gme_cli.py interp): -bs 4 .. 64, -sw 0 .. 8, --bias 0 .. 2^16, --upconvert; the frame halfway between two frames by a bilateral search, borders replicated   (interp.py)")
+    print("frame retiming (gme_cli.py retime): -bs 4 .. 64, -sw 0 .. 16, --bias 0 .. 2^16, --rate-in A --rate-out B | --slow K | -fi I --phase n/d (d <= 64); the frame at any phase between two frames by a bilateral quarter-pel search, frame-rate conversion and slow motion   (retime.py)")
     print("overlapped block compensation (gme_cli.py obmc): -bs 4 .. 64, --subpel 0 .. 2, --hier; every pixel blended from its block's and the nearest neighbours' predictions under a linear ramp, borders replicated   (obmc.py)")
     print("temporal denoising (gme_cli.py denoise): -bs 4 .. 64, --radius 1 .. 2, --subpel 0 .. 2, --strength 1 .. 64 (default 24, a convention); every frame averaged with the overlapped predictions of it from its neighbours, each pixel gated by its 3 x 3 prediction error   (denoise.py)")
     try:

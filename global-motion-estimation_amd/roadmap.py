@@ -79,6 +79,13 @@ are opt-in and tested for self-consistency (``tests/test_gpu_round2.py``).
    ``interp.upconvert`` doubles the frame rate of a clip.  A block's whole search runs in one wave of one kernel (k_interp,
    csrc/bbme_interp.hip; host definition interp.py); ``Sequence.interp`` computes and returns in one call and
    keeps nothing.
+   **Frame retiming.**  ``retime.frame`` makes the frame at any phase n / d (d <= 64) between two frames: a candidate V within
+   +-16 whole pixels is how far content moves between them, the past frame is read -n V / d and the next one (d - n) V / d away,
+   rounded to quarter pixels with one shared fraction and sampled with the four clamped taps of the quarter-pel section, and
+   the pixel is the weighted blend; ``retime.convert`` changes the frame rate of a clip (24 -> 60 fps is the step 2/5) and
+   ``retime.slow_motion`` slows it down, both over ``retime.schedule``.  A block's whole search runs in one wave of one kernel
+   that stages the interpolated windows once per fraction (k_retime, csrc/bbme_retime.hip; host definition retime.py; DESIGN.md
+   §7r); ``Context.retime_clip`` takes a host clip, computes and returns in one call and keeps nothing.
    **Overlapped block motion compensation.**  ``obmc.frame`` compensates a frame by a block field, whole or quarter pixels,
    without the jump at block edges where two neighbours disagree: every pixel is blended from the prediction of its own block and
    of the nearest vertical, horizontal and diagonal neighbour under a linear ramp, the border replicated per pixel so that no

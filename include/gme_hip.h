@@ -590,6 +590,37 @@ GME_API int gme_seq_interp(gme_seq *seq, int frame_distance, int block_size, int
                            int count, int32_t *mv_out, int64_t *cost_out, int64_t *dist_out, uint8_t *frames_out, int64_t *sse_out);
 
 /* ---------------------------------------------------------------------------
+ * Frame interpolation at any phase, for rate conversion and slow motion (csrc/bbme_retime.hip; host
+ * definition: retime.py): the frame at phase n / d between `past` (phase 0) and `next` (phase 1), 1 <= n < d <= 64 after n / d
+ * has been reduced.  A vector V = (Vx, Vy) within +-search_window, in whole pixels, is how far content moves from `past` to
+ * `next`.  Per component and in quarter pixels `past` is read at a(V) = -floor((8 n V + d) / (2 d)) and `next` at b(V) = a(V) +
+ * 4 V, through the four-tap sampler of the quarter-pel section with every tap clamped to the frame.  Block (i, j) takes the V
+ * that minimises J(V) = D(V) + bias (|Vx| + |Vy|), D the sum of |P - N| (pnorm 0) or (P - N)^2 (pnorm 1); the centre first, then
+ * column offset outer, both ascending, only a strictly smaller J replaces the incumbent.  A pixel of the new frame is
+ * ((d - n) P + n N + d / 2) / d, rounded down; beyond the last whole block V = 0.  All integer, byte-equal to retime.search and
+ * retime.interpolate.  block_size 4 .. 64 (H >= block_size and W >= block_size), search_window 0 .. 16, pnorm 0 or 1, bias
+ * 0 .. 2^16; anything else is GME_ERR_ARG.
+ * gme_retime_u8: one pair at one phase on host buffers -> mv_out int32[H/B][W/B][2], cost_out (J) and dist_out (D of the
+ *   winner) int64[H/B][W/B], frame_out uint8[H][W] (tight), *sse_out = exact squared error of the made frame against `truth`,
+ *   the true frame at that time, or -1 where truth is NULL.  Any output may be NULL.
+ * gme_retime_clip_u8: a host clip frames uint8[n_frames][H][stride] at a step of step_num / step_den input frames per output
+ *   (input rate over output rate; both >= 1).  Output m of M = ((n_frames - 1) step_den) / step_num + 1 lies at k = (m step_num)
+ *   / step_den, r = (m step_num) % step_den: frame k itself for r = 0, else the pair (k, k + 1) at phase r / step_den, reduced
+ *   (a denominator above 64 anywhere in the schedule is GME_ERR_ARG).  The outputs first_out .. first_out + count - 1 (a range
+ *   outside [0, M) is GME_ERR_ARG) -> frames_out uint8[count][H][W] (tight), mv_out int32[count][H/B][W/B][2], cost_out and
+ *   dist_out int64[count][H/B][W/B]; a copy comes out as the frame itself with zero vectors and costs.  Any output may be NULL.
+ *   Every input frame an output needs is uploaded once; the launches carry at most the per-launch limit of outputs
+ *   (GME_MAX_GRID_PAIRS lowers it); the call works in buffers of its own and keeps nothing.
+ * Blocking calls.  gme_last_bbme_info names the kernel instance: k_retime<16>, k_retime<32>, or k_retime<0> (block size at run
+ * time). */
+GME_API int gme_retime_u8(gme_ctx *ctx, const uint8_t *past, const uint8_t *next, const uint8_t *truth /* may be NULL */, int H, int W,
+                          int stride, int block_size, int search_window, int pnorm, int bias, int n, int d, int32_t *mv_out,
+                          int64_t *cost_out, int64_t *dist_out, uint8_t *frame_out, int64_t *sse_out);
+GME_API int gme_retime_clip_u8(gme_ctx *ctx, const uint8_t *frames, int n_frames, int H, int W, int stride, int block_size,
+                               int search_window, int pnorm, int bias, int step_num, int step_den, int first_out, int count,
+                               uint8_t *frames_out, int32_t *mv_out, int64_t *cost_out, int64_t *dist_out);
+
+/* ---------------------------------------------------------------------------
  * Overlapped block motion compensation (csrc/bbme_obmc.hip; host definition: obmc.py): `prev` compensated
  * by a block field, every pixel blended from the predictions of its own block and of the nearest vertical, horizontal and
  * diagonal neighbour blocks under a linear ramp, so the prediction does not jump where two neighbours disagree.  field is
