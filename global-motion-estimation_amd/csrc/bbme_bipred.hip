@@ -19,6 +19,7 @@
 //   k_predict_bipred    bipred.predict per pixel, with the squared error of each predicted frame against its `mid`
 #include "bbme_predict.h"
 #include "bbme_wave_lds.h"
+#include "gme_passes.h"
 
 namespace {
 

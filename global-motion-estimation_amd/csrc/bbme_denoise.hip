@@ -13,6 +13,7 @@
 //               plane pointers stay scalar.  The squared difference against the comparison plane is summed per workgroup (16 bytes
 //               of LDS) and added with one atomic.
 #include "bbme_predict.h"
+#include "gme_passes.h"
 
 namespace {
 

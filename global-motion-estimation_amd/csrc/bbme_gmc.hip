@@ -20,6 +20,7 @@
 //                    one integer atomic.
 #include "bbme_predict.h"
 #include "bbme_wave_lds.h"
+#include "gme_passes.h"
 #include "gme_warp.h"
 
 namespace {

@@ -16,7 +16,7 @@
 #include <type_traits>
 
 #include "bbme_wave_lds.h"
-#include "gme_internal.h"
+#include "gme_passes.h"
 
 namespace {
 

@@ -18,6 +18,7 @@
 //                       there is one
 #include "bbme_predict.h"
 #include "bbme_wave_lds.h"
+#include "gme_passes.h"
 
 namespace {
 

@@ -10,6 +10,7 @@
 //            other three samples as a whole, and a mixed wave takes them for all lanes and selects.  Every read is clamped, field
 //            indices and pixel coordinates alike: no vector can lead outside a plane.
 #include "bbme_predict.h"
+#include "gme_passes.h"
 
 namespace {
 

@@ -16,6 +16,7 @@
 //                 block of 16 is one dword per lane: scored one by one, a wave would wait for memory twenty times in a row);
 //                 <0> takes the block size at run time (and rows that are no multiple of four bytes) and scores one by one.
 #include "bbme_wave_lds.h"
+#include "gme_passes.h"
 
 namespace {
 

@@ -21,6 +21,7 @@
 //                       one
 #include "bbme_predict.h"
 #include "bbme_wave_lds.h"
+#include "gme_passes.h"
 
 namespace {
 

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "bbme_predict.h"
+#include "gme_passes.h"
 
 namespace {
 

@@ -18,6 +18,7 @@
 //                       H / h, which is another size when H is no multiple of the root), with the squared error per pair
 #include "bbme_predict.h"
 #include "bbme_wave_lds.h"
+#include "gme_passes.h"
 
 namespace {
 

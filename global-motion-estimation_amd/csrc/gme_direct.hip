@@ -10,6 +10,7 @@
 //   k_compensate_proj  compensation + squared error
 // Every launch of a refinement is queued up front (launch counts depend on max_iters only); a pair whose level has ended
 // returns at the top of each kernel.
+#include "gme_passes.h"
 #include "gme_warp.h"
 
 namespace {
@@ -429,9 +430,9 @@ static int direct_ws(gme_seq* s, int pairs, DirectWs* ws)
     const size_t b_st = P * sizeof(DirectState), b_hist = P * HIST_BINS * sizeof(uint32_t), b_slab = P * tiles * SLAB * sizeof(double);
     const size_t b_io = P * (8 + 8 + 48) * sizeof(double) + P * sizeof(int32_t);
     const size_t want = b_st + b_hist + b_slab + b_io;
-    const int rc = s->direct.ensure(want, "direct refinement workspace");
+    const int rc = s->passes->direct.ensure(want, "direct refinement workspace");
     if (rc) return rc;
-    char* b = (char*)s->direct.get();
+    char* b = (char*)s->passes->direct.get();
     ws->st = (DirectState*)b; b += b_st;
     ws->hist = (uint32_t*)b; b += b_hist;
     ws->slab = (double*)b; b += b_slab;

@@ -8,6 +8,7 @@
 //                    256-bin histogram per pixel in LDS, then a walk to rank (count - 1) / 2
 //   k_moving_mask    frame t against the sprite sampled at direct.warp(A_t, u, v) - (ox, oy): residuals of a tile and its
 //                    one-pixel halo staged in LDS, the 3x3 rule, known and moving pixels counted per frame
+#include "gme_passes.h"
 #include "gme_warp.h"
 
 namespace {

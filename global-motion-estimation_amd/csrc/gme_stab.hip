@@ -7,6 +7,7 @@
 //                  sample where the sample point lies in the frame, the fill value or the clamped point elsewhere; valid
 //                  samples counted per frame
 //   k_frame_sse    exact sum of squared differences of consecutive frames of a plane stack
+#include "gme_passes.h"
 #include "gme_warp.h"
 
 namespace {

@@ -8,6 +8,7 @@
 //   k_warp_fill   out frame t, pixel (u, v) = the first candidate j < n with sources[t][j] >= 0 whose sample point
 //                 direct.warp(warps[t][j], u, v) lies in frame sources[t][j], sampled bilinearly; the winning j (255: none)
 //                 per pixel where asked for; pixels won by candidate 0 and by a later one counted per frame
+#include "gme_passes.h"
 #include "gme_warp.h"
 
 namespace {

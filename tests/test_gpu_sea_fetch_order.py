@@ -227,8 +227,7 @@ def stamped_library():
     lib = os.path.join(REPO, "tools", "microbench", "libgme_stamps.so")
     newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in STAMPED + ("bbme_sea_common.h",))
     if not os.path.exists(lib) or os.path.getmtime(lib) < newest:
-        import re
-        srcs = re.search(r"^SRCS *:= *(.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
+        srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))       # as the Makefile's wildcard
         have_objects = all(os.path.exists(os.path.join(CSRC, "build", f[:-4] + ".o")) for f in srcs)
         cmd = ["bash", os.path.join(REPO, "tools", "build_variant.sh"), "stamps", "-DSEA_PHASE_STAMPS"] + ([" ".join(STAMPED)] if have_objects else [])
         subprocess.run(cmd, check=True, cwd=REPO, stdout=subprocess.DEVNULL)

@@ -489,6 +489,62 @@ def test_committed_profiles_belong_to_these_kernels():
         assert os.path.exists(stats) and kernel.split("<")[0] in open(stats).read(), stats
 
 
+def test_benchmarked_sources_stand_apart_from_the_passes():
+    """The guard above hashes bench.COMMON_SOURCES and a config's bench.CONFIG_SOURCES.  It tells a change of a benchmarked
+    kernel from a new pass only while those files hold the core alone: what they include, the entry points they define and
+    the Makefile must not grow with a pass.  The passes live in gme_api_passes.hip, gme_api_frames.hip and gme_passes.h."""
+    sys.path.insert(0, REPO)
+    import bench
+    csrc = os.path.join(REPO, "global-motion-estimation_amd", "csrc")
+    hashed = set(bench.COMMON_SOURCES).union(*bench.CONFIG_SOURCES.values())
+    # every file the hashed ones are compiled from is hashed itself.  dev_buf.h (device memory ownership, included by
+    # gme_internal.h) is the one exception: bench.py's lists leave it out, and they are not this test's to change.
+    reached, todo = set(), sorted(hashed)
+    while todo:
+        name = todo.pop()
+        if name in reached:
+            continue
+        reached.add(name)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, name)).read(), re.M):
+            path = os.path.normpath(os.path.join(csrc, inc))
+            if os.path.dirname(path) == csrc:                  # the public header lies outside csrc/
+                todo.append(os.path.basename(path))
+    assert reached <= hashed | {"dev_buf.h"}, \
+        "benchmarked sources include %s: declare what a pass needs in gme_passes.h" % sorted(reached - hashed - {"dev_buf.h"})
+    # the C ABI the hashed files define: the core (gme_api.hip), the communicator (gme_comm.hip) and the stamp reader of the
+    # instrumented elimination build (bbme_sea.hip)
+    core = set("""
+        gme_last_error gme_device_count gme_create gme_destroy gme_sync gme_last_bbme_info gme_last_bbme_listed gme_stream
+        gme_device_info gme_device_bus_id gme_timer_start gme_timer_stop gme_host_alloc gme_host_free
+        gme_bbme_u8 gme_pyrdown_u8 gme_affine_field gme_model2_field gme_compensate_u8 gme_sse_u8
+        gme_solve_fit_sums gme_solve_model2_sums
+        gme_seq_create gme_seq_destroy gme_seq_set_frames gme_seq_upload gme_seq_synth gme_seq_invalidate gme_seq_read_frame
+        gme_seq_bbme gme_seq_bbme_streamed gme_seq_read_mv gme_seq_set_split_phase gme_seq_wait gme_seq_poll
+        gme_seq_gme_begin gme_seq_gme_begin_fit gme_seq_gme_begin_fit2 gme_seq_gme_fit gme_seq_gme_fit2 gme_seq_gme_read_stage
+        gme_seq_compensate gme_seq_compensate2 gme_seq_gme_device_solve gme_seq_gme_device_solve2
+        gme_seq_read_compensated gme_seq_read_compensated_range
+        gme_comm_probe gme_comm_unique_id gme_comm_init gme_comm_destroy gme_comm_info gme_shard_gather gme_comm_allreduce_max
+        gme_seq_mv_summary gme_seq_mv_summary_gather
+        gme_sea_phase_stamps""".split())
+    defined = {}
+    for name in sorted(hashed):
+        for fn in re.findall(r'^extern "C" [^;{(]*?(\w+)\s*\(', open(os.path.join(csrc, name)).read(), re.M):
+            defined[fn] = name
+    extra = {fn: f for fn, f in defined.items() if fn not in core}
+    assert not extra, "%s: the entry points of a pass belong in gme_api_passes.hip or gme_api_frames.hip, not in a benchmarked source" % extra
+    assert set(defined) == core, sorted(core - set(defined))
+    # ... and everything else the header declares is defined in a file no config hashes
+    elsewhere = set()
+    for name in sorted(set(os.listdir(csrc)) - hashed):
+        if name.endswith(".hip"):
+            elsewhere.update(re.findall(r'^extern "C" [^;{(]*?(\w+)\s*\(', open(os.path.join(csrc, name)).read(), re.M))
+    header = open(os.path.join(REPO, "include", "gme_hip.h")).read()
+    declared = set(re.findall(r"GME_API [^;(]*?\b(gme_\w+)\s*\(", header))
+    assert declared - core == elsewhere and len(elsewhere) >= 40, sorted((declared - core) ^ elsewhere)
+    # the Makefile names no translation unit, so a new one does not change it
+    assert not re.search(r"\w\.hip\b", open(os.path.join(csrc, "Makefile")).read())
+
+
 def test_benched_kernel_instances_do_not_spill():
     """DESIGN.md said "the R = 5 body no longer spills to scratch" while the committed sources compiled to
     215 spilled VGPRs and 192 bytes of scratch per lane.  The Makefile now keeps the compiler's own resource remarks
@@ -688,6 +744,6 @@ def test_device_memory_has_one_owner():
     api = open(os.path.join(csrc, "gme_api.hip")).read()
     uploader = api[api.index("struct Uploader"):api.index("Uploader g_uploader")]
     assert "never freed" in uploader and "runtime" in uploader             # the exception is explained where it is declared
-    internal = open(os.path.join(csrc, "gme_internal.h")).read()
+    internal = open(os.path.join(csrc, "gme_internal.h")).read() + open(os.path.join(csrc, "gme_passes.h")).read()
     assert "plane_free" not in internal
     assert re.findall(r"\b[a-z0-9_]+_bytes\b", internal) == []
